@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: concept heat maps per second on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given and prints
+the line.  Everything else it can measure or check -- the CPU baseline, the per-launch HIP-event timing behind
+`roofline` / `roofline_attention`, the double-block timing forward, the single-item re-run (`batched_equals_single`),
+the finiteness / normalisation checks of the maps and the HBM traffic figure read from profiles/ -- runs with --full only.
 
 One *step* = one generate_image-equivalent call of the hot path on synthetic inputs already
 resident in HBM: flux-schnell geometry, 1024x1024 (4096 image tokens), 256 text tokens, 4 concepts,
@@ -12,9 +17,9 @@ round-robin over ranks, ONE RCCL all_gather of the (C,64,64) fp32 maps at the en
 Each GPU sends `--batch` (default 5) independent work items through every forward -- one launch per kernel for all
 of them, so the last round of workgroups of every launch is full (5 x 17 GEMM row tiles, 5 x 408 attention
 workgroups on 256 CUs) -- on `--streams` (default 1) HIP streams; per item the results are bit-identical to a
-single-item call, and rank 0 re-runs the last timed item alone after the timed region to check exactly that
-(`batched_equals_single`).  The LAST group of --batch items of every rank carries the per-launch HIP-event timing
-behind `roofline.achieved`; the groups before it run unperturbed.  `--steps` should be a multiple of `--batch`
+single-item call, and with --full rank 0 re-runs the last timed item alone after the timed region to check exactly that
+(`batched_equals_single`).  With --full the LAST group of --batch items of every rank carries the per-launch HIP-event
+timing behind `roofline.achieved`; the groups before it run unperturbed.  `--steps` should be a multiple of `--batch`
 (a ragged last group is run and warmed up too, as a smaller forward).
 Rank 0 prints ONE JSON line.  `value` = heat maps produced by all ranks / wall time (max over ranks).
 """
@@ -90,6 +95,23 @@ def cpu_baseline(p, L, T, C, steps_per_call, n_layers_double, n_layers_single):
                        f"{reps} reps each after 1 warm-up, extrapolated x({n_layers_double},{n_layers_single}) "
                        f"x{steps_per_call} steps = {call_s:.0f} s per call"),
             "seconds_per_call": call_s}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32.  Above DUMP_LIMIT_BYTES in all, each array is
+    replaced by the same fixed, seeded sample of its flattened elements (sorted indices, in proportion to its size)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(t.numel() * 4 for t in outputs.values())
+    for name, t in outputs.items():
+        a = t.float().cpu().numpy()
+        if total > DUMP_LIMIT_BYTES:
+            n = max(1, a.size * DUMP_LIMIT_BYTES // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def stub_main(args):
@@ -181,6 +203,15 @@ def main():
     ap.add_argument("--residual", choices=("fp32", "bf16"), default="fp32",
                     help="storage type of the residual streams (fp32 = the product default; bf16 = the reference's "
                          "activation dtype, an A/B aid: see DESIGN.md section 2 for what it costs in heat-map error)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline, the "
+                         "per-launch HIP-event timing of the GEMM and attention kernels, the double-block timing forward, "
+                         "the single-item re-run, the finiteness / normalisation checks of the maps and the HBM traffic "
+                         "figure from profiles/ (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps rank 0 writes what its last timed step returned as DIR/<name>.npy, "
+                         "float32 (generate: image_latent, concept_heatmaps, cross_attention_maps; encode and sweep: "
+                         "the two map sets); inputs and weights are seeded, so equal arguments give equal inputs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true",
                     help="skip the per-launch HIP-event timing of the GEMM kernel (roofline.achieved then "
@@ -206,7 +237,7 @@ def main():
     args = ap.parse_args()
     if args.concepts is None:
         args.concepts = 2 if args.workload == "encode" else 4
-    if args.profile_mode:
+    if args.profile_mode or not args.full:
         args.no_solo_check = args.no_block_timing = args.no_cpu_baseline = args.no_kernel_timing = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -256,17 +287,20 @@ def main():
 
     wl = args.workload
     SWEEP_STEPS = 50   # the schedule the noise levels index (test_segmentations_per_time.py:75-104 sweeps 50 levels)
+    last_outputs = {}  # what a caller of the path received for the most recent item (--dump-outputs)
     if wl == "generate":
         gen_kw = dict(layer_indices=layer_indices, num_inference_steps=args.diffusion_steps, guidance=0.0)
 
         def run_many(js, n_streams, batch):
             res = pipe.generate_many_on_device([inputs[j] for j in js], n_streams=n_streams, batch=batch, **gen_kw)
+            last_outputs.update(zip(("image_latent", "concept_heatmaps", "cross_attention_maps"), res[-1]))
             return [torch.stack((hm[0], cm[0])) for _, hm, cm in res]           # [2, C, side, side] per item
     elif wl == "encode":
         enc_kw = dict(layer_indices=layer_indices, num_samples=1, num_steps=4, noise_timestep=2, seed=0)
 
         def run_many(js, n_streams, batch):
             res = pipe.encode_many_on_device([inputs[j] for j in js], n_streams=n_streams, batch=batch, **enc_kw)
+            last_outputs.update(zip(("concept_heatmaps", "cross_attention_maps"), res[-1]))
             return [torch.stack((ho[0], hc[0])) for ho, hc in res]
     else:   # sweep: every item is one noise level of the SAME image (item 0's inputs); all 19 layers per level
         img0 = item_inputs(0)
@@ -275,6 +309,7 @@ def main():
             out, cross = pipe.layer_noise_sweep_on_device(img0["latent"], img0["txt"], img0["vec"], img0["concepts"],
                                                           [j % SWEEP_STEPS for j in js], num_steps=SWEEP_STEPS,
                                                           batch=batch)
+            last_outputs.update(concept_heatmaps=out[-1:], cross_attention_maps=cross[-1:])   # the last level's rows
             return [torch.stack((out[k], cross[k])) for k in range(len(js))]   # [2, 19, C, side, side] per level
 
     def run_item(j):
@@ -374,6 +409,8 @@ def main():
     elapsed = time.perf_counter() - t0
     gpu_elapsed = ev0.elapsed_time(ev1) * 1e-3
     elapsed = D.max_over_ranks(elapsed, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_outputs)
 
     calls = n_timed
     # evidence that the job's collectives ran over `world` ranks on `world` different devices (rank 0 prints it)
@@ -418,14 +455,15 @@ def main():
                          "per work item", "us": med,
                  "tflop": dbl_flops / 1e12, "achieved_tflops": dbl_flops / med / 1e6,
                  "mfma_frac": dbl_flops / med / 1e6 / MFMA_BF16_PEAK_TFLOPS}
-    if not bool(torch.isfinite(all_maps).all().item()):
-        raise SystemExit("bench: non-finite heat maps")
-    # the softmax over the concepts makes every patch's maps sum to 1 (concept_attention_pipeline.py:64-65); cheap, and
-    # it catches a forward that produced finite garbage
-    col = all_maps.float().sum(dim=-3)
-    if float((col - 1.0).abs().max().item()) > 1e-3:
-        raise SystemExit(f"bench: heat maps are not normalised over the concepts (max |sum - 1| = "
-                         f"{float((col - 1.0).abs().max().item()):.3e})")
+    if args.full:
+        if not bool(torch.isfinite(all_maps).all().item()):
+            raise SystemExit("bench: non-finite heat maps")
+        # the softmax over the concepts makes every patch's maps sum to 1 (concept_attention_pipeline.py:64-65); cheap,
+        # and it catches a forward that produced finite garbage
+        col = all_maps.float().sum(dim=-3)
+        if float((col - 1.0).abs().max().item()) > 1e-3:
+            raise SystemExit(f"bench: heat maps are not normalised over the concepts (max |sum - 1| = "
+                             f"{float((col - 1.0).abs().max().item()):.3e})")
     # ---- the batched forward against the reference's unit of work (ONE item per call,
     # concept_attention_pipeline.py:115-202): the last timed item of rank 0 again, alone, outside the timed region;
     # its maps must equal the ones the batched group produced bit for bit
@@ -522,39 +560,40 @@ def main():
         # HBM-side bytes per launch of that kernel: PMC counters cannot be read from inside the process,
         # so this is the rocprofv3 FETCH_SIZE/WRITE_SIZE measurement of this same command, committed
         # under profiles/ (method and the gfx950 x2 FETCH_SIZE correction are recorded in the file)
-        try:
-            import glob
-            # a per-launch average is only this launch's traffic if every profiled launch had the timed shape: every
-            # file states its launch mix (tools/profile_round.py); the newest one of THIS run's mix is used, none otherwise
-            pmc_doc = pmc_file = None
-            seen = []
-            for cand in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_hbm_traffic.json")), reverse=True):
-                doc = json.load(open(cand))
-                mix = doc.get("launch_mix") or {}
-                seen.append(os.path.basename(cand))
-                if (mix.get("items_per_forward") == args.batch and mix.get("workload") == wl
-                        and mix.get("model") == args.model and mix.get("concepts") == C
-                        and mix.get("size") == args.size and mix.get("only_batched_launches") is True
-                        and mix.get("precision", "bf16") == args.precision):
-                    pmc_doc, pmc_file = doc, cand
-                    break
-            if pmc_doc is None:
-                roof["traffic_source"] = (f"no profiles/r*_pmc_hbm_traffic.json holds this run's launch mix (looked at "
-                                          f"{seen[:4]}): traffic not reported")
-            else:
-                pmc = pmc_doc["kernels"]
-                key = roof.get("kernel", "").split(" ")[0]
-                if key in pmc and not fp8:
-                    roof["traffic"] = pmc[key]["bytes_per_launch"]
-                    roof["traffic_source"] = (f"profiles/{os.path.basename(pmc_file)} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
-                                              f"passes of `{pmc_doc.get('command', 'bench.py --profile-mode')}` at "
-                                              f"{pmc_doc.get('git_head', 'an earlier commit')}: every launch of that process is a "
-                                              f"{args.batch}-item launch; counters cannot be read from inside the process)")
-                akey = roof_attn["kernel"].split(" ")[0] if roof_attn is not None else None
-                if akey in pmc and not fp8:
-                    roof_attn["traffic"] = pmc[akey]["bytes_per_launch"]
-        except (OSError, KeyError, ValueError, IndexError):
-            pass
+        if args.full:
+            try:
+                import glob
+                # a per-launch average is only this launch's traffic if every profiled launch had the timed shape: every
+                # file states its launch mix (tools/profile_round.py); the newest one of THIS run's mix is used, none otherwise
+                pmc_doc = pmc_file = None
+                seen = []
+                for cand in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_hbm_traffic.json")), reverse=True):
+                    doc = json.load(open(cand))
+                    mix = doc.get("launch_mix") or {}
+                    seen.append(os.path.basename(cand))
+                    if (mix.get("items_per_forward") == args.batch and mix.get("workload") == wl
+                            and mix.get("model") == args.model and mix.get("concepts") == C
+                            and mix.get("size") == args.size and mix.get("only_batched_launches") is True
+                            and mix.get("precision", "bf16") == args.precision):
+                        pmc_doc, pmc_file = doc, cand
+                        break
+                if pmc_doc is None:
+                    roof["traffic_source"] = (f"no profiles/r*_pmc_hbm_traffic.json holds this run's launch mix (looked at "
+                                              f"{seen[:4]}): traffic not reported")
+                else:
+                    pmc = pmc_doc["kernels"]
+                    key = roof.get("kernel", "").split(" ")[0]
+                    if key in pmc and not fp8:
+                        roof["traffic"] = pmc[key]["bytes_per_launch"]
+                        roof["traffic_source"] = (f"profiles/{os.path.basename(pmc_file)} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
+                                                  f"passes of `{pmc_doc.get('command', 'bench.py --profile-mode')}` at "
+                                                  f"{pmc_doc.get('git_head', 'an earlier commit')}: every launch of that process is a "
+                                                  f"{args.batch}-item launch; counters cannot be read from inside the process)")
+                    akey = roof_attn["kernel"].split(" ")[0] if roof_attn is not None else None
+                    if akey in pmc and not fp8:
+                        roof_attn["traffic"] = pmc[akey]["bytes_per_launch"]
+            except (OSError, KeyError, ValueError, IndexError):
+                pass
         roof["frac"] = roof["achieved"] / roof["peak"]
         roof["path_achieved"] = path_tflops
         roof["path_frac"] = path_tflops / MFMA_BF16_PEAK_TFLOPS

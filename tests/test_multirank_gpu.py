@@ -26,7 +26,7 @@ def _bench(tmp, name, gpus, steps, extra):
         env.pop(k, None)
     path = os.path.join(tmp, name + ".npy")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", str(steps),
-                        "--warmup", "0", "--no-cpu-baseline", "--no-kernel-timing", "--dump-maps", path] + extra,
+                        "--warmup", "0", "--full", "--no-cpu-baseline", "--no-kernel-timing", "--dump-maps", path] + extra,
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -22,7 +22,7 @@ code = ("import sys, runpy; sys.path.insert(0, {root!r}); import conceptattentio
         "        n, v = kv.split('=', 1)\n"
         "        setattr(self, n, eval(v))\n"
         "F.HipFluxDiT.__init__ = init\n"
-        "sys.argv = ['bench.py', '--no-cpu-baseline'] + {extra!r}\n"
+        "sys.argv = ['bench.py', '--full', '--no-cpu-baseline'] + {extra!r}\n"
         "runpy.run_path({bench!r}, run_name='__main__')")
 for rep in range(reps):
     for setting in args:

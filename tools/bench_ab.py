@@ -14,7 +14,7 @@ if args and args[0] == "--reps":
     reps, args = int(args[1]), args[2:]
 code = ("import sys, runpy; sys.path.insert(0, {root!r}); from conceptattention_amd import _lib; "
         "_lib.LIB_PATH = {lib!r} if {lib!r} != 'HEAD' else _lib.LIB_PATH; "
-        "sys.argv = ['bench.py', '--steps', '10', '--warmup', '1', '--no-cpu-baseline'] + {extra!r}; "
+        "sys.argv = ['bench.py', '--steps', '10', '--warmup', '1', '--full', '--no-cpu-baseline'] + {extra!r}; "
         "runpy.run_path({bench!r}, run_name='__main__')")
 for rep in range(reps):
     for lib in args:

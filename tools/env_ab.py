@@ -25,7 +25,7 @@ for rep in range(reps):
         for kv in setting.split():
             k, v = kv.split("=", 1)
             env[k] = v
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"] + bench_args,
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"] + bench_args,
                              capture_output=True, text=True, cwd=ROOT, env=env)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if not line:

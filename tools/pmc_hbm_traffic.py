@@ -1,7 +1,7 @@
 """Build profiles/rNN_pmc_hbm_traffic.json from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of bench.py.
 
     rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_FETCH_SIZE -- python3 bench.py \\
-        --steps 5 --warmup 1 --streams 1 --profile-mode
+        --full --steps 5 --warmup 1 --streams 1 --profile-mode
     rocprofv3 --pmc WRITE_SIZE ... -d gpurun_out/pmc_WRITE_SIZE -- (same command)
     python tools/pmc_hbm_traffic.py gpurun_out/pmc_FETCH_SIZE gpurun_out/pmc_WRITE_SIZE out.json
 

@@ -7,7 +7,7 @@
                                                        # bench.py: files profiles/rNN_<workload>[_b<batch>]_*; --no-pmc skips
                                                        # the three counter passes (kernel trace + bench line only)
 
-On the box, for the exact bench command (`python3 bench.py --steps 5 --warmup 1 --streams 1 --profile-mode`: one
+On an MI355X, for the exact bench command (`python3 bench.py --full --steps 5 --warmup 1 --streams 1 --profile-mode`: one
 warm-up group and one timed group of 5 work items on one stream and NOTHING else -- no single-item re-run, no
 block-timing forward, no per-launch events -- so every launch in the trace is a 5-item launch, the two groups hold the
 same launch list, and a kernel's AverageNs is the average over one 5-item call's launches, which is what bench.py's
@@ -31,7 +31,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BENCH = ["python3", "bench.py", "--steps", "5", "--warmup", "1", "--streams", "1", "--profile-mode"]
+BENCH = ["python3", "bench.py", "--full", "--steps", "5", "--warmup", "1", "--streams", "1", "--profile-mode"]
 LAUNCH_MIX = {"items_per_forward": 5, "workload": "generate", "model": "flux-schnell", "concepts": 4, "size": 1024,
               "groups_in_process": 2, "only_batched_launches": True, "precision": "bf16"}
 
@@ -40,8 +40,8 @@ def configure(workload: str, batch: int):
     """Bench command, launch mix and file tag of one (workload, items per forward) pair; the default pair keeps the
     names of rounds 1-4 (rNN_rocprofv3_kernel_stats.csv ...)."""
     global BENCH, LAUNCH_MIX
-    BENCH = ["python3", "bench.py", "--workload", workload, "--batch", str(batch), "--steps", str(batch), "--warmup", "1",
-             "--streams", "1", "--profile-mode"]
+    BENCH = ["python3", "bench.py", "--full", "--workload", workload, "--batch", str(batch), "--steps", str(batch),
+             "--warmup", "1", "--streams", "1", "--profile-mode"]
     LAUNCH_MIX = dict(LAUNCH_MIX, workload=workload, items_per_forward=batch, concepts=2 if workload == "encode" else 4)
     return "" if (workload, batch) == ("generate", 5) else f"{workload}{'' if batch == 5 else f'_b{batch}'}_"
 
