@@ -12,10 +12,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CA_LIB_PATH: another build of the same library (A/B and diagnostic builds under tools/ab); still no fallback
 LIB_PATH = os.environ.get("CA_LIB_PATH") or os.path.join(_HERE, "libconceptattn.so")
 
-CA_VERSION = 125
+CA_VERSION = 126
 EPI_BIAS, EPI_GELU_TANH, EPI_GATE_RESIDUAL, EPI_SPLIT_GELU, EPI_QKV_NORM_ROPE = 0, 1, 2, 3, 4
 TILE_AUTO, TILE_256x256, TILE_256x192, TILE_256x128, TILE_256x64 = 0, 1, 2, 3, 4
 TILE_PP_256x256, TILE_PP_256x128, TILE_PP_256x192 = 5, 6, 7
+GEMM_KERNEL_NONE, GEMM_KERNEL_CLASSIC, GEMM_KERNEL_PP, GEMM_KERNEL_PP_FP8 = 0, 1, 2, 3
 NORM_SOFTMAX, NORM_SPARSEMAX, NORM_ENTMAX15 = 0, 1, 2
 NORMS = {"softmax": NORM_SOFTMAX, "sparsemax": NORM_SPARSEMAX, "entmax15": NORM_ENTMAX15}
 MAX_SEGMENTS = 16
@@ -36,6 +37,12 @@ class GemmProblem(C.Structure):
                 ("epilogue", C.c_int32), ("ldp", C.c_int32), ("out_f32", C.c_int32), ("gate_stride", C.c_int32),
                 ("gate_item_rows", C.c_int32), ("gate2_item_rows", C.c_int32),
                 ("qpre_f32", C.c_int32), ("q_out_scale", C.c_float), ("qk_f16", C.c_int32), ("_pad", C.c_int32)]
+
+
+class GemmPlanInfo(C.Structure):
+    _fields_ = [("tile", C.c_int32), ("kernel", C.c_int32), ("grid", C.c_int32), ("persistent", C.c_int32),
+                ("main_tiles", C.c_int32), ("thin_tiles", C.c_int32), ("thin_mf", C.c_int32), ("thin_nw", C.c_int32),
+                ("thin_groups", C.c_int32), ("thin_grid_x", C.c_int32), ("n_cu", C.c_int32), ("_pad", C.c_int32)]
 
 
 class AttnProblem(C.Structure):
@@ -69,6 +76,8 @@ SIGNATURES = {
     "ca_gemm_bf16": (C.c_int, [C.POINTER(GemmProblem), C.c_int32, C.c_int32, C.c_void_p]),
     "ca_gemm_auto_tile": (C.c_int, [C.POINTER(GemmProblem), C.c_int32]),
     "ca_gemm_fp8": (C.c_int, [C.POINTER(GemmProblem), C.c_int32, C.c_void_p]),
+    "ca_gemm_plan": (C.c_int, [C.POINTER(GemmProblem), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                               C.POINTER(GemmPlanInfo)]),
     "ca_attn_fwd_bf16": (C.c_int, [C.POINTER(AttnProblem), C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     "ca_attn_fwd_qk16": (C.c_int, [C.POINTER(AttnProblem), C.c_int32, C.c_int32, C.c_void_p]),
     "ca_attn_stats": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int32]),

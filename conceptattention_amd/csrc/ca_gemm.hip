@@ -1325,11 +1325,8 @@ int launch_thin_mf(const GemmLaunch &L, int groups, hipStream_t stream) {
   return CA_OK;
 }
 
-int launch_thin(const GemmLaunch &L, hipStream_t stream) {
-  // (diagnostic builds, TIMING ONLY: CA_GEMM_KO_THIN=1 skips every thin-row launch -- wrong results; the ceiling of
-  // anything that could still be done about those rows, tools/env_ab.py)
-  static const int ko = ca_ab_env("CA_GEMM_KO_THIN", 0);
-  if (ko) return CA_OK;
+// Form of the thin-row launch: MF x 16 rows and NW waves per workgroup, `groups` grid rows.  Part of plan_gemm.
+void pick_thin(const GemmLaunch &L, int *mf, int *nw, int *groups) {
   int rows = 1;  // rows of the longest thin part
   bool heads = false;   // the fused QK-norm + RoPE epilogue needs a head's 128 columns in one workgroup
   for (int i = 0; i < CA_GEMM_MAX_PROBLEMS; ++i)
@@ -1343,9 +1340,18 @@ int launch_thin(const GemmLaunch &L, hipStream_t stream) {
   // ... where the launch is short of workgroups (N / 128 <= 256), not for the modulation GEMM's million columns
   static const int narrow_env = ca_ab_env("CA_GEMM_THIN_NARROW", 1);
   const bool narrow = narrow_env && !heads && L.thin_nt[0] + L.thin_nt[1] <= 256;
-  if (rows <= 32) return narrow ? launch_thin_mf<2, 1>(L, 1, stream) : launch_thin_mf<2, 4>(L, 1, stream);
-  if (narrow) return launch_thin_mf<4, 1>(L, (rows + 63) / 64, stream);   // (flux-dev's 5 x 8 concept rows)
-  return launch_thin_mf<4, 4>(L, (rows + 63) / 64, stream);
+  *mf = rows <= 32 ? 2 : 4;   // (flux-dev's 5 x 8 concept rows: 4)
+  *nw = narrow ? 1 : 4;
+  *groups = rows <= 32 ? 1 : (rows + 63) / 64;
+}
+
+int launch_thin(const GemmLaunch &L, int mf, int nw, int groups, hipStream_t stream) {
+  // (diagnostic builds, TIMING ONLY: CA_GEMM_KO_THIN=1 skips every thin-row launch -- wrong results; the ceiling of
+  // anything that could still be done about those rows, tools/env_ab.py)
+  static const int ko = ca_ab_env("CA_GEMM_KO_THIN", 0);
+  if (ko) return CA_OK;
+  if (mf == 2) return nw == 1 ? launch_thin_mf<2, 1>(L, groups, stream) : launch_thin_mf<2, 4>(L, groups, stream);
+  return nw == 1 ? launch_thin_mf<4, 1>(L, groups, stream) : launch_thin_mf<4, 4>(L, groups, stream);
 }
 
 template <int NL, int NHI, bool FP8 = false>
@@ -1443,8 +1449,8 @@ bool thin_kernel_enabled() {   // CA_GEMM_THIN_KERNEL=0: thin rows stay 256-colu
 
 // Pick the tile that minimises (rounds over the CUs) x (time of one round).  Round times are
 // per 48 K-steps, measured on MI355X (tools/bench_kernels.py): they only need to rank the choices.
-int auto_tile(const ca_gemm_problem *p, int n) {
-  const int n_cu = ca_cu_count() > 0 ? ca_cu_count() : 256;
+int auto_tile(const ca_gemm_problem *p, int n, int cus) {
+  const int n_cu = cus > 0 ? cus : 256;
   static const struct { int tile; double round_us; } cands[] = {
       {CA_TILE_PP_256x256, 80.0}, {CA_TILE_PP_256x192, 70.5}, {CA_TILE_PP_256x128, 51.0}, {CA_TILE_256x64, 35.0}};
   int best = 0;
@@ -1508,7 +1514,7 @@ extern "C" int ca_gemm_auto_tile(const ca_gemm_problem *problems, int32_t n_prob
     ca_set_error("ca_gemm_auto_tile: n_problems=%d out of range", n_problems);
     return CA_ERR_ARG;
   }
-  const int t = auto_tile(problems, n_problems);
+  const int t = auto_tile(problems, n_problems, ca_cu_count());
   if (!t) {
     ca_set_error("ca_gemm_auto_tile: no tile width divides N (need N %% 64 == 0)");
     return CA_ERR_ARG;
@@ -1518,9 +1524,22 @@ extern "C" int ca_gemm_auto_tile(const ca_gemm_problem *problems, int32_t n_prob
 
 namespace {
 
-// shared argument checking + launch of ca_gemm_bf16 / ca_gemm_fp8 (FN = the entry point's name for messages)
-int gemm_impl(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile, ca_stream_t stream, bool fp8,
-              const char *FN) {
+// The launch plan of one ca_gemm_bf16 / ca_gemm_fp8 call: the GemmLaunch, the tile kernel and its grid, the thin-row
+// launch.  ONE function for the launch (gemm_impl) and for the query (ca_gemm_plan), so that what the query reports is
+// what the launch does.
+struct GemmPlan {
+  GemmLaunch L;
+  int tile;      // CA_TILE_* (AUTO resolved)
+  int kernel;    // CA_GEMM_KERNEL_*: the tile kernel, NONE when every tile is a thin-row tile
+  int total;     // tiles of the tile kernel's walk
+  int grid;      // its workgroups (0: no tile launch)
+  int thin_mf, thin_nw, thin_groups, thin_grid_x;   // the thin-row launch, 0: none
+};
+
+// shared argument checking + planning of ca_gemm_bf16 / ca_gemm_fp8 / ca_gemm_plan (FN = the entry point's name for
+// messages; n_cu = the CUs of the device, <= 0 if unknown)
+int plan_gemm(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile, bool fp8, int n_cu, const char *FN,
+              GemmPlan *out) {
   if (!problems || n_problems < 1 || n_problems > CA_GEMM_MAX_PROBLEMS) {
     ca_set_error("%s: n_problems=%d out of range [1,%d]", FN, n_problems, CA_GEMM_MAX_PROBLEMS);
     return CA_ERR_ARG;
@@ -1532,14 +1551,15 @@ int gemm_impl(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile,
     }
     tile = CA_TILE_PP_256x256;
   }
-  if (tile == CA_TILE_AUTO) tile = auto_tile(problems, n_problems);
+  if (tile == CA_TILE_AUTO) tile = auto_tile(problems, n_problems, n_cu);
   const int bn = tile_n_of(tile);
   const int kq = fp8 ? 128 : 64, ldq = fp8 ? 16 : 8, es = fp8 ? 1 : 2;
   if (!bn) {
     ca_set_error("%s: no tile configuration fits (tile=%d)", FN, tile);
     return CA_ERR_ARG;
   }
-  GemmLaunch L = {};
+  *out = GemmPlan{};
+  GemmLaunch &L = out->L;
   int total = 0;
   for (int i = 0; i < n_problems; ++i) {
     const ca_gemm_problem &p = problems[i];
@@ -1633,7 +1653,6 @@ int gemm_impl(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile,
   // owning one eighth of the order each: all of them stream the same group of A rows at a time (CA_GEMM_XCD_INTERLEAVE=0:
   // rounds 1-3's contiguous ranges)
   static const int xil_env = ca_ab_env("CA_GEMM_XCD_INTERLEAVE", 1);
-  const int n_cu = ca_cu_count();
   // (the order's "round" is 256 tiles = 32 per XCD, which is what runs together only on a 256-CU part: elsewhere the
   // contiguous ranges, whose mapping does not assume a grid size)
   const int xil = xil_env && n_cu == 256;
@@ -1669,7 +1688,6 @@ int gemm_impl(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile,
   }
   const bool pp_tile = fp8 || tile == CA_TILE_PP_256x256 || tile == CA_TILE_PP_256x192 || tile == CA_TILE_PP_256x128;
   if (pp_tile) total = total_pp;  // (the simple kernel keeps every row tile)
-  hipStream_t s = (hipStream_t)stream;
   {  // persistent walk of the tiles when there is more than one round of them (CA_GEMM_PERSIST=0 disables)
     static const int persist_env = ca_ab_env("CA_GEMM_PERSIST", 1);
     const int n = n_cu;
@@ -1678,15 +1696,38 @@ int gemm_impl(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile,
       L.persist_tiles_grid = n;
     }
   }
+  out->tile = fp8 ? CA_TILE_PP_256x256 : tile;
+  out->total = total;
+  // (only the ping-pong kernel walks persistently: the classic kernel runs one workgroup per tile whatever
+  // persist_tiles says)
+  out->kernel = fp8 ? CA_GEMM_KERNEL_PP_FP8 : pp_tile ? CA_GEMM_KERNEL_PP : CA_GEMM_KERNEL_CLASSIC;
+  out->grid = (pp_tile && L.persist_tiles > 0) ? min(total, L.persist_tiles_grid) : total;
+  if (!fp8 && tile == CA_TILE_PP_256x256 && L.thin_nt[0] + L.thin_nt[1] > 0) {
+    if (total == 0) out->kernel = CA_GEMM_KERNEL_NONE;
+    pick_thin(L, &out->thin_mf, &out->thin_nw, &out->thin_groups);
+    out->thin_grid_x = (L.thin_nt[0] + L.thin_nt[1]) * (4 / out->thin_nw);
+  }
+  return CA_OK;
+}
+
+// shared argument checking + launch of ca_gemm_bf16 / ca_gemm_fp8 (FN = the entry point's name for messages)
+int gemm_impl(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile, ca_stream_t stream, bool fp8,
+              const char *FN) {
+  GemmPlan P;
+  const int rc = plan_gemm(problems, n_problems, tile, fp8, ca_cu_count(), FN, &P);
+  if (rc != CA_OK) return rc;
+  const GemmLaunch &L = P.L;
+  const int total = P.total;
+  hipStream_t s = (hipStream_t)stream;
   if (fp8) return launch_pp<2, 2, true>(L, total, s);
-  if (tile == CA_TILE_PP_256x256 && L.thin_nt[0] + L.thin_nt[1] > 0) {
+  if (P.thin_mf) {
     if (total > 0) {
       const int rc = launch_pp<2, 2>(L, total, s);
       if (rc != CA_OK) return rc;
     }
-    return launch_thin(L, s);
+    return launch_thin(L, P.thin_mf, P.thin_nw, P.thin_groups, s);
   }
-  switch (tile) {
+  switch (P.tile) {
     case CA_TILE_PP_256x256: return launch_pp<2, 2>(L, total, s);
     case CA_TILE_PP_256x192: return launch_pp<2, 1>(L, total, s);
     case CA_TILE_PP_256x128: return launch_pp<1, 1>(L, total, s);
@@ -1706,6 +1747,30 @@ extern "C" int ca_gemm_bf16(const ca_gemm_problem *problems, int32_t n_problems,
 
 extern "C" int ca_gemm_fp8(const ca_gemm_problem *problems, int32_t n_problems, ca_stream_t stream) {
   return gemm_impl(problems, n_problems, CA_TILE_PP_256x256, stream, true, "ca_gemm_fp8");
+}
+
+extern "C" int ca_gemm_plan(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile, int32_t fp8, int32_t n_cu,
+                            ca_gemm_plan_info *out) {
+  if (!out || n_cu < 0 || (fp8 != 0 && fp8 != 1)) {
+    ca_set_error("ca_gemm_plan: need out != NULL, n_cu >= 0 and fp8 in {0, 1} (n_cu=%d fp8=%d)", n_cu, fp8);
+    return CA_ERR_ARG;
+  }
+  *out = ca_gemm_plan_info{};
+  GemmPlan P;
+  const int rc = plan_gemm(problems, n_problems, tile, fp8 != 0, n_cu ? n_cu : ca_cu_count(), "ca_gemm_plan", &P);
+  if (rc != CA_OK) return rc;
+  out->tile = P.tile;
+  out->kernel = P.kernel;
+  out->grid = P.kernel == CA_GEMM_KERNEL_NONE ? 0 : P.grid;
+  out->persistent = P.kernel != CA_GEMM_KERNEL_NONE && P.grid < P.total;
+  out->main_tiles = P.kernel == CA_GEMM_KERNEL_CLASSIC ? P.total : P.L.main_total;
+  out->thin_tiles = P.kernel == CA_GEMM_KERNEL_CLASSIC ? 0 : P.L.nthin[0] + P.L.nthin[1];
+  out->thin_mf = P.thin_mf;
+  out->thin_nw = P.thin_nw;
+  out->thin_groups = P.thin_groups;
+  out->thin_grid_x = P.thin_grid_x;
+  out->n_cu = n_cu ? n_cu : ca_cu_count();
+  return CA_OK;
 }
 
 #ifdef CA_GEMM_STAMP

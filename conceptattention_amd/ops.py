@@ -6,6 +6,7 @@ library for shapes/alignment (ValueError on a rejected argument, nothing is laun
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -77,8 +78,8 @@ class Gemm:
     gate2_item_rows: int = 0
 
 
-def gemm(problems: Sequence[Gemm], tile: int = L.TILE_AUTO) -> None:
-    lib = L.load()
+def _gemm_problems(problems: Sequence[Gemm]):
+    """The ca_gemm_problem array of a grouped launch and whether its operands are fp8."""
     arr = (L.GemmProblem * len(problems))()
     fp8 = problems[0].a.dtype == torch.uint8
     op_dtype = torch.uint8 if fp8 else torch.bfloat16
@@ -135,6 +136,12 @@ def gemm(problems: Sequence[Gemm], tile: int = L.TILE_AUTO) -> None:
             if g.out2 is None:
                 raise ValueError(f"gemm[{i}]: SPLIT_GELU needs out2")
             p.out2, p.ld2, p.n_split = _chk(g.out2, torch.bfloat16, "out2").data_ptr(), g.out2.stride(0), g.n_split
+    return arr, fp8
+
+
+def gemm(problems: Sequence[Gemm], tile: int = L.TILE_AUTO) -> None:
+    lib = L.load()
+    arr, fp8 = _gemm_problems(problems)
     if fp8:
         if tile not in (L.TILE_AUTO, L.TILE_PP_256x256):
             raise ValueError("gemm: fp8 operands run on the 256x256 ping-pong tile only")
@@ -152,6 +159,24 @@ def gemm(problems: Sequence[Gemm], tile: int = L.TILE_AUTO) -> None:
         _gemm_hook(arr, tile, lambda: L.check(lib.ca_gemm_bf16(arr, len(problems), tile, _stream()), "ca_gemm_bf16"))
         return
     L.check(lib.ca_gemm_bf16(arr, len(problems), tile, _stream()), "ca_gemm_bf16")
+
+
+def gemm_plan(problems, tile: int = L.TILE_AUTO, n_cu: int = 0, fp8: Optional[bool] = None) -> dict:
+    """What ``gemm(problems, tile)`` would launch on a device with ``n_cu`` CUs (0: the current device's), as a dict of
+    ca_gemm_plan_info's fields; nothing is launched.  ``problems``: Gemm problems (fp8 from their dtype), or a ctypes
+    array of L.GemmProblem together with ``fp8`` (no tensors, no GPU needed when n_cu > 0).  ValueError where the
+    launch would reject the arguments."""
+    lib = L.load()
+    if isinstance(problems, C.Array):
+        arr = problems
+        if fp8 is None:
+            raise ValueError("gemm_plan: a raw problem array needs fp8=True / False")
+    else:
+        arr, dt_fp8 = _gemm_problems(problems)
+        fp8 = dt_fp8 if fp8 is None else fp8
+    info = L.GemmPlanInfo()
+    L.check(lib.ca_gemm_plan(arr, len(arr), tile, int(bool(fp8)), n_cu, C.byref(info)), "ca_gemm_plan")
+    return {name: getattr(info, name) for name, _ in L.GemmPlanInfo._fields_ if not name.startswith("_")}
 
 
 # Optional instrumentation used by bench.py: hook(problem_array, tile, launch) must call launch().

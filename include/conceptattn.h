@@ -28,9 +28,9 @@
 extern "C" {
 #endif
 
-#define CA_VERSION 125 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
+#define CA_VERSION 126 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
                           CA_ATTN_Q_PRESCALED; .1: ca_axpy_f32, ca_split_bf16; .2: ca_attn_stats; .3: ca_gemm_problem.qk_f16,
-                          ca_attn_fwd_qk16; .4: ca_qpre_finish_rope_f32; .5: ca_heatmap_fused */
+                          ca_attn_fwd_qk16; .4: ca_qpre_finish_rope_f32; .5: ca_heatmap_fused; .6: ca_gemm_plan */
 
 #define CA_OK 0
 #define CA_ERR_ARG (-1)    /* bad shape / null pointer / misalignment */
@@ -138,6 +138,33 @@ int ca_gemm_auto_tile(const ca_gemm_problem *problems, int32_t n_problems);
  * block scales), out/resid/bias/gates stay bf16/fp32 as above.  256x256 ping-pong tile only (N % 256 == 0).
  */
 int ca_gemm_fp8(const ca_gemm_problem *problems, int32_t n_problems, ca_stream_t stream);
+
+/* The launch plan of ca_gemm_bf16 (fp8 = 0, `tile` as there) or ca_gemm_fp8 (fp8 = 1, tile AUTO or PP_256x256) for
+ * these problems on a device with n_cu CUs (0 = the current device's, as the launch uses): which kernels run, on which
+ * grids.  Same argument checks and return codes as the launch (the pointers are checked, never dereferenced); no
+ * launch, and no GPU needed when n_cu > 0.  The launch itself plans through the same code. */
+enum { CA_GEMM_KERNEL_NONE = 0,     /* no tile launch: every tile is a thin-row tile */
+       CA_GEMM_KERNEL_CLASSIC = 1,  /* ca_gemm_kernel, one workgroup per tile (the CA_TILE_256x* tiles) */
+       CA_GEMM_KERNEL_PP = 2,       /* the bf16 ping-pong kernel (the CA_TILE_PP_* tiles) */
+       CA_GEMM_KERNEL_PP_FP8 = 3 }; /* its fp8 instantiation */
+
+typedef struct {
+  int32_t tile;        /* CA_TILE_* of the launch (AUTO resolved) */
+  int32_t kernel;      /* CA_GEMM_KERNEL_* */
+  int32_t grid;        /* workgroups of the tile launch (0: none) */
+  int32_t persistent;  /* 1: those workgroups walk main_tiles + thin_tiles tiles with a stride of the grid */
+  int32_t main_tiles;  /* full-K-loop tiles of the tile launch */
+  int32_t thin_tiles;  /* thin last-row tiles walked by the tile launch (at its end, the thin copy of the K loop) */
+  int32_t thin_mf;     /* thin-row kernel launched behind it: 16-row fragments per workgroup (2 or 4), 0 = none */
+  int32_t thin_nw;     /* its waves per workgroup (1 or 4) */
+  int32_t thin_groups; /* its grid rows (grid y) */
+  int32_t thin_grid_x; /* its grid columns */
+  int32_t n_cu;        /* the CU count the plan was made for (-1: unknown, no persistent walk) */
+  int32_t _pad;
+} ca_gemm_plan_info;
+
+int ca_gemm_plan(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile, int32_t fp8, int32_t n_cu,
+                 ca_gemm_plan_info *out);
 
 /* ------------------------------------------------------------------------------------------
  * Flash attention forward, head_dim 128, no mask:  out = softmax(q k^T * scale) v  per head.

@@ -69,6 +69,16 @@ def test_binding_fields_match_header_field_for_field():
     assert [_CT[t] for t, _ in hdr] == [t for _, t in L.GemmProblem._fields_]
 
 
+def test_gemm_plan_info_fields_match_header():
+    hdr = _header_struct_fields("ca_gemm_plan_info")
+    assert [f for _, f in hdr] == [f for f, _ in L.GemmPlanInfo._fields_]
+    assert [_CT[t] for t, _ in hdr] == [t for _, t in L.GemmPlanInfo._fields_]
+    text = open(os.path.join(ROOT, "include", "conceptattn.h")).read()
+    kernels = dict((k, int(v)) for k, v in re.findall(r"CA_GEMM_KERNEL_(\w+) = (\d+)", text))
+    assert kernels == {"NONE": L.GEMM_KERNEL_NONE, "CLASSIC": L.GEMM_KERNEL_CLASSIC, "PP": L.GEMM_KERNEL_PP,
+                       "PP_FP8": L.GEMM_KERNEL_PP_FP8}
+
+
 def test_attn_problem_fields_match_header():
     hdr = _header_struct_fields("ca_attn_problem")
     assert [f for _, f in hdr] == [f for f, _ in L.AttnProblem._fields_]

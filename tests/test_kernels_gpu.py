@@ -130,7 +130,9 @@ def test_gemm_qkv_norm_rope_epilogue(tail):
         close(out2.cpu(), torch.nn.functional.gelu(lin[:, 3 * Hd:], approximate="tanh"), atol=2e-2)
     # fp32 pre-RoPE q (the cross-attention-space vectors without their bf16 rounding) and the rotated q pre-multiplied
     # by softmax_scale * log2(e) in fp32 before its one rounding; k, v and the bf16 form of q_prerope unchanged.
-    # M = 300 = one full row tile + 44 rows: both the ping-pong and the thin-row kernel's epilogue are exercised.
+    # (M = 300 = one full row tile + 44 thin rows: on a 256-CU part at most 5 + 5 tiles, so the thin rows ride at the
+    # end of the ping-pong walk and only the ping-pong kernel's epilogue runs; the thin-row kernel's forms are pinned
+    # route by route in tests/test_gemm_routes_gpu.py.)
     qs = 0.088388347648 * 1.4426950408889634
     out_s = torch.zeros_like(out)
     pre32 = torch.zeros(M, Hd, device=DEV, dtype=torch.float32)
@@ -146,16 +148,36 @@ def test_gemm_qkv_norm_rope_epilogue(tail):
                            out2=out2 if tail else None)], L.TILE_PP_256x128)
 
 
+def tile_w(tile):
+    return {L.TILE_PP_256x256: 256, L.TILE_PP_256x192: 192, L.TILE_PP_256x128: 128}[tile]
+
+
 @pytest.mark.parametrize("tile,N", [(L.TILE_PP_256x256, 768), (L.TILE_PP_256x192, 384), (L.TILE_PP_256x128, 256)])
 @pytest.mark.parametrize("rem", [1, 20, 32, 44, 128])
 def test_gemm_thin_last_row_tile_is_bit_identical(tile, N, rem):
-    """A last row tile with few valid rows (<= 128) leaves the ordinary tile walk: under the bf16 256x256 tile it goes
-    to the thin-row kernel (32 x 128 tiles, its own launch), otherwise it takes a copy of the ping-pong K loop
-    without the MFMAs and LDS reads of row fragments past M and is walked last.  Its rows must come out bit for bit as when the same rows sit in a FULL row tile of a longer
-    problem, for every epilogue -- the k order per accumulator is the contract."""
+    """A last row tile with few valid rows (<= 128) leaves the ordinary tile walk: it takes a copy of the ping-pong K
+    loop without the MFMAs and LDS reads of row fragments past M and is walked last (N as given: its tiles fit into
+    the CUs the main tiles leave idle in their last round), or, under the bf16 256x256 tile when they do not (N widened
+    to more column tiles than half the device's CUs, so that the main and the thin tiles do not fit into one round),
+    it goes to the thin-row kernel (32 x 128 tiles, its own launch).  Which one ran is asserted through the launch plan.  Its rows
+    must come out bit for bit as when the same rows sit in a FULL row tile of a longer problem, for every epilogue --
+    the k order per accumulator is the contract."""
+    _thin_bit_identity(tile, N, rem, "walk")
+    if tile == L.TILE_PP_256x256:
+        n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+        _thin_bit_identity(tile, 768 * (n_cu // 6 + 1), rem, "kernel")   # (256 CUs: 129 column tiles, N = 33024)
+
+
+def _thin_bit_identity(tile, N, rem, route):
     K, Mfull = 448, 512
     a, w, b = rnd(Mfull, K), rnd(N, K, scale=0.1), rnd(N)
     M = 256 + rem
+    info = ops.gemm_plan([ops.Gemm(a[:M], w, b, torch.empty(M, N, device=DEV, dtype=torch.bfloat16))], tile)
+    if route == "walk":
+        assert info["thin_tiles"] == N // tile_w(tile) and info["thin_mf"] == 0, info
+    else:   # (32 x 128 tiles of one wave while the launch has at most 256 of them, else of four)
+        assert info["thin_tiles"] == 0 and info["main_tiles"] == N // 256, info
+        assert (info["thin_mf"], info["thin_nw"]) == (2 if rem <= 32 else 4, 4 if N // 128 > 256 else 1), info
     for epi in (L.EPI_BIAS, L.EPI_GELU_TANH):
         full = ops.linear(a, w, b, epilogue=epi, tile=tile)
         thin = ops.linear(a[:M], w, b, epilogue=epi, tile=tile)
