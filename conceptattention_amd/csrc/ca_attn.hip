@@ -25,9 +25,6 @@
 
 #include "ca_common.h"
 #include "ca_attn_common.h"
-#ifndef CA_ATTN_KPF
-#define CA_ATTN_KPF 4
-#endif
 
 namespace {
 using namespace ca_attn_detail;
@@ -40,10 +37,7 @@ __device__ __forceinline__ bf16x8 pack8(const f32x16 &s, int base) {
 }
 
 // NW = waves per workgroup: 8 (256 query rows, 1 workgroup per CU) or 4 (128 rows, 2 per CU).
-// PRE = the q rows already carry softmax_scale * log2(e) (CA_ATTN_Q_PRESCALED): a tile's scores then leave the
-// K Q^T chain as s - reference (the chain's first MFMA takes a register block holding -reference as its C operand),
-// so a probability is ONE v_exp_f32 per score: no multiply, no subtract.
-template <int NW, bool PRE = false>
+template <int NW>
 __global__ __launch_bounds__(NW * 64, 2) void ca_attn_kernel(const AttnLaunch L) {
   extern __shared__ __attribute__((aligned(256))) char smem[];
   const int tid = threadIdx.x;
@@ -148,10 +142,7 @@ __global__ __launch_bounds__(NW * 64, 2) void ca_attn_kernel(const AttnLaunch L)
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
   float m_run = -1e30f, l_run = 0.f;
-  const float sl2 = PRE ? 1.0f : L.scale_log2;
-  f32x16 negm;   // PRE: every register = -m_run of this lane's query row (rewritten only when the reference moves)
-#pragma unroll
-  for (int r = 0; r < 16; ++r) negm[r] = 0.f;
+  const float sl2 = L.scale_log2;
 
   const int nt = (nkeys + KV_TILE - 1) / KV_TILE;
   stage_tile(0, 0);
@@ -181,25 +172,18 @@ __global__ __launch_bounds__(NW * 64, 2) void ca_attn_kernel(const AttnLaunch L)
     // added to l or O^T at that point, so everything at the old reference is rescaled exactly once.
     f32x16 s[2];
     float rs = 0.f;
-    // K Q^T of the tile; CINIT = the accumulators start from `negm` (PRE fast pass) instead of zero
-    auto qk = [&](auto cinit_tag) {
-      constexpr bool CINIT = decltype(cinit_tag)::value;
+    // K Q^T of the tile
+    auto qk = [&]() {
       asm volatile("" ::: "memory");  // the K fragments are re-read per pass (hoisted, they would pin 64 VGPRs)
       // K fragments PF MFMAs ahead of their use: an LDS read takes 2-4 MFMA slots to come back, and left to itself
       // hipcc sinks every read to its MFMA (one fragment register, lgkmcnt(0) before each MFMA) to save registers.
       // sched_barrier(0) pins the order; the wait counts are still the compiler's.
-      constexpr int PF = CA_ATTN_KPF;
+      constexpr int PF = 4;
       bf16x8 kq[PF];
 #pragma unroll
       for (int i = 0; i < PF; ++i) kq[i] = *(const bf16x8 *)(kbuf + (i >> 3) * 8192 + (k_lane ^ ((i & 7) << 5)));
-      if constexpr (CINIT) {
-        asm volatile("" : "+v"(negm));  // opaque: hipcc must keep the block in registers, not re-splat it per tile
-        s[0] = negm;
-        s[1] = negm;
-      } else {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) s[0][r] = s[1][r] = 0.f;
-      }
+      for (int r = 0; r < 16; ++r) s[0][r] = s[1][r] = 0.f;
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
@@ -220,60 +204,39 @@ __global__ __launch_bounds__(NW * 64, 2) void ca_attn_kernel(const AttnLaunch L)
           }
       }
     };
-    bool done = false;
-    if constexpr (PRE && !FIRST) {
-      // fast pass: scores arrive as s - reference, a probability is one v_exp_f32
-      qk(std::true_type{});
+    bool with_max = FIRST;
+#pragma nounroll
+    for (;;) {
+      qk();
+      if (with_max) {  // wave-uniform
+        // this lane: query row ql, 32 of the tile's 64 keys; lane^32 has the rest
+        float mx = s[0][0];
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kb][r]);
+        mx = fmaxf(mx, __shfl_xor(mx, 32)) * sl2;
+        const float m_new = fmaxf(m_run, mx);
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+        m_run = m_new;
+        l_run *= alpha;
+#pragma unroll
+        for (int db = 0; db < 4; ++db)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
+      }
       rs = 0.f;
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float p = __builtin_amdgcn_exp2f(s[kb][r]);
+          const float p = __builtin_amdgcn_exp2f(fmaf(s[kb][r], sl2, -m_run));
           s[kb][r] = p;
           rs += p;
         }
-      done = __builtin_amdgcn_ballot_w64(!(rs <= REDO_LIMIT)) == 0;
-    }
-    if (!done) {
-      bool with_max = FIRST || PRE;   // (PRE: this block is the first tile or a redo, both with the maximum)
-#pragma nounroll
-      for (;;) {
-        qk(std::false_type{});
-        if (with_max) {  // wave-uniform
-          // this lane: query row ql, 32 of the tile's 64 keys; lane^32 has the rest
-          float mx = s[0][0];
-#pragma unroll
-          for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kb][r]);
-          mx = fmaxf(mx, __shfl_xor(mx, 32)) * sl2;
-          const float m_new = fmaxf(m_run, mx);
-          const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-          m_run = m_new;
-          l_run *= alpha;
-#pragma unroll
-          for (int db = 0; db < 4; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
-          if constexpr (PRE) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) negm[r] = -m_run;
-          }
-        }
-        rs = 0.f;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float p = __builtin_amdgcn_exp2f(PRE ? s[kb][r] - m_run : fmaf(s[kb][r], sl2, -m_run));
-            s[kb][r] = p;
-            rs += p;
-          }
-        // (a row whose keys are all masked so far has m_run = -1e30 and rs = 0: not > the limit; inf compares true)
-        if (with_max || __builtin_amdgcn_ballot_w64(!(rs <= REDO_LIMIT)) == 0) break;
-        with_max = true;
-      }
+      // (a row whose keys are all masked so far has m_run = -1e30 and rs = 0: not > the limit; inf compares true)
+      if (with_max || __builtin_amdgcn_ballot_w64(!(rs <= REDO_LIMIT)) == 0) break;
+      with_max = true;
     }
     l_run += rs;
     // ---- O^T[d][q] += sum_key V[key][d] P[q][key]; P^T fragments straight from the S^T registers
@@ -394,18 +357,13 @@ static int ca_attn_fwd_impl(const ca_attn_problem *problems, int32_t n_problems,
   // (The 128-row, 4-wave form of rounds 1-4 -- slower, and its pre-scaled instantiation spilled -- is gone.)
   constexpr int nw = 8;
   // pre-scaled q (the model path): the one-wave-per-SIMD kernel (ca_attn4.hip; 4 waves x 64 rows = 256 rows per workgroup
-  // as well, same numerics contract).  Every call that passes a scale runs on the two-waves-per-SIMD kernel below
-  // (diagnostic builds: CA_ATTN_KERNEL=8 sends pre-scaled q there too).
-  static const bool want4 = ca_ab_env("CA_ATTN_KERNEL", 4) != 8;
-  const bool use4 = (pre && want4) || qk_f16;   // (half-precision q / k exist in the one-wave-per-SIMD kernel only)
+  // as well, same numerics contract).  Every call that passes a scale runs on the two-waves-per-SIMD kernel below.
+  const bool use4 = pre || qk_f16;   // (half-precision q / k exist in the one-wave-per-SIMD kernel only)
   const int qrows = use4 ? 256 : nw * 32;
   AttnLaunch L = {};
   L.num_heads = num_heads;
   L.n_problems = n_problems;
   L.scale_log2 = scale * 1.4426950408889634f;
-  static const bool no_reref = ca_ab_env("CA_ATTN_REREF", 1) == 0;      // (diagnostic builds: tools/attn_peaky.py)
-  static const bool limit60 = ca_ab_env("CA_ATTN_LIMIT60", 0) == 1;
-  L.flags = (no_reref ? 1 : 0) | (limit60 ? 2 : 0);
   const int hx = (num_heads + 7) / 8;  // heads per XCD group
   int total = 0;
   for (int i = 0; i < n_problems; ++i) {
@@ -467,19 +425,15 @@ static int ca_attn_fwd_impl(const ca_attn_problem *problems, int32_t n_problems,
   static std::atomic<unsigned long long> attr_done{0};  // one bit per device: the attribute is per device
   const unsigned long long dev_bit = ca_device_bit();
   if (!(attr_done.load(std::memory_order_acquire) & dev_bit)) {
-    hipError_t e = hipSuccess;
-    for (const void *fn : {(const void *)ca_attn_kernel<8>, (const void *)ca_attn_kernel<8, true>})
-      if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_LDS);
+    const hipError_t e = hipFuncSetAttribute((const void *)ca_attn_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             ATTN_LDS);
     if (e != hipSuccess) {
       ca_set_error("ca_attn_fwd_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
       return CA_ERR_LAUNCH;
     }
     attr_done.fetch_or(dev_bit, std::memory_order_release);  // idempotent: a race only repeats the call
   }
-  if (pre)
-    hipLaunchKernelGGL((ca_attn_kernel<8, true>), dim3(total), dim3(512), ATTN_LDS, (hipStream_t)stream, L);
-  else
-    hipLaunchKernelGGL((ca_attn_kernel<8, false>), dim3(total), dim3(512), ATTN_LDS, (hipStream_t)stream, L);
+  hipLaunchKernelGGL(ca_attn_kernel<8>, dim3(total), dim3(512), ATTN_LDS, (hipStream_t)stream, L);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     ca_set_error("ca_attn_fwd_bf16: launch failed: %s", hipGetErrorString(e));

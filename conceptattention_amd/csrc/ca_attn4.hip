@@ -53,7 +53,6 @@ constexpr int DUMP_OFF = FLAG_OFF + 1024;                  // 16 KiB nobody read
 constexpr int LDS_BYTES = DUMP_OFF + TILE_BYTES;
 constexpr float L_LIMIT = 1267650600228229401496703205376.0f;   // 2^100: a finite row sum below this is exact enough to
                                                                 // divide by (O <= l max|v| stays far from fp32's 2^128)
-constexpr float L_LIMIT_R3 = 1152921504606846976.0f;       // 2^60: round 3's limit (CA_ATTN_LIMIT60=1, an A/B aid for tools/attn_peaky.py)
 constexpr float REREF_ABOVE = 18446744073709551616.0f;     // 2^64: running row sum that triggers the in-place re-reference
                                                            // (36 octaves of headroom per three tiles up to L_LIMIT; measured
                                                            // with 2^20: 1.7 / 7.7 events per wave at logit std 8 / 16 nats cost
@@ -65,13 +64,6 @@ constexpr float REREF_ABOVE = 18446744073709551616.0f;     // 2^64: running row 
 __device__ unsigned long long ca_attn4_counters[2];
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-#ifdef CA_A4_STAMP   // diagnostic build only (tools/stamp_attn4.py): cycles per loop segment, per workgroup and wave
-__device__ unsigned long long ca_a4_dbg[4 * 4 * 4096];
-#define CA_A4_T(x) do { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(x) :: "memory"); } while (0)
-#else
-#define CA_A4_T(x) do { } while (0)
-#endif
 
 #define CA_A4_KERNEL ca_attn4_kernel
 #define CA_A4_QK_T "bf16"
@@ -90,12 +82,6 @@ __device__ unsigned long long ca_a4_dbg[4 * 4 * 4096];
 #undef CA_A4_QK_T
 
 }  // namespace
-
-#ifdef CA_A4_STAMP
-extern "C" int ca_debug_read_attn4(unsigned long long *out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(ca_a4_dbg), sizeof(unsigned long long) * 4 * 4 * 4096);
-}
-#endif
 
 int ca_attn4_read_counters(unsigned long long *out, int reset) {
   hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(ca_attn4_counters), 2 * sizeof(unsigned long long));
@@ -123,13 +109,11 @@ int ca_attn4_launch(const AttnLaunch &L, int total, bool qk_f16, hipStream_t str
     }
     attr_done.fetch_or(dev_bit, std::memory_order_release);
   }
-  // more units than CUs: one workgroup per CU walks them (no workgroup dispatch between units; CA_ATTN_PERSIST=0: one
-  // workgroup per unit, round 3's launch)
-  static const bool persist = ca_ab_env("CA_ATTN_PERSIST", 1) != 0;
+  // more units than CUs: one workgroup per CU walks them (no workgroup dispatch between units)
   const int n_cu = ca_cu_count();
   AttnLaunch LL = L;
   LL.total_units = total;
-  const int grid = (persist && n_cu > 0 && n_cu % 8 == 0 && total > n_cu) ? n_cu : total;
+  const int grid = (n_cu > 0 && n_cu % 8 == 0 && total > n_cu) ? n_cu : total;
   if (qk_f16)
     hipLaunchKernelGGL(ca_attn4_qk16_kernel, dim3(grid), dim3(256), a4::LDS_BYTES, stream, LL);
   else

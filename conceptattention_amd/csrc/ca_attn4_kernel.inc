@@ -141,19 +141,14 @@ __global__ __launch_bounds__(256, 1) void CA_A4_KERNEL(const AttnLaunch L) {
   } while (0)
 #define CA_A4_ADVANCE() do { SOK += tile_step; SOV += tile_step; } while (0)
   // one compare per three tiles: has any partial row sum of this wave left the comfortable range?
-  const bool reref_on = active && !(L.flags & 1);
-#ifdef CA_A4_NO_REREF   // A/B build only (what the compare and the rare block cost the loop's code generation)
-#define CA_A4_REREF_CHECK() do { } while (0)
-#else
 #define CA_A4_REREF_CHECK()                                                                                            \
   do {                                                                                                                 \
     /* (the sums are >= 0, so their bit patterns order like the values; a NaN's pattern is above every finite one) */ \
-    if (reref_on && __builtin_expect(__builtin_amdgcn_ballot_w64(                                                      \
+    if (active && __builtin_expect(__builtin_amdgcn_ballot_w64(                                                        \
                         max(max(__float_as_int(l0), __float_as_int(l0b)),                                              \
                             max(__float_as_int(l1), __float_as_int(l1b))) > __float_as_int(a4::REREF_ABOVE)) != 0, 0)) \
       rereference();                                                                                                   \
   } while (0)
-#endif
   auto stage_pieces = [&](uint32_t kdst_off, uint32_t vdst_off) {   // the same 8 pieces from a wave that computes nothing
     auto piece = [&](const i32x4 &ds, uint32_t so, uint32_t off, uint32_t dst) {   // (its query rows do not exist)
       asm volatile("s_mov_b32 m0, %3\n\ts_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
@@ -168,16 +163,6 @@ __global__ __launch_bounds__(256, 1) void CA_A4_KERNEL(const AttnLaunch L) {
   auto drain_and_barrier = [&]() {   // this wave's DMA has landed, its LDS reads have returned; then everyone's
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   };
-#ifdef CA_A4_KO_BARRIER2
-  // TIMING-ONLY knock-out (tools/attn4_barrier_knockout.py; the results of such a build are wrong): the tile loop's barrier
-  // on every second tile only -- an upper bound on what a one-barrier-per-two-tiles schedule (4-slot K ring) could gain
-  auto tile_barrier = [&](int tile) {
-    if (tile & 1) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  };
-#else
-  auto tile_barrier = [&](int) { drain_and_barrier(); };
-#endif
 
   // ---- fragment addresses (bytes): K relative to the K ring, V with the V ring's base included
   const uint32_t k_lane = ql * 256 + (((h ^ (ql & 15)) & 15) << 4);
@@ -299,31 +284,6 @@ __global__ __launch_bounds__(256, 1) void CA_A4_KERNEL(const AttnLaunch L) {
 
   drain_and_barrier();
 
-#ifdef CA_A4_PLAIN   // bisecting aid: every tile the plain way (no pipelined stream), same prologue and epilogue
-  if (active) {
-    CA_A4_QK_PLAIN_ZERO(0u);
-    if (nt_full == 0) mask_tail(0);
-    float x0, x1;
-    row_max(x0, x1);
-    set_reference(x0, x1);
-    exp_sum(x0, x1);
-    pack_all();
-    CA_A4_PV_PLAIN(0u);
-  }
-  for (int t = 1; t < nt; ++t) {
-    drain_and_barrier();
-    stage(t, 0, false);
-    stage(t, 0, true);
-    drain_and_barrier();
-    if (active) {
-      CA_A4_QK_PLAIN_NEGM(0u);
-      if (ragged && t == nt - 1) mask_tail(t);
-      exp_sum(0.f, 0.f);
-      pack_all();
-      CA_A4_PV_PLAIN(0u);
-    }
-  }
-#else
   // ---- tile 0 sets the reference (the only tile whose maximum is computed)
   if (active) {
     CA_A4_QK_PLAIN_ZERO(0u);
@@ -354,16 +314,9 @@ __global__ __launch_bounds__(256, 1) void CA_A4_KERNEL(const AttnLaunch L) {
   // iteration are instruction immediates (t % 3), so the loop body is three iterations in a row.
   const int T = nt_full > 0 ? nt_full - 1 : 0;
   if (T > 0 && active) CA_A4_PRELOAD_K0((uint32_t)TILE_BYTES);
-  unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, acc0 = 0, acc1 = 0, acc2 = 0;
-  (void)ts0, (void)ts1, (void)ts2, (void)ts3, (void)acc0, (void)acc1, (void)acc2;
-#ifdef CA_A4_STAMP
-#define CA_A4_ACC() do { acc0 += ts1 - ts0; acc1 += ts2 - ts1; acc2 += ts3 - ts2; } while (0)
-#else
-#define CA_A4_ACC() do { } while (0)
-#endif
   int t = 0;
   while (t + 3 <= T) {
-    { constexpr int R = 0; (void)R; CA_A4_T(ts0); CA_A4_BOOKKEEPING(0); CA_A4_REREF_CHECK(); CA_A4_T(ts1);
+    { constexpr int R = 0; (void)R; CA_A4_BOOKKEEPING(0); CA_A4_REREF_CHECK();
       if (active) {
 #define CA_A4_SCHEDULE
 #include "ca_attn4_sched.inc"
@@ -371,8 +324,8 @@ __global__ __launch_bounds__(256, 1) void CA_A4_KERNEL(const AttnLaunch L) {
       } else {   // a wave whose query rows do not exist: its share of the staging only
         stage_pieces((uint32_t)(0 * TILE_BYTES), (uint32_t)(a4::V_BASE + ((0 + 1) % 3) * TILE_BYTES));
       }
-      CA_A4_ADVANCE(); CA_A4_T(ts2); tile_barrier(t); CA_A4_T(ts3); CA_A4_ACC(); ++t; }
-    { constexpr int R = 1; (void)R; CA_A4_T(ts0); CA_A4_BOOKKEEPING(1); CA_A4_T(ts1);
+      CA_A4_ADVANCE(); drain_and_barrier(); ++t; }
+    { constexpr int R = 1; (void)R; CA_A4_BOOKKEEPING(1);
       if (active) {
 #define CA_A4_SCHEDULE
 #include "ca_attn4_sched.inc"
@@ -380,8 +333,8 @@ __global__ __launch_bounds__(256, 1) void CA_A4_KERNEL(const AttnLaunch L) {
       } else {   // a wave whose query rows do not exist: its share of the staging only
         stage_pieces((uint32_t)(1 * TILE_BYTES), (uint32_t)(a4::V_BASE + ((1 + 1) % 3) * TILE_BYTES));
       }
-      CA_A4_ADVANCE(); CA_A4_T(ts2); tile_barrier(t); CA_A4_T(ts3); CA_A4_ACC(); ++t; }
-    { constexpr int R = 2; (void)R; CA_A4_T(ts0); CA_A4_BOOKKEEPING(2); CA_A4_T(ts1);
+      CA_A4_ADVANCE(); drain_and_barrier(); ++t; }
+    { constexpr int R = 2; (void)R; CA_A4_BOOKKEEPING(2);
       if (active) {
 #define CA_A4_SCHEDULE
 #include "ca_attn4_sched.inc"
@@ -389,10 +342,10 @@ __global__ __launch_bounds__(256, 1) void CA_A4_KERNEL(const AttnLaunch L) {
       } else {   // a wave whose query rows do not exist: its share of the staging only
         stage_pieces((uint32_t)(2 * TILE_BYTES), (uint32_t)(a4::V_BASE + ((2 + 1) % 3) * TILE_BYTES));
       }
-      CA_A4_ADVANCE(); CA_A4_T(ts2); tile_barrier(t); CA_A4_T(ts3); CA_A4_ACC(); ++t; }
+      CA_A4_ADVANCE(); drain_and_barrier(); ++t; }
   }
   if (t < T) {   // (t % 3 == 0 here) one or two iterations left
-    { constexpr int R = 0; (void)R; CA_A4_T(ts0); CA_A4_BOOKKEEPING(0); CA_A4_T(ts1);
+    { constexpr int R = 0; (void)R; CA_A4_BOOKKEEPING(0);
       if (active) {
 #define CA_A4_SCHEDULE
 #include "ca_attn4_sched.inc"
@@ -400,8 +353,8 @@ __global__ __launch_bounds__(256, 1) void CA_A4_KERNEL(const AttnLaunch L) {
       } else {   // a wave whose query rows do not exist: its share of the staging only
         stage_pieces((uint32_t)(0 * TILE_BYTES), (uint32_t)(a4::V_BASE + ((0 + 1) % 3) * TILE_BYTES));
       }
-      CA_A4_ADVANCE(); CA_A4_T(ts2); tile_barrier(t); CA_A4_T(ts3); CA_A4_ACC(); ++t; }
-    if (t < T) { constexpr int R = 1; (void)R; CA_A4_T(ts0); CA_A4_BOOKKEEPING(1); CA_A4_T(ts1);
+      CA_A4_ADVANCE(); drain_and_barrier(); ++t; }
+    if (t < T) { constexpr int R = 1; (void)R; CA_A4_BOOKKEEPING(1);
       if (active) {
 #define CA_A4_SCHEDULE
 #include "ca_attn4_sched.inc"
@@ -409,14 +362,8 @@ __global__ __launch_bounds__(256, 1) void CA_A4_KERNEL(const AttnLaunch L) {
       } else {   // a wave whose query rows do not exist: its share of the staging only
         stage_pieces((uint32_t)(1 * TILE_BYTES), (uint32_t)(a4::V_BASE + ((1 + 1) % 3) * TILE_BYTES));
       }
-      CA_A4_ADVANCE(); CA_A4_T(ts2); tile_barrier(t); CA_A4_T(ts3); CA_A4_ACC(); ++t; }
+      CA_A4_ADVANCE(); drain_and_barrier(); ++t; }
   }
-#ifdef CA_A4_STAMP
-  if (lane == 0 && unit < 4096) {   // (per unit: in the persistent walk a workgroup takes several)
-    unsigned long long *d = ca_a4_dbg + ((size_t)unit * 4 + wave) * 4;
-    d[0] = acc0, d[1] = acc1, d[2] = acc2, d[3] = (unsigned long long)T;
-  }
-#endif
   // softmax done through tile T, P.V through tile T-1
   if (active) {
     asm volatile("s_nop 15\n\ts_nop 7" : "+v"(S00), "+v"(S01), "+v"(S10), "+v"(S11));
@@ -446,16 +393,13 @@ __global__ __launch_bounds__(256, 1) void CA_A4_KERNEL(const AttnLaunch L) {
       CA_A4_PV_PLAIN((uint32_t)(((T + 1) % 3) * TILE_BYTES));
     }
   }
-
-#endif  // CA_A4_PLAIN
   // ---- did any row leave the safe range?  (workgroup-uniform decision: the recomputation stages tiles together)
   int *flag = (int *)(smem + a4::FLAG_OFF);
   if (tid == 0) *flag = 0;
   drain_and_barrier();
   l0 += l0b, l1 += l1b;
   l0b = l1b = 0.f;
-  const float l_limit = (L.flags & 2) ? a4::L_LIMIT_R3 : a4::L_LIMIT;
-  if (active && __builtin_amdgcn_ballot_w64(!(l0 <= l_limit) || !(l1 <= l_limit)) != 0 && lane == 0) *flag = 1;
+  if (active && __builtin_amdgcn_ballot_w64(!(l0 <= a4::L_LIMIT) || !(l1 <= a4::L_LIMIT)) != 0 && lane == 0) *flag = 1;
   drain_and_barrier();
   if (*flag) {
     // classical online softmax, one tile at a time, nothing overlapped (rare: a row sum that overflowed between two
@@ -564,4 +508,3 @@ __global__ __launch_bounds__(256, 1) void CA_A4_KERNEL(const AttnLaunch L) {
 #undef CA_A4_BOOKKEEPING
 #undef CA_A4_ADVANCE
 #undef CA_A4_REREF_CHECK
-#undef CA_A4_ACC

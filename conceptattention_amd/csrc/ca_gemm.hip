@@ -53,9 +53,7 @@ struct GemmLaunch {
 // is the thin tiles that spill into a partial last round.  Why: the [concept | text] stream of a 5-item double
 // block has 1300 rows = 5 row tiles + 20 rows; those 20 rows cost every launch of the block one more round of
 // full-price tiles (proj and mlp.2: 1032 tiles = 4.03 rounds -> 5), 9 % of the block (tools/remainder_probe.py).
-#ifndef CA_GEMM_THIN_ROWS
-#define CA_GEMM_THIN_ROWS 128
-#endif
+constexpr int THIN_ROWS = 128;
 
 template <int M_REP, int N_REP>
 struct Cfg {
@@ -68,10 +66,6 @@ struct Cfg {
   static constexpr int NLOAD = (BM + BN) / 64;  // global_load_lds per wave per K tile
   static_assert(BM % 64 == 0, "A/W boundary must be wave-instruction aligned");
 };
-
-#ifndef CA_GEMM_TWO_PHASE
-#define CA_GEMM_TWO_PHASE 1
-#endif
 
 constexpr int GROUP_M = 8;
 
@@ -331,22 +325,6 @@ __device__ __forceinline__ ca_v8i ca_cat32(bf16x8 lo, bf16x8 hi) {
   return ca_v8i{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 }
 
-#ifdef CA_GEMM_STAMP
-// Diagnostic build only (tools/stamp_gemm.py, tools/stamp_gemm_persist.py): s_memtime of wave 0 of every tile
-// (index = tile id of the walk) at tile entry, after the prologue barrier, after the K loop and after the epilogue.
-__device__ unsigned long long ca_gemm_dbg[8 * 2048];  // 8 stamps per tile: 0-3 the tile, 4-7 inside the fused qkv epilogue
-#define CA_GSTAMP(SLOT)                                                                 \
-  {                                                                                     \
-    unsigned long long ts_;                                                             \
-    __builtin_amdgcn_sched_barrier(0);                                                  \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts_)::"memory");        \
-    __builtin_amdgcn_sched_barrier(0);                                                  \
-    if (tid == 0 && bid < 2048) ca_gemm_dbg[bid * 8 + (SLOT)] = ts_;                    \
-  }
-#else
-#define CA_GSTAMP(SLOT)
-#endif
-
 template <int NL, int NHI>  // 16-column fragments per wave in the lo / hi half of the W tile
 struct PPCfg {
   static constexpr int BM = 256, BN = 64 * (NL + NHI), BK = 64, ROW_BYTES = 128;
@@ -386,7 +364,6 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
-  CA_GSTAMP(0);
 
   int prob, mtile, ntile;
   if (bid < L.main_total) {
@@ -546,7 +523,6 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     \
   __builtin_amdgcn_sched_barrier(0)
 
-#if CA_GEMM_TWO_PHASE
   // ---- TWO phases per K tile: (A-lo x W-lo, W-hi) then (A-hi x W-lo, W-hi), 32 MFMAs per wave and phase, so the
   // loop passes 4 barriers per K tile instead of 8 (the barrier hand-off between the two wave groups, not LDS
   // or MFMA issue, is what the 4-phase loop loses: 2458 vs 2048 cycles per K tile).  Staging and hand-off:
@@ -568,7 +544,6 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
   stageWL(1, 1);
   ca_wait_vmcnt<C::CNT_A + NL>();
   CA_PP_SYNC();
-  CA_GSTAMP(1);
   if (wm == 1) { CA_PP_SYNC(); }  // stagger: group 1 runs one barrier behind group 0
   // The loop exists twice: as written for full tiles, and for thin tiles (a last row tile with few valid rows,
   // walked last) with the LDS reads and MFMAs of row fragments past M left out -- same staging, waits and barriers,
@@ -607,59 +582,8 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
       CA_PP_SYNC();
     }
   };
-  if (rows_valid <= CA_GEMM_THIN_ROWS) kloop(std::true_type{});
+  if (rows_valid <= THIN_ROWS) kloop(std::true_type{});
   else kloop(std::false_type{});
-#else
-  constexpr bool THIN = false;  // (the 4-phase loop has no thin variant)
-  // ---- prologue: AL(0) WL(0) WH(0) AH(0) WL(1).  Group 1 executes no retire-wait between this
-  // barrier and group 0's first read of W-hi(0), so everything but AH(0), WL(1) must have landed.
-  stageA(0, 0, 0);
-  stageWL(0, 0);
-  stageWH(0, 0);
-  stageA(0, 1, 0);
-  stageWL(1, 1);
-  ca_wait_vmcnt<C::CNT_A + NL>();
-  CA_PP_SYNC();
-  CA_GSTAMP(1);
-  if (wm == 1) { CA_PP_SYNC(); }  // stagger: group 1 runs one barrier behind group 0
-
-  // retire-waits leave the two youngest half tiles in flight: phase 1: WL(t+2 of the previous
-  // tile's phase 4) + AL; phase 2: AL + WH; phase 3: WH + AH; phase 4: AH + WL
-  for (int t = 0; t < nk; ++t) {
-    const int b = t & 1;
-    // phase 1: (A-lo, W-lo)
-    readA(b, 0);
-    readWL(b);
-    stageA(b ^ 1, 0, t + 1);
-    CA_PP_WAIT_READS();
-    CA_PP_SYNC();
-    CA_PP_MMA(0, 0, wl, NL, nv_lo);
-    ca_wait_vmcnt<NL + C::CNT_A>();
-    CA_PP_SYNC();
-    // phase 2: (A-lo, W-hi)
-    readWH(b);
-    stageWH(b ^ 1, t + 1);
-    CA_PP_WAIT_READS();
-    CA_PP_SYNC();
-    CA_PP_MMA(0, NL, wh, NHI, nv_lo);
-    ca_wait_vmcnt<C::CNT_A + NHI>();
-    CA_PP_SYNC();
-    // phase 3: (A-hi, W-hi)
-    readA(b, 1);
-    stageA(b ^ 1, 1, t + 1);
-    CA_PP_WAIT_READS();
-    CA_PP_SYNC();
-    CA_PP_MMA(4, NL, wh, NHI, nv_hi);
-    ca_wait_vmcnt<NHI + C::CNT_A>();
-    CA_PP_SYNC();
-    // phase 4: (A-hi, W-lo); W-lo of tile t+2 goes into the buffer whose W-lo was consumed in phase 1
-    stageWL(b, t + 2);
-    CA_PP_SYNC();
-    CA_PP_MMA(4, 0, wl, NL, nv_hi);
-    ca_wait_vmcnt<C::CNT_A + NL>();
-    CA_PP_SYNC();
-  }
-#endif
   if (wm == 0) { CA_PP_SYNC(); }
   // No LDS-DMA may be outstanding when the workgroup retires or the epilogue reuses the LDS.  Through the BUILTIN
   // (0x0F70 = vmcnt 0): hipcc's wait-count pass does not see waits in inline asm, keeps believing that the loop's
@@ -667,7 +591,6 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
   // which there waits for the acknowledgement of every global store issued so far (the fused QK-norm + RoPE epilogue
   // read its row sums fragment by fragment between stores: 940 cycles per fragment).
   __builtin_amdgcn_s_waitcnt(0x0F70);
-  CA_GSTAMP(2);
   if constexpr (FP8) {
     // dequantise: acc[m][n] *= a_scale[m] * w_scale[n] (column order of the accumulators: see below)
     float sa[8];
@@ -790,16 +713,13 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
         }
       }
       if constexpr (FP8) load_rope();
-      CA_GSTAMP(4);
       __syncthreads();
       // every load of this epilogue has been issued: wait for them HERE, once, through the builtin.  Otherwise hipcc
       // covers each use of the RoPE values below with s_waitcnt vmcnt(0), which by then also waits for the stores of
       // the fragments before it (vmcnt counts stores and retires in order).
       __builtin_amdgcn_s_waitcnt(0x0F70);
-      CA_GSTAMP(5);
 #pragma unroll
       for (int hn = 0; hn < 2; ++hn) {
-        if (hn == 1) { CA_GSTAMP(6); }
         const int head_col = (n0 - (is_q ? 0 : hd)) + hn * 128;  // first column of this head in its third
 #pragma unroll
         for (int mi = 0; mi < 8; ++mi) {
@@ -1012,10 +932,6 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
   };
   half_epilogue(std::integral_constant<int, NL>{}, 0, nb_lo, braw_lo, graw_lo);
   half_epilogue(std::integral_constant<int, NHI>{}, NL, nb_hi, braw_hi, graw_hi);
-#ifdef CA_GEMM_STAMP
-  if (CA_GEMM_STAMP != 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // 2: stores left in flight (the walk as shipped)
-  CA_GSTAMP(3);
-#endif
 }
 
 // One workgroup per tile, or (persist_tiles > 0) a grid of one workgroup per CU walking the tiles with a stride of
@@ -1036,7 +952,7 @@ __global__ __launch_bounds__(512, 2) void ca_gemm_pp_kernel(const GemmLaunch L) 
 }
 
 // =============================================================================================
-// Thin-row kernel: the last row tile of a problem when it is thin (<= CA_GEMM_THIN_ROWS rows: the 5 x 4 concept rows
+// Thin-row kernel: the last row tile of a problem when it is thin (<= THIN_ROWS rows: the 5 x 4 concept rows
 // that the [concept | text] stream of a 5-item double block carries past its 5 full row tiles; the 4 rows a single
 // item leaves over), 32 rows per workgroup (grid y).  As 256-column tiles of the ping-pong kernel those rows cost a launch 12 full-price tiles -- one
 // CU streams 256 weight rows per tile through its vector L1 whatever the row count -- and with them a fifth round
@@ -1338,18 +1254,13 @@ void pick_thin(const GemmLaunch &L, int *mf, int *nw, int *groups) {
   // -- the conditioning vectors of the modulation GEMM, longer thin parts -- keeps 4 waves (the weights stream once per
   // 64 rows either way, and its N is a million columns: the chip is full)
   // ... where the launch is short of workgroups (N / 128 <= 256), not for the modulation GEMM's million columns
-  static const int narrow_env = ca_ab_env("CA_GEMM_THIN_NARROW", 1);
-  const bool narrow = narrow_env && !heads && L.thin_nt[0] + L.thin_nt[1] <= 256;
+  const bool narrow = !heads && L.thin_nt[0] + L.thin_nt[1] <= 256;
   *mf = rows <= 32 ? 2 : 4;   // (flux-dev's 5 x 8 concept rows: 4)
   *nw = narrow ? 1 : 4;
   *groups = rows <= 32 ? 1 : (rows + 63) / 64;
 }
 
 int launch_thin(const GemmLaunch &L, int mf, int nw, int groups, hipStream_t stream) {
-  // (diagnostic builds, TIMING ONLY: CA_GEMM_KO_THIN=1 skips every thin-row launch -- wrong results; the ceiling of
-  // anything that could still be done about those rows, tools/env_ab.py)
-  static const int ko = ca_ab_env("CA_GEMM_KO_THIN", 0);
-  if (ko) return CA_OK;
   if (mf == 2) return nw == 1 ? launch_thin_mf<2, 1>(L, groups, stream) : launch_thin_mf<2, 4>(L, groups, stream);
   return nw == 1 ? launch_thin_mf<4, 1>(L, groups, stream) : launch_thin_mf<4, 4>(L, groups, stream);
 }
@@ -1418,14 +1329,13 @@ int tile_n_of(int tile) {
 // consecutive tiles of that order: a group_m x (32 / group_m) patch of the output, i.e. group_m A panels and 32 / group_m
 // W panels through the XCD's L2, and rows of 32 / group_m x 512 contiguous output bytes in the round's store burst.
 // It had been 8 everywhere (a square-ish patch: the fewest panels).  Round 4 measured the model's six grouped launches with
-// 1 .. 32 (tools/gemm_group_m.py, profiles/r04_gemm_group_m.txt): at 5 items per forward every launch is 2-4 % faster with
-// FEWER row tiles per group (wider rows of output per XCD and round), and which count is best depends on the number of
-// column tiles -- 12 (N = 3072: proj, mlp.2, linear2): 1;  36-48 (qkv, mlp.0): 4;  84 (linear1): 2-3.  With one item per
-// forward (17 row tiles) the choice matters less than 1 %, except that the N = 3072 launches prefer 2-4 to 1.
-// CA_GEMM_GROUP_M overrides (A/B aid).  The order of the tiles changes nothing about any tile's result.
+// 1 .. 32 (profiles/r04_gemm_group_m.txt; tools/gemm_group_m.py at commit a5286e4): at 5 items per forward every launch
+// is 2-4 % faster with FEWER row tiles per group (wider rows of output per XCD and round), and which count is best
+// depends on the number of column tiles -- 12 (N = 3072: proj, mlp.2, linear2): 1;  36-48 (qkv, mlp.0): 4;  84 (linear1):
+// 2-3.  With one item per forward (17 row tiles) the choice matters less than 1 %, except that the N = 3072 launches
+// prefer 2-4 to 1.
+// The order of the tiles changes nothing about any tile's result.
 int pick_group_m(int nt, int mt, bool interleave) {
-  static const int env = ca_ab_env("CA_GEMM_GROUP_M", 0);
-  if (env > 0) return env;
   // (with the XCDs sharing each run of 256 tiles the choice is flat over 4 .. 8; one item per forward -- 17 row tiles --
   // prefers 4 for the widest launch: linear1 414 vs 423 us)
   if (interleave) return (nt <= 16 || (nt >= 64 && mt < 48)) ? 4 : 6;
@@ -1435,16 +1345,9 @@ int pick_group_m(int nt, int mt, bool interleave) {
 }
 
 // Do the thin last-row tiles of a launch ride in the ping-pong walk (in the CUs the main tiles leave idle in their last
-// round) instead of getting the thin-row kernel's own launch?  ONE predicate for the tile chooser and for gemm_impl
-// (CA_GEMM_THIN_INWALK=0: never; round 3's behaviour, A/B aid).
+// round) instead of getting the thin-row kernel's own launch?  ONE predicate for the tile chooser and for gemm_impl.
 bool thin_rides_in_walk(long main_all, long thin_all, int n_cu) {
-  static const int inwalk_env = ca_ab_env("CA_GEMM_THIN_INWALK", 1);
-  return inwalk_env && n_cu > 0 && thin_all > 0 && main_all % n_cu != 0 && main_all % n_cu + thin_all <= n_cu;
-}
-
-bool thin_kernel_enabled() {   // CA_GEMM_THIN_KERNEL=0: thin rows stay 256-column tiles of the ping-pong walk (A/B aid)
-  static const int env = ca_ab_env("CA_GEMM_THIN_KERNEL", 1);
-  return env != 0;
+  return n_cu > 0 && thin_all > 0 && main_all % n_cu != 0 && main_all % n_cu + thin_all <= n_cu;
 }
 
 // Pick the tile that minimises (rounds over the CUs) x (time of one round).  Round times are
@@ -1469,7 +1372,7 @@ int auto_tile(const ca_gemm_problem *p, int n, int cus) {
       const int rem = p[i].M % 256;
       // a thin last row tile leaves the 256x256 ping-pong walk for the thin-row kernel (a fraction of a round); the
       // same predicate as gemm_impl's `own`, M <= 128 (no ping-pong tile at all) included
-      if (c.tile == CA_TILE_PP_256x256 && rem > 0 && rem <= CA_GEMM_THIN_ROWS) {
+      if (c.tile == CA_TILE_PP_256x256 && rem > 0 && rem <= THIN_ROWS) {
         --mt;
         if (p[i].K > thin_k) thin_k = p[i].K;
       }
@@ -1490,12 +1393,11 @@ int auto_tile(const ca_gemm_problem *p, int n, int cus) {
       long main_t = 0, thin_t = 0;
       for (int i = 0; i < n; ++i) {
         const int rem = p[i].M % 256;
-        const int thin = (rem > 0 && rem <= CA_GEMM_THIN_ROWS) ? 1 : 0;
+        const int thin = (rem > 0 && rem <= THIN_ROWS) ? 1 : 0;
         main_t += ((p[i].M + 255) / 256 - thin) * (long)(p[i].N / 256);
         thin_t += thin * (long)(p[i].N / 256);
       }
       if (thin_rides_in_walk(main_t, thin_t, n_cu)) thin_cost = 0.0;
-      else if (!thin_kernel_enabled()) thin_cost = 0.75 * c.round_us * thin_k;   // full-width thin tiles after the walk
     }
     const double cost = rounds * c.round_us * kmax + thin_cost;
     if (cost < best_cost) {
@@ -1648,17 +1550,14 @@ int plan_gemm(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile,
     L.mt[1] = L.nt[1] = 1;
     L.p[1] = L.p[0];
   }
-  const bool thin_kernel_env = thin_kernel_enabled();
   // the 8 XCDs share each run of 256 consecutive tiles of the order (XCD x: its tiles 32 x .. 32 x + 31) instead of
-  // owning one eighth of the order each: all of them stream the same group of A rows at a time (CA_GEMM_XCD_INTERLEAVE=0:
-  // rounds 1-3's contiguous ranges)
-  static const int xil_env = ca_ab_env("CA_GEMM_XCD_INTERLEAVE", 1);
+  // owning one eighth of the order each: all of them stream the same group of A rows at a time
   // (the order's "round" is 256 tiles = 32 per XCD, which is what runs together only on a 256-CU part: elsewhere the
   // contiguous ranges, whose mapping does not assume a grid size)
-  const int xil = xil_env && n_cu == 256;
+  const int xil = n_cu == 256;
   L.xcd_interleave = xil;
   L.group_m = pick_group_m(L.nt[0], L.mt[0], xil != 0);
-  // Thin last row tiles (<= CA_GEMM_THIN_ROWS valid rows) under the bf16 256x256 tile normally get their own launch of
+  // Thin last row tiles (<= THIN_ROWS valid rows) under the bf16 256x256 tile normally get their own launch of
   // 32 x 128 tiles behind the main one (ca_gemm_thin_kernel).  But when the main tiles leave enough CUs idle in their
   // last round for every thin tile -- the one-item forward: 204 + 12 tiles on 256 CUs -- the thin tiles ride in the walk
   // (they are walked last, cost 0.75 of a full tile and finish inside the round that runs anyway): no second launch.
@@ -1666,7 +1565,7 @@ int plan_gemm(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile,
   int main_all = 0, thin_all = 0;
   for (int i = 0; i < n_problems; ++i) {
     const int rem = L.p[i].M % 256;
-    const int thin = (rem > 0 && rem <= CA_GEMM_THIN_ROWS) ? 1 : 0;
+    const int thin = (rem > 0 && rem <= THIN_ROWS) ? 1 : 0;
     main_all += (L.mt[i] - thin) * L.nt[i];
     thin_all += thin * L.nt[i];
   }
@@ -1674,10 +1573,10 @@ int plan_gemm(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile,
   int total_pp = 0;
   for (int i = 0; i < CA_GEMM_MAX_PROBLEMS; ++i) {  // tile order of the ping-pong kernel: thin last row tiles go last
     const int rem = i < n_problems ? L.p[i].M % 256 : 0;
-    const int thin = (rem > 0 && rem <= CA_GEMM_THIN_ROWS) ? 1 : 0;
+    const int thin = (rem > 0 && rem <= THIN_ROWS) ? 1 : 0;
     // under the bf16 256x256 tile: their own launch of 32 x 128 tiles instead (ca_gemm_thin_kernel), one grid row
     // per 32 rows
-    const bool own = thin && !fp8 && tile == CA_TILE_PP_256x256 && thin_kernel_env && !thin_fits;
+    const bool own = thin && !fp8 && tile == CA_TILE_PP_256x256 && !thin_fits;
     L.mt_main[i] = i < n_problems ? L.mt[i] - thin : 1;
     L.ntiles_main[i] = i < n_problems ? L.mt_main[i] * L.nt[i] : 0;
     L.nthin[i] = (thin && !own) ? L.nt[i] : 0;
@@ -1688,13 +1587,9 @@ int plan_gemm(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile,
   }
   const bool pp_tile = fp8 || tile == CA_TILE_PP_256x256 || tile == CA_TILE_PP_256x192 || tile == CA_TILE_PP_256x128;
   if (pp_tile) total = total_pp;  // (the simple kernel keeps every row tile)
-  {  // persistent walk of the tiles when there is more than one round of them (CA_GEMM_PERSIST=0 disables)
-    static const int persist_env = ca_ab_env("CA_GEMM_PERSIST", 1);
-    const int n = n_cu;
-    if (persist_env && n > 0 && n % 8 == 0 && total > n) {
-      L.persist_tiles = total;
-      L.persist_tiles_grid = n;
-    }
+  if (n_cu > 0 && n_cu % 8 == 0 && total > n_cu) {   // persistent walk of the tiles when there is more than one round
+    L.persist_tiles = total;
+    L.persist_tiles_grid = n_cu;
   }
   out->tile = fp8 ? CA_TILE_PP_256x256 : tile;
   out->total = total;
@@ -1772,9 +1667,3 @@ extern "C" int ca_gemm_plan(const ca_gemm_problem *problems, int32_t n_problems,
   out->n_cu = n_cu ? n_cu : ca_cu_count();
   return CA_OK;
 }
-
-#ifdef CA_GEMM_STAMP
-extern "C" int ca_debug_read_gemm(unsigned long long *out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(ca_gemm_dbg), sizeof(unsigned long long) * 8 * 2048);
-}
-#endif

@@ -25,7 +25,6 @@ concept attention reads [concept keys | image keys] as two row segments without 
 from __future__ import annotations
 
 import math
-import os
 
 from dataclasses import dataclass
 from typing import Optional
@@ -209,16 +208,17 @@ class HipFluxDiT:
         # attention kernel's probability is a bare exp2 (include/conceptattn.h CA_ATTN_Q_PRESCALED); False = the kernel
         # multiplies every score instead (A/B aid)
         self.prescale_q = True
-        # sampling.denoise keeps the latent in fp32 between the Euler steps when the model says so (A/B: CA_FP32_LATENT=0)
-        self.fp32_latent = os.environ.get("CA_FP32_LATENT", "1") != "0"
+        # sampling.denoise keeps the latent in fp32 between the Euler steps when the model says so (False = bf16, A/B aid)
+        self.fp32_latent = True
         # An fp32 copy of the captured layers' [text | image] attention rows for the output-space logits (round 3).
         # Round 5 re-measured it at full depth (VERDICT r04 weak #5 asked to drop it: 1 011 vs 888 us per captured 5-item
         # attention launch, 53 MB per item): layer 0's map moves by 2e-5 (tests/tools/diag_out_space.py), but deeper
         # layers do not agree -- without it the worst step-0 map is 8.1e-4 (layer 4) instead of 3.8e-4 and the final
         # maps 1.45e-4 instead of 7.9e-5 from the fp32 oracle (tests/test_full_depth_gpu.py fails its 1.5 x bounds).
         # So the fp32 precision stays -- but since round 5 without the copy: epilogue_logits (below) forms the logits from
-        # the attention kernel's accumulators; this switch only matters with epilogue_logits = False ("0" = the bf16 rows).
-        self.f32_image_vectors = os.environ.get("CA_F32_IMAGE_VECTORS", "1") != "0"
+        # the attention kernel's accumulators; this attribute only matters with epilogue_logits = False (False = the bf16
+        # rows).
+        self.f32_image_vectors = True
         # The cross-attention-space vectors (post-QKNorm, pre-RoPE q) of the captured layers from the UNROUNDED
         # LayerNorm output: the bf16 rounding of that GEMM operand is ~90 % of the cross-space heat-map error
         # (tests/tools/error_budget.py: 3.3e-3 -> 3.5e-4 per map).  The LayerNorm writes a second bf16 plane with what
@@ -235,10 +235,10 @@ class HipFluxDiT:
         # ("all") the maps are no closer to the oracle (profiles/r04_full_depth_parity*.json: 5.6e-4 / 9.6e-4 worst single
         # map against 5.7e-4 / 8.4e-4) at -0.6 % heat maps/s.  "0": bf16 everywhere, as the reference (A/B aid).
         # Needs the pre-scaled-q kernel (prescale_q = False switches it off: _qk16).
-        self.qk_f16 = os.environ.get("CA_QK_F16", "captured")
+        self.qk_f16 = "captured"
         # the ATTENTION's q of the captured layers' image / concept rows from the unrounded LayerNorm output as well
-        # (ops.qpre_finish writes it over the epilogue's; _double_block); "0" = round 3's q (A/B aid)
-        self.split_q_attention = os.environ.get("CA_SPLIT_Q_ATTENTION", "1") != "0"
+        # (ops.qpre_finish writes it over the epilogue's; _double_block); False = round 3's q (A/B aid)
+        self.split_q_attention = True
         # Exact independence of everything the forward returns from WHICH layers' maps are requested (the reference's
         # property: the concept stream and the capture are read-only side computations, modified_double_stream_block.py:
         # 105-119, 185-191).  False (default): a captured layer's attention uses the accurate q for its image and concept
@@ -254,7 +254,7 @@ class HipFluxDiT:
         self._layer_indep = False   # (set per layer by _double_block, read by _capture)
         self._layer_part = False
         # fp8 mode: the qkv projection of a layer whose maps are requested stays bf16 (_double_block)
-        self.fp8_bf16_qkv_when_captured = os.environ.get("CA_FP8_QKV_BF16_CAPTURED", "1") != "0"
+        self.fp8_bf16_qkv_when_captured = True
         # the heat-map updates of a captured layer (all work items, both spaces) as ONE ca_heatmap_fused launch; False =
         # logits + weighting launches per item and space (the same bits; parity / A-B aid, and what C > 8 uses)
         self.fused_heatmaps = True
@@ -266,8 +266,6 @@ class HipFluxDiT:
         # and 250 MB of reads in the heat-map launch).  The same arithmetic in another summation order (per head, then
         # over the heads).  False = the fp32 rows (rounds 3-4; A/B aid).  Needs fused_heatmaps and the pre-scaled-q kernel.
         self.epilogue_logits = True
-        if self.qk_f16 not in ("all", "captured", "0"):
-            raise ValueError("CA_QK_F16 must be all, captured or 0")
         self.set_precision(precision)
 
     # ---- reduced-precision mode (BASELINE.json configs[4]; no counterpart in the reference)
@@ -664,7 +662,7 @@ class HipFluxDiT:
 
     def _f32_image_vectors(self, capture: bool, heatmaps) -> bool:
         """The attention kernel writes an fp32 copy of the [text | image] output rows in captured layers when the maps
-        are reduced on the device (fused heat-map path); A/B: CA_F32_IMAGE_VECTORS=0."""
+        are reduced on the device (fused heat-map path); A/B: f32_image_vectors = False."""
         return bool(capture and heatmaps is not None and self.f32_image_vectors)
 
     def _ones_gate(self, n: int) -> torch.Tensor:

@@ -56,8 +56,7 @@ int ca_check_device(void);
  * pointers.  M is arbitrary (rows are masked).  A call is one kernel launch on `stream`, or two:
  * under the 256x256 ping-pong tile a problem's last row tile with at most 128 rows (M % 256 in
  * [1, 128]: the concept rows a [concept | text] stream carries past its full row tiles) runs as
- * 32 x 128 tiles of a second kernel queued right behind the first (bit-identical results; set
- * CA_GEMM_THIN_KERNEL=0 in the environment to keep those rows in the first kernel's tile walk).
+ * 32 x 128 tiles of a second kernel queued right behind the first (bit-identical results).
  */
 enum {
   CA_EPI_BIAS = 0,          /* out = acc + bias */

@@ -200,7 +200,7 @@ def test_latent_dependence_on_the_captured_layer_set(pipe, golden):
     returns -- moves at rounding level with ``layer_indices``.  This pins HOW MUCH: the final
     latent of a 4-step generation capturing no layer, layers 15-18 (the default) and all 19, against each other and
     against the fp32 oracle's latent.  Bounds = 1.5 x measured (profiles/r05_full_depth_parity.json);
-    CA_SPLIT_Q_ATTENTION=0 CA_QK_F16=0 removes the dependence (at 7.8e-4 instead of 2.2e-4 per single output-space map)."""
+    split_q_attention = False with qk_f16 = "0" removes the dependence (at 7.8e-4 instead of 2.2e-4 per single output-space map)."""
     g = golden("full_depth_schnell.npz")
     p = pipe.params
     inp = bf_inputs(p, 1024, 256, 4)

@@ -219,7 +219,7 @@ def test_odd_sizes_end_to_end_vs_oracle(size, n_txt, C):
 
 
 def test_reference_shaped_bf16_latent_loop_stays_exercised():
-    """CA_FP32_LATENT=0 (HipFluxDiT.fp32_latent = False): the Euler state is a bf16 tensor re-rounded after every step
+    """HipFluxDiT.fp32_latent = False: the Euler state is a bf16 tensor re-rounded after every step
     and the prediction is bf16 -- the reference's own loop, flux/sampling.py:141 -- next to the default fp32 state.  Both
     against the fp32 oracle; the default is at least as close, and the two latents differ by about 2^-9 per step, which
     is what a caller comparing returned latents with a bf16 reference run will see."""
@@ -231,7 +231,7 @@ def test_reference_shaped_bf16_latent_loop_stays_exercised():
     pl = ConceptAttentionFluxPipeline("flux-schnell", device=DEV, weights=sd, params=p, n_text_tokens=8)
     args = (inp["latent"].to(DEV), inp["txt"].to(DEV), inp["vec"].to(DEV), inp["concepts"].to(DEV))
     kw = dict(layer_indices=[0, 1], num_inference_steps=4)
-    default = pl.model.fp32_latent                     # True unless CA_FP32_LATENT=0 is set for the whole run
+    default = pl.model.fp32_latent                     # True
     pl.model.fp32_latent = True
     img32, hm32, _ = pl.generate_on_device(*args, **kw)
     pl.model.fp32_latent = False

@@ -1,7 +1,7 @@
 """Development aid for the one-wave-per-SIMD attention kernel: accuracy against the fp32 reference on a ladder of
 shapes (pre-scaled q, one / two key segments, ragged tails, inactive waves), then the timing of the Flux shape and of
-the 5-item launch.  Run once with CA_ATTN_KERNEL=4 and once without (the switch is read once per process).
-usage: [CA_ATTN_KERNEL=4] python tools/attn4_check.py [--no-time] [--only-time]"""
+the 5-item launch.
+usage: python tools/attn4_check.py [--no-time] [--only-time]"""
 import math
 import os
 import sys

@@ -5,20 +5,14 @@ the synthetic weights' near-uniform attention (logit std ~ 1 nat).  This tool ti
 path (5 x [256 text + 4096 image rows], 24 heads, q pre-scaled) on logits of std 1 / 4 / 8 / 16 nats and on a structured
 case (every row: its first 64 keys -- the text tile -- near -20 nats, five image keys near +25, the rest near 0), reads
 the kernel's rare-path counters (ca_attn_stats: recomputed workgroups, in-place re-reference events) and checks the
-result against an fp32 softmax on a sample of rows.  Run once per mode in fresh processes: the default kernel and
-CA_ATTN_REREF=0 (round 3's behaviour: no in-place re-reference, a row sum that leaves the safe range costs its
-workgroup a full classical recomputation).
+result against an fp32 softmax on a sample of rows.  (Round 3's behaviour, without the in-place re-reference, was
+measured from a diagnostic build that commit a5286e4 still has: profiles/r04_attn_peaky.json.)
 
     python tools/attn_peaky.py [out.json]        (GPU box; default gpurun_out/attn_peaky.json)
 """
 import json
 import math
 import os
-# the switches this tool flips exist in the diagnostic build only: python -m conceptattention_amd.csrc.build --ab
-_AB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "ab", "switches", "libca.so")
-if os.path.exists(_AB):
-    os.environ.setdefault("CA_LIB_PATH", _AB)
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -54,7 +48,7 @@ def make(kind, dev):
     return q.reshape(n, H), k.reshape(n, H).bfloat16(), v.reshape(n, H).bfloat16()
 
 
-def run_mode(out_path):
+def run():
     import torch
     from conceptattention_amd import ops
     from tools.bench_kernels import timeit
@@ -93,28 +87,19 @@ def run_mode(out_path):
                      "sample_logit_std_nats": float(lg.std()), "sample_logit_max_minus_tile0_max_nats":
                          float((lg.max(1).values - lg[:, :64].max(1).values).max())}
         print(kind, json.dumps(res[kind]), flush=True)
-    json.dump(res, open(out_path, "w"))
+    return res
 
 
 def main():
-    if len(sys.argv) > 2 and sys.argv[1] == "--mode":
-        return run_mode(sys.argv[2])
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out", "attn_peaky.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     doc = {"shape": f"{B} problems x ({T} + {Li}) rows, {NH} heads, head_dim 128, q pre-scaled (ca_attn4_kernel)",
            "method": "best of 3 x 10 launches after 2 warm-ups (HIP events); counters of ONE launch (ca_attn_stats); error on "
                      "320 query rows x 2 heads of item 0 against an fp32 softmax of the same bf16 inputs"}
-    for mode, env in (("default(limit 2^100, in-place re-reference above 2^64)", {}),
-                      ("no_rereference(CA_ATTN_REREF=0, limit 2^100)", {"CA_ATTN_REREF": "0"}),
-                      ("round3(CA_ATTN_REREF=0 CA_ATTN_LIMIT60=1: limit 2^60, recomputation only)",
-                       {"CA_ATTN_REREF": "0", "CA_ATTN_LIMIT60": "1"})):
-        tmp = out + "." + mode.split("(")[0] + ".tmp"
-        subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", tmp], check=True, env=dict(os.environ, **env))
-        doc[mode] = json.load(open(tmp))
-        os.remove(tmp)
-    base = doc["default(limit 2^100, in-place re-reference above 2^64)"]["std1"]["us_per_launch"]
-    doc["slowdown_vs_std1"] = {m: {k: doc[m][k]["us_per_launch"] / base for k in KINDS}
-                               for m in doc if isinstance(doc[m], dict) and "std1" in doc[m]}
+    mode = "default(limit 2^100, in-place re-reference above 2^64)"
+    doc[mode] = run()
+    base = doc[mode]["std1"]["us_per_launch"]
+    doc["slowdown_vs_std1"] = {mode: {k: doc[mode][k]["us_per_launch"] / base for k in KINDS}}
     json.dump(doc, open(out, "w"), indent=1)
     print("written", out)
 

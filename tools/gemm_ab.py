@@ -1,5 +1,5 @@
 """Same-box A/B of the GEMM source under different -D flags: builds each into a scratch .so and times the model's
-launch shapes.   usage: python tools/gemm_ab.py "-DCA_GEMM_TWO_PHASE=0" "-DCA_GEMM_TWO_PHASE=1" """
+launch shapes.   usage: python tools/gemm_ab.py "<-D flags of build A>" "<-D flags of build B>" """
 import os
 import subprocess
 import sys

@@ -27,12 +27,6 @@ import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.environ.get("CA_A4_OUT") or os.path.join(ROOT, "conceptattention_amd", "csrc", "ca_attn4_sched.inc")
-# timing-only knock-outs (tools/attn4_knockouts.py; the results of such a build are wrong): a comma list of
-#   nop4 (s_nop 0 in place of the SGPR->VMEM s_nop 4), exp (v_mov for v_exp), add, cvt, lds (no LDS reads / waits), dma
-KO = set(filter(None, os.environ.get("CA_A4_KO", "").split(",")))
-# placement inside a gap (A/B aid): "split" = [MFMA, memory] | [VALU] as two statements (shipped), "valu_first" /
-# "mem_first" = one statement per slot
-ORDER = os.environ.get("CA_A4_ORDER", "split")
 
 AO, AQ, AK, AV = 0, 128, 192, 224
 QK_T = '" CA_A4_QK_T "'   # spliced into the asm string literal: ..."v_mfma_f32_32x32x16_" CA_A4_QK_T " %0, ..."
@@ -92,18 +86,12 @@ class Stream:
         self.lines.append(f"    // {c}")
 
     def read_k(self, ring, off, ks, name):
-        if "lds" in KO:
-            self.tag[name] = self.lds
-            return
         self.ins(f"ds_read_b128 {areg(AK + 4 * ring, 4)}, {{0}} offset:{off}", (f"ka{ks}", "r"))
         self.lds += 1
         self.tag[name] = self.lds
 
     def read_v(self, ring, vslot_off, kb, sk, db, name):
         row = (32 * kb + 16 * sk) * 256
-        if "lds" in KO:
-            self.tag[name] = self.lds
-            return
         self.ins(f"ds_read_b64_tr_b16 {areg(AV + 4 * ring, 2)}, {{0}} offset:{vslot_off + row}", (f"va0{db}", "r"))
         self.ins(f"ds_read_b64_tr_b16 {areg(AV + 4 * ring + 2, 2)}, {{0}} offset:{vslot_off + row + 2048}",
                  (f"va1{db}", "r"))
@@ -112,8 +100,6 @@ class Stream:
 
     def wait_for(self, name):
         assert name in self.tag, f"{name} waited for before it was issued"
-        if "lds" in KO:
-            return
         self.ins(f"s_waitcnt lgkmcnt({min(self.lds - self.tag[name], 15)})")   # the counter field has 4 bits
 
 
@@ -194,14 +180,13 @@ def gen_iteration(r):
 
     def exp_and_add(g):
         kb, qb, i = exps_of[g]
-        st.ins(("v_mov_b32 {0}, {0}" if "exp" in KO else "v_exp_f32 {0}, {0}"), (f"{S(kb, qb)}[{i}]", "rw"))
+        st.ins("v_exp_f32 {0}, {0}", (f"{S(kb, qb)}[{i}]", "rw"))
         for akb, aqb, ai, sfx in adds_of[g]:
-            if "add" not in KO:
-                st.ins("v_add_f32 {0}, {0}, {1}", (f"l{aqb}{sfx}", "rw"), (f"{S(akb, aqb)}[{ai}]", "r"))
+            st.ins("v_add_f32 {0}, {0}, {1}", (f"l{aqb}{sfx}", "rw"), (f"{S(akb, aqb)}[{ai}]", "r"))
 
     st.comment(f"---- iteration variant r = {r}: K(t+1) slot {(r + 1) % 3}, K(t+2) slot {(r + 2) % 3}, V(t) slot {r}")
     for s in range(64):
-        dma = dma_of.get(s) if "dma" not in KO else None
+        dma = dma_of.get(s)
         if dma:
             j, isv = dma
             st.ins(f"s_add_u32 m0, {{0}}, {(vdst if isv else kdst) + 1024 * j}", ("LWV" if isv else "LWK", "rs"))
@@ -223,38 +208,23 @@ def gen_iteration(r):
             o = areg(AO + 16 * (qb * 4 + db), 16)
             v = areg(AV + 4 * (f & 7), 4)
             st.ins(f"v_mfma_f32_32x32x16_bf16 {o}, {v}, {{0}}, {o}", (f"P{kb}{qb}{sk}", "r"))
-        def mem_ops():
-            if dma:
-                j, isv = dma
-                st.ins("buffer_load_dwordx4 {0}, {1}, {2} offen lds", (f"{'voff' if isv else 'koff'}{j}", "r"),
-                       ("DSV" if isv else "DSK", "rs"), ("SOV" if isv else "SOK", "rs"))
-            for rd in reads[s]:
-                if rd[0] == "k":
-                    st.read_k(rd[1], rd[2], rd[3], rd[4])
-                else:
-                    st.read_v(rd[1], rd[2], rd[3], rd[4], rd[5], rd[6])
-
-        def valu_ops():
-            seen = set()
-            for (kb, qb, sk, j) in cvt_of[s]:
-                assert (kb, qb, sk) not in seen        # one written element per vector variable and statement
-                seen.add((kb, qb, sk))
-                if "cvt" in KO:
-                    continue
-                st.ins("v_cvt_pk_bf16_f32 {0}, {1}, {2}", (f"P{kb}{qb}{sk}[{j}]", "w"),
-                       (f"{S(kb, qb)}[{8 * sk + 2 * j}]", "r"), (f"{S(kb, qb)}[{8 * sk + 2 * j + 1}]", "r"))
-            exp_and_add(s)
-
-        if ORDER == "split":
-            mem_ops()
-            st.flush()  # statement A: M0, wait, MFMA, DMA, LDS reads.  Statement B: the VALU fillers
-            valu_ops()
-        elif ORDER == "valu_first":     # one statement per slot: M0, wait, MFMA, the VALU fillers, then DMA / LDS reads
-            valu_ops()
-            mem_ops()
-        else:                           # "mem_first": one statement per slot, memory operations before the VALU fillers
-            mem_ops()
-            valu_ops()
+        if dma:
+            j, isv = dma
+            st.ins("buffer_load_dwordx4 {0}, {1}, {2} offen lds", (f"{'voff' if isv else 'koff'}{j}", "r"),
+                   ("DSV" if isv else "DSK", "rs"), ("SOV" if isv else "SOK", "rs"))
+        for rd in reads[s]:
+            if rd[0] == "k":
+                st.read_k(rd[1], rd[2], rd[3], rd[4])
+            else:
+                st.read_v(rd[1], rd[2], rd[3], rd[4], rd[5], rd[6])
+        st.flush()  # statement A: M0, wait, MFMA, DMA, LDS reads.  Statement B: the VALU fillers
+        seen = set()
+        for (kb, qb, sk, j) in cvt_of[s]:
+            assert (kb, qb, sk) not in seen        # one written element per vector variable and statement
+            seen.add((kb, qb, sk))
+            st.ins("v_cvt_pk_bf16_f32 {0}, {1}, {2}", (f"P{kb}{qb}{sk}[{j}]", "w"),
+                   (f"{S(kb, qb)}[{8 * sk + 2 * j}]", "r"), (f"{S(kb, qb)}[{8 * sk + 2 * j + 1}]", "r"))
+        exp_and_add(s)
         st.flush()
     check_schedule(exps_of, adds_of, cvt_of, reads, waits)
     return st.lines

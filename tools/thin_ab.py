@@ -1,5 +1,6 @@
 """Thin-row GEMM launches alone (the 5 x 4 concept rows of a batch; the modulation GEMM of 40 / 10 conditioning vectors):
-microseconds per launch for whichever library CA_LIB_PATH names.  usage: [CA_LIB_PATH=tools/ab/.../libca.so] python tools/thin_ab.py"""
+microseconds per launch for whichever library CA_LIB_PATH names (default: the in-tree one).
+usage: [CA_LIB_PATH=/path/to/libconceptattn.so] python tools/thin_ab.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
