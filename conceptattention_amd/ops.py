@@ -223,6 +223,11 @@ def attention(problems: Sequence[Attn], num_heads: int, scale: Optional[float] =
     for i, a in enumerate(problems):
         for n in ("q", "out", "k0", "v0"):
             _chk(getattr(a, n), torch.bfloat16, n)
+        for n in ("q", "out", "k0", "v0", "k1", "v1", "q1", "out1", "out_f32"):
+            t = getattr(a, n)
+            if t is not None and (t.dim() != 2 or t.shape[1] != num_heads * 128):
+                raise ValueError(f"attention[{i}]: {n} must be 2-D with num_heads*128 = {num_heads * 128} columns, "
+                                 f"got {tuple(t.shape)}")
         p = arr[i]
         p.q, p.out, p.k0, p.v0 = a.q.data_ptr(), a.out.data_ptr(), a.k0.data_ptr(), a.v0.data_ptr()
         p.nq, p.n0 = a.q.shape[0], a.k0.shape[0]
