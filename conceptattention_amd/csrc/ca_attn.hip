@@ -381,6 +381,14 @@ static int ca_attn_fwd_impl(const ca_attn_problem *problems, int32_t n_problems,
       ca_set_error("ca_attn_fwd_bf16[%d]: row strides must be >= num_heads*128 and multiples of 8", i);
       return CA_ERR_ARG;
     }
+    // Both kernels form the K / V byte offsets of a tile in 32 bits: the lane offsets koff / voff (< 64 rows), and in
+    // ca_attn4_kernel the scalar tile offset t * 64 * ldkv * 2 counted from key 0 over both segments
+    if (((uint64_t)p.n0 + (uint64_t)p.n1) * (uint64_t)p.ldkv * 2u >= (1ull << 32) ||
+        64ull * (uint64_t)p.ldkv * 2u >= (1ull << 32)) {
+      ca_set_error("ca_attn_fwd_bf16[%d]: keys larger than 4 GiB: (n0 + n1) * ldkv * 2 = %llu bytes (and 64 * ldkv * 2) "
+                   "must stay below 2^32", i, (unsigned long long)(((uint64_t)p.n0 + (uint64_t)p.n1) * (uint64_t)p.ldkv * 2u));
+      return CA_ERR_ARG;
+    }
     if (p.hm_con || p.hm_part) {
       if (!p.hm_con || !p.hm_part || p.hm_C < 1 || p.hm_C > 8 || p.ldhc % 4 || p.ldhc < num_heads * 128 ||
           (((uintptr_t)p.hm_con | (uintptr_t)p.hm_part) & 15) || !use4 || p.nq0 <= 0 || p.nq0 >= p.nq) {

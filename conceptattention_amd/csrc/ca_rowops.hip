@@ -870,14 +870,14 @@ __global__ __launch_bounds__(256) void ca_axpy_f32_kernel(float *__restrict__ x,
 __global__ __launch_bounds__(256) void ca_timestep_embedding_kernel(const float *__restrict__ t, int nt,
                                                                     float *__restrict__ out, int dim,
                                                                     float time_factor, float max_period) {
-  const int half = dim / 2;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= nt * half) return;
-  const int v = i / half, k = i - v * half;
-  const float freq = expf(-logf(max_period) * (float)k / (float)half);
-  const float arg = time_factor * t[v] * freq;
-  out[(size_t)v * dim + k] = cosf(arg);
-  out[(size_t)v * dim + half + k] = sinf(arg);
+  const long half = dim / 2;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nt * half; i += (long)gridDim.x * 256) {
+    const int v = (int)(i / half), k = (int)(i - v * half);
+    const float freq = expf(-logf(max_period) * (float)k / (float)half);
+    const float arg = time_factor * t[v] * freq;
+    out[(size_t)v * dim + k] = cosf(arg);
+    out[(size_t)v * dim + half + k] = sinf(arg);
+  }
 }
 
 int check_launch(const char *what) {
@@ -1226,9 +1226,9 @@ namespace {
 template <bool SILU>
 __global__ __launch_bounds__(256) void ca_silu_split_kernel(const float *__restrict__ x, int ldx, bf16 *__restrict__ hi,
                                                             bf16 *__restrict__ lo, int ldo, int rows, int K) {
-  const int per_row = K >> 2;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < rows * per_row; i += gridDim.x * 256) {
-    const int r = i / per_row, k = (i - r * per_row) << 2;
+  const long per_row = K >> 2;   // (64-bit: rows * per_row passes 2^31 long before the planes pass device memory)
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < rows * per_row; i += (long)gridDim.x * 256) {
+    const int r = (int)(i / per_row), k = (int)(i - r * per_row) << 2;
     const f32x4 v = *(const f32x4 *)(x + (size_t)r * ldx + k);
     bf16x4 h, l;
 #pragma unroll
@@ -1339,8 +1339,9 @@ extern "C" int ca_timestep_embedding_f32(const float *t, int32_t nt, float *out,
     ca_set_error("ca_timestep_embedding_f32: bad arguments (nt=%d dim=%d)", nt, dim);
     return CA_ERR_ARG;
   }
-  const int n = nt * (dim / 2);
-  hipLaunchKernelGGL(ca_timestep_embedding_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, t, nt,
+  const long n = (long)nt * (dim / 2);
+  const long blocks = (n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096;
+  hipLaunchKernelGGL(ca_timestep_embedding_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, t, nt,
                      out, dim, time_factor, max_period);
   return check_launch("ca_timestep_embedding_f32");
 }

@@ -53,7 +53,10 @@ int ca_check_device(void);
  * Up to CA_GEMM_MAX_PROBLEMS problems share one launch (image stream + text/concept stream of a
  * double block), so the grid fills all 256 CUs.
  * Requirements: K % 64 == 0, N % tile_n == 0, lda/ldw/ldc/ldr/ld2 % 8 == 0, 16-byte aligned
- * pointers.  M is arbitrary (rows are masked).  A call is one kernel launch on `stream`, or two:
+ * pointers.  M is arbitrary (rows are masked) up to the extent limit: the A and W operands are addressed with
+ * unsigned 32-bit byte offsets from their base, so M * lda * elem_size and N * ldw * elem_size must each stay below
+ * 2^32 (CA_ERR_ARG "operand larger than 4 GiB" otherwise); out, resid, out2, q_prerope, rope and the gate vectors
+ * are addressed in 64 bits and have no limit.  A call is one kernel launch on `stream`, or two:
  * under the 256x256 ping-pong tile a problem's last row tile with at most 128 rows (M % 256 in
  * [1, 128]: the concept rows a [concept | text] stream carries past its full row tiles) runs as
  * 32 x 128 tiles of a second kernel queued right behind the first (bit-identical results).
@@ -179,6 +182,9 @@ int ca_gemm_plan(const ca_gemm_problem *problems, int32_t n_problems, int32_t ti
  * The query rows of a problem (and the output rows with them) may themselves come in two row segments: rows
  * [0, nq0) at q / out, rows [nq0, nq) at q1 / out1 -- in a batched forward an item's text rows and image rows are
  * not adjacent.  nq0 = 0 or nq0 = nq: one segment (q1 / out1 unused).
+ * Extent limit: the kernels address the key / value rows with unsigned 32-bit byte offsets counted from key 0 over
+ * both segments, so (n0 + n1) * ldkv * 2 and 64 * ldkv * 2 must each stay below 2^32 (CA_ERR_ARG "keys larger than
+ * 4 GiB" otherwise, nothing is launched).  q, out, out_f32, hm_con and hm_part are addressed in 64 bits: no limit.
  */
 #define CA_ATTN_MAX_PROBLEMS 16
 typedef struct {
@@ -362,6 +368,7 @@ int ca_heatmap_fused(const ca_heatmap_problem *problems, int32_t n_problems, int
 
 /* Sinusoidal timestep embedding (timestep_embedding, flux/modules/layers.py:28-49):
  * out[v, 0:dim/2] = cos(time_factor*t[v]*f_i), out[v, dim/2:] = sin(...), f_i = max_period^(-i/(dim/2)). */
+/* (nt * dim / 2 is formed in 64 bits: no limit below int32 nt and dim) */
 int ca_timestep_embedding_f32(const float *t, int32_t nt, float *out, int32_t dim, float time_factor,
                               float max_period, ca_stream_t stream);
 
@@ -381,7 +388,8 @@ int ca_split_bf16(const float *x, int32_t ldx, void *hi, void *lo, int32_t ldo, 
  * bf16 planes, hi = bf16(s), lo = bf16(s - hi): hi + lo carries s to ~16 mantissa bits, so that the adaLN modulation
  * of every block -- [2 * items * steps, H] x [sum N, H]^T, the weights streamed ONCE -- can run as two bf16 MFMA GEMMs
  * (ca_gemm_bf16, the second one accumulating) instead of one weight pass per 4 vectors (ca_gemv_bf16).
- * x fp32 [rows, K] (row stride ldx), hi / lo bf16 [rows, K] (row stride ldo), K % 4 == 0. */
+ * x fp32 [rows, K] (row stride ldx), hi / lo bf16 [rows, K] (row stride ldo), K % 4 == 0.  Element indices and row
+ * offsets are 64-bit in both split entry points: no limit below int32 rows, K and strides. */
 int ca_silu_split_bf16(const float *x, int32_t ldx, void *hi, void *lo, int32_t ldo, int32_t rows, int32_t K,
                        ca_stream_t stream);
 

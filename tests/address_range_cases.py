@@ -1,0 +1,166 @@
+"""The placement, far-row and limit cases of tests/test_address_range_gpu.py, and a numpy uint32 emulation of the
+32-bit address expressions DESIGN.md ("Address arithmetic") lists for the guarded kernels.  Nothing here needs a GPU:
+tests/test_address_range_cpu.py checks the coverage, the limits and that named slips move the emulated addresses."""
+from __future__ import annotations
+
+import numpy as np
+
+import gemm_route_cases as G
+from conceptattention_amd import _lib as L
+
+LINE = 1 << 32
+
+# ---- a. placement: one case of attn_cases.py per attention kernel, with every operand role the kernel has
+ATTN_PLACEMENT = {
+    "ca_attn_kernel<8>": "scale_nk145_ragged_straddle_tail",
+    "ca_attn4_kernel": "pre_hm_C1",
+    "ca_attn4_qk16_kernel": "qk16_hm_C1",
+}
+_QKV = ["q", "q1", "k0/v0", "k1/v1", "out", "out1", "out_f32"]
+ATTN_ROLES = {
+    "ca_attn_kernel<8>": _QKV,                        # (hm_con / hm_part: refused for this kernel by the validator)
+    "ca_attn4_kernel": _QKV + ["hm_con", "hm_part"],
+    "ca_attn4_qk16_kernel": _QKV + ["hm_con", "hm_part"],
+}
+
+# GEMM: per launch route the epilogues that between them use every operand role the route's kernel can take
+GEMM_EPIS = ["gate_items_bf16", "gate_rows_f32", "split_gelu", "qkv_single_qpre_f32_f16"]
+GEMM_INPUT_FIELD = {"A": "a", "W": "w", "bias": "bias", "scales": "a_scale", "w_scale": "w_scale", "gates": "gate",
+                    "gate2": "gate2", "rope": "rope", "norm_q": "norm_q", "norm_k": "norm_k"}
+GEMM_ISSUE_ROLES = {"A", "W", "bias", "out", "resid", "out2", "q_prerope", "rope", "gates", "scales"}
+
+
+def gemm_roles(epi: str, fp8: bool) -> list:
+    """The operand roles of one GEMM placement case (the buffers test_gemm_routes_gpu.build names), in the order run."""
+    e = G.EPIS[epi]["epi"]
+    roles = ["A", "W", "bias", "out"] + (["scales", "w_scale"] if fp8 else [])
+    if e == L.EPI_GATE_RESIDUAL:
+        roles += ["resid", "gates", "gate2"]
+    elif e == L.EPI_SPLIT_GELU:
+        roles += ["out2"]
+    elif e == L.EPI_QKV_NORM_ROPE:
+        roles += ["norm_q", "norm_k", "rope", "out2", "q_prerope"]
+    return roles
+
+
+def rowop_roles(case) -> list:
+    """The input and output planes of one row-op case (the buffers the run helpers of test_rowop_routes_gpu name)."""
+    s, op = case.shape, case.op
+    if op == "ln":
+        return ["x", "shift", "scale", "out"] + {"split": ["out_lo"], "fp8": ["out_scale"]}.get(s["out"], [])
+    if op == "qk":
+        return ["qkv", "q_scale", "k_scale", "rope"] + (["q_prerope"] if s["pre"] else [])
+    if op == "qpre":
+        return ["x", "scale"] + (["d"] if s["d"] else []) + (["rope", "q_out"] if s["rope"] else [])
+    if op == "gemv":
+        return ["x", "w", "out"] + (["bias"] if s["bias"] else [])
+    if op == "combine":
+        return ["pair", "out"] + (["bias"] if s["bias"] else [])
+    if op == "fused":
+        return ["acc", "logits"] + (["part"] if s["form"] == "part" else ["img", "con"])
+    return {"quant": ["x", "out", "out_scale"], "split": ["x", "hi", "lo"], "logits": ["img", "con", "logits"],
+            "norm": ["logits", "acc"], "axpy": ["x", "y"], "temb": ["t", "out"]}[op]
+
+
+# ---- b. far rows.  GEMM: A alone, then W alone, per launch route, at 3 GiB and at the largest accepted extent
+GEMM_FAR_EPI = "bias_bf16"
+GEMM_FAR = [(role, name, ext) for role in ("A", "W") for name, ext in (("3GiB", 3 << 30), ("max", (1 << 32) - 1))]
+# one real modulation_gemm chunk (ops.modulation_gemm): thin-row kernel, the stacked planes of 8 vectors, K = 3072, W rows
+# contiguous over just under 4 GiB; checked rows: the first, the middle and the last 256
+MOD_CHUNK = dict(M=16, K=3072, N=((1 << 32) - 1) // (3072 * 2) // 256 * 256)
+# operands the audit calls 64-bit clean: one case each with the last row more than 4 GiB from the base
+PAST_4GIB = 5 << 30
+GEMM_PAST = [("pp256", "bias_bf16", "out"), ("pp256", "bias_f32", "out"), ("pp256", "gate_items_bf16", "resid"),
+             ("pp256", "split_gelu", "out2"), ("pp256", "qkv_single_qpre_f32_f16", "q_prerope"),
+             ("thin_4x4", "bias_f32", "out"), ("thin_4x4", "qkv_single_qpre_f32_f16", "q_prerope"),
+             ("classic_128", "gate_items_bf16", "resid"), ("fp8", "split_gelu", "out2")]
+ATTN_PAST = ["q", "out", "out_f32"]
+ROWOP_PAST = [("ln_rows6_split_seg15", "x"), ("ln_rows6_split_seg15", "out"), ("ln_rows6_split_seg15", "out_lo"),
+              ("ln_split_H264_M9", "x"), ("ln_split_H264_M9", "out"), ("ln_split_H264_M9", "out_lo"),
+              ("ln_bf16_H264_M8", "x"), ("ln_bf16_H264_M8", "out"), ("ln_fp8_f32_H4096_seg15", "out"),
+              ("qk_h3_seg16_pre", "qkv"), ("logits_bf16_C5_L4352", "img"), ("logits_f32_C8_L257_dim4096", "img"),
+              ("fused4_bf16_vectors", "img"), ("fused8_f32_vectors", "img")]
+
+
+def far_ld(rows: int, itemsize: int, extent: int) -> int:
+    """The largest row stride (a multiple of 64 elements) with rows * ld * itemsize <= extent."""
+    return extent // (rows * itemsize) // 64 * 64
+
+
+def gemm_epis_for(route: str) -> list:
+    return [e for e in GEMM_EPIS if G.compatible(route, e)]
+
+
+def gemm_kernel_of(route: str) -> str:
+    """The kernel instantiation a route of gemm_route_cases.ROUTES launches for its main or thin part."""
+    r = G.ROUTES[route]
+    if isinstance(r.thin, tuple):
+        return f"ca_gemm_thin_kernel<{r.thin[0]},{r.thin[1]}>"
+    fam = {L.GEMM_KERNEL_CLASSIC: "ca_gemm_kernel", L.GEMM_KERNEL_PP: "ca_gemm_pp_kernel",
+           L.GEMM_KERNEL_PP_FP8: "ca_gemm_pp_fp8_kernel"}[r.kernel]
+    return f"{fam}<{G.TILE_W[r.tile]}>" + ("+thin tiles" if r.thin == "walk" else "")
+
+
+# ---- b. far rows (attention): (nq, n0, n1, nq0), the value of (n0 + n1) * ldkv * 2 aimed at
+ATTN_FAR = {
+    "seg0_3GiB": ((70, 389, 0, 30), 3 << 30),
+    "seg0_max": ((70, 389, 0, 30), LINE - 1),
+    "seg1_3GiB": ((70, 100, 289, 30), 3 << 30),      # tile 1 straddles the segments, tile 6 is ragged
+    "seg1_max": ((70, 100, 289, 30), LINE - 1),
+}
+# ---- c. limits: name -> (keys, the smallest ldkv the validator refuses)
+ATTN_LIMITS = {
+    "(n0 + n1) * ldkv * 2 < 2^32": (512, 1 << 22),
+    "64 * ldkv * 2 < 2^32": (32, 1 << 25),
+}
+
+
+def far_ldkv(nk: int, extent: int) -> int:
+    """The largest row stride (a multiple of 8 elements) with nk * ldkv * 2 <= extent."""
+    return extent // (2 * nk) // 8 * 8
+
+
+def attn_accepts(n0: int, n1: int, ldkv: int) -> bool:
+    """The extent check of ca_attn_fwd_impl."""
+    return (n0 + n1) * ldkv * 2 < LINE and 64 * ldkv * 2 < LINE
+
+
+# ---- emulation of the 32-bit expressions (ca_attn.hip:94-95, ca_attn4_kernel.inc:60-61, 106, 128)
+def attn_offsets_u32(n0: int, n1: int, ldkv: int, slip=None):
+    """For every 16-byte K access of the fast path of ca_attn4_kernel (full tiles inside one segment): the kernel's
+    32-bit arithmetic (scalar offset SO = tile * 64 * ldkv * 2 in uint32 plus lane offset koff = (r * ldkv + chunk * 8)
+    * 2 in uint32, added to the descriptor base in 64 bits) and the exact 64-bit byte offset from key 0.
+    Returns (emulated uint64 array, exact uint64 array).  slip: None | "sign_extend" (the scalar offset sign-extended) |
+    "row_ld_i32" (row * ldkv as a signed 32-bit product).  (SO + koff stays below 2^32 for every accepted extent, so
+    adding the two in 32 bits is no slip; the dropped carry into bit 32 is a slip of the base: base_address_slips.)"""
+    nk = n0 + n1
+    nt_full = nk // 64
+    t_str = n0 // 64 if (n0 % 64 and n0 < nk) else -1
+    tiles = np.array([t for t in range(nt_full) if t != t_str], dtype=np.uint64)
+    r = np.arange(64, dtype=np.uint64)
+    chunk = np.uint64(15)                                       # the highest 16-byte chunk of a 256-byte head row
+    exact = ((tiles[:, None] * np.uint64(64) + r[None, :]) * np.uint64(ldkv) + chunk * np.uint64(8)) * np.uint64(2)
+    with np.errstate(over="ignore"):
+        so = (tiles.astype(np.uint32) * np.uint32(64)) * np.uint32(ldkv) * np.uint32(2)
+        koff = (r.astype(np.uint32) * np.uint32(ldkv) + np.uint32(15 * 8)) * np.uint32(2)
+        if slip == "row_ld_i32":
+            key = (tiles[:, None] * np.uint64(64) + r[None, :]).astype(np.int64)
+            prod = (key * ldkv * 2 + 240).astype(np.int32)     # one signed 32-bit product for the whole offset
+            return prod.astype(np.int64).astype(np.uint64).ravel(), exact.ravel()
+        emu = so[:, None].astype(np.uint64) + koff[None, :].astype(np.uint64)
+        if slip == "sign_extend":
+            emu = (so[:, None].astype(np.int32).astype(np.int64) + koff[None, :].astype(np.uint64).astype(np.int64)
+                   ).astype(np.uint64)
+    return emu.ravel(), exact.ravel()
+
+
+def base_address_slips(start: int, nbytes: int, step: int = 16):
+    """The absolute addresses of a buffer's 16-byte accesses, and the same with the low half sign-extended / the carry
+    into bit 32 dropped (base halves rebuilt wrongly from two readfirstlanes)."""
+    a = np.arange(start, start + nbytes, step, dtype=np.uint64)
+    lo = (a & np.uint64(0xffffffff)).astype(np.uint32)
+    hi = a >> np.uint64(32)
+    sign = ((hi.astype(np.int64) << 32) + lo.astype(np.int32).astype(np.int64)).astype(np.uint64)
+    base_hi = np.uint64(start >> 32)
+    nocarry = (base_hi << np.uint64(32)) | lo.astype(np.uint64)
+    return a, sign, nocarry

@@ -226,6 +226,8 @@ CASES += [
          dict(nt=7, dim=256, tmax=1.0, tf=1000.0), 111),
     Case("temb_dim256_guidance", "ca_timestep_embedding_f32", "ca_timestep_embedding_kernel", "temb",
          dict(nt=5, dim=256, tmax=3.5, tf=1000.0), 112),
+    Case("temb_grid_stride", "ca_timestep_embedding_f32", "ca_timestep_embedding_kernel", "temb",
+         dict(nt=8200, dim=256, tmax=1.0, tf=1000.0), 113),                    # nt dim / 2 = 1.05 M > 4096 x 256 threads
 ]
 BY_ID = {c.id: c for c in CASES}
 

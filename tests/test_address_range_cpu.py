@@ -1,0 +1,167 @@
+"""The address-range cases (tests/address_range_cases.py, tests/placement.py) without a GPU: every kernel and operand
+role of the attention and GEMM case tables has a placement case, the limits DESIGN.md ("Address arithmetic") states
+are the ones at which the kernels' 32-bit expressions stop equalling the 64-bit address, the GEMM limit goes through
+ca_gemm_plan, and named slips move at least one touched 16-byte access on the chosen placements."""
+import numpy as np
+import pytest
+
+import address_range_cases as C
+import attn_cases as A
+import gemm_route_cases as G
+import placement as PL
+from conceptattention_amd import _lib as L
+
+LINE = 1 << 32
+
+# Roles the audit proves are never dereferenced at a placement of their own: none
+NEVER_DEREFERENCED = {}
+
+
+def test_every_attention_kernel_and_role_has_a_placement_case():
+    kernels = {c.kernel for c in A.CASES}
+    assert kernels == set(C.ATTN_PLACEMENT), kernels ^ set(C.ATTN_PLACEMENT)
+    for kernel, cid in C.ATTN_PLACEMENT.items():
+        case = A.BY_ID[cid]
+        assert case.kernel == kernel and len(case.probs) == 1
+        p = case.probs[0]
+        have = {"q", "k0/v0", "out"}
+        if p.two_q:
+            have |= {"q1", "out1"}
+        if p.n1:
+            have.add("k1/v1")
+        if p.f32:
+            have.add("out_f32")
+        if p.hm_C:
+            have |= {"hm_con", "hm_part"}
+        assert have == set(C.ATTN_ROLES[kernel]), (kernel, have ^ set(C.ATTN_ROLES[kernel]))
+    all_roles = {"q", "q1", "k0/v0", "k1/v1", "out", "out1", "out_f32", "hm_con", "hm_part"}
+    assert set(C.ATTN_ROLES["ca_attn4_kernel"]) == all_roles == set(C.ATTN_ROLES["ca_attn4_qk16_kernel"])
+    # the scaling kernel takes no heat-map operands: the validator refuses them ("... and the pre-scaled-q kernel")
+    assert all_roles - set(C.ATTN_ROLES["ca_attn_kernel<8>"]) == {"hm_con", "hm_part"}
+    assert not any(p.hm_C for c in A.CASES if c.form == "scale" for p in c.probs)
+    assert set(C.ATTN_PAST) == {"q", "out", "out_f32"}
+    assert {f for f in A.FORMS} == {"scale", "pre", "qk16"} and len(C.ATTN_FAR) == 4       # far rows: every form x 4
+
+
+def test_every_gemm_route_and_role_has_a_placement_and_a_far_row_case():
+    """The GPU file runs gemm_roles(epi, fp8) for every (route, epi) of gemm_epis_for, and GEMM_FAR for every route."""
+    placed = {}
+    for route in G.ROUTES:
+        epis = C.gemm_epis_for(route)
+        assert epis, route
+        assert all(G.Case(route, e) in G.CASES for e in epis), route     # existing cases of the table
+        placed[C.gemm_kernel_of(route)] = set().union(*(C.gemm_roles(e, G.ROUTES[route].fp8) for e in epis))
+    assert len(placed) >= 12, placed            # 4 classic, 3 ping-pong (+ thin tiles in the walk), 4 thin-row, fp8
+    for kernel, roles in placed.items():
+        want = set(C.GEMM_ISSUE_ROLES)
+        if "fp8" not in kernel:
+            want -= {"scales"}
+        if not any(G.compatible(r, "qkv_single_qpre_f32_f16") for r in G.ROUTES if C.gemm_kernel_of(r) == kernel):
+            want -= {"q_prerope", "rope"}       # the qkv epilogue exists under the 256-wide ping-pong tile, NW = 4 only
+        assert want <= roles, (kernel, want - roles)
+    assert {r for r, _, _ in C.GEMM_FAR} == {"A", "W"} and {n for _, n, _ in C.GEMM_FAR} == {"3GiB", "max"}
+    assert C.MOD_CHUNK["K"] == 3072 and LINE - (1 << 21) < C.MOD_CHUNK["N"] * 3072 * 2 < LINE and C.MOD_CHUNK["N"] % 256 == 0
+    assert {(e, r) for _, e, r in C.GEMM_PAST} >= {("bias_bf16", "out"), ("bias_f32", "out"), ("gate_items_bf16", "resid"),
+                                                   ("split_gelu", "out2"), ("qkv_single_qpre_f32_f16", "q_prerope")}
+
+
+def test_every_rowop_form_and_plane_has_a_placement_case():
+    """The GPU file places every case of rowop_cases.py, once per plane of rowop_roles(case)."""
+    import rowop_cases as R
+    assert len({c.kernel for c in R.CASES}) == 35
+    for c in R.CASES:
+        roles = C.rowop_roles(c)
+        assert len(roles) == len(set(roles)) >= 2, c.id
+    past = {(R.BY_ID[cid].op, role) for cid, role in C.ROWOP_PAST}
+    assert past >= {("ln", "x"), ("ln", "out"), ("ln", "out_lo"), ("qk", "qkv"), ("logits", "img"), ("fused", "img")}
+    assert R.BY_ID["temb_grid_stride"].shape["nt"] * 128 > 4096 * 256     # a second trip through the grid-stride loop
+
+
+def test_no_role_is_left_out():
+    assert not NEVER_DEREFERENCED
+
+
+@pytest.mark.parametrize("base", [0x7F0000000000, 0x7F00C0000000 - 1, 0x7F0040000010, 0x7F00FFFFF000, 0x100000000])
+def test_arena_boundary_and_straddle_arithmetic(base):
+    b = PL.boundary_in(base)
+    assert b % LINE == 0 and b - base >= PL.GIB and base + PL.ARENA_BYTES - b >= PL.GIB
+    s = PL.straddle_start(b, PL.mid(40, 30, 3 * 384 + 24, 384, 384), 2, 80 * (3 * 384 + 24) * 2)
+    assert s % 16 == 0 and s < b < s + 80 * (3 * 384 + 24) * 2
+    lo = max(base, b - 2 * PL.GIB)
+    assert (lo >> 31) & 1 and ((b - 1) >> 31) & 1 and (lo >> 32) == ((b - 1) >> 32)
+
+
+def test_attention_limits_are_where_the_32_bit_offsets_stop_being_exact():
+    # accepted far-row extents: the emulated 32-bit arithmetic equals the 64-bit offset for every access
+    for name, ((nq, n0, n1, nq0), extent) in C.ATTN_FAR.items():
+        ld = C.far_ldkv(n0 + n1, extent)
+        assert C.attn_accepts(n0, n1, ld) and ld % 8 == 0, name
+        if "max" in name:
+            assert LINE - (n0 + n1) * ld * 2 < ld * 2, "the last row ends within one row of 2^32"
+        emu, exact = C.attn_offsets_u32(n0, n1, ld)
+        assert emu.size and np.array_equal(emu, exact), name
+        assert int(exact.max()) + 16 <= (n0 + n1) * ld * 2 < LINE
+    for name, (nk, ld_at) in C.ATTN_LIMITS.items():
+        assert C.attn_accepts(nk, 0, ld_at - 8) and not C.attn_accepts(nk, 0, ld_at), name
+    # at the first limit the scalar tile offset wraps; one tile more of keys and an access is wrong
+    nk, ld_at = C.ATTN_LIMITS["(n0 + n1) * ldkv * 2 < 2^32"]
+    emu, exact = C.attn_offsets_u32(nk, 0, ld_at - 8)
+    assert np.array_equal(emu, exact)
+    emu, exact = C.attn_offsets_u32(nk + 64, 0, ld_at)
+    assert not np.array_equal(emu, exact)
+    # at the second limit koff of row 63 needs 64 * ldkv * 2 > 2^32 - one row: the lane offset itself wraps
+    ld2 = C.ATTN_LIMITS["64 * ldkv * 2 < 2^32"][1]
+    with np.errstate(over="ignore"):
+        koff = (np.arange(64, dtype=np.uint32) * np.uint32(ld2 - 8) + np.uint32(120)) * np.uint32(2)
+    assert np.array_equal(koff.astype(np.uint64), (np.arange(64, dtype=np.uint64) * np.uint64(ld2 - 8) + np.uint64(120)) * np.uint64(2))
+    with np.errstate(over="ignore"):
+        koff = (np.arange(65, dtype=np.uint32) * np.uint32(ld2) + np.uint32(120)) * np.uint32(2)
+    assert int(koff[64]) != 64 * ld2 * 2 + 240
+
+
+def test_gemm_operand_limit_through_the_plan():
+    """M * lda * 2 and N * ldw * 2 below 2^32 (ca_gemm.hip plan_gemm), through ca_gemm_plan(n_cu=256): no launch."""
+    from conceptattention_amd import ops
+    K = 3072
+
+    def plan(M, N, lda, ldw):
+        arr = (L.GemmProblem * 1)()
+        G._raw_problem(arr[0], M, N, K, L.EPI_BIAS)
+        arr[0].lda, arr[0].ldw = lda, ldw
+        return ops.gemm_plan(arr, tile=L.TILE_PP_256x256, n_cu=256, fp8=False)
+
+    M, lda = 2048, LINE // (2 * 2048)                 # M * lda * 2 == 2^32 exactly
+    assert M * lda * 2 == LINE
+    plan(M, 256, lda - 8, K)
+    with pytest.raises(ValueError, match="operand larger than 4 GiB"):
+        plan(M, 256, lda, K)
+    N, ldw = 4096, LINE // (2 * 4096)
+    plan(256, N, K, ldw - 8)
+    with pytest.raises(ValueError, match="operand larger than 4 GiB"):
+        plan(256, N, K, ldw)
+    # the 32-bit row offsets of the staging loads equal the 64-bit ones under the limit, and wrap at it
+    with np.errstate(over="ignore"):
+        off = np.arange(M, dtype=np.uint32) * np.uint32(lda - 8) * np.uint32(2) + np.uint32(112)
+        assert np.array_equal(off.astype(np.uint64), np.arange(M, dtype=np.uint64) * np.uint64(lda - 8) * np.uint64(2) + np.uint64(112))
+        off = np.arange(M + 1, dtype=np.uint32) * np.uint32(lda) * np.uint32(2)
+        assert int(off[M]) != M * lda * 2
+
+
+@pytest.mark.parametrize("slip", ["sign_extend", "row_ld_i32"])
+def test_offset_slips_move_an_access_on_the_far_row_cases(slip):
+    for name, ((nq, n0, n1, nq0), extent) in C.ATTN_FAR.items():
+        emu, exact = C.attn_offsets_u32(n0, n1, C.far_ldkv(n0 + n1, extent), slip)
+        assert int((emu != exact).sum()) >= 1, (slip, name)
+
+
+def test_base_address_slips_move_an_access_on_the_placements():
+    """A sign-extended low half breaks every access of a bit31 buffer; a dropped carry into bit 32 breaks the upper
+    part of a straddling one (and nothing of a bit31 buffer: why both placements are run)."""
+    B = PL.boundary_in(0x7F0012345000)
+    n = 1 << 20
+    a, sign, nocarry = C.base_address_slips(B - 3 * n, n)                 # bit31
+    assert (a != sign).all() and (a == nocarry).all()
+    s = PL.straddle_start(B, n // 4, 2, n)
+    a, sign, nocarry = C.base_address_slips(s, n)                          # straddle
+    assert (a != nocarry).any() and (a != sign).any()
+    assert (a[a >= B] != nocarry[a >= B]).all()

@@ -17,6 +17,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import attn_cases as A  # noqa: E402
+import placement  # noqa: E402
 from conceptattention_amd import ops  # noqa: E402
 
 DEV = "cuda"
@@ -28,23 +29,35 @@ def _bytes(t):
     return t.contiguous().view(torch.uint8)
 
 
-def launch(case, inp):
-    """Run the case; returns per problem the output buffers and the owned masks."""
+def launch(case, inp, alloc=None):
+    """Run the case; returns per problem the output buffers and the owned masks.  `alloc` (tests/placement.py) decides
+    where every buffer the kernel sees lies; by default they are ordinary torch allocations."""
+    al = alloc or placement.Plain(DEV)
     D = case.heads * 128
     attns, res = [], []
     for p, x in zip(case.probs, inp):
-        qbuf, kvbuf = x.qbuf.to(DEV), x.kvbuf.to(DEV)
+        nq1 = p.nq - p.nq0 if p.two_q else 0
+        nq0 = p.nq - nq1
+        qroles = {"q": placement.mid(x.gq0, nq0, x.ldq, 0, D)}
+        oroles = {"out": placement.mid(x.gq0, nq0, x.ldo, 0, D)}
+        if nq1:
+            qroles["q1"] = placement.mid(x.gq1, nq1, x.ldq, 0, D)
+            oroles["out1"] = placement.mid(x.gq1, nq1, x.ldo, 0, D)
+        kroles = {"k0/v0": placement.mid(x.gk0, p.n0, x.ldkv, D, D)}
+        if p.n1:
+            kroles["k1/v1"] = placement.mid(x.gk1, p.n1, x.ldkv, D, D)
+        qbuf, kvbuf = al.to(x.qbuf, qroles), al.to(x.kvbuf, kroles)
         gx = dataclasses.replace(x, qbuf=qbuf, kvbuf=kvbuf)
         q0, q1, k0, v0, k1, v1 = A.views(case, p, gx)
-        nq1 = q1.shape[0] if q1 is not None else 0
-        nq0 = p.nq - nq1
-        out = torch.full((x.out_rows, x.ldo), NAN, device=DEV, dtype=torch.bfloat16)
+        assert nq1 == (q1.shape[0] if q1 is not None else 0)
+        out = al.full((x.out_rows, x.ldo), NAN, torch.bfloat16, oroles)
         own = torch.zeros(out.shape, dtype=torch.bool, device=DEV)
         own[x.gq0:x.gq0 + nq0, :D] = True
         own[x.gq1:x.gq1 + nq1, :D] = True
-        f32 = torch.full((p.nq + 1, x.ldo32), NAN, device=DEV) if p.f32 else None
-        hmcon = x.hmbuf.to(DEV) if x.hmbuf is not None else None
-        hmp = torch.full((case.heads, nq1, 8), NAN, device=DEV) if p.hm_C else None
+        f32 = al.full((p.nq + 1, x.ldo32), NAN, torch.float32,
+                      {"out_f32": placement.mid(0, p.nq, x.ldo32, 0, D)}) if p.f32 else None
+        hmcon = al.to(x.hmbuf, {"hm_con": placement.mid(0, p.hm_C, x.ldhc, 0, D)}) if x.hmbuf is not None else None
+        hmp = al.full((case.heads, nq1, 8), NAN, torch.float32, {"hm_part": None}) if p.hm_C else None
         attns.append(ops.Attn(q0, out[x.gq0:x.gq0 + nq0, :D], k0, v0, k1, v1,
                               out_f32=f32[:p.nq, :D] if f32 is not None else None,
                               q1=q1, out1=out[x.gq1:x.gq1 + nq1, :D] if nq1 else None,

@@ -9,6 +9,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import gemm_route_cases as G  # noqa: E402
+import placement  # noqa: E402
 from conceptattention_amd import _lib as L  # noqa: E402
 from conceptattention_amd import ops  # noqa: E402
 
@@ -26,34 +27,44 @@ def shape_or_skip(route, epi, K):
     return s
 
 
-def build(x: G.Inputs):
-    """ops.Gemm of the problem on the device and a function that returns its outputs by name."""
+def build(x: G.Inputs, alloc=None, keep=None):
+    """ops.Gemm of the problem on the device and a function that returns its outputs by name.  `alloc`
+    (tests/placement.py) decides where every buffer lies (default: ordinary torch allocations); `keep`, a dict,
+    receives the device buffers by operand role."""
+    al = alloc or placement.Plain(DEV)
     e = G.EPIS[x.epi]
     M, N, ns = x.M, x.N, x.n_split
-    a, w, bias = x.a.to(DEV), x.w.to(DEV), x.bias.to(DEV)
+    nan = float("nan")
+    a, w, bias = al.to(x.a, {"A": None}), al.to(x.w, {"W": None}), al.to(x.bias, {"bias": None})
+    bufs = dict(A=a, W=w, bias=bias)
     kw = {}
     if x.fp8:
-        kw.update(a_scale=x.a_scale.to(DEV), w_scale=x.w_scale.to(DEV))
+        kw.update(a_scale=al.to(x.a_scale, {"scales": None}), w_scale=al.to(x.w_scale, {"w_scale": None}))
+        bufs.update(scales=kw["a_scale"], w_scale=kw["w_scale"])
     get = {}
     if e["epi"] in (L.EPI_BIAS, L.EPI_GELU_TANH):
-        out = torch.full((M, N), float("nan"), device=DEV, dtype=torch.float32 if e["f32"] else torch.bfloat16)
+        out = al.full((M, N), nan, torch.float32 if e["f32"] else torch.bfloat16, {"out": None})
         get["out"] = lambda: out
     elif e["epi"] == L.EPI_GATE_RESIDUAL:
-        out = x.resid.to(DEV).clone()                    # in place: resid is out
-        kw.update(resid=out, gate=x.gate.to(DEV), gate2=x.gate2.to(DEV), gate_rows=x.gate_rows,
-                  gate_stride=x.gate_stride, gate_item_rows=x.gate_item_rows, gate2_item_rows=x.gate2_item_rows)
+        out = al.to(x.resid, {"resid": None, "out": None})   # in place: resid is out
+        kw.update(resid=out, gate=al.to(x.gate, {"gates": None}), gate2=al.to(x.gate2, {"gate2": None}),
+                  gate_rows=x.gate_rows, gate_stride=x.gate_stride, gate_item_rows=x.gate_item_rows,
+                  gate2_item_rows=x.gate2_item_rows)
+        bufs.update(gates=kw["gate"], gate2=kw["gate2"])
         get["out"] = lambda: out
     elif e["epi"] == L.EPI_SPLIT_GELU:
-        out = torch.full((M, ns), float("nan"), device=DEV, dtype=torch.bfloat16)
-        buf2 = torch.full((M, N - ns + 24), float("nan"), device=DEV, dtype=torch.bfloat16)
+        out = al.full((M, ns), nan, torch.bfloat16, {"out": None})
+        buf2 = al.full((M, N - ns + 24), nan, torch.bfloat16, {"out2": None})
         out2 = buf2[:, 8:8 + N - ns]                     # at a column offset of a wider buffer
         kw.update(out2=out2, n_split=ns)
+        bufs.update(out2=buf2, out2_cols=(8, 8 + N - ns))
         get["out"], get["out2"] = (lambda: out), (lambda: out2)
     else:
         hd = ns // 3
-        out = torch.full((M, min(N, ns)), float("nan"), device=DEV, dtype=torch.bfloat16)
-        kw.update(n_split=ns, norm_q=x.norm_q.to(DEV), norm_k=x.norm_k.to(DEV), rope=x.rope.to(DEV),
-                  q_out_scale=e["qos"], qk_f16=bool(e.get("f16")))
+        out = al.full((M, min(N, ns)), nan, torch.bfloat16, {"out": None})
+        kw.update(n_split=ns, norm_q=al.to(x.norm_q, {"norm_q": None}), norm_k=al.to(x.norm_k, {"norm_k": None}),
+                  rope=al.to(x.rope, {"rope": None}), q_out_scale=e["qos"], qk_f16=bool(e.get("f16")))
+        bufs.update(norm_q=kw["norm_q"], norm_k=kw["norm_k"], rope=kw["rope"])
         qk = (lambda t: t.view(torch.float16)) if e.get("f16") else (lambda t: t)
         get["q"] = lambda: qk(out[:, :hd])
         if N > hd:
@@ -61,25 +72,30 @@ def build(x: G.Inputs):
         if N >= ns:
             get["v"] = lambda: out[:, 2 * hd:3 * hd]
         if N > ns:
-            buf2 = torch.full((M, N - ns + 24), float("nan"), device=DEV, dtype=torch.bfloat16)
+            buf2 = al.full((M, N - ns + 24), nan, torch.bfloat16, {"out2": None})
             out2 = buf2[:, 16:16 + N - ns]
             kw["out2"] = out2
+            bufs.update(out2=buf2, out2_cols=(16, 16 + N - ns))
             get["out2"] = lambda: out2
         if e["qpre"] is not None:
             if e["qpre"] == 3:
-                pre = x.qraw.to(DEV).clone()
+                pre = al.to(x.qraw, {"q_prerope": None})
             else:
-                pre = torch.full((M, hd), float("nan"), device=DEV,
-                                 dtype=torch.bfloat16 if e["qpre"] == 0 else torch.float32)
+                pre = al.full((M, hd), nan, torch.bfloat16 if e["qpre"] == 0 else torch.float32, {"q_prerope": None})
             kw.update(q_prerope=pre, qpre_raw=e["qpre"] == 2, qpre_add=e["qpre"] == 3)
+            bufs["q_prerope"] = pre
             get["q_prerope"] = lambda: pre
+    bufs["out"] = out
+    if keep is not None:
+        keep.update(bufs)
     g = ops.Gemm(a, w, bias, out, e["epi"], **kw)
     return g, (lambda: {k: f().clone() for k, f in get.items()})
 
 
-def launch(problems, tile, route=None, expect=None):
-    """Plan (asserting the route), launch, return the outputs of every problem."""
-    gs = [build(x) for x in problems]
+def launch(problems, tile, route=None, expect=None, alloc=None, keep=None):
+    """Plan (asserting the route), launch, return the outputs of every problem.  `alloc` / `keep`: as in build (keep
+    receives the buffers of the first problem)."""
+    gs = [build(x, alloc, keep if i == 0 else None) for i, x in enumerate(problems)]
     info = ops.gemm_plan([g for g, _ in gs], tile=tile)
     if route is not None:
         assert G.route_matches(info, G.ROUTES[route]), (route, info)

@@ -10,6 +10,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import placement  # noqa: E402
 import rowop_cases as R  # noqa: E402
 from conceptattention_amd import _lib as L  # noqa: E402
 from conceptattention_amd import ops  # noqa: E402
@@ -34,24 +35,36 @@ def _nan(shape, dtype):
     return torch.full(shape, NAN, device=DEV, dtype=dtype)
 
 
-def run_ln(c, inp):
+def _al(alloc):
+    """The allocator of a run helper (tests/placement.py): where every buffer the kernel sees lies; by default ordinary
+    torch allocations.  Every buffer is named by its operand role."""
+    return alloc or placement.Plain(DEV)
+
+
+def _seg_vectors(al, vecs, role):
+    """Per-segment vectors: the middle segment's carries the role (one buffer per role can straddle)."""
+    return [al.to(v, {role: None} if i == len(vecs) // 2 else {f"{role}[{i}]": None}) for i, v in enumerate(vecs)]
+
+
+def run_ln(c, inp, alloc=None):
+    al = _al(alloc)
     s = c.shape
     M, H = s["M"], s["H"]
-    x = inp["x"].to(DEV)
+    x = al.to(inp["x"], {"x": None})
     x0 = x.clone()
-    segs = [(re, sh.to(DEV), sc.to(DEV)) for re, sh, sc in zip(s["segs"], inp["shift"], inp["scale"])]
+    segs = list(zip(s["segs"], _seg_vectors(al, inp["shift"], "shift"), _seg_vectors(al, inp["scale"], "scale")))
     pads = []
     if s["out"] == "fp8":
-        buf = torch.full((M, s["ldo"]), 0xFF, device=DEV, dtype=torch.uint8)
-        scale = _nan((M,), torch.float32)
+        buf = al.full((M, s["ldo"]), 0xFF, torch.uint8, {"out": None})
+        scale = al.full((M,), NAN, torch.float32, {"out_scale": None})
         pads.append((buf, buf.clone(), H))
         ops.ln_modulate(x[:, :H], buf[:, :H], segs, out_scale=scale)
         got = {"scale": scale, "q": _fp8(buf[:, :H])}
     else:
-        buf = _nan((M, s["ldo"]), torch.bfloat16)
+        buf = al.full((M, s["ldo"]), NAN, torch.bfloat16, {"out": None})
         pads.append((buf, buf.clone(), H))
         if s["out"] == "split":
-            lo = _nan((M, s["ldlo"]), torch.bfloat16)
+            lo = al.full((M, s["ldlo"]), NAN, torch.bfloat16, {"out_lo": None})
             pads.append((lo, lo.clone(), H))
             ops.ln_modulate(x[:, :H], buf[:, :H], segs, out_lo=lo[:, :H])
             got = {"out": buf[:, :H], "hi+lo": buf[:, :H].double() + lo[:, :H].double()}
@@ -63,34 +76,38 @@ def run_ln(c, inp):
     return got, pads
 
 
-def run_quant(c, inp):
+def run_quant(c, inp, alloc=None):
+    al = _al(alloc)
     s = c.shape
     M, K = s["M"], s["K"]
-    x = inp["x"].to(DEV)
-    buf = torch.full((M, s["ldo"]), 0xFF, device=DEV, dtype=torch.uint8)
-    scale = _nan((M,), torch.float32)
+    x = al.to(inp["x"], {"x": None})
+    x0 = x.clone()
+    buf = al.full((M, s["ldo"]), 0xFF, torch.uint8, {"out": None})
+    scale = al.full((M,), NAN, torch.float32, {"out_scale": None})
     pads = [(buf, buf.clone(), K)]
     ops.quantize_rows_fp8(x[:, :K], out=buf[:, :K], out_scale=scale)
     torch.cuda.synchronize()
+    assert_same_bytes(x, x0, "x")
     zero = (inp["x"][:, :K].float() == 0).all(1)
     assert bool((buf[zero.to(DEV), :K] == 0).all()), "zero rows: bytes must be 0"
     assert bool((scale[zero.to(DEV)] == 1).all()), "zero rows: scale must be 1"
     return {"scale": scale, "q": _fp8(buf[:, :K])}, pads
 
 
-def run_qk(c, inp):
+def run_qk(c, inp, alloc=None):
+    al = _al(alloc)
     s = c.shape
     M, nh = s["M"], s["heads"]
     W = nh * 128
-    qkv = inp["qkv"].to(DEV)
+    qkv = al.to(inp["qkv"], {"qkv": None})
     q0 = qkv.clone()
-    segs = [(re, a.to(DEV), b.to(DEV)) for re, a, b in zip(s["segs"], inp["q_scale"], inp["k_scale"])]
+    segs = list(zip(s["segs"], _seg_vectors(al, inp["q_scale"], "q_scale"), _seg_vectors(al, inp["k_scale"], "k_scale")))
     pads, pre = [(qkv, q0, 3 * W)], None
     if s["pre"]:
-        pbuf = _nan((M, s["ldp"]), torch.bfloat16)
+        pbuf = al.full((M, s["ldp"]), NAN, torch.bfloat16, {"q_prerope": None})
         pads.append((pbuf, pbuf.clone(), W))
         pre = pbuf[:, :W]
-    ops.qknorm_rope(qkv[:, :3 * W], nh, segs, inp["rope"].to(DEV), q_prerope=pre)
+    ops.qknorm_rope(qkv[:, :3 * W], nh, segs, al.to(inp["rope"], {"rope": None}), q_prerope=pre)
     torch.cuda.synchronize()
     got = {"q": qkv[:, :W], "k": qkv[:, W:2 * W], "v": qkv[:, 2 * W:3 * W]}
     if pre is not None:
@@ -98,23 +115,24 @@ def run_qk(c, inp):
     return got, pads
 
 
-def run_qpre(c, inp):
+def run_qpre(c, inp, alloc=None):
+    al = _al(alloc)
     s = c.shape
     M, W = s["M"], s["heads"] * 128
-    x = inp["x"].to(DEV)
+    x = al.to(inp["x"], {"x": None})
     pads = [(x, x.clone(), W)]
     d = None
     if s["d"]:
-        dd = inp["d"].to(DEV)
+        dd = al.to(inp["d"], {"d": None})
         d0 = dd.clone()
         d = dd[:, :W]
-    sc = inp["scale"].to(DEV)
+    sc = al.to(inp["scale"], {"scale": None})
     got = {}
     if s["rope"]:
-        qb = _nan((M, s["ldq"]), torch.bfloat16)
+        qb = al.full((M, s["ldq"]), NAN, torch.bfloat16, {"q_out": None})
         pads.append((qb, qb.clone(), W))
-        ops.qpre_finish(x[:, :W], d, sc, s["heads"], rope=inp["rope"].to(DEV), q_out=qb[:, :W], q_out_scale=s["qos"],
-                        q_f16=s["f16"])
+        ops.qpre_finish(x[:, :W], d, sc, s["heads"], rope=al.to(inp["rope"], {"rope": None}), q_out=qb[:, :W],
+                        q_out_scale=s["qos"], q_f16=s["f16"])
         got["q"] = qb[:, :W].view(torch.float16) if s["f16"] else qb[:, :W]
     else:
         ops.qpre_finish(x[:, :W], d, sc, s["heads"])
@@ -125,26 +143,29 @@ def run_qpre(c, inp):
     return got, pads
 
 
-def run_gemv(c, inp):
+def run_gemv(c, inp, alloc=None):
+    al = _al(alloc)
     s = c.shape
     nv, K, N = s["nv"], s["K"], s["N"]
-    out = _nan((nv, s["ldo"]), torch.float32)
+    out = al.full((nv, s["ldo"]), NAN, torch.float32, {"out": None})
     if s["acc"]:
         out[:, :N] = inp["out0"].to(DEV)
     pads = [(out, out.clone(), N)]
-    x = inp["x"].to(DEV)
-    bias = inp["bias"].to(DEV) if s["bias"] else None
-    ops.gemv(x[:, :K], inp["w"].to(DEV), bias, out[:, :N], silu_input=s["silu"], accumulate=s["acc"])
+    x = al.to(inp["x"], {"x": None})
+    bias = al.to(inp["bias"], {"bias": None}) if s["bias"] else None
+    ops.gemv(x[:, :K], al.to(inp["w"], {"w": None}), bias, out[:, :N], silu_input=s["silu"], accumulate=s["acc"])
     torch.cuda.synchronize()
     return {"out": out[:, :N]}, pads
 
 
-def run_split(c, inp):
+def run_split(c, inp, alloc=None):
+    al = _al(alloc)
     s = c.shape
     rows, K = s["rows"], s["K"]
-    x = inp["x"].to(DEV)
+    x = al.to(inp["x"], {"x": None})
     x0 = x.clone()
-    hi, lo = _nan((rows, s["ldo"]), torch.bfloat16), _nan((rows, s["ldo"]), torch.bfloat16)
+    hi = al.full((rows, s["ldo"]), NAN, torch.bfloat16, {"hi": None})
+    lo = al.full((rows, s["ldo"]), NAN, torch.bfloat16, {"lo": None})
     pads = [(hi, hi.clone(), K), (lo, lo.clone(), K)]
     (ops.silu_split if s["silu"] else ops.split_planes)(x[:, :K], hi[:, :K], lo[:, :K])
     torch.cuda.synchronize()
@@ -154,13 +175,14 @@ def run_split(c, inp):
     return {"hi": hi[:, :K], "lo": lo[:, :K]}, pads
 
 
-def run_combine(c, inp):
+def run_combine(c, inp, alloc=None):
     """ca_modulation_combine_f32 on its own (ops calls it only inside modulation_gemm), through the C ABI."""
+    al = _al(alloc)
     s = c.shape
     nv, N = s["nv"], s["N"]
-    pair = inp["pair"].to(DEV)
-    bias = inp["bias"].to(DEV) if s["bias"] else None
-    out = _nan((nv, s["ldo"]), torch.float32)
+    pair = al.to(inp["pair"], {"pair": None})
+    bias = al.to(inp["bias"], {"bias": None}) if s["bias"] else None
+    out = al.full((nv, s["ldo"]), NAN, torch.float32, {"out": None})
     pads = [(out, out.clone(), N)]
     L.check(L.load().ca_modulation_combine_f32(pair.data_ptr(), pair.stride(0), None if bias is None else bias.data_ptr(),
                                                out.data_ptr(), out.stride(0), nv, N,
@@ -169,19 +191,21 @@ def run_combine(c, inp):
     return {"out": out[:, :N]}, pads
 
 
-def run_logits(c, inp):
+def run_logits(c, inp, alloc=None):
+    al = _al(alloc)
     s = c.shape
-    img, con = inp["img"].to(DEV), inp["con"].to(DEV)
-    lg = _nan((s["C"], s["L"]), torch.float32)
+    img, con = al.to(inp["img"], {"img": None}), al.to(inp["con"], {"con": None})
+    lg = al.full((s["C"], s["L"]), NAN, torch.float32, {"logits": None})
     ops.heatmap_logits(img[:, :s["dim"]], con[:, :s["dim"]], lg)
     torch.cuda.synchronize()
     return {"logits": lg}, []
 
 
-def run_norm(c, inp):
+def run_norm(c, inp, alloc=None):
+    al = _al(alloc)
     s = c.shape
-    lg = inp["logits"].to(DEV)
-    acc = inp["acc0"].to(DEV).clone()
+    lg = al.to(inp["logits"], {"logits": None})
+    acc = al.to(inp["acc0"], {"acc": None})
     norm = L.NORMS[s["norm"]]
     if c.entry == "ca_heatmap_norm_accumulate":      # (ops sends softmax to ca_heatmap_softmax_accumulate directly)
         L.check(L.load().ca_heatmap_norm_accumulate(lg.data_ptr(), s["C"], s["L"], norm, s["w"], acc.data_ptr(),
@@ -193,31 +217,35 @@ def run_norm(c, inp):
     return {"acc": acc}, []
 
 
-def run_fused(c, inp):
+def run_fused(c, inp, alloc=None):
+    al = _al(alloc)
     s = c.shape
-    acc = inp["acc0"].to(DEV).clone()
-    lg = _nan((s["C"], s["L"]), torch.float32)
+    acc = al.to(inp["acc0"], {"acc": None})
+    lg = al.full((s["C"], s["L"]), NAN, torch.float32, {"logits": None})
     if s["form"] == "part":
-        h = ops.Heatmap(None, None, acc=acc, weight=R.FUSED_W, logits=lg, part=inp["part"].to(DEV))
+        h = ops.Heatmap(None, None, acc=acc, weight=R.FUSED_W, logits=lg, part=al.to(inp["part"], {"part": None}))
     else:
-        h = ops.Heatmap(inp["img"].to(DEV), inp["con"].to(DEV), acc=acc, weight=R.FUSED_W, logits=lg)
+        h = ops.Heatmap(al.to(inp["img"], {"img": None}), al.to(inp["con"], {"con": None}), acc=acc, weight=R.FUSED_W,
+                        logits=lg)
     ops.heatmap_fused([h], norm=L.NORMS[s["norm"]])
     torch.cuda.synchronize()
     return {"logits": lg, "acc": acc}, []
 
 
-def run_axpy(c, inp):
+def run_axpy(c, inp, alloc=None):
+    al = _al(alloc)
     s = c.shape
-    x, y = inp["x"].to(DEV).clone(), inp["y"].to(DEV)
+    x, y = al.to(inp["x"], {"x": None}), al.to(inp["y"], {"y": None})
     (ops.axpy if x.dtype == torch.bfloat16 else ops.axpy_f32)(x, y, s["a"])
     torch.cuda.synchronize()
     return {"x": x}, []
 
 
-def run_temb(c, inp):
+def run_temb(c, inp, alloc=None):
+    al = _al(alloc)
     s = c.shape
-    out = _nan((s["nt"], s["dim"]), torch.float32)
-    ops.timestep_embedding(inp["t"].to(DEV), out, time_factor=s["tf"])
+    out = al.full((s["nt"], s["dim"]), NAN, torch.float32, {"out": None})
+    ops.timestep_embedding(al.to(inp["t"], {"t": None}), out, time_factor=s["tf"])
     torch.cuda.synchronize()
     return {"out": out}, []
 
