@@ -27,7 +27,7 @@ from __future__ import annotations
 import math
 
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -161,6 +161,24 @@ class HeatmapRequest:
     norm: int = L.NORM_SOFTMAX    # weighting across concepts: softmax | sparsemax | entmax15 (_lib.NORM_*)
 
 
+class LayerRoute(NamedTuple):
+    """What HipFluxDiT._layer_route decides for one double block."""
+    capture: bool    # the layer's vectors are returned or turned into heat maps
+    fp8: bool        # proj and the MLP on e4m3 operands
+    fp8_qkv: bool    # the qkv projection too
+    split: bool      # q of the image / concept rows from the unrounded LayerNorm output (low-plane GEMM)
+    indep: bool      # that q only in map-side attention problems; what feeds proj is formed as in an uncaptured layer
+    qk16: bool       # rotated q / k stored as IEEE half
+    use_part: bool   # output-space logits as per-head partials from the attention epilogue (PART)
+    f32img: bool     # ... or from an fp32 copy of the [text | image] attention rows (ATTI32)
+
+
+# what the qkv epilogue multiplies the rotated q by: softmax_scale * log2(e) at head_dim 128, folded into q in fp32
+# before its one rounding, so the attention kernel's probability is a bare exp2 (include/conceptattn.h
+# CA_ATTN_Q_PRESCALED)
+Q_OUT_SCALE = (1.0 / math.sqrt(128.0)) * 1.4426950408889634
+
+
 class HipFluxDiT:
     """Drop-in for the reference's ``ModifiedFluxDiT`` instance on the hot path (inference only)."""
 
@@ -189,8 +207,8 @@ class HipFluxDiT:
         # rounding the running sum to bf16 after each add (as a bf16 activation tensor does, the reference's own
         # bf16 run included) is what makes the heat-map error grow with depth -- 38 roundings by layer 18.
         # Measured (tests/tools/error_budget.py): 5e-3 -> 1.3e-3 max-abs on layers 15..18.
-        # Cost: 27 MB more per LayerNorm read / projection write-back per block.  torch.bfloat16 restores the old
-        # layout (A/B aid, and what the reference's activations are).
+        # Cost: 27 MB more per LayerNorm read / projection write-back per block.  torch.bfloat16 is the layout of the
+        # reference's activations.
         if residual_dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("residual_dtype must be torch.float32 or torch.bfloat16")
         self.residual_dtype = residual_dtype
@@ -200,45 +218,18 @@ class HipFluxDiT:
         # Default False = the fp32 oracle's behaviour (t and 1000 t exact); True reproduces the reference's bf16
         # values (pinned by tests/golden/timestep_embedding_bf16.npz).
         self.bf16_timesteps = bool(bf16_timesteps)
-        # adaLN modulations of MANY conditioning vectors (all steps x items, precompute_conditioning) as two bf16 MFMA
-        # GEMMs instead of one weight-streaming GEMV pass per 4 vectors (_modulation_rows); False = GEMV only (A/B aid:
-        # set the attribute; round 5 retired the CA_MODULATION_GEMM / CA_ATTN_PRESCALE / CA_SPLIT_Q_CAPTURE variables)
-        self.modulation_by_gemm = True
-        # softmax_scale * log2(e) folded into q by the qkv epilogue (in fp32, before q's one rounding to bf16), so the
-        # attention kernel's probability is a bare exp2 (include/conceptattn.h CA_ATTN_Q_PRESCALED); False = the kernel
-        # multiplies every score instead (A/B aid)
-        self.prescale_q = True
-        # sampling.denoise keeps the latent in fp32 between the Euler steps when the model says so (False = bf16, A/B aid)
+        # sampling.denoise keeps the latent in fp32 between the Euler steps when the model says so (False = bf16, as the
+        # reference's loop)
         self.fp32_latent = True
-        # An fp32 copy of the captured layers' [text | image] attention rows for the output-space logits (round 3).
-        # Round 5 re-measured it at full depth (VERDICT r04 weak #5 asked to drop it: 1 011 vs 888 us per captured 5-item
-        # attention launch, 53 MB per item): layer 0's map moves by 2e-5 (tests/tools/diag_out_space.py), but deeper
-        # layers do not agree -- without it the worst step-0 map is 8.1e-4 (layer 4) instead of 3.8e-4 and the final
-        # maps 1.45e-4 instead of 7.9e-5 from the fp32 oracle (tests/test_full_depth_gpu.py fails its 1.5 x bounds).
-        # So the fp32 precision stays -- but since round 5 without the copy: epilogue_logits (below) forms the logits from
-        # the attention kernel's accumulators; this attribute only matters with epilogue_logits = False (False = the bf16
-        # rows).
-        self.f32_image_vectors = True
-        # The cross-attention-space vectors (post-QKNorm, pre-RoPE q) of the captured layers from the UNROUNDED
-        # LayerNorm output: the bf16 rounding of that GEMM operand is ~90 % of the cross-space heat-map error
-        # (tests/tools/error_budget.py: 3.3e-3 -> 3.5e-4 per map).  The LayerNorm writes a second bf16 plane with what
-        # the rounding drops, one more GEMM applies the q weights to it (image rows and concept rows of the captured
-        # layers only: +0.45 % FLOPs per call), and ops.qpre_finish normalises the sum.  The q the ATTENTION uses is
-        # untouched, so the image does not depend on which layers are captured.  False = one rounding more (A/B aid).
-        self.split_q_capture = True
         # The rotated q and k of the attention as IEEE half instead of bf16 (ca_gemm_problem.qk_f16 ->
         # ca_attn_fwd_qk16): their bf16 rounding is one of the two things that bound a single output-space heat map
-        # (round 4, tests/tools/error_budget.py --out-space2: 9e-4 -> 2.5e-4 per map with 11-bit q / k; v and the
-        # probabilities do not matter), and behind an RMS norm the values sit far inside fp16's range.  "captured"
-        # (default): the layers whose maps are requested -- where the attention's q is special anyway (split_q_attention
-        # below); the chip clocks the f16 MFMA 1.6 % lower than the bf16 one, and with every block in half precision
-        # ("all") the maps are no closer to the oracle (profiles/r04_full_depth_parity*.json: 5.6e-4 / 9.6e-4 worst single
-        # map against 5.7e-4 / 8.4e-4) at -0.6 % heat maps/s.  "0": bf16 everywhere, as the reference (A/B aid).
-        # Needs the pre-scaled-q kernel (prescale_q = False switches it off: _qk16).
+        # (tests/tools/error_budget.py --out-space2: 9e-4 -> 2.5e-4 per map with 11-bit q / k; v and the probabilities
+        # do not matter), and behind an RMS norm the values sit far inside fp16's range.  "captured" (default): the
+        # layers whose maps are requested -- where the attention's q is special anyway (_double_block); the chip clocks
+        # the f16 MFMA 1.6 % lower than the bf16 one, and with every block in half precision ("all") the maps are no
+        # closer to the oracle (profiles/r04_full_depth_parity*.json: 5.6e-4 / 9.6e-4 worst single map against
+        # 5.7e-4 / 8.4e-4) at -0.6 % heat maps/s.  "0": bf16 everywhere, as the reference.
         self.qk_f16 = "captured"
-        # the ATTENTION's q of the captured layers' image / concept rows from the unrounded LayerNorm output as well
-        # (ops.qpre_finish writes it over the epilogue's; _double_block); False = round 3's q (A/B aid)
-        self.split_q_attention = True
         # Exact independence of everything the forward returns from WHICH layers' maps are requested (the reference's
         # property: the concept stream and the capture are read-only side computations, modified_double_stream_block.py:
         # 105-119, 185-191).  False (default): a captured layer's attention uses the accurate q for its image and concept
@@ -251,22 +242,25 @@ class HipFluxDiT:
         # generate call with 4 of 57 layers captured; +15 % of a 19-layer sweep forward); single output-space maps then
         # carry k's bf16 rounding again (measured in the same test file).
         self.capture_independent_image = False
-        self._layer_indep = False   # (set per layer by _double_block, read by _capture)
-        self._layer_part = False
-        # fp8 mode: the qkv projection of a layer whose maps are requested stays bf16 (_double_block)
+        # fp8 mode: the qkv projection of a layer whose maps are requested stays bf16 (_layer_route)
         self.fp8_bf16_qkv_when_captured = True
         # the heat-map updates of a captured layer (all work items, both spaces) as ONE ca_heatmap_fused launch; False =
-        # logits + weighting launches per item and space (the same bits; parity / A-B aid, and what C > 8 uses)
+        # logits + weighting launches per item and space (the same bits; the parity reference, and what C > 8 uses)
         self.fused_heatmaps = True
-        # (round 5) The output-space logits of a captured layer from the attention kernel's own accumulators: the concept
+        # The output-space logits of a captured layer from the attention kernel's own accumulators: the concept
         # problems run first (their fp32 rows ATT32 must exist), every main problem's epilogue then forms, per head, the
         # dot products of its image rows (fp32, before their bf16 rounding) with the C concept rows and leaves
         # [heads, L, 8] partial logits (PART, 3 MB per item), which ca_heatmap_fused sums over the heads -- instead of an
         # fp32 copy of every [text | image] row (ATTI32: 53 MB per item, +115 us per captured 5-item attention launch,
         # and 250 MB of reads in the heat-map launch).  The same arithmetic in another summation order (per head, then
-        # over the heads).  False = the fp32 rows (rounds 3-4; A/B aid).  Needs fused_heatmaps and the pre-scaled-q kernel.
+        # over the heads).  False = the fp32 rows (the parity reference).  Needs fused_heatmaps.
         self.epilogue_logits = True
         self.set_precision(precision)
+
+    # Every setting above that selects a route or a number format: what a replica on another stream must share with the
+    # model it stands in for (pipeline._stream_models copies them before every run).
+    ROUTE_SETTINGS = ("precision", "keep_bf16_layers", "residual_dtype", "bf16_timesteps", "fp32_latent", "qk_f16",
+                      "capture_independent_image", "fp8_bf16_qkv_when_captured", "fused_heatmaps", "epilogue_logits")
 
     # ---- reduced-precision mode (BASELINE.json configs[4]; no counterpart in the reference)
     FP8_LINEARS = ("img_attn.qkv", "txt_attn.qkv", "img_attn.proj", "txt_attn.proj", "img_mlp.0", "txt_mlp.0",
@@ -299,11 +293,6 @@ class HipFluxDiT:
         if self.precision == "fp8":
             self._fp8_weights()
         return self
-
-    @staticmethod
-    def _launch_gemm(problems):
-        """One grouped GEMM launch (image-weight rows + text-weight rows of all work items)."""
-        ops.gemm(problems)
 
     def _gemm(self, fp8, a, a8, a8s, wname, bias, out, *args, **kw):
         """One problem of a grouped launch in the current precision."""
@@ -352,13 +341,12 @@ class HipFluxDiT:
     WS_CACHE_ENTRIES = 3
 
     # Buffers only some forwards need (the captured layers' fp32 vectors: ~0.55 GB per work item at 1024 x 1024; +53 MB
-    # with f32_image_vectors) are allocated on first use, per activation set: a model that never returns maps never pays
-    # for them.  An fp8-mode forward WITH captured layers does (round 4: their qkv projection stays bf16, so the split-q
-    # buffers XML / QD / QPRE are used there too).  name -> (rows, columns..., dtype) of the set's geometry
+    # where the fp32 rows ATTI32 are used) are allocated on first use, per activation set: a model that never returns
+    # maps never pays for them.  An fp8-mode forward WITH captured layers does (their qkv projection stays bf16, so the
+    # split-q buffers XML / QPRE are used there too).  name -> (rows, columns..., dtype) of the set's geometry
     _LAZY_BUFFERS = {
         "QPRE": lambda n, B, T, L, H: ((n, H), torch.float32),       # post-QKNorm pre-RoPE q (cross-space vectors)
         "XML": lambda n, B, T, L, H: ((n, H), torch.bfloat16),       # low plane of XM: bf16(y - float(bf16(y)))
-        "QD": lambda n, B, T, L, H: ((n, H), torch.float32),         # its q projection (ops.qpre_finish adds it)
         "ATTI32": lambda n, B, T, L, H: ((B, T + L, H), torch.float32),   # fp32 [text | image] attention rows
         # capture_independent_image: the accurate q of the captured layers' image / concept rows (the map-side attention
         # problems' queries) and those problems' bf16 output rows, which nothing but the heat maps reads
@@ -379,7 +367,6 @@ class HipFluxDiT:
 
     QPRE = property(lambda self: self._lazy_buffer("QPRE"))
     XML = property(lambda self: self._lazy_buffer("XML"))
-    QD = property(lambda self: self._lazy_buffer("QD"))
     ATTI32 = property(lambda self: self._lazy_buffer("ATTI32"))
     PART = property(lambda self: self._lazy_buffer("PART"))
     QACC = property(lambda self: self._lazy_buffer("QACC"))
@@ -413,7 +400,7 @@ class HipFluxDiT:
             ATT=torch.zeros(n, H, **bf),
             HID=torch.zeros(n, MLP, **bf),
             CAT=torch.zeros(B * (T + L_img), H + MLP, **bf),
-            # (QPRE, XML, QD, ATTI32 -- the fp32 vectors of the captured layers -- are allocated on first use: _LAZY_BUFFERS)
+            # (QPRE, XML, ATTI32 -- the fp32 vectors of the captured layers -- are allocated on first use: _LAZY_BUFFERS)
             ATT32=torch.zeros(max(B * C, 1), H, **f32),  # fp32 copy of the concept attention rows
             TXT_IN=torch.zeros(B * (C + T), p.context_in_dim, **bf),
             PRED=torch.zeros(B * L_img, p.in_channels, **bf),
@@ -527,10 +514,10 @@ class HipFluxDiT:
             ops.split_planes(img_flat.contiguous(), img_in, img_lo)
         else:
             img_in = img_flat.to(bf).contiguous()
-        self._launch_gemm([ops.Gemm(img_in, W["img_in.weight"], W["img_in.bias"], X[g.oI:]),
+        ops.gemm([ops.Gemm(img_in, W["img_in.weight"], W["img_in.bias"], X[g.oI:]),
                            ops.Gemm(self.TXT_IN, W["txt_in.weight"], W["txt_in.bias"], X[:g.oI])])
         if split_in:
-            self._launch_gemm([ops.Gemm(img_lo, W["img_in.weight"], None, X[g.oI:], L.EPI_GATE_RESIDUAL,
+            ops.gemm([ops.Gemm(img_lo, W["img_in.weight"], None, X[g.oI:], L.EPI_GATE_RESIDUAL,
                                         resid=X[g.oI:], gate=self._ones_gate(W["img_in.weight"].shape[0]))])
 
         # ---- conditioning vectors: row 0 = vec (y), row 1 = concept_vec (modified_flux_dit.py:99-119)
@@ -558,7 +545,7 @@ class HipFluxDiT:
                                               for j in range(B)])
         # the prediction has the latent's type: an fp32 latent (sampling.denoise on this path) gets it unrounded
         pred = self.PRED32 if split_in else self.PRED
-        self._launch_gemm([ops.Gemm(XM[g.oI:], W["final_layer.linear.weight"], W["final_layer.linear.bias"], pred)])
+        ops.gemm([ops.Gemm(XM[g.oI:], W["final_layer.linear.weight"], W["final_layer.linear.bias"], pred)])
         return pred.view(B, Li, -1).clone(), out
 
     def _vec_chain(self, tv, yin, gv, hv, vecs):
@@ -644,11 +631,11 @@ class HipFluxDiT:
         GEMV launches of 4 vectors (4 x 3072 fp32 inputs leave room for 3 workgroups per CU in LDS; with 8 the weight
         stream drops from 5.3 to 2.2 TB/s: tools/gemv_bench.py), i.e. once per 4 vectors."""
         W = self.weights
-        if self.modulation_by_gemm:  # (for ANY vector count: the per-call and the all-steps path must round alike)
-            if getattr(W, "mod_ones", None) is None:
-                W.mod_ones = torch.ones(W.mod_rows, device=self.device, dtype=torch.float32)
-            if ops.modulation_gemm(vecs, W.mod_w, W.mod_b, mod2, W.mod_ones):
-                return
+        # (the GEMM for ANY vector count: the per-call and the all-steps path must round alike)
+        if getattr(W, "mod_ones", None) is None:
+            W.mod_ones = torch.ones(W.mod_rows, device=self.device, dtype=torch.float32)
+        if ops.modulation_gemm(vecs, W.mod_w, W.mod_b, mod2, W.mod_ones):
+            return
         for r0 in range(0, vecs.shape[0], 4):
             r = slice(r0, min(r0 + 4, vecs.shape[0]))
             ops.gemv(vecs[r], W.mod_w, W.mod_b, mod2[r], silu_input=True)
@@ -660,23 +647,32 @@ class HipFluxDiT:
         self._modulation_rows(self.VEC[:mod2.shape[0]], mod2)
         self._mod_cur = self.MOD
 
-    def _f32_image_vectors(self, capture: bool, heatmaps) -> bool:
-        """The attention kernel writes an fp32 copy of the [text | image] output rows in captured layers when the maps
-        are reduced on the device (fused heat-map path); A/B: f32_image_vectors = False."""
-        return bool(capture and heatmaps is not None and self.f32_image_vectors)
-
     def _ones_gate(self, n: int) -> torch.Tensor:
         g = getattr(self, "_ones_gate_vec", None)
         if g is None or g.shape[0] != n:
             g = self._ones_gate_vec = torch.ones(n, device=self.device, dtype=torch.float32)
         return g
 
-    def _qk16(self, capture: bool) -> bool:
-        return self.prescale_q and (self.qk_f16 == "all" or (self.qk_f16 == "captured" and bool(capture)))
-
-    def _q_out_scale(self) -> float:
-        """What the qkv epilogue multiplies the rotated q by: softmax_scale * log2(e) (head_dim 128), or 0 (= 1)."""
-        return (1.0 / math.sqrt(128.0)) * 1.4426950408889634 if self.prescale_q else 0.0
+    def _layer_route(self, i, C, return_vectors, heatmaps) -> LayerRoute:
+        """The route of double block ``i`` with C concept tokens, from the settings in ROUTE_SETTINGS alone."""
+        maps = heatmaps is not None
+        capture = bool(return_vectors or (maps and any(i in h.layer_indices for h in heatmaps)))
+        fp8 = self.precision == "fp8" and i not in self.keep_bf16_layers
+        # fp8 mode: the qkv projection of a layer whose maps are requested stays bf16.  Its q / k / v ARE the vectors of
+        # that layer's maps, and e4m3's 3 mantissa bits on their GEMM operands cost a map 2-4e-2 against the fp32 oracle
+        # (tests/test_full_depth_gpu.py::test_fp8_forward_full_size_vs_fp32_oracle); proj and the MLP reach a map only
+        # through the residual stream.  25 % of a double block's projection FLOPs.
+        fp8_qkv = fp8 and not (capture and self.fp8_bf16_qkv_when_captured)
+        # The bf16 rounding of the qkv GEMM's operand is ~90 % of the cross-space heat-map error and reaches a single
+        # output-space map through q (tests/tools/error_budget.py: 3.3e-3 -> 3.5e-4 per cross-space map; 7.8e-4 ->
+        # 2.5e-4 per output-space map, tests/tools/diag_out_space.py): the LayerNorm writes a second bf16 plane with
+        # what the rounding drops, and the q weights are applied to it as well (+0.45 % FLOPs per call).
+        split = capture and not fp8_qkv and self.residual_dtype == torch.float32 and C > 0
+        indep = split and self.capture_independent_image
+        qk16 = self.qk_f16 == "all" or (self.qk_f16 == "captured" and capture and not self.capture_independent_image)
+        use_part = (capture and maps and not indep and self.epilogue_logits and self.fused_heatmaps
+                    and ops.heatmap_fused_fits(C, self.hidden_size))
+        return LayerRoute(capture, fp8, fp8_qkv, split, indep, qk16, use_part, f32img=capture and maps and not use_part)
 
     def _double_block(self, i, g, joint_attention_kwargs=None, out=None, return_vectors=False, heatmaps=None):
         """ModifiedDoubleStreamBlock.forward (modified_double_stream_block.py:69-204) on the resident X rows
@@ -692,13 +688,8 @@ class HipFluxDiT:
             self_ = joint_attention_kwargs.get("concept_self_attention", True)
         b = f"double_blocks.{i}."
         im, tm = b + "img_mod.lin", b + "txt_mod.lin"
-        capture = return_vectors or (heatmaps is not None and any(i in h.layer_indices for h in heatmaps))
-        fp8 = self.precision == "fp8" and i not in self.keep_bf16_layers
-        # fp8 mode: the qkv projection of a layer whose maps are requested stays bf16 (round 4).  Its q / k / v ARE the
-        # vectors of that layer's maps, and e4m3's 3 mantissa bits on their GEMM operands cost a map 2-4e-2 against the
-        # fp32 oracle (tests/test_full_depth_gpu.py::test_fp8_forward_full_size_vs_fp32_oracle); proj and the MLP reach a
-        # map only through the residual stream.  25 % of a double block's projection FLOPs.
-        fp8_qkv = fp8 and not (capture and self.fp8_bf16_qkv_when_captured)
+        route = self._layer_route(i, C, return_vectors, heatmaps)
+        capture, fp8, fp8_qkv, split, indep, qk16, use_part, f32img = route
         if fp8:
             XM8, XMS, ATT8, ATTS, HID8, HIDS = self.XM8, self.XMS, self.ATT8, self.ATTS, self.HID8, self.HIDS
             xm_out = dict(out=XM8, out_scale=XMS)
@@ -720,70 +711,42 @@ class HipFluxDiT:
         gs = 0 if B == 1 else self._mod_cur.stride(0)   # floats between consecutive items' gate vectors
         G = self._gemm
         # K4: LayerNorm + (1+scale)*x+shift, per row range and item (:88-89,94-95,100-101)
-        split = capture and not fp8_qkv and self.split_q_capture and self.residual_dtype == torch.float32 and C > 0
         ops.ln_modulate(X, segments=[sg for sg in segs(0, 1) if sg[0] > 0], **xm_out_qkv,
                         **({"out_lo": self.XML} if split else {}))
         # K5+K6+K7: qkv projections (image stream + [concept|text] stream in one grouped launch) with
         # QK-RMSNorm and RoPE fused into the epilogue; pre-RoPE q kept for the cross-attention maps
         qpre = self.QPRE if capture else None
-        # (capture_independent_image: q / k exactly as in an uncaptured layer; the accurate q goes to QACC instead)
-        indep = bool(split and self.capture_independent_image and self.split_q_attention)
-        qk16 = self._qk16(capture and not self.capture_independent_image)
-        self._layer_indep = indep
-        def qkv_launch():
-            self._launch_gemm([G(fp8_qkv, XM[oI:], rows(XM8, oI, n), rows(XMS, oI, n), b + "img_attn.qkv.weight",
-                                 W.tensors.get(b + "img_attn.qkv.bias"), QKV[oI:],
-                                 L.EPI_QKV_NORM_ROPE, n_split=3 * H, norm_q=W[b + "img_attn.norm.query_norm.scale"],
-                                 norm_k=W[b + "img_attn.norm.key_norm.scale"], rope=self.ROPE[oI:],
-                                 q_prerope=None if qpre is None else qpre[oI:], q_out_scale=self._q_out_scale(),
-                                 qpre_raw=split, qk_f16=qk16),
-                               G(fp8_qkv, XM[:oI], rows(XM8, 0, oI), rows(XMS, 0, oI), b + "txt_attn.qkv.weight",
-                                 W.tensors.get(b + "txt_attn.qkv.bias"), QKV[:oI],
-                                 L.EPI_QKV_NORM_ROPE, n_split=3 * H, norm_q=W[b + "txt_attn.norm.query_norm.scale"],
-                                 norm_k=W[b + "txt_attn.norm.key_norm.scale"], rope=self.ROPE[:oI],
-                                 q_prerope=None if qpre is None else qpre[:oI], q_out_scale=self._q_out_scale(),
-                                 qpre_raw=split, qk_f16=qk16)])
-        # (256 x 256 tiles named for the low-plane launches: the automatic choice prices the concept rows' problem and
-        # lands on 256 x 128, 376 vs 332 us per 5-item launch)
-        lo_tile = L.TILE_PP_256x256 if B * Li >= 4096 else L.TILE_AUTO
-        if split and self.split_q_attention:
-            # (round 5) the q weights applied to the low plane of y -- image rows and concept rows; text rows are not
-            # captured -- with the correction, the RMS norm, the rotation and the store of the ATTENTION's q fused into
-            # that launch's epilogue (qpre_f32 = 3): the main launch leaves the hi plane's raw q projection in QPRE, this
-            # one adds its own product, normalises (QPRE <- the cross-attention-space vectors, fp32) and writes the
-            # rotated, scaled q over what the main epilogue formed from bf16(y).  A single output-space map: 7.8e-4 ->
-            # 2.5e-4 from the fp32 oracle (the operand's rounding reaches the map through q; tests/tools/diag_out_space.py).
-            # Rounds 3-4 had a second GEMM output (QD) and ca_qpre_finish_rope_f32 for it: 18 instead of 10 bytes per
-            # element past the GEMM and 2 launches more per captured layer.
-            qkv_launch()
+        ops.gemm([G(fp8_qkv, XM[oI:], rows(XM8, oI, n), rows(XMS, oI, n), b + "img_attn.qkv.weight",
+                    W.tensors.get(b + "img_attn.qkv.bias"), QKV[oI:],
+                    L.EPI_QKV_NORM_ROPE, n_split=3 * H, norm_q=W[b + "img_attn.norm.query_norm.scale"],
+                    norm_k=W[b + "img_attn.norm.key_norm.scale"], rope=self.ROPE[oI:],
+                    q_prerope=None if qpre is None else qpre[oI:], q_out_scale=Q_OUT_SCALE,
+                    qpre_raw=split, qk_f16=qk16),
+                  G(fp8_qkv, XM[:oI], rows(XM8, 0, oI), rows(XMS, 0, oI), b + "txt_attn.qkv.weight",
+                    W.tensors.get(b + "txt_attn.qkv.bias"), QKV[:oI],
+                    L.EPI_QKV_NORM_ROPE, n_split=3 * H, norm_q=W[b + "txt_attn.norm.query_norm.scale"],
+                    norm_k=W[b + "txt_attn.norm.key_norm.scale"], rope=self.ROPE[:oI],
+                    q_prerope=None if qpre is None else qpre[:oI], q_out_scale=Q_OUT_SCALE,
+                    qpre_raw=split, qk_f16=qk16)])
+        if split:
+            # the q weights applied to the low plane of y -- image rows and concept rows; text rows are not captured --
+            # with the correction, the RMS norm, the rotation and the store of the ATTENTION's q fused into that launch's
+            # epilogue: the main launch leaves the hi plane's raw q projection in QPRE, this one adds its own product,
+            # normalises (QPRE <- the cross-attention-space vectors, fp32) and writes the rotated, scaled q over what the
+            # main epilogue formed from bf16(y) -- or, with capture_independent_image, to QACC: q / k / the attention
+            # output that feeds proj then stay exactly as in an uncaptured layer.
+            # (256 x 256 tiles named: the automatic choice prices the concept rows' problem and lands on 256 x 128,
+            # 376 vs 332 us per 5-item launch)
             q_acc = self.QACC if indep else qs
-            lo = dict(epilogue=L.EPI_QKV_NORM_ROPE, n_split=3 * H, q_out_scale=self._q_out_scale(), qpre_add=True,
-                      qk_f16=qk16)
+            lo = dict(epilogue=L.EPI_QKV_NORM_ROPE, n_split=3 * H, q_out_scale=Q_OUT_SCALE, qpre_add=True, qk_f16=qk16)
             ops.gemm([ops.Gemm(self.XML[oI:], W[b + "img_attn.qkv.weight"][:H], None, q_acc[oI:],
                                norm_q=W[b + "img_attn.norm.query_norm.scale"], norm_k=W[b + "img_attn.norm.key_norm.scale"],
                                rope=self.ROPE[oI:], q_prerope=qpre[oI:], **lo),
                       ops.Gemm(self.XML[:oT], W[b + "txt_attn.qkv.weight"][:H], None, q_acc[:oT],
                                norm_q=W[b + "txt_attn.norm.query_norm.scale"], norm_k=W[b + "txt_attn.norm.key_norm.scale"],
                                rope=self.ROPE[:oT], q_prerope=qpre[:oT], **lo)], L.TILE_PP_256x256)
-        elif split:
-            # split_q_attention = False (A/B aid): only the cross-attention-space vectors take the correction; the
-            # attention's q stays the main epilogue's (rounds 3's route: second GEMM output + finish kernel)
-            ops.gemm([ops.Gemm(self.XML[oI:], W[b + "img_attn.qkv.weight"][:H], None, self.QD[oI:]),
-                      ops.Gemm(self.XML[:oT], W[b + "txt_attn.qkv.weight"][:H], None, self.QD[:oT])], lo_tile)
-            qkv_launch()
-            ops.qpre_finish(qpre[oI:], self.QD[oI:], W[b + "img_attn.norm.query_norm.scale"], NH)
-            ops.qpre_finish(qpre[:oT], self.QD[:oT], W[b + "txt_attn.norm.query_norm.scale"], NH)
-        else:
-            qkv_launch()
-        # K8+K9: per item, joint text+image attention and the concept rows; one launch (concept problems first)
-        f32img = self._f32_image_vectors(capture, heatmaps)
-        # per-head partial logits from the attention epilogue instead of fp32 rows (self.epilogue_logits above)
-        use_part = bool(capture and heatmaps is not None and not indep and self.epilogue_logits and self.fused_heatmaps
-                        and self.prescale_q and 1 <= C <= 8 and ops.heatmap_fused_fits(C, H))
-        self._layer_part = use_part
-        if use_part:
-            f32img = False
 
+        # K8+K9: per item, joint text+image attention and the concept rows; one launch (concept problems first)
         def concept_problem(j, q_rows, out_rows, out32):
             cj, ij = slice(j * C, (j + 1) * C), slice(oI + j * Li, oI + (j + 1) * Li)
             if cross and self_:
@@ -802,7 +765,7 @@ class HipFluxDiT:
             # the concept rows first, in their own launch (102 us for a 5-item layer): the main problems' epilogues read
             # ATT32.  (A bandwidth-style kernel for these <= 8-row problems -- keys split over workgroups, fp32 scores --
             # was built and measured at the same 100 us and the same maps: removed again)
-            ops.attention(probs, NH, q_prescaled=self.prescale_q, qk_f16=qk16)
+            ops.attention(probs, NH, q_prescaled=True, qk_f16=qk16)
             probs = []
         for j in range(B):
             tj, ij = slice(oT + j * T, oT + (j + 1) * T), slice(oI + j * Li, oI + (j + 1) * Li)
@@ -816,19 +779,19 @@ class HipFluxDiT:
                 tj, ij = slice(oT + j * T, oT + (j + 1) * T), slice(oI + j * Li, oI + (j + 1) * Li)
                 probs.append(ops.Attn(self.QACC[ij], self.ATTM[ij], ks[tj], vs[tj], ks[ij], vs[ij],
                                       out_f32=self.ATTI32[j, T:] if f32img else None))
-        ops.attention(probs[:L.ATTN_MAX_PROBLEMS], NH, q_prescaled=self.prescale_q, qk_f16=qk16)
+        ops.attention(probs[:L.ATTN_MAX_PROBLEMS], NH, q_prescaled=True, qk_f16=qk16)
         if len(probs) > L.ATTN_MAX_PROBLEMS:
-            ops.attention(probs[L.ATTN_MAX_PROBLEMS:], NH, q_prescaled=self.prescale_q, qk_f16=qk16)
+            ops.attention(probs[L.ATTN_MAX_PROBLEMS:], NH, q_prescaled=True, qk_f16=qk16)
         if indep and C > 0 and (cross or self_):
             # ... and of the concept rows (B tiny problems: their own launch, the first one is full at 5 items)
             ops.attention([concept_problem(j, self.QACC, self.ATTM, self.ATT32[j * C:(j + 1) * C]) for j in range(B)],
-                          NH, q_prescaled=self.prescale_q, qk_f16=qk16)
+                          NH, q_prescaled=True, qk_f16=qk16)
         if capture:
-            self._capture(out, i, g, NH, return_vectors, heatmaps)
+            self._capture(out, i, g, NH, return_vectors, heatmaps, route)
         if fp8:
             ops.quantize_rows_fp8(ATT, ATT8, ATTS)
         # K12: proj + gated residual (:194,198,201); concept rows use txt weights + concept gate
-        self._launch_gemm([G(fp8, ATT[oI:], rows(ATT8, oI, n), rows(ATTS, oI, n), b + "img_attn.proj.weight",
+        ops.gemm([G(fp8, ATT[oI:], rows(ATT8, oI, n), rows(ATTS, oI, n), b + "img_attn.proj.weight",
                              W[b + "img_attn.proj.bias"], X[oI:],
                              L.EPI_GATE_RESIDUAL, resid=X[oI:], gate=self._mod(im, 0, 2), gate_stride=gs,
                              gate_item_rows=Li),
@@ -838,13 +801,13 @@ class HipFluxDiT:
                              gate_rows=oT, gate_stride=gs, gate_item_rows=max(C, 1), gate2_item_rows=T)])
         # K13: LN + modulate + MLP + gated residual (:196,199,202)
         ops.ln_modulate(X, segments=[sg for sg in segs(3, 4) if sg[0] > 0], **xm_out)
-        self._launch_gemm([G(fp8, XM[oI:], rows(XM8, oI, n), rows(XMS, oI, n), b + "img_mlp.0.weight",
+        ops.gemm([G(fp8, XM[oI:], rows(XM8, oI, n), rows(XMS, oI, n), b + "img_mlp.0.weight",
                              W[b + "img_mlp.0.bias"], HID[oI:], L.EPI_GELU_TANH),
                            G(fp8, XM[:oI], rows(XM8, 0, oI), rows(XMS, 0, oI), b + "txt_mlp.0.weight",
                              W[b + "txt_mlp.0.bias"], HID[:oI], L.EPI_GELU_TANH)])
         if fp8:
             ops.quantize_rows_fp8(HID, HID8, HIDS)
-        self._launch_gemm([G(fp8, HID[oI:], rows(HID8, oI, n), rows(HIDS, oI, n), b + "img_mlp.2.weight",
+        ops.gemm([G(fp8, HID[oI:], rows(HID8, oI, n), rows(HIDS, oI, n), b + "img_mlp.2.weight",
                              W[b + "img_mlp.2.bias"], X[oI:],
                              L.EPI_GATE_RESIDUAL, resid=X[oI:], gate=self._mod(im, 0, 5), gate_stride=gs,
                              gate_item_rows=Li),
@@ -873,28 +836,29 @@ class HipFluxDiT:
         else:
             xm8 = xms8 = None
             ops.ln_modulate(xs, xms, segs)
-        self._launch_gemm([G(fp8, xms, xm8, xms8, b + "linear1.weight", W[b + "linear1.bias"], qkvs,
+        ops.gemm([G(fp8, xms, xm8, xms8, b + "linear1.weight", W[b + "linear1.bias"], qkvs,
                              L.EPI_QKV_NORM_ROPE, out2=CAT[:, H:], n_split=3 * H, norm_q=W[b + "norm.query_norm.scale"],
                              norm_k=W[b + "norm.key_norm.scale"], rope=self.ROPE[oT:],
-                             q_out_scale=self._q_out_scale(), qk_f16=self._qk16(False))])
+                             q_out_scale=Q_OUT_SCALE, qk_f16=self.qk_f16 == "all")])
         qh, kh, vh, oh = qkvs[:, :H], qkvs[:, H:2 * H], qkvs[:, 2 * H:], CAT[:, :H]
         probs = []
         for j in range(B):
             tj, ij = slice(j * T, (j + 1) * T), slice(nT + j * Li, nT + (j + 1) * Li)
             probs.append(ops.Attn(qh[tj], oh[tj], kh[tj], vh[tj], kh[ij], vh[ij], q1=qh[ij], out1=oh[ij]))
-        ops.attention(probs, NH, q_prescaled=self.prescale_q, qk_f16=self._qk16(False))
+        ops.attention(probs, NH, q_prescaled=True, qk_f16=self.qk_f16 == "all")
         if fp8:
             ops.quantize_rows_fp8(CAT, self.CAT8, self.CATS)
         gate = self._mod(m, 0, 2)
-        self._launch_gemm([G(fp8, CAT, self.CAT8 if fp8 else None, self.CATS if fp8 else None, b + "linear2.weight",
+        ops.gemm([G(fp8, CAT, self.CAT8 if fp8 else None, self.CATS if fp8 else None, b + "linear2.weight",
                              W[b + "linear2.bias"], xs, L.EPI_GATE_RESIDUAL, resid=xs, gate=gate, gate2=gate,
                              gate_rows=nT, gate_stride=0 if B == 1 else self._mod_cur.stride(0),
                              gate_item_rows=T, gate2_item_rows=Li)])
 
     forward = __call__
 
-    def _capture(self, out, layer, g, NH, return_vectors, heatmaps):
-        """Dict capture (modified_double_stream_block.py:185-191) and/or fused heat-map update, per work item."""
+    def _capture(self, out, layer, g, NH, return_vectors, heatmaps, route):
+        """Dict capture (modified_double_stream_block.py:185-191) and/or fused heat-map update, per work item;
+        ``route``: this layer's LayerRoute, which says where the attention left the output-space logits' inputs."""
         ATT, QPRE = self.ATT, self.QPRE
         B, C, Li, oT, oI = g.B, g.C, g.L, g.oT, g.oI
         fused = self.fused_heatmaps and ops.heatmap_fused_fits(C, self.hidden_size)
@@ -908,9 +872,7 @@ class HipFluxDiT:
             # is the dominant heat-map error otherwise -- DESIGN.md "tolerance")
             li = hm.layer_indices.index(layer)
             cj, ij = slice(j * C, (j + 1) * C), slice(oI + j * Li, oI + (j + 1) * Li)
-            part = self._layer_part   # (_layer_part / _layer_indep: set by _double_block for this layer)
-            img_out = None if part else (self.ATTI32[j, g.T:] if self._f32_image_vectors(True, heatmaps) else
-                                         (self.ATTM[ij] if self._layer_indep else ATT[ij]))
+            img_out = None if route.use_part else self.ATTI32[j, g.T:]   # (a layer with maps has use_part or f32img)
             for img_vec, con_vec, acc, table in ((img_out, self.ATT32[cj], hm.out_space, hm.per_layer_out),
                                                  (QPRE[ij], QPRE[cj], hm.cross_space, hm.per_layer_cross)):
                 if acc is None and table is None:
@@ -921,7 +883,7 @@ class HipFluxDiT:
                         None if table is None else table[li], hm.per_layer_weight,
                         part=self.PART[j] if img_vec is None else None))
                     continue
-                # the three-launch form (more than 8 concepts, or fused_heatmaps = False: the A/B and parity aid)
+                # the three-launch form (more than 8 concepts, or fused_heatmaps = False: the parity reference)
                 ops.heatmap_logits(img_vec, con_vec, self.LOGITS[:C])
                 if acc is not None:
                     ops.heatmap_softmax_accumulate(self.LOGITS[:C], acc, hm.weight, hm.norm)

@@ -116,6 +116,17 @@ class ConceptAttentionFluxPipeline:
     def _decode(self, x: torch.Tensor, height: int, width: int):
         return self.flux_generator.decode(x, height, width)
 
+    def _stream_models(self, n_streams: int):
+        """One model (activation set on self.model's weights) and one HIP stream per slot, every replica with
+        self.model's current settings: a work item computes the same whichever stream it lands on."""
+        while len(self._replicas) < n_streams:
+            self._replicas.append(HipFluxDiT(self.params, self.device, weights=self.model.weights))
+        for r in self._replicas[1:]:
+            for name in HipFluxDiT.ROUTE_SETTINGS:
+                setattr(r, name, getattr(self.model, name))
+        while len(self._streams) < n_streams:
+            self._streams.append(torch.cuda.Stream(device=self.device))
+
     # ------------------------------------------------------------------ generate_image (:115-202)
     @torch.no_grad()
     @on_own_device
@@ -156,15 +167,7 @@ class ConceptAttentionFluxPipeline:
         batch = max(1, min(batch, _lib.ATTN_MAX_PROBLEMS // 2, _lib.MAX_SEGMENTS // 3))  # launch limits: 5 items
         groups = [list(range(g0, min(g0 + batch, len(items)))) for g0 in range(0, len(items), batch)]
         n_streams = max(1, min(n_streams, len(groups)))
-        while len(self._replicas) < n_streams:
-            self._replicas.append(HipFluxDiT(self.params, self.device, weights=self.model.weights,
-                                             precision=self.model.precision,
-                                             residual_dtype=self.model.residual_dtype)
-                                  .set_precision(self.model.precision, self.model.keep_bf16_layers))
-        for r in self._replicas:
-            r.capture_independent_image = self.model.capture_independent_image
-        while len(self._streams) < n_streams:
-            self._streams.append(torch.cuda.Stream(device=self.device))
+        self._stream_models(n_streams)
         cur = torch.cuda.current_stream(self.device)
         self.model.materialize()  # shared fp8 weight images: built on `cur`, which every side stream waits on
         results = [None] * len(items)
@@ -414,15 +417,7 @@ class ConceptAttentionFluxPipeline:
         batch = max(1, min(batch, _lib.ATTN_MAX_PROBLEMS // 2, _lib.MAX_SEGMENTS // 3))
         groups = [list(range(g0, min(g0 + batch, len(items)))) for g0 in range(0, len(items), batch)]
         n_streams = max(1, min(n_streams, len(groups)))
-        while len(self._replicas) < n_streams:
-            self._replicas.append(HipFluxDiT(self.params, self.device, weights=self.model.weights,
-                                             precision=self.model.precision,
-                                             residual_dtype=self.model.residual_dtype)
-                                  .set_precision(self.model.precision, self.model.keep_bf16_layers))
-        for r in self._replicas:
-            r.capture_independent_image = self.model.capture_independent_image
-        while len(self._streams) < n_streams:
-            self._streams.append(torch.cuda.Stream(device=self.device))
+        self._stream_models(n_streams)
         cur = torch.cuda.current_stream(self.device)
         self.model.materialize()  # shared fp8 weight images: built on `cur`, which every side stream waits on
         for st in self._streams[:n_streams]:

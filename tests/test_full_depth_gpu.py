@@ -33,7 +33,7 @@ REPORT = {}
 # Absolute bounds on the max-abs map error vs the fp32 oracle, each <= 1.5 x the value measured on MI355X
 # (profiles/r03_full_depth_parity.json).  The north star's bound is 1e-3 on the maps generate_image returns.
 # Cross space: with the same input as the oracle (step 0 of a generation, the encode path) a map is within 4.5e-4 -- the
-# q vectors come from the unrounded LayerNorm output (HipFluxDiT.split_q_capture); at steps >= 1 of a generation the
+# q vectors come from the unrounded LayerNorm output (LayerRoute.split in flux_dit.py); at steps >= 1 of a generation the
 # latent itself has moved (pred: 0.24-0.37 % rms off the fp32 trajectory after 57 bf16 blocks per step) and the
 # cross-space logits amplify that: 2-4e-3 per map, 1.07e-3 for the 16-map mean.
 # Round 4 (profiles/r04_full_depth_parity.json): the attention's q of the captured layers comes from the unrounded
@@ -168,7 +168,7 @@ def test_four_steps_full_depth_vs_fp32_golden_with_reference_bf16_yardstick(pipe
     assert rep["final_latent_rel_rms"] <= max(0.02, rep["reference_bf16_final_latent_rel_rms"])
     # the product entry point gives the same final maps as per-layer tables of the SAME captured layers (same kernels,
     # same order).  The captured set matters at rounding level since round 4: in a captured layer the attention's q of the
-    # image and concept rows is formed from the unrounded LayerNorm output (HipFluxDiT.split_q_attention), so a run that
+    # image and concept rows is formed from the unrounded LayerNorm output (LayerRoute.split in flux_dit.py), so a run that
     # captures all 19 layers carries slightly different residual rows into layers 15-18 than one that captures only those.
     d = {k: v.to(DEV) for k, v in inp.items()}
     _, hm, cm = pipe.generate_on_device(d["latent"], d["txt"].bfloat16(), d["vec"].bfloat16(), d["concepts"].bfloat16())
@@ -196,11 +196,11 @@ def test_latent_dependence_on_the_captured_layer_set(pipe, golden):
     """In the reference the concept stream is a read-only side computation (modified_double_stream_block.py:105-119 vs
     :120-168): the generated image does not depend on which maps are asked for.  On this path a layer whose maps are
     requested forms the attention's q of its image rows from the unrounded LayerNorm output and stores q / k as IEEE
-    half (HipFluxDiT.split_q_attention, qk_f16 = "captured"), so the residual stream -- and the latent generate_image
+    half (LayerRoute.split and HipFluxDiT.qk_f16 = "captured"), so the residual stream -- and the latent generate_image
     returns -- moves at rounding level with ``layer_indices``.  This pins HOW MUCH: the final
     latent of a 4-step generation capturing no layer, layers 15-18 (the default) and all 19, against each other and
     against the fp32 oracle's latent.  Bounds = 1.5 x measured (profiles/r05_full_depth_parity.json);
-    split_q_attention = False with qk_f16 = "0" removes the dependence (at 7.8e-4 instead of 2.2e-4 per single output-space map)."""
+    HipFluxDiT.capture_independent_image = True removes the dependence (measured in the test below)."""
     g = golden("full_depth_schnell.npz")
     p = pipe.params
     inp = bf_inputs(p, 1024, 256, 4)

@@ -190,3 +190,52 @@ def test_gemm_tile_order_is_a_bijection_for_any_tile_count():
             if nthin[1]:
                 want |= {(1, mt[1] - 1, n) for n in range(NT)}
         assert seen == want, (mt0, mt1, NT, gm, xil, thin, len(seen), len(want))
+
+
+_ROUTE_DEFAULTS = dict(precision="bf16", keep_bf16_layers=frozenset(), residual_dtype=torch.float32, bf16_timesteps=False,
+                       fp32_latent=True, qk_f16="captured", capture_independent_image=False,
+                       fp8_bf16_qkv_when_captured=True, fused_heatmaps=True, epilogue_logits=True)
+_T, _F = True, False
+# (settings that differ from the defaults, C, return_vectors, layers with maps or None,
+#  expected (capture, fp8, fp8_qkv, split, indep, qk16, use_part, f32img)) for double block 1
+_ROUTE_TABLE = [
+    ({}, 4, _F, (0,), (_F, _F, _F, _F, _F, _F, _F, _F)),                     # defaults, maps of another layer only
+    ({}, 4, _F, None, (_F, _F, _F, _F, _F, _F, _F, _F)),
+    ({}, 4, _F, (1,), (_T, _F, _F, _T, _F, _T, _T, _F)),                     # defaults, captured
+    ({}, 4, _T, None, (_T, _F, _F, _T, _F, _T, _F, _F)),                     # the vector stacks alone: no logits at all
+    ({}, 4, _T, (0,), (_T, _F, _F, _T, _F, _T, _T, _F)),
+    ({}, 0, _F, (1,), (_T, _F, _F, _F, _F, _T, _F, _T)),                     # no concept rows to correct or to weigh
+    ({}, 8, _F, (1,), (_T, _F, _F, _T, _F, _T, _T, _F)),
+    ({}, 9, _F, (1,), (_T, _F, _F, _T, _F, _T, _F, _T)),                     # more concepts than the epilogue holds
+    (dict(precision="fp8"), 4, _F, (0,), (_F, _T, _T, _F, _F, _F, _F, _F)),
+    (dict(precision="fp8"), 4, _F, (1,), (_T, _T, _F, _T, _F, _T, _T, _F)),  # a captured layer's qkv stays bf16
+    (dict(precision="fp8", fp8_bf16_qkv_when_captured=False), 4, _F, (1,), (_T, _T, _T, _F, _F, _T, _T, _F)),
+    (dict(precision="fp8", keep_bf16_layers=frozenset({1})), 4, _F, (1,), (_T, _F, _F, _T, _F, _T, _T, _F)),
+    (dict(capture_independent_image=True), 4, _F, (1,), (_T, _F, _F, _T, _T, _F, _F, _T)),
+    (dict(capture_independent_image=True), 4, _F, (0,), (_F, _F, _F, _F, _F, _F, _F, _F)),
+    (dict(capture_independent_image=True, qk_f16="all"), 4, _F, (1,), (_T, _F, _F, _T, _T, _T, _F, _T)),
+    (dict(capture_independent_image=True, residual_dtype=torch.bfloat16), 4, _F, (1,), (_T, _F, _F, _F, _F, _F, _T, _F)),
+    (dict(epilogue_logits=False), 4, _F, (1,), (_T, _F, _F, _T, _F, _T, _F, _T)),
+    (dict(fused_heatmaps=False), 4, _F, (1,), (_T, _F, _F, _T, _F, _T, _F, _T)),
+    (dict(qk_f16="0"), 4, _F, (1,), (_T, _F, _F, _T, _F, _F, _T, _F)),
+    (dict(qk_f16="0"), 4, _F, (0,), (_F, _F, _F, _F, _F, _F, _F, _F)),
+    (dict(qk_f16="all"), 4, _F, (1,), (_T, _F, _F, _T, _F, _T, _T, _F)),
+    (dict(qk_f16="all"), 4, _F, (0,), (_F, _F, _F, _F, _F, _T, _F, _F)),
+    (dict(residual_dtype=torch.bfloat16), 4, _F, (1,), (_T, _F, _F, _F, _F, _T, _T, _F)),
+]
+
+
+@pytest.mark.parametrize("case", range(len(_ROUTE_TABLE)))
+def test_layer_route_table(case):
+    """HipFluxDiT._layer_route against values worked out by hand from the inline decisions of _double_block as of
+    47341e4 (with the five retired attributes at their defaults).  The function reads settings only, so a plain
+    namespace stands in for the model, which cannot be built without a GPU."""
+    from types import SimpleNamespace
+    from conceptattention_amd.flux_dit import HipFluxDiT, LayerRoute
+    assert set(_ROUTE_DEFAULTS) == set(HipFluxDiT.ROUTE_SETTINGS)
+    settings, C, return_vectors, layers, want = _ROUTE_TABLE[case]
+    model = SimpleNamespace(hidden_size=3072, **{**_ROUTE_DEFAULTS, **settings})
+    heatmaps = None if layers is None else [SimpleNamespace(layer_indices=layers)] * 2
+    got = HipFluxDiT._layer_route(model, 1, C, return_vectors, heatmaps)
+    assert tuple(bool(v) for v in got) == want, (got, want)
+    assert LayerRoute._fields == ("capture", "fp8", "fp8_qkv", "split", "indep", "qk16", "use_part", "f32img")

@@ -84,6 +84,28 @@ def test_two_streams_equal_sequential(pipe):
             assert torch.equal(x, y)
 
 
+def test_two_streams_share_the_first_models_settings(pipe):
+    """A setting changed on pipe.model holds on every stream: with bf16 q / k everywhere (qk_f16 = "0", which only acts
+    in layers whose maps are requested) two streams give the bits of one stream."""
+    from conceptattention_amd.weights import synthetic_inputs
+    items = []
+    for j in range(3):
+        inp = synthetic_inputs(pipe.params, 256, 256, 8, 3, seed=50 + j, dtype=torch.bfloat16)
+        items.append({k: inp[k].to(DEV) for k in ("latent", "txt", "vec", "concepts")})
+    kw = dict(layer_indices=[0, 1], num_inference_steps=2)
+    before = pipe.model.qk_f16
+    pipe.model.qk_f16 = "0"
+    try:
+        one = pipe.generate_many_on_device(items, n_streams=1, **kw)
+        two = pipe.generate_many_on_device(items, n_streams=2, **kw)
+        torch.cuda.synchronize()
+    finally:
+        pipe.model.qk_f16 = before
+    for a, b in zip(one, two):
+        for x, y in zip(a, b):
+            assert torch.equal(x, y)
+
+
 def test_generate_image_argument_checks(pipe):
     with pytest.raises(AssertionError):
         pipe.generate_image("p", ["a"], width=256, height=128)
