@@ -1,9 +1,7 @@
-// Host-side plumbing of libconceptattn: version, thread-local error text, device check.
+// Host-side plumbing of libconceptattn: version, thread-local error text, device check, launch helpers.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
-
-#include <atomic>
 
 #include "ca_common.h"
 
@@ -27,6 +25,30 @@ int ca_cu_count() {
     cus[dev & 63].store(n, std::memory_order_relaxed);
   }
   return n;
+}
+
+int ca_raise_lds_limit(std::initializer_list<const void *> kernels, int bytes, std::atomic<unsigned long long> &done,
+                       const char *FN) {
+  const unsigned long long dev_bit = ca_device_bit();
+  if (done.load(std::memory_order_acquire) & dev_bit) return CA_OK;
+  for (const void *k : kernels) {
+    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) {
+      ca_set_error("%s: hipFuncSetAttribute(%d bytes LDS): %s", FN, bytes, hipGetErrorString(e));
+      return CA_ERR_LAUNCH;
+    }
+  }
+  done.fetch_or(dev_bit, std::memory_order_release);
+  return CA_OK;
+}
+
+int ca_check_launch(const char *FN) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    ca_set_error("%s: launch failed: %s", FN, hipGetErrorString(e));
+    return CA_ERR_LAUNCH;
+  }
+  return CA_OK;
 }
 
 extern "C" int ca_version(void) { return CA_VERSION; }

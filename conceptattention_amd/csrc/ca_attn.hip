@@ -21,8 +21,6 @@
 
 #include <type_traits>
 
-#include <atomic>
-
 #include "ca_common.h"
 #include "ca_attn_common.h"
 
@@ -420,34 +418,12 @@ static int ca_attn_fwd_impl(const ca_attn_problem *problems, int32_t n_problems,
     total += 8 * hx * L.nqb[i];
     L.blk_end[i] = total;
   }
-  if (use4) {
-    const int rc = ca_attn4_launch(L, total, qk_f16, (hipStream_t)stream);
-    if (rc != CA_OK) return rc;
-    const hipError_t e4 = hipGetLastError();
-    if (e4 != hipSuccess) {
-      ca_set_error("ca_attn_fwd_bf16: launch failed: %s", hipGetErrorString(e4));
-      return CA_ERR_LAUNCH;
-    }
-    return CA_OK;
-  }
-  static std::atomic<unsigned long long> attr_done{0};  // one bit per device: the attribute is per device
-  const unsigned long long dev_bit = ca_device_bit();
-  if (!(attr_done.load(std::memory_order_acquire) & dev_bit)) {
-    const hipError_t e = hipFuncSetAttribute((const void *)ca_attn_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             ATTN_LDS);
-    if (e != hipSuccess) {
-      ca_set_error("ca_attn_fwd_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return CA_ERR_LAUNCH;
-    }
-    attr_done.fetch_or(dev_bit, std::memory_order_release);  // idempotent: a race only repeats the call
-  }
+  if (use4) return ca_attn4_launch(L, total, qk_f16, (hipStream_t)stream);
+  static std::atomic<unsigned long long> attr_done{0};
+  const int rc = ca_raise_lds_limit({(const void *)ca_attn_kernel<8>}, ATTN_LDS, attr_done, "ca_attn_fwd_bf16");
+  if (rc != CA_OK) return rc;
   hipLaunchKernelGGL(ca_attn_kernel<8>, dim3(total), dim3(512), ATTN_LDS, (hipStream_t)stream, L);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    ca_set_error("ca_attn_fwd_bf16: launch failed: %s", hipGetErrorString(e));
-    return CA_ERR_LAUNCH;
-  }
-  return CA_OK;
+  return ca_check_launch("ca_attn_fwd_bf16");
 }
 
 extern "C" int ca_attn_stats(unsigned long long *counters, int32_t reset) {

@@ -3,8 +3,6 @@
 // checks the emitted code for compiler-written AGPR accesses).
 #include <stdlib.h>
 
-#include <atomic>
-
 #include "ca_attn_common.h"
 
 namespace {
@@ -98,17 +96,9 @@ int ca_attn4_read_counters(unsigned long long *out, int reset) {
 
 int ca_attn4_launch(const AttnLaunch &L, int total, bool qk_f16, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_done{0};
-  const unsigned long long dev_bit = ca_device_bit();
-  if (!(attr_done.load(std::memory_order_acquire) & dev_bit)) {
-    for (const void *fn : {(const void *)ca_attn4_kernel, (const void *)ca_attn4_qk16_kernel}) {
-      const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, a4::LDS_BYTES);
-      if (e != hipSuccess) {
-        ca_set_error("ca_attn_fwd_bf16: hipFuncSetAttribute(ca_attn4_kernel): %s", hipGetErrorString(e));
-        return CA_ERR_LAUNCH;
-      }
-    }
-    attr_done.fetch_or(dev_bit, std::memory_order_release);
-  }
+  const int rc = ca_raise_lds_limit({(const void *)ca_attn4_kernel, (const void *)ca_attn4_qk16_kernel}, a4::LDS_BYTES,
+                                    attr_done, "ca_attn_fwd_bf16");
+  if (rc != CA_OK) return rc;
   // more units than CUs: one workgroup per CU walks them (no workgroup dispatch between units)
   const int n_cu = ca_cu_count();
   AttnLaunch LL = L;
@@ -118,5 +108,5 @@ int ca_attn4_launch(const AttnLaunch &L, int total, bool qk_f16, hipStream_t str
     hipLaunchKernelGGL(ca_attn4_qk16_kernel, dim3(grid), dim3(256), a4::LDS_BYTES, stream, LL);
   else
     hipLaunchKernelGGL(ca_attn4_kernel, dim3(grid), dim3(256), a4::LDS_BYTES, stream, LL);
-  return CA_OK;
+  return ca_check_launch("ca_attn_fwd_bf16");
 }

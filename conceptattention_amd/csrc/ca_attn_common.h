@@ -21,7 +21,7 @@ constexpr int ATTN_LDS = 2 * BUF_BYTES;
 
 }  // namespace ca_attn_detail
 
-// ca_attn4.hip: the one-wave-per-SIMD kernel for pre-scaled q (host side: attribute once per device, launch)
+// ca_attn4.hip: the one-wave-per-SIMD kernel for pre-scaled q (host side: attribute once per device, launch, launch check)
 int ca_attn4_launch(const ca_attn_detail::AttnLaunch &L, int total_workgroups, bool qk_f16, hipStream_t stream);
 // counters of its two rare paths: out[0] = recomputed workgroups, out[1] = re-reference events (synchronous copy)
 int ca_attn4_read_counters(unsigned long long *out, int reset);

@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <initializer_list>
+
 #include "../../include/conceptattn.h"
 
 typedef __bf16 bf16;
@@ -104,3 +107,10 @@ inline unsigned long long ca_device_bit() {
 // host-side plumbing (ca_api.hip): error text; CU count of the current device (cached; -1 if the query fails)
 void ca_set_error(const char *fmt, ...);
 int ca_cu_count();
+// Raise the dynamic-LDS limit of `kernels` to `bytes`, once per device (hipFuncSetAttribute is per device): `done` is
+// the call site's own flag word, one bit per device (ca_device_bit), set when all of them succeeded (a race only repeats the calls).
+// CA_OK, or CA_ERR_LAUNCH with the HIP error text under the entry point's name FN.
+int ca_raise_lds_limit(std::initializer_list<const void *> kernels, int bytes, std::atomic<unsigned long long> &done,
+                       const char *FN);
+// after a kernel launch: CA_OK, or CA_ERR_LAUNCH with the text of hipGetLastError under the entry point's name FN
+int ca_check_launch(const char *FN);

@@ -21,8 +21,6 @@
 
 #include <type_traits>
 
-#include <atomic>
-
 #include "ca_common.h"
 
 namespace {
@@ -45,7 +43,7 @@ struct GemmLaunch {
   int32_t nthin[CA_GEMM_MAX_PROBLEMS];       // thin tiles per problem (nt or 0)
   // thin-row kernel (a thin last row tile under the 256x256 bf16 ping-pong tile): 32 x 128 tiles
   int32_t thin_row0[CA_GEMM_MAX_PROBLEMS];   // first row of the problem's thin part
-  int32_t thin_nt[CA_GEMM_MAX_PROBLEMS];     // its 128-column tiles (N / 128), 0 = none
+  int32_t thin_nt[CA_GEMM_MAX_PROBLEMS];     // its width in units of THIN_NT_COLS columns (N / 128), 0 = none
 };
 
 // A last row tile with at most this many valid rows is "thin": its MFMAs on row fragments past M are skipped (the
@@ -81,6 +79,13 @@ __device__ __forceinline__ const float *ca_gate_of(const ca_gemm_problem &P, int
     g += (size_t)(r / (first ? P.gate_item_rows : P.gate2_item_rows)) * P.gate_stride;
   }
   return g;
+}
+
+// s_waitcnt vmcnt(N): at most N of this wave's vector-memory operations (LDS-DMA included) still outstanding
+template <int N>
+__device__ __forceinline__ void ca_wait_vmcnt() {
+  static_assert(N >= 0 && N <= 63, "vmcnt counts at most 63 outstanding loads");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 template <int M_REP, int N_REP>
@@ -178,13 +183,13 @@ __global__ __launch_bounds__(512, 2) void ca_gemm_kernel(const GemmLaunch L) {
   // ---- main loop: 2-deep LDS ring, next tile's global_load_lds in flight under the MFMAs
   const int nk = K / C::BK;
   stage(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  ca_wait_vmcnt<0>();
   __syncthreads();
   int cur = 0;
   for (int kt = 0; kt < nk - 1; ++kt) {
     stage(cur ^ 1, kt + 1);
     compute(cur);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    ca_wait_vmcnt<0>();
     __syncthreads();
     cur ^= 1;
   }
@@ -223,7 +228,7 @@ __global__ __launch_bounds__(512, 2) void ca_gemm_kernel(const GemmLaunch L) {
   const int mrow0 = m0 + wm * 16 * M_REP + (lane & 15);
 
   if (epi == CA_EPI_GATE_RESIDUAL) {
-    float gate_a[4 * N_REP], gate_b[4 * N_REP];
+    float gate[4 * N_REP];
     const char *resb = (const char *)P.resid;
 #pragma unroll
     for (int i = 0; i < M_REP; ++i) {
@@ -235,10 +240,9 @@ __global__ __launch_bounds__(512, 2) void ca_gemm_kernel(const GemmLaunch L) {
           for (int j = 0; j < N_REP; ++j) {
             const f32x4 ga = *(const f32x4 *)(gr + 4 * j);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) gate_a[4 * j + r] = gate_b[4 * j + r] = ga[r];
+            for (int r = 0; r < 4; ++r) gate[4 * j + r] = ga[r];
           }
         }
-        const bool first = true;
         if (P.out_f32) {  // fp32 residual stream: 16 bytes per 4 columns, read and written in place
           const f32x4 *rp = (const f32x4 *)(resb + ((size_t)m * P.ldr + nb) * 4);
           f32x4 *op = (f32x4 *)(outb + ((size_t)m * ldo + ncol) * 4);
@@ -249,10 +253,7 @@ __global__ __launch_bounds__(512, 2) void ca_gemm_kernel(const GemmLaunch L) {
           for (int j = 0; j < N_REP; ++j) {
             f32x4 v;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const float gt = first ? gate_a[4 * j + r] : gate_b[4 * j + r];
-              v[r] = res[j][r] + gt * (acc[i][j][r] + bias[4 * j + r]);
-            }
+            for (int r = 0; r < 4; ++r) v[r] = res[j][r] + gate[4 * j + r] * (acc[i][j][r] + bias[4 * j + r]);
             op[j] = v;
           }
           continue;
@@ -267,10 +268,7 @@ __global__ __launch_bounds__(512, 2) void ca_gemm_kernel(const GemmLaunch L) {
           float v[4];
           const bf16x4 r4 = __builtin_bit_cast(bf16x4, res[j]);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float gt = first ? gate_a[4 * j + r] : gate_b[4 * j + r];
-            v[r] = (float)r4[r] + gt * (acc[i][j][r] + bias[4 * j + r]);
-          }
+          for (int r = 0; r < 4; ++r) v[r] = (float)r4[r] + gate[4 * j + r] * (acc[i][j][r] + bias[4 * j + r]);
           op[j] = make_uint2(ca_pack2(v[0], v[1]), ca_pack2(v[2], v[3]));
         }
       }
@@ -336,18 +334,6 @@ struct PPCfg {
   static constexpr int LDS_BYTES = 2 * BUF_BYTES;
   static constexpr int CNT_A = 2;  // global_load_lds per thread per A half tile (W halves: NL, NHI)
 };
-
-template <int N>
-__device__ __forceinline__ void ca_wait_vmcnt() {
-  static_assert(N >= 0 && N <= 6, "unsupported vmcnt");
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-  if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-  if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-  if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-}
 
 // FP8: A and W hold OCP e4m3 bytes; a 128-byte LDS row is then 128 k-elements and the two 16-byte chunks a
 // lane reads per fragment form the 32-byte operand of ONE v_mfma_scale_f32_16x16x128_f8f6f4 (E8M0 scales fixed
@@ -442,18 +428,15 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
 #pragma unroll
     for (int i = 0; i < C::CNT_A; ++i) ca_glds16(Ab + offA[h][i] + kb, base + i * 64 * C::ROW_BYTES);
   };
-  auto stageWL = [&](int buf, int kt) {
+  auto stageW = [&](auto hi_tag, int buf, int kt) {  // the lo (W_LO) or hi (W_HI) half of the W tile
+    constexpr bool HI = decltype(hi_tag)::value;
     const uint32_t kb = (uint32_t)min(kt, nk - 1) * (C::BK * 2);
-    char *base = smem + buf * C::BUF_BYTES + C::OFF_WL + wave * 8 * C::ROW_BYTES;
+    char *base = smem + buf * C::BUF_BYTES + (HI ? C::OFF_WH : C::OFF_WL) + wave * 8 * C::ROW_BYTES;
 #pragma unroll
-    for (int i = 0; i < NL; ++i) ca_glds16(Wb + offWL[i] + kb, base + i * 64 * C::ROW_BYTES);
+    for (int i = 0; i < (HI ? NHI : NL); ++i) ca_glds16(Wb + (HI ? offWH : offWL)[i] + kb, base + i * 64 * C::ROW_BYTES);
   };
-  auto stageWH = [&](int buf, int kt) {
-    const uint32_t kb = (uint32_t)min(kt, nk - 1) * (C::BK * 2);
-    char *base = smem + buf * C::BUF_BYTES + C::OFF_WH + wave * 8 * C::ROW_BYTES;
-#pragma unroll
-    for (int i = 0; i < NHI; ++i) ca_glds16(Wb + offWH[i] + kb, base + i * 64 * C::ROW_BYTES);
-  };
+  constexpr std::false_type W_LO{};
+  constexpr std::true_type W_HI{};
 
   f32x4 acc[8][NT_];
 #pragma unroll
@@ -474,23 +457,16 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
         for (int ks = 0; ks < 2; ++ks)
           af[mi][ks] = *(const bf16x8 *)(b + ((a_off + mi * 16 * C::ROW_BYTES) ^ (ks * 64)));
   };
-  auto readWL = [&](int buf) {
-    const char *b = smem + buf * C::BUF_BYTES + C::OFF_WL;
-    const int w_off = wn * 16 * NL * C::ROW_BYTES + lane_off;
+  auto readW = [&](auto hi_tag, int buf) {  // into wl (W_LO) or wh (W_HI)
+    constexpr bool HI = decltype(hi_tag)::value;
+    constexpr int NF = HI ? NHI : NL;
+    const char *b = smem + buf * C::BUF_BYTES + (HI ? C::OFF_WH : C::OFF_WL);
+    const int w_off = wn * 16 * NF * C::ROW_BYTES + lane_off;
 #pragma unroll
-    for (int nj = 0; nj < NL; ++nj)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-        wl[nj][ks] = *(const bf16x8 *)(b + ((w_off + nj * 16 * C::ROW_BYTES) ^ (ks * 64)));
-  };
-  auto readWH = [&](int buf) {
-    const char *b = smem + buf * C::BUF_BYTES + C::OFF_WH;
-    const int w_off = wn * 16 * NHI * C::ROW_BYTES + lane_off;
-#pragma unroll
-    for (int nj = 0; nj < NHI; ++nj)
+    for (int nj = 0; nj < NF; ++nj)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
-        wh[nj][ks] = *(const bf16x8 *)(b + ((w_off + nj * 16 * C::ROW_BYTES) ^ (ks * 64)));
+        (HI ? wh : wl)[nj][ks] = *(const bf16x8 *)(b + ((w_off + nj * 16 * C::ROW_BYTES) ^ (ks * 64)));
   };
 #define CA_PP_MMA_BODY(MI0, NJ0, WF, NW, GUARD)                                                             \
   if constexpr (FP8) {                                                                                      \
@@ -537,11 +513,11 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
   //     one barrier before the read at the closest.  A-lo / W-lo(t+2): 6 intervals.
   // Prologue: tile 0 complete, A-lo(1), W-lo(1) in flight (retired by phase 1 of tile 0).
   stageA(0, 0, 0);
-  stageWL(0, 0);
-  stageWH(0, 0);
+  stageW(W_LO, 0, 0);
+  stageW(W_HI, 0, 0);
   stageA(0, 1, 0);
   stageA(1, 0, 1);
-  stageWL(1, 1);
+  stageW(W_LO, 1, 1);
   ca_wait_vmcnt<C::CNT_A + NL>();
   CA_PP_SYNC();
   if (wm == 1) { CA_PP_SYNC(); }  // stagger: group 1 runs one barrier behind group 0
@@ -559,10 +535,10 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
       // phase 1
       readA(b, 0, rlo);
       if (!THIN || rlo + rhi > 0) {
-        readWL(b);
-        readWH(b);
+        readW(W_LO, b);
+        readW(W_HI, b);
       }
-      stageWH(b ^ 1, t + 1);
+      stageW(W_HI, b ^ 1, t + 1);
       stageA(b ^ 1, 1, t + 1);
       CA_PP_WAIT_READS();
       ca_wait_vmcnt<NHI + C::CNT_A>();
@@ -573,7 +549,7 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
       // phase 2
       readA(b, 1, rhi);
       stageA(b, 0, t + 2);
-      stageWL(b, t + 2);
+      stageW(W_LO, b, t + 2);
       CA_PP_WAIT_READS();
       ca_wait_vmcnt<C::CNT_A + NL>();
       CA_PP_SYNC();
@@ -813,17 +789,17 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): nothing of this tile has been stored yet
   auto half_epilogue = [&](auto nfrag_tag, int nj0, int nb, const auto &braw, const auto &graw) {
     constexpr int NF = decltype(nfrag_tag)::value;
-    float bias[4 * NF], gate_a[4 * NF], gate_b[4 * NF];
+    float bias[4 * NF], gate[4 * NF];
 #pragma unroll
     for (int j = 0; j < NF; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         bias[4 * j + r] = (float)braw[j][r];
-        gate_a[4 * j + r] = gate_b[4 * j + r] = graw[j][r];
+        gate[4 * j + r] = graw[j][r];
       }
     // Gates: the usual tile lies inside one work item and one row range, so its rows share ONE gate vector, loaded
-    // once (gate_a; `straddle` false).  A tile that spans items or the gate_rows boundary (the concept | text tile)
-    // fetches the vector per row fragment instead.
+    // once (graw -> `gate` above; `straddle` false).  A tile that spans items or the gate_rows boundary (the
+    // concept | text tile) refills `gate` per row fragment instead (row_gate).
     bool straddle = false;
     if (epi == CA_EPI_GATE_RESIDUAL) {
       // (rows are monotonic in (range, item), so equal end points mean one vector for the whole tile; comparing the
@@ -838,7 +814,7 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
       for (int j = 0; j < NF; ++j) {
         const f32x4 ga = *(const f32x4 *)(gr + 4 * j);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) gate_a[4 * j + r] = ga[r];
+        for (int r = 0; r < 4; ++r) gate[4 * j + r] = ga[r];
       }
     };
     // the residual rows are fetched up front for all 8 row fragments (rows clamped, only the store is
@@ -864,7 +840,6 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
         for (int mq = 0; mq < 4; ++mq) {
           const int mi = mh * 4 + mq;
           const int m = m0 + (mi >> 2) * 128 + wm * 64 + 16 * (mi & 3) + (lane & 15);
-          const bool first = true;
           if (gated && straddle) row_gate(m);
           f32x4 *op = (f32x4 *)(outb + ((size_t)m * ldo + nb + col_shift) * 4);
 #pragma unroll
@@ -873,7 +848,7 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               v[r] = acc[mi][nj0 + j][r] + bias[4 * j + r];
-              if (gated) v[r] = __builtin_fmaf(first ? gate_a[4 * j + r] : gate_b[4 * j + r], v[r], r32[mq][j][r]);
+              if (gated) v[r] = __builtin_fmaf(gate[4 * j + r], v[r], r32[mq][j][r]);
             }
             if (m < M) op[j] = v;
           }
@@ -899,7 +874,6 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
       for (int mi = 0; mi < 8; ++mi) {
         const int m = m0 + (mi >> 2) * 128 + wm * 64 + 16 * (mi & 3) + (lane & 15);
         uint2 *op = (uint2 *)(outb + ((size_t)m * ldo + nb + col_shift) * 2);
-        const bool first = true;
         if (KIND == CA_EPI_GATE_RESIDUAL && straddle) row_gate(m);
         uint2 o[NF];
 #pragma unroll
@@ -913,7 +887,7 @@ __device__ __forceinline__ void ca_gemm_pp_tile(const GemmLaunch &L, char *smem,
           if (KIND == CA_EPI_GATE_RESIDUAL) {
             const bf16x4 r4 = __builtin_bit_cast(bf16x4, res[mi][j]);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = __builtin_fmaf(first ? gate_a[4 * j + r] : gate_b[4 * j + r], v[r], (float)r4[r]);
+            for (int r = 0; r < 4; ++r) v[r] = __builtin_fmaf(gate[4 * j + r], v[r], (float)r4[r]);
           }
           o[j] = make_uint2(ca_pack2(v[0], v[1]), ca_pack2(v[2], v[3]));
         }
@@ -978,20 +952,16 @@ __global__ __launch_bounds__(512, 2) void ca_gemm_pp_kernel(const GemmLaunch L) 
 // loads a wave may have outstanding).  The four-wave form keeps 4 slots: 6 / 7 were measured and change nothing (its
 // launches -- the modulation GEMM's 8 126 workgroups at 4.6-5.6 TB/s -- are not short of bytes in flight;
 // tools/thin_ab.py, round 5).
-constexpr int THIN_N = 128;
+constexpr int THIN_NT_COLS = 128;  // the column unit GemmLaunch::thin_nt counts in (one head), whatever the kernel's tile width
+constexpr int thin_tile_cols(int nw) { return 32 * nw; }  // columns of a thin-row workgroup of nw waves
 template <int MF, int NW>
 struct ThinCfg {
-  static constexpr int M = 16 * MF, N = 32 * NW, STAGE = (M + N) * 128;
+  static constexpr int M = 16 * MF, N = thin_tile_cols(NW), STAGE = (M + N) * 128;
   static constexpr int PIECES = (M + N) / 8 / NW;  // 1 KB pieces per wave and K tile (NW = 4: 5 or 6; NW = 1: 8 or 12)
   static constexpr int SLOTS = NW == 4 ? 4 : (MF == 2 ? 8 : 6);
   static constexpr int LDS = SLOTS * STAGE;
   static_assert(PIECES * (SLOTS - 1) <= 63, "vmcnt counts at most 63 outstanding loads");
 };
-template <int N>
-__device__ __forceinline__ void ca_wait_vmcnt_imm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 template <int MF, int NW>
 __global__ __launch_bounds__(64 * NW) void ca_gemm_thin_kernel(const GemmLaunch L) {
   using TC = ThinCfg<MF, NW>;
@@ -1001,7 +971,7 @@ __global__ __launch_bounds__(64 * NW) void ca_gemm_thin_kernel(const GemmLaunch 
   const int lane = tid & 63;
   const int wn = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave = 32-column group
   int u = blockIdx.x;
-  const int nt0 = L.thin_nt[0] * (4 / NW);   // (thin_nt counts 128-column tiles)
+  const int nt0 = L.thin_nt[0] * (THIN_NT_COLS / THIN_N);
   const int prob = (u >= nt0) ? 1 : 0;
   if (prob) u -= nt0;
   const ca_gemm_problem P = L.p[prob];
@@ -1043,7 +1013,7 @@ __global__ __launch_bounds__(64 * NW) void ca_gemm_thin_kernel(const GemmLaunch 
 #pragma unroll
   for (int i = 0; i < THIN_SLOTS - 1; ++i) stage(i, i);
   for (int t = 0; t < nk; ++t) {
-    ca_wait_vmcnt_imm<NP * (THIN_SLOTS - 2)>();  // all but my SLOTS - 2 youngest K tiles have landed: tile t is there
+    ca_wait_vmcnt<NP * (THIN_SLOTS - 2)>();  // all but my SLOTS - 2 youngest K tiles have landed: tile t is there
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -1068,7 +1038,7 @@ __global__ __launch_bounds__(64 * NW) void ca_gemm_thin_kernel(const GemmLaunch 
         for (int j = 0; j < 2; ++j)
           acc[mi][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][ks], af[mi][ks], acc[mi][j], 0, 0, 0);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  ca_wait_vmcnt<0>();
   __syncthreads();  // no LDS-DMA outstanding, every wave done reading: the LDS is free for the row sums
 
   // ---- epilogues: acc[mi][j][r] = C[m][n], m = m0 + 16*mi + (lane&15), n = n0 + wn*32 + 8*(lane>>4) + 4*j + r
@@ -1217,28 +1187,15 @@ __global__ __launch_bounds__(64 * NW) void ca_gemm_thin_kernel(const GemmLaunch 
   }
 }
 
-template <int MF, int NW>
-int launch_thin_mf(const GemmLaunch &L, int groups, hipStream_t stream) {
-  using TC = ThinCfg<MF, NW>;
-  static std::atomic<unsigned long long> attr_done{0};  // one bit per device: the attribute is per device
-  const unsigned long long dev_bit = ca_device_bit();
-  if (!(attr_done.load(std::memory_order_acquire) & dev_bit)) {
-    hipError_t e = hipFuncSetAttribute((const void *)ca_gemm_thin_kernel<MF, NW>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, TC::LDS);
-    if (e != hipSuccess) {
-      ca_set_error("ca_gemm_bf16: hipFuncSetAttribute(%d bytes LDS): %s", TC::LDS, hipGetErrorString(e));
-      return CA_ERR_LAUNCH;
-    }
-    attr_done.fetch_or(dev_bit, std::memory_order_release);
-  }
-  hipLaunchKernelGGL((ca_gemm_thin_kernel<MF, NW>), dim3((L.thin_nt[0] + L.thin_nt[1]) * (4 / NW), groups), dim3(64 * NW),
-                     TC::LDS, stream, L);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    ca_set_error("ca_gemm_bf16: thin-row launch failed: %s", hipGetErrorString(e));
-    return CA_ERR_LAUNCH;
-  }
-  return CA_OK;
+// One kernel launch of this unit: the kernel's dynamic-LDS limit raised once per device (one flag per instantiation, i.e.
+// per kernel), the launch, its check.  FN = the entry point's name for messages.
+template <void (*KERNEL)(const GemmLaunch)>
+int launch_kernel(const GemmLaunch &L, int lds_bytes, dim3 grid, dim3 block, hipStream_t stream, const char *FN) {
+  static std::atomic<unsigned long long> attr_done{0};
+  const int rc = ca_raise_lds_limit({(const void *)KERNEL}, lds_bytes, attr_done, FN);
+  if (rc != CA_OK) return rc;
+  hipLaunchKernelGGL(KERNEL, grid, block, lds_bytes, stream, L);
+  return ca_check_launch(FN);
 }
 
 // Form of the thin-row launch: MF x 16 rows and NW waves per workgroup, `groups` grid rows.  Part of plan_gemm.
@@ -1260,56 +1217,23 @@ void pick_thin(const GemmLaunch &L, int *mf, int *nw, int *groups) {
   *groups = rows <= 32 ? 1 : (rows + 63) / 64;
 }
 
-int launch_thin(const GemmLaunch &L, int mf, int nw, int groups, hipStream_t stream) {
-  if (mf == 2) return nw == 1 ? launch_thin_mf<2, 1>(L, groups, stream) : launch_thin_mf<2, 4>(L, groups, stream);
-  return nw == 1 ? launch_thin_mf<4, 1>(L, groups, stream) : launch_thin_mf<4, 4>(L, groups, stream);
+// the three kernels' instantiations with their LDS bytes and block size
+template <int MF, int NW>
+int launch_thin_mf(const GemmLaunch &L, dim3 grid, hipStream_t stream, const char *FN) {
+  return launch_kernel<ca_gemm_thin_kernel<MF, NW>>(L, ThinCfg<MF, NW>::LDS, grid, dim3(64 * NW), stream, FN);
 }
-
 template <int NL, int NHI, bool FP8 = false>
-int launch_pp(const GemmLaunch &L, int total_tiles, hipStream_t stream) {
-  using C = PPCfg<NL, NHI>;
-  static std::atomic<unsigned long long> attr_done{0};  // one bit per device: the attribute is per device
-  const unsigned long long dev_bit = ca_device_bit();
-  if (!(attr_done.load(std::memory_order_acquire) & dev_bit)) {
-    hipError_t e = hipFuncSetAttribute((const void *)ca_gemm_pp_kernel<NL, NHI, FP8>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-    if (e != hipSuccess) {
-      ca_set_error("ca_gemm_bf16: hipFuncSetAttribute(%d bytes LDS): %s", C::LDS_BYTES, hipGetErrorString(e));
-      return CA_ERR_LAUNCH;
-    }
-    attr_done.fetch_or(dev_bit, std::memory_order_release);  // idempotent: a race only repeats the call
-  }
-  const int grid = L.persist_tiles > 0 ? min(total_tiles, L.persist_tiles_grid) : total_tiles;
-  hipLaunchKernelGGL((ca_gemm_pp_kernel<NL, NHI, FP8>), dim3(grid), dim3(512), C::LDS_BYTES, stream, L);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    ca_set_error("ca_gemm_bf16: launch failed: %s", hipGetErrorString(e));
-    return CA_ERR_LAUNCH;
-  }
-  return CA_OK;
+int launch_pp(const GemmLaunch &L, int grid, hipStream_t stream, const char *FN) {
+  return launch_kernel<ca_gemm_pp_kernel<NL, NHI, FP8>>(L, PPCfg<NL, NHI>::LDS_BYTES, dim3(grid), dim3(512), stream, FN);
+}
+template <int N_REP>
+int launch_classic(const GemmLaunch &L, int grid, hipStream_t stream, const char *FN) {
+  return launch_kernel<ca_gemm_kernel<8, N_REP>>(L, Cfg<8, N_REP>::LDS_BYTES, dim3(grid), dim3(512), stream, FN);
 }
 
-template <int M_REP, int N_REP>
-int launch(const GemmLaunch &L, int total_tiles, hipStream_t stream) {
-  using C = Cfg<M_REP, N_REP>;
-  static std::atomic<unsigned long long> attr_done{0};  // one bit per device: the attribute is per device
-  const unsigned long long dev_bit = ca_device_bit();
-  if (!(attr_done.load(std::memory_order_acquire) & dev_bit)) {
-    hipError_t e = hipFuncSetAttribute((const void *)ca_gemm_kernel<M_REP, N_REP>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-    if (e != hipSuccess) {
-      ca_set_error("ca_gemm_bf16: hipFuncSetAttribute(%d bytes LDS): %s", C::LDS_BYTES, hipGetErrorString(e));
-      return CA_ERR_LAUNCH;
-    }
-    attr_done.fetch_or(dev_bit, std::memory_order_release);  // idempotent: a race only repeats the call
-  }
-  hipLaunchKernelGGL((ca_gemm_kernel<M_REP, N_REP>), dim3(total_tiles), dim3(512), C::LDS_BYTES, stream, L);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    ca_set_error("ca_gemm_bf16: launch failed: %s", hipGetErrorString(e));
-    return CA_ERR_LAUNCH;
-  }
-  return CA_OK;
+int launch_thin(const GemmLaunch &L, int mf, int nw, dim3 grid, hipStream_t stream, const char *FN) {
+  if (mf == 2) return nw == 1 ? launch_thin_mf<2, 1>(L, grid, stream, FN) : launch_thin_mf<2, 4>(L, grid, stream, FN);
+  return nw == 1 ? launch_thin_mf<4, 1>(L, grid, stream, FN) : launch_thin_mf<4, 4>(L, grid, stream, FN);
 }
 
 int tile_n_of(int tile) {
@@ -1344,10 +1268,33 @@ int pick_group_m(int nt, int mt, bool interleave) {
   return 4;
 }
 
+// The tiles of a launch at tile width bn, split into main tiles and the tiles of thin last row tiles (THIN_ROWS).
+// ONE split for the tile chooser and for plan_gemm.
+struct TileSplit {
+  bool thin[CA_GEMM_MAX_PROBLEMS];     // the problem's last row tile is thin
+  int mt_main[CA_GEMM_MAX_PROBLEMS];   // its row tiles without that one
+  long main[CA_GEMM_MAX_PROBLEMS];     // main tiles = mt_main * (N / bn)
+  long nthin[CA_GEMM_MAX_PROBLEMS];    // tiles of the thin last row tile: N / bn or 0
+  long main_all, thin_all;             // summed over the launch
+};
+TileSplit split_tiles(const ca_gemm_problem *p, int n, int bn) {
+  TileSplit s = {};
+  for (int i = 0; i < n; ++i) {
+    const int rem = p[i].M % 256;
+    s.thin[i] = rem > 0 && rem <= THIN_ROWS;
+    s.mt_main[i] = (p[i].M + 255) / 256 - s.thin[i];
+    s.main[i] = (long)s.mt_main[i] * (p[i].N / bn);
+    s.nthin[i] = s.thin[i] ? p[i].N / bn : 0;
+    s.main_all += s.main[i];
+    s.thin_all += s.nthin[i];
+  }
+  return s;
+}
+
 // Do the thin last-row tiles of a launch ride in the ping-pong walk (in the CUs the main tiles leave idle in their last
-// round) instead of getting the thin-row kernel's own launch?  ONE predicate for the tile chooser and for gemm_impl.
-bool thin_rides_in_walk(long main_all, long thin_all, int n_cu) {
-  return n_cu > 0 && thin_all > 0 && main_all % n_cu != 0 && main_all % n_cu + thin_all <= n_cu;
+// round) instead of getting the thin-row kernel's own launch?
+bool thin_rides_in_walk(const TileSplit &s, int n_cu) {
+  return n_cu > 0 && s.thin_all > 0 && s.main_all % n_cu != 0 && s.main_all % n_cu + s.thin_all <= n_cu;
 }
 
 // Pick the tile that minimises (rounds over the CUs) x (time of one round).  Round times are
@@ -1360,25 +1307,19 @@ int auto_tile(const ca_gemm_problem *p, int n, int cus) {
   double best_cost = 1e300;
   for (const auto &c : cands) {
     const int bn = tile_n_of(c.tile);
+    // a thin last row tile leaves the 256x256 ping-pong walk for the thin-row kernel (a fraction of a round), M <= 128
+    // (no ping-pong tile at all) included; under every other tile it is a tile like the others
+    const bool thin_leaves = c.tile == CA_TILE_PP_256x256;
+    const TileSplit s = split_tiles(p, n, bn);
     bool ok = true;
     double work = 0;  // tile-rounds weighted by K (a workgroup's time is proportional to its K loop)
-    long tiles = 0;
     int kmax = 0, thin_k = 0;
     for (int i = 0; i < n; ++i) {
       if (p[i].N % bn) ok = false;
       if (p[i].epilogue == CA_EPI_SPLIT_GELU && p[i].n_split % bn) ok = false;
       if (p[i].epilogue == CA_EPI_QKV_NORM_ROPE && c.tile != CA_TILE_PP_256x256) ok = false;
-      long mt = (p[i].M + 255) / 256;
-      const int rem = p[i].M % 256;
-      // a thin last row tile leaves the 256x256 ping-pong walk for the thin-row kernel (a fraction of a round); the
-      // same predicate as gemm_impl's `own`, M <= 128 (no ping-pong tile at all) included
-      if (c.tile == CA_TILE_PP_256x256 && rem > 0 && rem <= THIN_ROWS) {
-        --mt;
-        if (p[i].K > thin_k) thin_k = p[i].K;
-      }
-      const long t = mt * (p[i].N / bn);
-      tiles += t;
-      work += (double)t * p[i].K;
+      if (thin_leaves && s.thin[i] && p[i].K > thin_k) thin_k = p[i].K;
+      work += (double)(thin_leaves ? s.main[i] : s.main[i] + s.nthin[i]) * p[i].K;
       if (p[i].K > kmax) kmax = p[i].K;
     }
     if (!ok) continue;
@@ -1386,25 +1327,15 @@ int auto_tile(const ca_gemm_problem *p, int n, int cus) {
     double rounds = work / kmax / (double)n_cu;
     rounds = work == 0 ? 0.0 : rounds <= 1.0 ? 1.0 : (double)(long)(rounds + 0.999);
     // the thin-row launch behind the main one: measured 0.3 of a 256x256 round at its K (profiles/r02_remainder_probe.txt)
-    // -- unless the thin tiles fit into the CUs the main tiles leave idle in their last round (gemm_impl's thin_fits):
-    // then they ride in the walk and cost nothing
+    // -- unless the thin tiles fit into the CUs the main tiles leave idle in their last round: then they ride in the
+    // walk and cost nothing
     double thin_cost = 0.3 * c.round_us * thin_k;
-    if (c.tile == CA_TILE_PP_256x256 && thin_k > 0) {
-      long main_t = 0, thin_t = 0;
-      for (int i = 0; i < n; ++i) {
-        const int rem = p[i].M % 256;
-        const int thin = (rem > 0 && rem <= THIN_ROWS) ? 1 : 0;
-        main_t += ((p[i].M + 255) / 256 - thin) * (long)(p[i].N / 256);
-        thin_t += thin * (long)(p[i].N / 256);
-      }
-      if (thin_rides_in_walk(main_t, thin_t, n_cu)) thin_cost = 0.0;
-    }
+    if (thin_k > 0 && thin_rides_in_walk(s, n_cu)) thin_cost = 0.0;
     const double cost = rounds * c.round_us * kmax + thin_cost;
     if (cost < best_cost) {
       best_cost = cost;
       best = c.tile;
     }
-    (void)tiles;
   }
   return best;
 }
@@ -1438,8 +1369,88 @@ struct GemmPlan {
   int thin_mf, thin_nw, thin_groups, thin_grid_x;   // the thin-row launch, 0: none
 };
 
-// shared argument checking + planning of ca_gemm_bf16 / ca_gemm_fp8 / ca_gemm_plan (FN = the entry point's name for
-// messages; n_cu = the CUs of the device, <= 0 if unknown)
+// argument checking of problem i of a launch (tile resolved, bn = its width; FN = the entry point's name for messages)
+int check_problem(const ca_gemm_problem &p, int i, int tile, int bn, bool fp8, const char *FN) {
+  const int kq = fp8 ? 128 : 64, ldq = fp8 ? 16 : 8, es = fp8 ? 1 : 2;
+  if (!p.A || !p.W || !p.out || p.M < 1 || p.N < 1 || p.K < 64) {
+    ca_set_error("%s[%d]: null pointer or empty shape (M=%d N=%d K=%d)", FN, i, p.M, p.N, p.K);
+    return CA_ERR_ARG;
+  }
+  if (p.K % kq || p.N % bn || p.lda % ldq || p.ldw % ldq || (p.ldc % 8 && !p.out_f32)) {
+    ca_set_error("%s[%d]: need K%%%d==0, N%%%d==0, lda/ldw%%%d==0, ldc%%8==0 (M=%d N=%d K=%d lda=%d ldw=%d ldc=%d)",
+                 FN, i, kq, bn, ldq, p.M, p.N, p.K, p.lda, p.ldw, p.ldc);
+    return CA_ERR_ARG;
+  }
+  if (fp8 && (!p.a_scale || !p.w_scale || ((uintptr_t)p.w_scale & 15) || ((uintptr_t)p.a_scale & 3))) {
+    ca_set_error("%s[%d]: fp8 operands need a_scale (fp32 [M]) and w_scale (fp32 [N], 16-byte aligned)", FN, i);
+    return CA_ERR_ARG;
+  }
+  if (((uintptr_t)p.A | (uintptr_t)p.W | (uintptr_t)p.out | (uintptr_t)p.bias) & 15) {
+    ca_set_error("%s[%d]: pointers must be 16-byte aligned", FN, i);
+    return CA_ERR_ARG;
+  }
+  if (p.lda < p.K || p.ldw < p.K) {
+    ca_set_error("%s[%d]: lda/ldw smaller than K", FN, i);
+    return CA_ERR_ARG;
+  }
+  if ((uint64_t)p.M * p.lda * es >= (1ull << 32) || (uint64_t)p.N * p.ldw * es >= (1ull << 32)) {
+    ca_set_error("%s[%d]: operand larger than 4 GiB", FN, i);
+    return CA_ERR_ARG;
+  }
+  if (p.out_f32 && ((p.epilogue != CA_EPI_BIAS && p.epilogue != CA_EPI_GATE_RESIDUAL) || p.ldc % 4 ||
+                    (p.epilogue == CA_EPI_GATE_RESIDUAL && p.ldr % 4))) {
+    ca_set_error("%s[%d]: out_f32 needs the BIAS or GATE_RESIDUAL epilogue and ldc/ldr %% 4 == 0", FN, i);
+    return CA_ERR_ARG;
+  }
+  switch (p.epilogue) {
+    case CA_EPI_BIAS:
+    case CA_EPI_GELU_TANH:
+      if (p.ldc < p.N) { ca_set_error("%s[%d]: ldc < N", FN, i); return CA_ERR_ARG; }
+      break;
+    case CA_EPI_GATE_RESIDUAL:
+      if (!p.resid || !p.gate || (p.ldr % 8 && !p.out_f32) || p.ldc < p.N || ((uintptr_t)p.resid & 15) ||
+          ((uintptr_t)p.gate & 15) || ((uintptr_t)p.gate2 & 15) || (p.gate_rows < p.M && !p.gate2)) {
+        ca_set_error("%s[%d]: GATE_RESIDUAL needs resid, gate (and gate2 when gate_rows < M), 16-byte aligned", FN, i);
+        return CA_ERR_ARG;
+      }
+      if (p.gate_stride && (p.gate_stride % 4 || p.gate_stride < 0 || (p.gate_rows > 0 && p.gate_item_rows < 1) ||
+                            (p.gate_rows < p.M && p.gate2_item_rows < 1))) {
+        ca_set_error("%s[%d]: per-item gates need gate_stride %% 4 == 0 and gate_item_rows / gate2_item_rows >= 1", FN, i);
+        return CA_ERR_ARG;
+      }
+      break;
+    case CA_EPI_QKV_NORM_ROPE:
+      // (N == n_split / 3: the q third alone -- the low-plane q projection of a captured layer, qpre_f32 = 3)
+      if (tile != CA_TILE_PP_256x256 || p.n_split <= 0 || p.n_split % 768 ||
+          (p.n_split > p.N && p.N != p.n_split / 3) || !p.norm_q ||
+          !p.norm_k || !p.rope || (p.n_split < p.N && (!p.out2 || p.ld2 % 8 || p.ld2 < p.N - p.n_split)) ||
+          p.ldc < (p.N < p.n_split ? p.N : p.n_split) ||
+          (p.q_prerope && (p.ldp % (p.qpre_f32 ? 4 : 8) || p.ldp < p.n_split / 3 || p.qpre_f32 < 0 || p.qpre_f32 > 3)) ||
+          (p.qpre_f32 == 3 && (!p.q_prerope || fp8)) ||
+          (p.qk_f16 != 0 && p.qk_f16 != 1) ||
+          (((uintptr_t)p.norm_q | (uintptr_t)p.norm_k | (uintptr_t)p.rope | (uintptr_t)p.q_prerope |
+            (uintptr_t)p.out2) & 15)) {
+        ca_set_error("%s[%d]: QKV_NORM_ROPE needs the 256x256 ping-pong tile, n_split = 3*heads*128 <= N, "
+                     "norm_q/norm_k/rope (16-byte aligned) and out2 when N > n_split", FN, i);
+        return CA_ERR_ARG;
+      }
+      break;
+    case CA_EPI_SPLIT_GELU:
+      if (!p.out2 || p.n_split <= 0 || p.n_split >= p.N || p.n_split % bn || p.ld2 % 8 ||
+          ((uintptr_t)p.out2 & 15) || p.ldc < p.n_split || p.ld2 < p.N - p.n_split) {
+        ca_set_error("%s[%d]: SPLIT_GELU needs out2 and 0 < n_split < N, n_split %% %d == 0", FN, i, bn);
+        return CA_ERR_ARG;
+      }
+      break;
+    default:
+      ca_set_error("%s[%d]: unknown epilogue %d", FN, i, p.epilogue);
+      return CA_ERR_ARG;
+  }
+  return CA_OK;
+}
+
+// shared planning of ca_gemm_bf16 / ca_gemm_fp8 / ca_gemm_plan, every problem checked first (FN = the entry point's name
+// for messages; n_cu = the CUs of the device, <= 0 if unknown)
 int plan_gemm(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile, bool fp8, int n_cu, const char *FN,
               GemmPlan *out) {
   if (!problems || n_problems < 1 || n_problems > CA_GEMM_MAX_PROBLEMS) {
@@ -1455,7 +1466,6 @@ int plan_gemm(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile,
   }
   if (tile == CA_TILE_AUTO) tile = auto_tile(problems, n_problems, n_cu);
   const int bn = tile_n_of(tile);
-  const int kq = fp8 ? 128 : 64, ldq = fp8 ? 16 : 8, es = fp8 ? 1 : 2;
   if (!bn) {
     ca_set_error("%s: no tile configuration fits (tile=%d)", FN, tile);
     return CA_ERR_ARG;
@@ -1465,80 +1475,8 @@ int plan_gemm(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile,
   int total = 0;
   for (int i = 0; i < n_problems; ++i) {
     const ca_gemm_problem &p = problems[i];
-    if (!p.A || !p.W || !p.out || p.M < 1 || p.N < 1 || p.K < 64) {
-      ca_set_error("%s[%d]: null pointer or empty shape (M=%d N=%d K=%d)", FN, i, p.M, p.N, p.K);
-      return CA_ERR_ARG;
-    }
-    if (p.K % kq || p.N % bn || p.lda % ldq || p.ldw % ldq || (p.ldc % 8 && !p.out_f32)) {
-      ca_set_error("%s[%d]: need K%%%d==0, N%%%d==0, lda/ldw%%%d==0, ldc%%8==0 (M=%d N=%d K=%d lda=%d ldw=%d ldc=%d)",
-                   FN, i, kq, bn, ldq, p.M, p.N, p.K, p.lda, p.ldw, p.ldc);
-      return CA_ERR_ARG;
-    }
-    if (fp8 && (!p.a_scale || !p.w_scale || ((uintptr_t)p.w_scale & 15) || ((uintptr_t)p.a_scale & 3))) {
-      ca_set_error("%s[%d]: fp8 operands need a_scale (fp32 [M]) and w_scale (fp32 [N], 16-byte aligned)", FN, i);
-      return CA_ERR_ARG;
-    }
-    if (((uintptr_t)p.A | (uintptr_t)p.W | (uintptr_t)p.out | (uintptr_t)p.bias) & 15) {
-      ca_set_error("%s[%d]: pointers must be 16-byte aligned", FN, i);
-      return CA_ERR_ARG;
-    }
-    if (p.lda < p.K || p.ldw < p.K) {
-      ca_set_error("%s[%d]: lda/ldw smaller than K", FN, i);
-      return CA_ERR_ARG;
-    }
-    if ((uint64_t)p.M * p.lda * es >= (1ull << 32) || (uint64_t)p.N * p.ldw * es >= (1ull << 32)) {
-      ca_set_error("%s[%d]: operand larger than 4 GiB", FN, i);
-      return CA_ERR_ARG;
-    }
-    if (p.out_f32 && ((p.epilogue != CA_EPI_BIAS && p.epilogue != CA_EPI_GATE_RESIDUAL) || p.ldc % 4 ||
-                      (p.epilogue == CA_EPI_GATE_RESIDUAL && p.ldr % 4))) {
-      ca_set_error("%s[%d]: out_f32 needs the BIAS or GATE_RESIDUAL epilogue and ldc/ldr %% 4 == 0", FN, i);
-      return CA_ERR_ARG;
-    }
-    switch (p.epilogue) {
-      case CA_EPI_BIAS:
-      case CA_EPI_GELU_TANH:
-        if (p.ldc < p.N) { ca_set_error("%s[%d]: ldc < N", FN, i); return CA_ERR_ARG; }
-        break;
-      case CA_EPI_GATE_RESIDUAL:
-        if (!p.resid || !p.gate || (p.ldr % 8 && !p.out_f32) || p.ldc < p.N || ((uintptr_t)p.resid & 15) ||
-            ((uintptr_t)p.gate & 15) || ((uintptr_t)p.gate2 & 15) || (p.gate_rows < p.M && !p.gate2)) {
-          ca_set_error("%s[%d]: GATE_RESIDUAL needs resid, gate (and gate2 when gate_rows < M), 16-byte aligned", FN, i);
-          return CA_ERR_ARG;
-        }
-        if (p.gate_stride && (p.gate_stride % 4 || p.gate_stride < 0 || (p.gate_rows > 0 && p.gate_item_rows < 1) ||
-                              (p.gate_rows < p.M && p.gate2_item_rows < 1))) {
-          ca_set_error("%s[%d]: per-item gates need gate_stride %% 4 == 0 and gate_item_rows / gate2_item_rows >= 1", FN, i);
-          return CA_ERR_ARG;
-        }
-        break;
-      case CA_EPI_QKV_NORM_ROPE:
-        // (N == n_split / 3: the q third alone -- the low-plane q projection of a captured layer, qpre_f32 = 3)
-        if (tile != CA_TILE_PP_256x256 || p.n_split <= 0 || p.n_split % 768 ||
-            (p.n_split > p.N && p.N != p.n_split / 3) || !p.norm_q ||
-            !p.norm_k || !p.rope || (p.n_split < p.N && (!p.out2 || p.ld2 % 8 || p.ld2 < p.N - p.n_split)) ||
-            p.ldc < (p.N < p.n_split ? p.N : p.n_split) ||
-            (p.q_prerope && (p.ldp % (p.qpre_f32 ? 4 : 8) || p.ldp < p.n_split / 3 || p.qpre_f32 < 0 || p.qpre_f32 > 3)) ||
-            (p.qpre_f32 == 3 && (!p.q_prerope || fp8)) ||
-            (p.qk_f16 != 0 && p.qk_f16 != 1) ||
-            (((uintptr_t)p.norm_q | (uintptr_t)p.norm_k | (uintptr_t)p.rope | (uintptr_t)p.q_prerope |
-              (uintptr_t)p.out2) & 15)) {
-          ca_set_error("%s[%d]: QKV_NORM_ROPE needs the 256x256 ping-pong tile, n_split = 3*heads*128 <= N, "
-                       "norm_q/norm_k/rope (16-byte aligned) and out2 when N > n_split", FN, i);
-          return CA_ERR_ARG;
-        }
-        break;
-      case CA_EPI_SPLIT_GELU:
-        if (!p.out2 || p.n_split <= 0 || p.n_split >= p.N || p.n_split % bn || p.ld2 % 8 ||
-            ((uintptr_t)p.out2 & 15) || p.ldc < p.n_split || p.ld2 < p.N - p.n_split) {
-          ca_set_error("%s[%d]: SPLIT_GELU needs out2 and 0 < n_split < N, n_split %% %d == 0", FN, i, bn);
-          return CA_ERR_ARG;
-        }
-        break;
-      default:
-        ca_set_error("%s[%d]: unknown epilogue %d", FN, i, p.epilogue);
-        return CA_ERR_ARG;
-    }
+    const int rc = check_problem(p, i, tile, bn, fp8, FN);
+    if (rc != CA_OK) return rc;
     L.p[i] = p;
     L.mt[i] = (p.M + 255) / 256;
     L.nt[i] = p.N / bn;
@@ -1562,26 +1500,18 @@ int plan_gemm(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile,
   // last round for every thin tile -- the one-item forward: 204 + 12 tiles on 256 CUs -- the thin tiles ride in the walk
   // (they are walked last, cost 0.75 of a full tile and finish inside the round that runs anyway): no second launch.
   // All three forms give the same bits per row (tests/test_kernels_gpu.py: thin rows in-walk / own kernel / full tile).
-  int main_all = 0, thin_all = 0;
-  for (int i = 0; i < n_problems; ++i) {
-    const int rem = L.p[i].M % 256;
-    const int thin = (rem > 0 && rem <= THIN_ROWS) ? 1 : 0;
-    main_all += (L.mt[i] - thin) * L.nt[i];
-    thin_all += thin * L.nt[i];
-  }
-  const bool thin_fits = thin_rides_in_walk(main_all, thin_all, n_cu);
+  const TileSplit ts = split_tiles(problems, n_problems, bn);
+  const bool thin_fits = thin_rides_in_walk(ts, n_cu);
   int total_pp = 0;
   for (int i = 0; i < CA_GEMM_MAX_PROBLEMS; ++i) {  // tile order of the ping-pong kernel: thin last row tiles go last
-    const int rem = i < n_problems ? L.p[i].M % 256 : 0;
-    const int thin = (rem > 0 && rem <= THIN_ROWS) ? 1 : 0;
     // under the bf16 256x256 tile: their own launch of 32 x 128 tiles instead (ca_gemm_thin_kernel), one grid row
     // per 32 rows
-    const bool own = thin && !fp8 && tile == CA_TILE_PP_256x256 && !thin_fits;
-    L.mt_main[i] = i < n_problems ? L.mt[i] - thin : 1;
-    L.ntiles_main[i] = i < n_problems ? L.mt_main[i] * L.nt[i] : 0;
-    L.nthin[i] = (thin && !own) ? L.nt[i] : 0;
+    const bool own = ts.thin[i] && !fp8 && tile == CA_TILE_PP_256x256 && !thin_fits;
+    L.mt_main[i] = i < n_problems ? ts.mt_main[i] : 1;
+    L.ntiles_main[i] = (int)ts.main[i];
+    L.nthin[i] = own ? 0 : (int)ts.nthin[i];
     L.thin_row0[i] = own ? (L.mt[i] - 1) * 256 : 0;
-    L.thin_nt[i] = own ? L.p[i].N / THIN_N : 0;
+    L.thin_nt[i] = own ? L.p[i].N / THIN_NT_COLS : 0;
     L.main_total += L.ntiles_main[i];
     total_pp += L.ntiles_main[i] + L.nthin[i];
   }
@@ -1600,36 +1530,36 @@ int plan_gemm(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile,
   if (!fp8 && tile == CA_TILE_PP_256x256 && L.thin_nt[0] + L.thin_nt[1] > 0) {
     if (total == 0) out->kernel = CA_GEMM_KERNEL_NONE;
     pick_thin(L, &out->thin_mf, &out->thin_nw, &out->thin_groups);
-    out->thin_grid_x = (L.thin_nt[0] + L.thin_nt[1]) * (4 / out->thin_nw);
+    out->thin_grid_x = (L.thin_nt[0] + L.thin_nt[1]) * (THIN_NT_COLS / thin_tile_cols(out->thin_nw));
   }
   return CA_OK;
 }
 
-// shared argument checking + launch of ca_gemm_bf16 / ca_gemm_fp8 (FN = the entry point's name for messages)
+// shared planning + launch of ca_gemm_bf16 / ca_gemm_fp8 (FN = the entry point's name for messages)
 int gemm_impl(const ca_gemm_problem *problems, int32_t n_problems, int32_t tile, ca_stream_t stream, bool fp8,
               const char *FN) {
   GemmPlan P;
   const int rc = plan_gemm(problems, n_problems, tile, fp8, ca_cu_count(), FN, &P);
   if (rc != CA_OK) return rc;
   const GemmLaunch &L = P.L;
-  const int total = P.total;
   hipStream_t s = (hipStream_t)stream;
-  if (fp8) return launch_pp<2, 2, true>(L, total, s);
+  const int grid = P.grid;  // one workgroup per tile, or the CU-sized grid of the ping-pong kernel's persistent walk
+  if (fp8) return launch_pp<2, 2, true>(L, grid, s, FN);
   if (P.thin_mf) {
-    if (total > 0) {
-      const int rc = launch_pp<2, 2>(L, total, s);
+    if (P.total > 0) {
+      const int rc = launch_pp<2, 2>(L, grid, s, FN);
       if (rc != CA_OK) return rc;
     }
-    return launch_thin(L, P.thin_mf, P.thin_nw, P.thin_groups, s);
+    return launch_thin(L, P.thin_mf, P.thin_nw, dim3(P.thin_grid_x, P.thin_groups), s, FN);
   }
   switch (P.tile) {
-    case CA_TILE_PP_256x256: return launch_pp<2, 2>(L, total, s);
-    case CA_TILE_PP_256x192: return launch_pp<2, 1>(L, total, s);
-    case CA_TILE_PP_256x128: return launch_pp<1, 1>(L, total, s);
-    case CA_TILE_256x256: return launch<8, 4>(L, total, s);
-    case CA_TILE_256x192: return launch<8, 3>(L, total, s);
-    case CA_TILE_256x128: return launch<8, 2>(L, total, s);
-    default: return launch<8, 1>(L, total, s);
+    case CA_TILE_PP_256x256: return launch_pp<2, 2>(L, grid, s, FN);
+    case CA_TILE_PP_256x192: return launch_pp<2, 1>(L, grid, s, FN);
+    case CA_TILE_PP_256x128: return launch_pp<1, 1>(L, grid, s, FN);
+    case CA_TILE_256x256: return launch_classic<4>(L, grid, s, FN);
+    case CA_TILE_256x192: return launch_classic<3>(L, grid, s, FN);
+    case CA_TILE_256x128: return launch_classic<2>(L, grid, s, FN);
+    default: return launch_classic<1>(L, grid, s, FN);
   }
 }
 

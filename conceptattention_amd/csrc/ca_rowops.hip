@@ -2,7 +2,6 @@
 // QK-RMSNorm+RoPE, small-batch GEMV (weight streaming), concept heat-map reduction, Euler axpy.
 // All use 16-byte-per-lane coalesced accesses and fp32 arithmetic; none of them is shaped into
 // an MFMA product (they are bandwidth-bound: see DESIGN.md for bytes per unit).
-#include <atomic>
 #include <type_traits>
 
 #include "ca_common.h"
@@ -880,15 +879,6 @@ __global__ __launch_bounds__(256) void ca_timestep_embedding_kernel(const float 
   }
 }
 
-int check_launch(const char *what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    ca_set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-    return CA_ERR_LAUNCH;
-  }
-  return CA_OK;
-}
-
 }  // namespace
 
 namespace {
@@ -934,7 +924,7 @@ int ln_modulate_impl(const char *FN, const void *x, int32_t ldx, void *out, int3
     else
       hipLaunchKernelGGL((ca_ln_modulate_rows_kernel<6, false>), g2, block, 0, st, (const float *)x, ldx, (bf16 *)out, ldo,
                          M, eps, A, (bf16 *)nullptr, 0);
-    return check_launch(FN);
+    return ca_check_launch(FN);
   }
   if (out_lo)
     hipLaunchKernelGGL((ca_ln_modulate_kernel<false, float, true>), grid, block, 0, st, (const float *)x, ldx, out, ldo,
@@ -951,7 +941,7 @@ int ln_modulate_impl(const char *FN, const void *x, int32_t ldx, void *out, int3
   else
     hipLaunchKernelGGL((ca_ln_modulate_kernel<false, bf16>), grid, block, 0, st, (const bf16 *)x, ldx, out, ldo, M, H,
                        eps, (float *)nullptr, A);
-  return check_launch(FN);
+  return ca_check_launch(FN);
 }
 }  // namespace
 
@@ -1006,7 +996,7 @@ extern "C" int ca_quantize_rows_fp8(const void *x, int32_t ldx, void *out8, int3
   }
   hipLaunchKernelGGL(ca_quantize_rows_fp8_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream,
                      (const bf16 *)x, ldx, (uint8_t *)out8, ldo, out_scale, M, K);
-  return check_launch("ca_quantize_rows_fp8");
+  return ca_check_launch("ca_quantize_rows_fp8");
 }
 
 extern "C" int ca_qknorm_rope_bf16(void *qkv, int32_t ld, int32_t M, int32_t num_heads,
@@ -1037,7 +1027,7 @@ extern "C" int ca_qknorm_rope_bf16(void *qkv, int32_t ld, int32_t M, int32_t num
   const long units = (long)M * 2 * num_heads;
   hipLaunchKernelGGL(ca_qknorm_rope_kernel, dim3((unsigned)((units + 15) / 16)), dim3(256), 0, (hipStream_t)stream,
                      (bf16 *)qkv, ld, M, num_heads, rope_cos_sin, (bf16 *)q_prerope, ldp, A);
-  return check_launch("ca_qknorm_rope_bf16");
+  return ca_check_launch("ca_qknorm_rope_bf16");
 }
 
 extern "C" int ca_gemv_bf16(const float *x, int32_t nv, int32_t ldx, const void *W, const void *bias, float *out,
@@ -1056,20 +1046,11 @@ extern "C" int ca_gemv_bf16(const float *x, int32_t nv, int32_t ldx, const void 
   hipLaunchKernelGGL(ca_gemv_kernel<NV>, dim3(grid), dim3(256), lds, s, x, ldx, (const bf16 *)W, (const bf16 *)bias, \
                      out, ldo, N, K, silu_input, accumulate)
   if (lds > 64 * 1024) {  // 5..8 vectors of K > 2048: opt in to the large dynamic-LDS carve-out once
-    static std::atomic<unsigned long long> attr_done{0};  // one bit per device: the attribute is per device
-    const unsigned long long dev_bit = ca_device_bit();
-    if (!(attr_done.load(std::memory_order_acquire) & dev_bit)) {
-      hipError_t e = hipSuccess;
-      const void *fns[] = {(const void *)ca_gemv_kernel<5>, (const void *)ca_gemv_kernel<6>,
-                           (const void *)ca_gemv_kernel<7>, (const void *)ca_gemv_kernel<8>};
-      for (const void *f : fns)
-        if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4096 * 4);
-      if (e != hipSuccess) {
-        ca_set_error("ca_gemv_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return CA_ERR_LAUNCH;
-      }
-      attr_done.fetch_or(dev_bit, std::memory_order_release);  // idempotent: a race only repeats the call
-    }
+    static std::atomic<unsigned long long> attr_done{0};
+    const int rc = ca_raise_lds_limit({(const void *)ca_gemv_kernel<5>, (const void *)ca_gemv_kernel<6>,
+                                       (const void *)ca_gemv_kernel<7>, (const void *)ca_gemv_kernel<8>},
+                                      8 * 4096 * 4, attr_done, "ca_gemv_bf16");
+    if (rc != CA_OK) return rc;
   }
   switch (nv) {
     case 1: CA_GEMV_LAUNCH(1); break;
@@ -1082,7 +1063,7 @@ extern "C" int ca_gemv_bf16(const float *x, int32_t nv, int32_t ldx, const void 
     default: CA_GEMV_LAUNCH(8); break;
   }
 #undef CA_GEMV_LAUNCH
-  return check_launch("ca_gemv_bf16");
+  return ca_check_launch("ca_gemv_bf16");
 }
 
 extern "C" int ca_heatmap_logits_bf16(const void *img_vec, int32_t ldi, const void *con_vec, int32_t ldc,
@@ -1109,7 +1090,7 @@ extern "C" int ca_heatmap_logits_bf16(const void *img_vec, int32_t ldi, const vo
     else
       hipLaunchKernelGGL((ca_heatmap_logits_kernel<4, bf16>), dim3(grid), dim3(256), lds, (hipStream_t)stream,
                          (const bf16 *)img_vec, ldi, (const bf16 *)con_vec, ldc, L, C, c0, dim, logits);
-    const int rc = check_launch("ca_heatmap_logits_bf16");
+    const int rc = ca_check_launch("ca_heatmap_logits_bf16");
     if (rc) return rc;
   }
   return CA_OK;
@@ -1131,7 +1112,7 @@ extern "C" int ca_qpre_finish_rope_f32(float *x, int32_t ldx, const float *d, in
   const long threads = (long)M * heads * 16;
   hipLaunchKernelGGL(ca_qpre_finish_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      x, ldx, d, ldd, (const bf16 *)norm_scale, M, heads, rope, q_out, ldq, q_out_scale, q_f16);
-  return check_launch("ca_qpre_finish_f32");
+  return ca_check_launch("ca_qpre_finish_f32");
 }
 
 extern "C" int ca_qpre_finish_f32(float *x, int32_t ldx, const float *d, int32_t ldd, const void *norm_scale, int32_t M,
@@ -1147,7 +1128,7 @@ extern "C" int ca_heatmap_softmax_accumulate(const float *logits, int32_t C, int
   }
   hipLaunchKernelGGL(ca_heatmap_softmax_kernel, dim3((L + 255) / 256), dim3(256), 0, (hipStream_t)stream, logits, C, L,
                      weight, acc);
-  return check_launch("ca_heatmap_softmax_accumulate");
+  return ca_check_launch("ca_heatmap_softmax_accumulate");
 }
 
 extern "C" int ca_heatmap_norm_accumulate(const float *logits, int32_t C, int32_t L, int32_t norm, float weight,
@@ -1166,7 +1147,7 @@ extern "C" int ca_heatmap_norm_accumulate(const float *logits, int32_t C, int32_
     if (C <= 8) hipLaunchKernelGGL((ca_heatmap_sparse_kernel<8, true>), grid, block, 0, s, logits, C, L, weight, acc);
     else hipLaunchKernelGGL((ca_heatmap_sparse_kernel<16, true>), grid, block, 0, s, logits, C, L, weight, acc);
   }
-  return check_launch("ca_heatmap_norm_accumulate");
+  return ca_check_launch("ca_heatmap_norm_accumulate");
 }
 
 extern "C" int ca_heatmap_fused(const ca_heatmap_problem *problems, int32_t n_problems, int32_t L, int32_t C,
@@ -1197,16 +1178,9 @@ extern "C" int ca_heatmap_fused(const ca_heatmap_problem *problems, int32_t n_pr
   const size_t lds = (size_t)cc * dim * sizeof(float);
   if (lds > 64 * 1024) {   // C > 4 at the model's dim: above the default dynamic LDS limit
     static std::atomic<unsigned long long> attr_done{0};
-    const unsigned long long dev_bit = ca_device_bit();
-    if (!(attr_done.load(std::memory_order_acquire) & dev_bit)) {
-      const hipError_t e = hipFuncSetAttribute((const void *)ca_heatmap_fused_kernel<8>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4096 * (int)sizeof(float));
-      if (e != hipSuccess) {
-        ca_set_error("ca_heatmap_fused: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return CA_ERR_LAUNCH;
-      }
-      attr_done.fetch_or(dev_bit, std::memory_order_release);
-    }
+    const int rc = ca_raise_lds_limit({(const void *)ca_heatmap_fused_kernel<8>}, 8 * 4096 * (int)sizeof(float), attr_done,
+                                      "ca_heatmap_fused");
+    if (rc != CA_OK) return rc;
   }
   // workgroups per problem: a wave takes 2 patches per pass; about 3 (C <= 4: 48 KB of LDS each) or 2 workgroups per CU
   // in all, so that the concept vectors are pulled into LDS a few hundred times per launch, not once per 8 patches
@@ -1219,7 +1193,7 @@ extern "C" int ca_heatmap_fused(const ca_heatmap_problem *problems, int32_t n_pr
     hipLaunchKernelGGL(ca_heatmap_fused_kernel<4>, dim3(gx, n_problems), dim3(threads), lds, (hipStream_t)stream, A);
   else
     hipLaunchKernelGGL(ca_heatmap_fused_kernel<8>, dim3(gx, n_problems), dim3(threads), lds, (hipStream_t)stream, A);
-  return check_launch("ca_heatmap_fused");
+  return ca_check_launch("ca_heatmap_fused");
 }
 
 namespace {
@@ -1254,7 +1228,7 @@ extern "C" int ca_silu_split_bf16(const float *x, int32_t ldx, void *hi, void *l
   const long blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
   hipLaunchKernelGGL(ca_silu_split_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, ldx,
                      (bf16 *)hi, (bf16 *)lo, ldo, rows, K);
-  return check_launch("ca_silu_split_bf16");
+  return ca_check_launch("ca_silu_split_bf16");
 }
 
 extern "C" int ca_split_bf16(const float *x, int32_t ldx, void *hi, void *lo, int32_t ldo, int32_t rows, int32_t K,
@@ -1268,7 +1242,7 @@ extern "C" int ca_split_bf16(const float *x, int32_t ldx, void *hi, void *lo, in
   const long blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
   hipLaunchKernelGGL(ca_silu_split_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, ldx,
                      (bf16 *)hi, (bf16 *)lo, ldo, rows, K);
-  return check_launch("ca_split_bf16");
+  return ca_check_launch("ca_split_bf16");
 }
 
 namespace {
@@ -1304,7 +1278,7 @@ extern "C" int ca_modulation_combine_f32(const float *pair, int32_t ldp, const v
   const long blocks = (n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048;
   hipLaunchKernelGGL(ca_modulation_combine_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, pair, ldp,
                      (const bf16 *)bias, out, ldo, nv, N);
-  return check_launch("ca_modulation_combine_f32");
+  return ca_check_launch("ca_modulation_combine_f32");
 }
 
 extern "C" int ca_axpy_bf16(void *x, const void *y, float a, int64_t n, ca_stream_t stream) {
@@ -1315,7 +1289,7 @@ extern "C" int ca_axpy_bf16(void *x, const void *y, float a, int64_t n, ca_strea
   const long blocks = (n + 2047) / 2048;
   hipLaunchKernelGGL(ca_axpy_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (bf16 *)x,
                      (const bf16 *)y, a, (long)n);
-  return check_launch("ca_axpy_bf16");
+  return ca_check_launch("ca_axpy_bf16");
 }
 
 extern "C" int ca_axpy_f32(float *x, const void *y, int32_t y_is_f32, float a, int64_t n, ca_stream_t stream) {
@@ -1330,7 +1304,7 @@ extern "C" int ca_axpy_f32(float *x, const void *y, int32_t y_is_f32, float a, i
   else
     hipLaunchKernelGGL(ca_axpy_f32_kernel<bf16>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x,
                        (const bf16 *)y, a, (long)n);
-  return check_launch("ca_axpy_f32");
+  return ca_check_launch("ca_axpy_f32");
 }
 
 extern "C" int ca_timestep_embedding_f32(const float *t, int32_t nt, float *out, int32_t dim, float time_factor,
@@ -1343,5 +1317,5 @@ extern "C" int ca_timestep_embedding_f32(const float *t, int32_t nt, float *out,
   const long blocks = (n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096;
   hipLaunchKernelGGL(ca_timestep_embedding_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, t, nt,
                      out, dim, time_factor, max_period);
-  return check_launch("ca_timestep_embedding_f32");
+  return ca_check_launch("ca_timestep_embedding_f32");
 }
