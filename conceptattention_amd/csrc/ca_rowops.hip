@@ -2,11 +2,12 @@
 // QK-RMSNorm+RoPE, small-batch GEMV (weight streaming), concept heat-map reduction, Euler axpy.
 // All use 16-byte-per-lane coalesced accesses and fp32 arithmetic; none of them is shaped into
 // an MFMA product (they are bandwidth-bound: see DESIGN.md for bytes per unit).
+#include <climits>
 #include <type_traits>
 
 #include "ca_common.h"
 
-namespace {
+namespace {   // device code
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -14,18 +15,42 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-// ------------------------------------------------------------------------------------------
-// out = (1 + scale) * LayerNorm(x) + shift ; one wave per row, row kept in registers.
-struct LnArgs {
-  ca_mod_segment seg[CA_MAX_SEGMENTS];
-  int32_t n_segs;
-};
-constexpr int LN_MAXCH = 8;  // H <= 8 * 512
-
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
   return v;
+}
+
+// 8 consecutive elements of an fp32 or bf16 row (16-byte aligned) as floats
+__device__ __forceinline__ void load8(const float *p, float *v) {
+  const f32x4 t0 = *(const f32x4 *)p, t1 = *(const f32x4 *)(p + 4);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = t0[j], v[4 + j] = t1[j];
+}
+__device__ __forceinline__ void load8(const bf16 *p, float *v) {
+  const bf16x8 t = *(const bf16x8 *)p;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = (float)t[j];
+}
+
+// a lane's 4 rotation pairs of a rope table row ([64 pairs][cos, sin]; rp = the row + 8 * the lane's 16th)
+__device__ __forceinline__ void rope_pairs(const float *rp, float (&cs)[4], float (&sn)[4]) {
+  const f32x4 r0 = *(const f32x4 *)rp, r1 = *(const f32x4 *)(rp + 4);
+  cs[0] = r0[0], cs[1] = r0[2], cs[2] = r1[0], cs[3] = r1[2];
+  sn[0] = r0[1], sn[1] = r0[3], sn[2] = r1[1], sn[3] = r1[3];
+}
+
+// 8 floats -> 8 bf16 in one 16-byte store
+__device__ __forceinline__ uint4 pack8_bf16(const float *v) {
+  return make_uint4(ca_pack2(v[0], v[1]), ca_pack2(v[2], v[3]), ca_pack2(v[4], v[5]), ca_pack2(v[6], v[7]));
+}
+
+// the part of 8 floats their bf16 rounding drops, as 8 bf16
+__device__ __forceinline__ uint4 pack8_bf16_residual(const float *y) {
+  float r[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = y[j] - (float)(bf16)y[j];
+  return pack8_bf16(r);
 }
 
 // 8 floats (already divided by the row scale) -> 8 OCP e4m3 bytes (v_cvt_pk_fp8_f32, RNE; inputs clamped to
@@ -43,11 +68,19 @@ __device__ __forceinline__ uint2 ca_pack_fp8x8(const float *y) {
   return make_uint2((uint32_t)lo, (uint32_t)hi);
 }
 
+// ------------------------------------------------------------------------------------------
+// out = (1 + scale) * LayerNorm(x) + shift ; one wave per row, row kept in registers.
 // FP8: the modulated row is quantised to e4m3 with one absmax scale per row (out8 row stride ldo BYTES,
 // out_scale[row] = absmax / 448): the A operand of ca_gemm_fp8.
 // LO (bf16 output only): a second plane out_lo = bf16(y - float(bf16(y))), the part of the modulated row its bf16
 // rounding drops; out + out_lo carries ~16 mantissa bits (the q projection of the layers whose cross-attention-space
 // vectors are captured is corrected with a product of this plane).
+struct LnArgs {
+  ca_mod_segment seg[CA_MAX_SEGMENTS];
+  int32_t n_segs;
+};
+constexpr int LN_MAXCH = 8;  // H <= 8 * 512
+
 // y = (1 + scale) * ((v - mean) * rstd) + shift, with its one fused multiply-add spelled out (both LayerNorm kernels
 // must round alike: a 5-item forward and a single-item one may run different ones)
 __device__ __forceinline__ float ln_apply(float v, float mean, float rstd, float scale1, float shift) {
@@ -58,8 +91,7 @@ template <bool FP8, typename XT = bf16, bool LO = false>
 __global__ __launch_bounds__(256) void ca_ln_modulate_kernel(const XT *__restrict__ x, int ldx,
                                                              void *__restrict__ out_, int ldo, int M, int H,
                                                              float eps, float *__restrict__ out_scale,
-                                                             const LnArgs A, bf16 *__restrict__ out_lo = nullptr,
-                                                             int ldlo = 0) {
+                                                             const LnArgs A, bf16 *__restrict__ out_lo, int ldlo) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
@@ -77,18 +109,7 @@ __global__ __launch_bounds__(256) void ca_ln_modulate_kernel(const XT *__restric
   for (int c = 0; c < LN_MAXCH; ++c) {
     const int k = c * 512 + lane * 8;
     if (k < H) {
-      if constexpr (std::is_same<XT, float>::value) {
-        const f32x4 t0 = *(const f32x4 *)(xr + k), t1 = *(const f32x4 *)(xr + k + 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          v[c][j] = t0[j];
-          v[c][4 + j] = t1[j];
-        }
-      } else {
-        const bf16x8 t = *(const bf16x8 *)(xr + k);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[c][j] = (float)t[j];
-      }
+      load8(xr + k, v[c]);
 #pragma unroll
       for (int j = 0; j < 8; ++j) sum += v[c][j];
     } else {
@@ -137,16 +158,8 @@ __global__ __launch_bounds__(256) void ca_ln_modulate_kernel(const XT *__restric
     for (int c = 0; c < LN_MAXCH; ++c) {
       const int k = c * 512 + lane * 8;
       if (k < H) {
-        *(uint4 *)((bf16 *)out_ + (size_t)row * ldo + k) =
-            make_uint4(ca_pack2(v[c][0], v[c][1]), ca_pack2(v[c][2], v[c][3]), ca_pack2(v[c][4], v[c][5]),
-                       ca_pack2(v[c][6], v[c][7]));
-        if constexpr (LO) {
-          float r[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) r[j] = v[c][j] - (float)(bf16)v[c][j];
-          *(uint4 *)(out_lo + (size_t)row * ldlo + k) =
-              make_uint4(ca_pack2(r[0], r[1]), ca_pack2(r[2], r[3]), ca_pack2(r[4], r[5]), ca_pack2(r[6], r[7]));
-        }
+        *(uint4 *)((bf16 *)out_ + (size_t)row * ldo + k) = pack8_bf16(v[c]);
+        if constexpr (LO) *(uint4 *)(out_lo + (size_t)row * ldlo + k) = pack8_bf16_residual(v[c]);
       }
     }
   }
@@ -191,11 +204,7 @@ __global__ __launch_bounds__(256, 2) void ca_ln_modulate_rows_kernel(const float
   auto load_row = [&](int buf, int row) {
     const float *xr = x + (size_t)row * ldx + lane * 8;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const f32x4 t0 = *(const f32x4 *)(xr + c * 512), t1 = *(const f32x4 *)(xr + c * 512 + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[buf][c][j] = t0[j], v[buf][c][4 + j] = t1[j];
-    }
+    for (int c = 0; c < NCH; ++c) load8(xr + c * 512, v[buf][c]);
   };
   auto do_row = [&](int buf, int row) {
     int si = 0;
@@ -237,15 +246,8 @@ __global__ __launch_bounds__(256, 2) void ca_ln_modulate_rows_kernel(const float
 #pragma unroll
       for (int j = 0; j < 8; ++j) y[j] = ln_apply(v[buf][c][j], mean, rstd, sc1[c][j], sh[c][j]);
       const int k = c * 512 + lane * 8;
-      *(uint4 *)(out + (size_t)row * ldo + k) =
-          make_uint4(ca_pack2(y[0], y[1]), ca_pack2(y[2], y[3]), ca_pack2(y[4], y[5]), ca_pack2(y[6], y[7]));
-      if constexpr (LO) {
-        float r[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = y[j] - (float)(bf16)y[j];
-        *(uint4 *)(out_lo + (size_t)row * ldlo + k) =
-            make_uint4(ca_pack2(r[0], r[1]), ca_pack2(r[2], r[3]), ca_pack2(r[4], r[5]), ca_pack2(r[6], r[7]));
-      }
+      *(uint4 *)(out + (size_t)row * ldo + k) = pack8_bf16(y);
+      if constexpr (LO) *(uint4 *)(out_lo + (size_t)row * ldlo + k) = pack8_bf16_residual(y);
     }
   };
   for (int i = 0; i < nrows; ++i) {   // (two waves per SIMD; requesting the next row ahead of the reduction -- a second row
@@ -325,22 +327,17 @@ __global__ __launch_bounds__(256) void ca_qknorm_rope_kernel(bf16 *__restrict__ 
 #pragma unroll
   for (int j = 0; j < 8; ++j) x[j] = x[j] * rrms * (float)sv[j];
   if (!valid) return;
-  if (q_prerope && which == 0) {
-    *(uint4 *)(q_prerope + (size_t)row * ldp + head * 128 + t16 * 8) =
-        make_uint4(ca_pack2(x[0], x[1]), ca_pack2(x[2], x[3]), ca_pack2(x[4], x[5]), ca_pack2(x[6], x[7]));
-  }
+  if (q_prerope && which == 0) *(uint4 *)(q_prerope + (size_t)row * ldp + head * 128 + t16 * 8) = pack8_bf16(x);
   // rope table row: [64 pairs][cos, sin]; this lane owns pairs 4*t16 .. 4*t16+3
-  const float *rp = rope + (size_t)row * 128 + t16 * 8;
-  const f32x4 r0 = *(const f32x4 *)rp, r1 = *(const f32x4 *)(rp + 4);
-  const float cs[4] = {r0[0], r0[2], r1[0], r1[2]};
-  const float sn[4] = {r0[1], r0[3], r1[1], r1[3]};
+  float cs[4], sn[4];
+  rope_pairs(rope + (size_t)row * 128 + t16 * 8, cs, sn);
   float y[8];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     y[2 * i] = cs[i] * x[2 * i] - sn[i] * x[2 * i + 1];
     y[2 * i + 1] = sn[i] * x[2 * i] + cs[i] * x[2 * i + 1];
   }
-  *(uint4 *)p = make_uint4(ca_pack2(y[0], y[1]), ca_pack2(y[2], y[3]), ca_pack2(y[4], y[5]), ca_pack2(y[6], y[7]));
+  *(uint4 *)p = pack8_bf16(y);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -453,10 +450,9 @@ __global__ __launch_bounds__(256) void ca_qpre_finish_kernel(float *__restrict__
   *(f32x4 *)xp = a0;
   *(f32x4 *)(xp + 4) = a1;
   if (q_out) {
-    const float *rp = rope + (size_t)row * 128 + t16 * 8;   // [64 pairs][cos, sin]: pairs 4 t16 .. 4 t16 + 3
-    const f32x4 r0 = *(const f32x4 *)rp, r1 = *(const f32x4 *)(rp + 4);
     const float y[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-    const float cs[4] = {r0[0], r0[2], r1[0], r1[2]}, sn[4] = {r0[1], r0[3], r1[1], r1[3]};
+    float cs[4], sn[4];
+    rope_pairs(rope + (size_t)row * 128 + t16 * 8, cs, sn);
     const float qos = q_out_scale == 0.0f ? 1.0f : q_out_scale;
     float z[8];
 #pragma unroll
@@ -466,7 +462,7 @@ __global__ __launch_bounds__(256) void ca_qpre_finish_kernel(float *__restrict__
     }
     uint4 o;
     if (q_f16) o = make_uint4(ca_pack2_f16(z[0], z[1]), ca_pack2_f16(z[2], z[3]), ca_pack2_f16(z[4], z[5]), ca_pack2_f16(z[6], z[7]));
-    else o = make_uint4(ca_pack2(z[0], z[1]), ca_pack2(z[2], z[3]), ca_pack2(z[4], z[5]), ca_pack2(z[6], z[7]));
+    else o = pack8_bf16(z);
     *(uint4 *)((char *)q_out + ((size_t)row * ldq + head * 128 + t16 * 8) * 2) = o;
   }
 }
@@ -834,7 +830,7 @@ __global__ __launch_bounds__(256) void ca_axpy_kernel(bf16 *__restrict__ x, cons
     float r[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) r[j] = fmaf(a, (float)yv[j], (float)xv[j]);
-    *(uint4 *)(x + i) = make_uint4(ca_pack2(r[0], r[1]), ca_pack2(r[2], r[3]), ca_pack2(r[4], r[5]), ca_pack2(r[6], r[7]));
+    *(uint4 *)(x + i) = pack8_bf16(r);
   } else {
     for (long j = i; j < n; ++j) x[j] = (bf16)fmaf(a, (float)y[j], (float)x[j]);
   }
@@ -846,15 +842,7 @@ __global__ __launch_bounds__(256) void ca_axpy_f32_kernel(float *__restrict__ x,
   const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 8;
   if (i + 8 <= n) {
     float yv[8];
-    if constexpr (sizeof(TY) == 2) {
-      const bf16x8 y8 = *(const bf16x8 *)(y + i);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) yv[j] = (float)y8[j];
-    } else {
-      const f32x4 y0 = *(const f32x4 *)(y + i), y1 = *(const f32x4 *)(y + i + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) yv[j] = y0[j], yv[4 + j] = y1[j];
-    }
+    load8(y + i, yv);
     f32x4 x0 = *(const f32x4 *)(x + i), x1 = *(const f32x4 *)(x + i + 4);
 #pragma unroll
     for (int j = 0; j < 4; ++j) x0[j] = fmaf(a, yv[j], x0[j]), x1[j] = fmaf(a, yv[4 + j], x1[j]);
@@ -879,14 +867,103 @@ __global__ __launch_bounds__(256) void ca_timestep_embedding_kernel(const float 
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// hi = bf16(f(x)), lo = bf16(f(x) - hi), f = silu or the identity: an fp32 [rows, K] matrix as two bf16 planes
+template <bool SILU>
+__global__ __launch_bounds__(256) void ca_silu_split_kernel(const float *__restrict__ x, int ldx, bf16 *__restrict__ hi,
+                                                            bf16 *__restrict__ lo, int ldo, int rows, int K) {
+  const long per_row = K >> 2;   // (64-bit: rows * per_row passes 2^31 long before the planes pass device memory)
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < rows * per_row; i += (long)gridDim.x * 256) {
+    const int r = (int)(i / per_row), k = (int)(i - r * per_row) << 2;
+    const f32x4 v = *(const f32x4 *)(x + (size_t)r * ldx + k);
+    bf16x4 h, l;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float s = SILU ? ca_silu(v[j]) : v[j];
+      h[j] = (bf16)s;
+      l[j] = (bf16)(s - (float)h[j]);
+    }
+    *(bf16x4 *)(hi + (size_t)r * ldo + k) = h;
+    *(bf16x4 *)(lo + (size_t)r * ldo + k) = l;
+  }
+}
+
+// out[v, :] = (pair[v, :] + bias) + pair[nv + v, :]: folds the products of the two planes of a modulation GEMM
+__global__ __launch_bounds__(256) void ca_modulation_combine_kernel(const float *__restrict__ pair, int ldp,
+                                                                    const bf16 *__restrict__ bias, float *__restrict__ out,
+                                                                    int ldo, int nv, int N) {
+  const long per_row = N >> 2;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv * per_row; i += (long)gridDim.x * 256) {
+    const int v = (int)(i / per_row), n = (int)(i - v * per_row) << 2;
+    const f32x4 h = *(const f32x4 *)(pair + (size_t)v * ldp + n), l = *(const f32x4 *)(pair + (size_t)(nv + v) * ldp + n);
+    f32x4 b = {0.f, 0.f, 0.f, 0.f};
+    if (bias) {
+      const bf16x4 b4 = *(const bf16x4 *)(bias + n);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b[j] = (float)b4[j];
+    }
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = (h[j] + b[j]) + l[j];
+    *(f32x4 *)(out + (size_t)v * ldo + n) = o;
+  }
+}
+
 }  // namespace
 
-namespace {
-int ln_modulate_impl(const char *FN, const void *x, int32_t ldx, void *out, int32_t ldo, float *out_scale, int32_t M,
-                     int32_t H, const ca_mod_segment *segs, int32_t n_segs, float eps, ca_stream_t stream,
-                     bool x_f32 = false, void *out_lo = nullptr, int32_t ldlo = 0) {
-  const bool fp8 = out_scale != nullptr;
-  if (out_lo && (fp8 || !x_f32 || ldlo % 8 || ldlo < H || ((uintptr_t)out_lo & 15))) {
+namespace {   // host helpers
+
+// One kernel launch of this unit and its check.  The arguments are converted to the kernel's parameter types (a void *
+// of the C interface becomes the kernel's typed pointer).  FN = the entry point's name for messages.
+template <typename... KA, typename... A>
+int launch(void (*kernel)(KA...), dim3 grid, dim3 block, size_t lds_bytes, ca_stream_t stream, const char *FN, A... args) {
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, (hipStream_t)stream, static_cast<KA>(args)...);
+  return ca_check_launch(FN);
+}
+
+// workgroups of a one-dimensional launch: n items, per_block of them per workgroup, at most cap workgroups
+unsigned grid_1d(long n, long per_block, long cap = LONG_MAX) {
+  const long blocks = (n + per_block - 1) / per_block;
+  return (unsigned)(blocks < cap ? blocks : cap);
+}
+
+// The segment table of a launch (1 <= n_segs <= CA_MAX_SEGMENTS) copied into the kernel's argument struct: row_end
+// non-decreasing and covering M rows, the two vectors `va`, `vb` of every segment present and 16-byte aligned.
+template <typename ARGS, typename SEG, typename T>
+int take_segments(const char *FN, ARGS &A, const SEG *segs, int n_segs, int M, T SEG::*va, T SEG::*vb) {
+  A.n_segs = n_segs;
+  int prev = 0;
+  for (int i = 0; i < n_segs; ++i) {
+    const void *a = segs[i].*va, *b = segs[i].*vb;
+    if (!a || !b || segs[i].row_end < prev || (((uintptr_t)a | (uintptr_t)b) & 15)) {
+      ca_set_error("%s: segment %d invalid (row_end must be non-decreasing, vectors 16-byte aligned)", FN, i);
+      return CA_ERR_ARG;
+    }
+    prev = segs[i].row_end;
+    A.seg[i] = segs[i];
+  }
+  if (prev < M) {
+    ca_set_error("%s: segments cover %d rows, M=%d", FN, prev, M);
+    return CA_ERR_ARG;
+  }
+  return CA_OK;
+}
+
+// The five ca_ln_modulate_* entry points: `form` says what the entry point reads and writes.
+enum { LN_F32IN = 1, LN_FP8 = 2, LN_SPLIT = 4 };
+int ln_modulate(const char *FN, int form, const void *x, int32_t ldx, void *out, int32_t ldo, float *out_scale,
+                void *out_lo, int32_t ldlo, int32_t M, int32_t H, const ca_mod_segment *segs, int32_t n_segs, float eps,
+                ca_stream_t stream) {
+  const bool x_f32 = form & LN_F32IN, fp8 = form & LN_FP8, split = form & LN_SPLIT;
+  if (fp8 && !out_scale) {
+    ca_set_error("%s: out_scale is NULL", FN);
+    return CA_ERR_ARG;
+  }
+  if (split && !out_lo) {
+    ca_set_error("%s: out_lo is NULL", FN);
+    return CA_ERR_ARG;
+  }
+  if (split && (ldlo % 8 || ldlo < H || ((uintptr_t)out_lo & 15))) {
     ca_set_error("%s: the low plane needs an fp32 input, a bf16 output, ldlo %% 8 == 0 and ldlo >= H", FN);
     return CA_ERR_ARG;
   }
@@ -898,93 +975,90 @@ int ln_modulate_impl(const char *FN, const void *x, int32_t ldx, void *out, int3
     return CA_ERR_ARG;
   }
   LnArgs A = {};
-  A.n_segs = n_segs;
-  int prev = 0;
-  for (int i = 0; i < n_segs; ++i) {
-    if (!segs[i].shift || !segs[i].scale || segs[i].row_end < prev ||
-        (((uintptr_t)segs[i].shift | (uintptr_t)segs[i].scale) & 15)) {
-      ca_set_error("%s: segment %d invalid (row_end must be non-decreasing, vectors 16-byte aligned)", FN, i);
-      return CA_ERR_ARG;
-    }
-    prev = segs[i].row_end;
-    A.seg[i] = segs[i];
+  if (const int rc = take_segments(FN, A, segs, n_segs, M, &ca_mod_segment::shift, &ca_mod_segment::scale)) return rc;
+  if (x_f32 && !fp8 && H == 3072) {   // the model's shape: a wave walks 8 rows (vectors kept in registers)
+    const auto kernel = split ? ca_ln_modulate_rows_kernel<6, true> : ca_ln_modulate_rows_kernel<6, false>;
+    return launch(kernel, grid_1d(M, 4 * LN_ROWS_PER_WAVE), 256, 0, stream, FN, x, ldx, out, ldo, M, eps, A, out_lo, ldlo);
   }
-  if (prev < M) {
-    ca_set_error("%s: segments cover %d rows, M=%d", FN, prev, M);
+  const auto go = [&](auto kernel) {
+    return launch(kernel, grid_1d(M, 4), 256, 0, stream, FN, x, ldx, out, ldo, M, H, eps, out_scale, A, out_lo, ldlo);
+  };
+  if (split) return go(ca_ln_modulate_kernel<false, float, true>);
+  if (x_f32) return fp8 ? go(ca_ln_modulate_kernel<true, float>) : go(ca_ln_modulate_kernel<false, float>);
+  return fp8 ? go(ca_ln_modulate_kernel<true, bf16>) : go(ca_ln_modulate_kernel<false, bf16>);
+}
+
+// ca_qpre_finish_f32 is ca_qpre_finish_rope_f32 without the q output
+int qpre_finish(const char *FN, float *x, int32_t ldx, const float *d, int32_t ldd, const void *norm_scale,
+                const float *rope, void *q_out, int32_t ldq, float q_out_scale, int32_t q_f16, int32_t M, int32_t heads,
+                ca_stream_t stream) {
+  if (!x || !norm_scale || M < 1 || heads < 1 || ldx % 4 || ldx < heads * 128 || (d && (ldd % 4 || ldd < heads * 128)) ||
+      (((uintptr_t)x | (uintptr_t)d | (uintptr_t)norm_scale) & 15)) {
+    ca_set_error("%s: bad arguments (M=%d heads=%d ldx=%d ldd=%d)", FN, M, heads, ldx, ldd);
     return CA_ERR_ARG;
   }
-  const dim3 grid((M + 3) / 4), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (x_f32 && !fp8 && H == 3072) {   // the model's shape: a wave walks 8 rows (vectors kept in registers)
-    const int waves = (M + LN_ROWS_PER_WAVE - 1) / LN_ROWS_PER_WAVE;
-    const dim3 g2((waves + 3) / 4);
-    if (out_lo)
-      hipLaunchKernelGGL((ca_ln_modulate_rows_kernel<6, true>), g2, block, 0, st, (const float *)x, ldx, (bf16 *)out, ldo,
-                         M, eps, A, (bf16 *)out_lo, ldlo);
-    else
-      hipLaunchKernelGGL((ca_ln_modulate_rows_kernel<6, false>), g2, block, 0, st, (const float *)x, ldx, (bf16 *)out, ldo,
-                         M, eps, A, (bf16 *)nullptr, 0);
-    return ca_check_launch(FN);
+  if (q_out && (!rope || ldq % 8 || ldq < heads * 128 || (((uintptr_t)rope | (uintptr_t)q_out) & 15) ||
+                !(q_out_scale >= 0.0f) || (q_f16 != 0 && q_f16 != 1))) {
+    ca_set_error("%s: q_out needs rope [M,64,2], ldq %% 8 == 0, ldq >= heads*128, 16-byte alignment", FN);
+    return CA_ERR_ARG;
   }
-  if (out_lo)
-    hipLaunchKernelGGL((ca_ln_modulate_kernel<false, float, true>), grid, block, 0, st, (const float *)x, ldx, out, ldo,
-                       M, H, eps, (float *)nullptr, A, (bf16 *)out_lo, ldlo);
-  else if (x_f32 && fp8)
-    hipLaunchKernelGGL((ca_ln_modulate_kernel<true, float>), grid, block, 0, st, (const float *)x, ldx, out, ldo, M, H,
-                       eps, out_scale, A);
-  else if (x_f32)
-    hipLaunchKernelGGL((ca_ln_modulate_kernel<false, float>), grid, block, 0, st, (const float *)x, ldx, out, ldo, M,
-                       H, eps, (float *)nullptr, A);
-  else if (fp8)
-    hipLaunchKernelGGL((ca_ln_modulate_kernel<true, bf16>), grid, block, 0, st, (const bf16 *)x, ldx, out, ldo, M, H,
-                       eps, out_scale, A);
-  else
-    hipLaunchKernelGGL((ca_ln_modulate_kernel<false, bf16>), grid, block, 0, st, (const bf16 *)x, ldx, out, ldo, M, H,
-                       eps, (float *)nullptr, A);
-  return ca_check_launch(FN);
+  return launch(ca_qpre_finish_kernel, grid_1d((long)M * heads * 16, 256), 256, 0, stream, FN, x, ldx, d, ldd, norm_scale,
+                M, heads, rope, q_out, ldq, q_out_scale, q_f16);
 }
+
+// ca_heatmap_norm_accumulate with CA_NORM_SOFTMAX is ca_heatmap_softmax_accumulate
+int heatmap_softmax(const char *FN, const float *logits, int32_t C, int32_t L, float weight, float *acc,
+                    ca_stream_t stream) {
+  if (!logits || !acc || C < 1 || L < 1) {
+    ca_set_error("%s: bad arguments (C=%d L=%d)", FN, C, L);
+    return CA_ERR_ARG;
+  }
+  return launch(ca_heatmap_softmax_kernel, grid_1d(L, 256), 256, 0, stream, FN, logits, C, L, weight, acc);
+}
+
+// ca_silu_split_bf16 and ca_split_bf16: `kernel` = ca_silu_split_kernel with and without the silu
+int split_planes(const char *FN, decltype(&ca_silu_split_kernel<true>) kernel, const float *x, int32_t ldx, void *hi,
+                 void *lo, int32_t ldo, int32_t rows, int32_t K, ca_stream_t stream) {
+  if (!x || !hi || !lo || rows < 1 || K < 4 || K % 4 || ldx < K || ldo < K || ldx % 4 || ldo % 4 ||
+      (((uintptr_t)x & 15) | (((uintptr_t)hi | (uintptr_t)lo) & 7))) {
+    ca_set_error("%s: bad arguments (rows=%d K=%d ldx=%d ldo=%d)", FN, rows, K, ldx, ldo);
+    return CA_ERR_ARG;
+  }
+  return launch(kernel, grid_1d((long)rows * (K / 4), 256, 1024), 256, 0, stream, FN, x, ldx, hi, lo, ldo, rows, K);
+}
+
 }  // namespace
 
 extern "C" int ca_ln_modulate_bf16(const void *x, int32_t ldx, void *out, int32_t ldo, int32_t M, int32_t H,
                                    const ca_mod_segment *segs, int32_t n_segs, float eps, ca_stream_t stream) {
-  return ln_modulate_impl("ca_ln_modulate_bf16", x, ldx, out, ldo, nullptr, M, H, segs, n_segs, eps, stream);
+  return ln_modulate("ca_ln_modulate_bf16", 0, x, ldx, out, ldo, nullptr, nullptr, 0, M, H, segs, n_segs, eps, stream);
 }
 
 extern "C" int ca_ln_modulate_fp8(const void *x, int32_t ldx, void *out8, int32_t ldo, float *out_scale, int32_t M,
                                   int32_t H, const ca_mod_segment *segs, int32_t n_segs, float eps,
                                   ca_stream_t stream) {
-  if (!out_scale) {
-    ca_set_error("ca_ln_modulate_fp8: out_scale is NULL");
-    return CA_ERR_ARG;
-  }
-  return ln_modulate_impl("ca_ln_modulate_fp8", x, ldx, out8, ldo, out_scale, M, H, segs, n_segs, eps, stream);
+  return ln_modulate("ca_ln_modulate_fp8", LN_FP8, x, ldx, out8, ldo, out_scale, nullptr, 0, M, H, segs, n_segs, eps,
+                     stream);
 }
 
 extern "C" int ca_ln_modulate_f32in(const float *x, int32_t ldx, void *out, int32_t ldo, int32_t M, int32_t H,
                                     const ca_mod_segment *segs, int32_t n_segs, float eps, ca_stream_t stream) {
-  return ln_modulate_impl("ca_ln_modulate_f32in", x, ldx, out, ldo, nullptr, M, H, segs, n_segs, eps, stream, true);
+  return ln_modulate("ca_ln_modulate_f32in", LN_F32IN, x, ldx, out, ldo, nullptr, nullptr, 0, M, H, segs, n_segs, eps,
+                     stream);
 }
 
 extern "C" int ca_ln_modulate_f32in_split(const float *x, int32_t ldx, void *out, int32_t ldo, void *out_lo,
                                           int32_t ldlo, int32_t M, int32_t H, const ca_mod_segment *segs,
                                           int32_t n_segs, float eps, ca_stream_t stream) {
-  if (!out_lo) {
-    ca_set_error("ca_ln_modulate_f32in_split: out_lo is NULL");
-    return CA_ERR_ARG;
-  }
-  return ln_modulate_impl("ca_ln_modulate_f32in_split", x, ldx, out, ldo, nullptr, M, H, segs, n_segs, eps, stream,
-                          true, out_lo, ldlo);
+  return ln_modulate("ca_ln_modulate_f32in_split", LN_F32IN | LN_SPLIT, x, ldx, out, ldo, nullptr, out_lo, ldlo, M, H,
+                     segs, n_segs, eps, stream);
 }
 
 extern "C" int ca_ln_modulate_f32in_fp8(const float *x, int32_t ldx, void *out8, int32_t ldo, float *out_scale,
                                         int32_t M, int32_t H, const ca_mod_segment *segs, int32_t n_segs, float eps,
                                         ca_stream_t stream) {
-  if (!out_scale) {
-    ca_set_error("ca_ln_modulate_f32in_fp8: out_scale is NULL");
-    return CA_ERR_ARG;
-  }
-  return ln_modulate_impl("ca_ln_modulate_f32in_fp8", x, ldx, out8, ldo, out_scale, M, H, segs, n_segs, eps, stream,
-                          true);
+  return ln_modulate("ca_ln_modulate_f32in_fp8", LN_F32IN | LN_FP8, x, ldx, out8, ldo, out_scale, nullptr, 0, M, H, segs,
+                     n_segs, eps, stream);
 }
 
 extern "C" int ca_quantize_rows_fp8(const void *x, int32_t ldx, void *out8, int32_t ldo, float *out_scale, int32_t M,
@@ -994,40 +1068,24 @@ extern "C" int ca_quantize_rows_fp8(const void *x, int32_t ldx, void *out8, int3
     ca_set_error("ca_quantize_rows_fp8: bad arguments (M=%d K=%d ldx=%d ldo=%d; need K%%8==0, ld%%8==0)", M, K, ldx, ldo);
     return CA_ERR_ARG;
   }
-  hipLaunchKernelGGL(ca_quantize_rows_fp8_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16 *)x, ldx, (uint8_t *)out8, ldo, out_scale, M, K);
-  return ca_check_launch("ca_quantize_rows_fp8");
+  return launch(ca_quantize_rows_fp8_kernel, grid_1d(M, 4), 256, 0, stream, "ca_quantize_rows_fp8", x, ldx, out8, ldo,
+                out_scale, M, K);
 }
 
 extern "C" int ca_qknorm_rope_bf16(void *qkv, int32_t ld, int32_t M, int32_t num_heads,
                                    const ca_norm_segment *segs, int32_t n_segs, const float *rope_cos_sin,
                                    void *q_prerope, int32_t ldp, ca_stream_t stream) {
+  const char *FN = "ca_qknorm_rope_bf16";
   if (!qkv || !segs || !rope_cos_sin || M < 1 || num_heads < 1 || n_segs < 1 || n_segs > CA_MAX_SEGMENTS ||
       ld % 8 || ld < 3 * num_heads * 128 || (((uintptr_t)qkv | (uintptr_t)rope_cos_sin | (uintptr_t)q_prerope) & 15) ||
       (q_prerope && (ldp % 8 || ldp < num_heads * 128))) {
-    ca_set_error("ca_qknorm_rope_bf16: bad arguments (M=%d heads=%d ld=%d n_segs=%d)", M, num_heads, ld, n_segs);
+    ca_set_error("%s: bad arguments (M=%d heads=%d ld=%d n_segs=%d)", FN, M, num_heads, ld, n_segs);
     return CA_ERR_ARG;
   }
   NormArgs A = {};
-  A.n_segs = n_segs;
-  int prev = 0;
-  for (int i = 0; i < n_segs; ++i) {
-    if (!segs[i].q_scale || !segs[i].k_scale || segs[i].row_end < prev ||
-        (((uintptr_t)segs[i].q_scale | (uintptr_t)segs[i].k_scale) & 15)) {
-      ca_set_error("ca_qknorm_rope_bf16: segment %d invalid", i);
-      return CA_ERR_ARG;
-    }
-    prev = segs[i].row_end;
-    A.seg[i] = segs[i];
-  }
-  if (prev < M) {
-    ca_set_error("ca_qknorm_rope_bf16: segments cover %d rows, M=%d", prev, M);
-    return CA_ERR_ARG;
-  }
-  const long units = (long)M * 2 * num_heads;
-  hipLaunchKernelGGL(ca_qknorm_rope_kernel, dim3((unsigned)((units + 15) / 16)), dim3(256), 0, (hipStream_t)stream,
-                     (bf16 *)qkv, ld, M, num_heads, rope_cos_sin, (bf16 *)q_prerope, ldp, A);
-  return ca_check_launch("ca_qknorm_rope_bf16");
+  if (const int rc = take_segments(FN, A, segs, n_segs, M, &ca_norm_segment::q_scale, &ca_norm_segment::k_scale)) return rc;
+  return launch(ca_qknorm_rope_kernel, grid_1d((long)M * 2 * num_heads, 16), 256, 0, stream, FN, qkv, ld, M, num_heads,
+                rope_cos_sin, q_prerope, ldp, A);
 }
 
 extern "C" int ca_gemv_bf16(const float *x, int32_t nv, int32_t ldx, const void *W, const void *bias, float *out,
@@ -1038,13 +1096,7 @@ extern "C" int ca_gemv_bf16(const float *x, int32_t nv, int32_t ldx, const void 
     ca_set_error("ca_gemv_bf16: bad arguments (nv=%d N=%d K=%d; need 1<=nv<=8, K%%8==0, K<=4096)", nv, N, K);
     return CA_ERR_ARG;
   }
-  const int rows_per_block = 4 * GEMV_ROWS;
-  const int grid = (N + rows_per_block - 1) / rows_per_block < 4096 ? (N + rows_per_block - 1) / rows_per_block : 4096;
   const size_t lds = (size_t)nv * K * sizeof(float);
-  hipStream_t s = (hipStream_t)stream;
-#define CA_GEMV_LAUNCH(NV)                                                                                     \
-  hipLaunchKernelGGL(ca_gemv_kernel<NV>, dim3(grid), dim3(256), lds, s, x, ldx, (const bf16 *)W, (const bf16 *)bias, \
-                     out, ldo, N, K, silu_input, accumulate)
   if (lds > 64 * 1024) {  // 5..8 vectors of K > 2048: opt in to the large dynamic-LDS carve-out once
     static std::atomic<unsigned long long> attr_done{0};
     const int rc = ca_raise_lds_limit({(const void *)ca_gemv_kernel<5>, (const void *)ca_gemv_kernel<6>,
@@ -1052,18 +1104,11 @@ extern "C" int ca_gemv_bf16(const float *x, int32_t nv, int32_t ldx, const void 
                                       8 * 4096 * 4, attr_done, "ca_gemv_bf16");
     if (rc != CA_OK) return rc;
   }
-  switch (nv) {
-    case 1: CA_GEMV_LAUNCH(1); break;
-    case 2: CA_GEMV_LAUNCH(2); break;
-    case 3: CA_GEMV_LAUNCH(3); break;
-    case 4: CA_GEMV_LAUNCH(4); break;
-    case 5: CA_GEMV_LAUNCH(5); break;
-    case 6: CA_GEMV_LAUNCH(6); break;
-    case 7: CA_GEMV_LAUNCH(7); break;
-    default: CA_GEMV_LAUNCH(8); break;
-  }
-#undef CA_GEMV_LAUNCH
-  return ca_check_launch("ca_gemv_bf16");
+  static constexpr decltype(&ca_gemv_kernel<1>) kernel[8] = {   // by nv - 1
+      ca_gemv_kernel<1>, ca_gemv_kernel<2>, ca_gemv_kernel<3>, ca_gemv_kernel<4>,
+      ca_gemv_kernel<5>, ca_gemv_kernel<6>, ca_gemv_kernel<7>, ca_gemv_kernel<8>};
+  return launch(kernel[nv - 1], grid_1d(N, 4 * GEMV_ROWS, 4096), 256, lds, stream, "ca_gemv_bf16", x, ldx, W, bias, out,
+                ldo, N, K, silu_input, accumulate);
 }
 
 extern "C" int ca_heatmap_logits_bf16(const void *img_vec, int32_t ldi, const void *con_vec, int32_t ldc,
@@ -1078,19 +1123,14 @@ extern "C" int ca_heatmap_logits_bf16(const void *img_vec, int32_t ldi, const vo
   }
   // 8 patches per workgroup and pass (2 per wave): the 4 * dim floats of concept vectors a workgroup puts into LDS are
   // then read once per 8 patches, and at most 512 workgroups keep them to 2 per CU's worth of L2 reads
-  const int grid = (L + 7) / 8 < 512 ? (L + 7) / 8 : 512;
-  const size_t lds = (size_t)4 * dim * sizeof(float);
   for (int c0 = 0; c0 < C; c0 += 4) {
-    if (img32)
-      hipLaunchKernelGGL((ca_heatmap_logits_kernel<4, float, float>), dim3(grid), dim3(256), lds, (hipStream_t)stream,
-                         (const float *)img_vec, ldi, (const float *)con_vec, ldc, L, C, c0, dim, logits);
-    else if (con32)
-      hipLaunchKernelGGL((ca_heatmap_logits_kernel<4, float>), dim3(grid), dim3(256), lds, (hipStream_t)stream,
-                         (const bf16 *)img_vec, ldi, (const float *)con_vec, ldc, L, C, c0, dim, logits);
-    else
-      hipLaunchKernelGGL((ca_heatmap_logits_kernel<4, bf16>), dim3(grid), dim3(256), lds, (hipStream_t)stream,
-                         (const bf16 *)img_vec, ldi, (const bf16 *)con_vec, ldc, L, C, c0, dim, logits);
-    const int rc = ca_check_launch("ca_heatmap_logits_bf16");
+    const auto go = [&](auto kernel) {
+      return launch(kernel, grid_1d(L, 8, 512), 256, (size_t)4 * dim * sizeof(float), stream, "ca_heatmap_logits_bf16",
+                    img_vec, ldi, con_vec, ldc, L, C, c0, dim, logits);
+    };
+    const int rc = img32   ? go(ca_heatmap_logits_kernel<4, float, float>)
+                   : con32 ? go(ca_heatmap_logits_kernel<4, float>)
+                           : go(ca_heatmap_logits_kernel<4, bf16>);
     if (rc) return rc;
   }
   return CA_OK;
@@ -1099,55 +1139,32 @@ extern "C" int ca_heatmap_logits_bf16(const void *img_vec, int32_t ldi, const vo
 extern "C" int ca_qpre_finish_rope_f32(float *x, int32_t ldx, const float *d, int32_t ldd, const void *norm_scale,
                                        const float *rope, void *q_out, int32_t ldq, float q_out_scale, int32_t q_f16,
                                        int32_t M, int32_t heads, ca_stream_t stream) {
-  if (!x || !norm_scale || M < 1 || heads < 1 || ldx % 4 || ldx < heads * 128 || (d && (ldd % 4 || ldd < heads * 128)) ||
-      (((uintptr_t)x | (uintptr_t)d | (uintptr_t)norm_scale) & 15)) {
-    ca_set_error("ca_qpre_finish_f32: bad arguments (M=%d heads=%d ldx=%d ldd=%d)", M, heads, ldx, ldd);
-    return CA_ERR_ARG;
-  }
-  if (q_out && (!rope || ldq % 8 || ldq < heads * 128 || (((uintptr_t)rope | (uintptr_t)q_out) & 15) ||
-                !(q_out_scale >= 0.0f) || (q_f16 != 0 && q_f16 != 1))) {
-    ca_set_error("ca_qpre_finish_rope_f32: q_out needs rope [M,64,2], ldq %% 8 == 0, ldq >= heads*128, 16-byte alignment");
-    return CA_ERR_ARG;
-  }
-  const long threads = (long)M * heads * 16;
-  hipLaunchKernelGGL(ca_qpre_finish_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     x, ldx, d, ldd, (const bf16 *)norm_scale, M, heads, rope, q_out, ldq, q_out_scale, q_f16);
-  return ca_check_launch("ca_qpre_finish_f32");
+  return qpre_finish("ca_qpre_finish_rope_f32", x, ldx, d, ldd, norm_scale, rope, q_out, ldq, q_out_scale, q_f16, M, heads,
+                     stream);
 }
 
 extern "C" int ca_qpre_finish_f32(float *x, int32_t ldx, const float *d, int32_t ldd, const void *norm_scale, int32_t M,
                                   int32_t heads, ca_stream_t stream) {
-  return ca_qpre_finish_rope_f32(x, ldx, d, ldd, norm_scale, nullptr, nullptr, 0, 0.0f, 0, M, heads, stream);
+  return qpre_finish("ca_qpre_finish_f32", x, ldx, d, ldd, norm_scale, nullptr, nullptr, 0, 0.0f, 0, M, heads, stream);
 }
 
 extern "C" int ca_heatmap_softmax_accumulate(const float *logits, int32_t C, int32_t L, float weight, float *acc,
                                              ca_stream_t stream) {
-  if (!logits || !acc || C < 1 || L < 1) {
-    ca_set_error("ca_heatmap_softmax_accumulate: bad arguments (C=%d L=%d)", C, L);
-    return CA_ERR_ARG;
-  }
-  hipLaunchKernelGGL(ca_heatmap_softmax_kernel, dim3((L + 255) / 256), dim3(256), 0, (hipStream_t)stream, logits, C, L,
-                     weight, acc);
-  return ca_check_launch("ca_heatmap_softmax_accumulate");
+  return heatmap_softmax("ca_heatmap_softmax_accumulate", logits, C, L, weight, acc, stream);
 }
 
 extern "C" int ca_heatmap_norm_accumulate(const float *logits, int32_t C, int32_t L, int32_t norm, float weight,
                                           float *acc, ca_stream_t stream) {
-  if (norm == CA_NORM_SOFTMAX) return ca_heatmap_softmax_accumulate(logits, C, L, weight, acc, stream);
+  const char *FN = "ca_heatmap_norm_accumulate";
+  if (norm == CA_NORM_SOFTMAX) return heatmap_softmax(FN, logits, C, L, weight, acc, stream);
   if (!logits || !acc || C < 1 || C > 16 || L < 1 || (norm != CA_NORM_SPARSEMAX && norm != CA_NORM_ENTMAX15)) {
-    ca_set_error("ca_heatmap_norm_accumulate: bad arguments (C=%d L=%d norm=%d; sparse norms need C <= 16)", C, L, norm);
+    ca_set_error("%s: bad arguments (C=%d L=%d norm=%d; sparse norms need C <= 16)", FN, C, L, norm);
     return CA_ERR_ARG;
   }
-  const dim3 grid((L + 255) / 256), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  if (norm == CA_NORM_SPARSEMAX) {
-    if (C <= 8) hipLaunchKernelGGL((ca_heatmap_sparse_kernel<8, false>), grid, block, 0, s, logits, C, L, weight, acc);
-    else hipLaunchKernelGGL((ca_heatmap_sparse_kernel<16, false>), grid, block, 0, s, logits, C, L, weight, acc);
-  } else {
-    if (C <= 8) hipLaunchKernelGGL((ca_heatmap_sparse_kernel<8, true>), grid, block, 0, s, logits, C, L, weight, acc);
-    else hipLaunchKernelGGL((ca_heatmap_sparse_kernel<16, true>), grid, block, 0, s, logits, C, L, weight, acc);
-  }
-  return ca_check_launch("ca_heatmap_norm_accumulate");
+  static constexpr decltype(&ca_heatmap_sparse_kernel<8, false>) kernel[2][2] = {   // by entmax15, C > 8
+      {ca_heatmap_sparse_kernel<8, false>, ca_heatmap_sparse_kernel<16, false>},
+      {ca_heatmap_sparse_kernel<8, true>, ca_heatmap_sparse_kernel<16, true>}};
+  return launch(kernel[norm == CA_NORM_ENTMAX15][C > 8], grid_1d(L, 256), 256, 0, stream, FN, logits, C, L, weight, acc);
 }
 
 extern "C" int ca_heatmap_fused(const ca_heatmap_problem *problems, int32_t n_problems, int32_t L, int32_t C,
@@ -1185,87 +1202,20 @@ extern "C" int ca_heatmap_fused(const ca_heatmap_problem *problems, int32_t n_pr
   // workgroups per problem: a wave takes 2 patches per pass; about 3 (C <= 4: 48 KB of LDS each) or 2 workgroups per CU
   // in all, so that the concept vectors are pulled into LDS a few hundred times per launch, not once per 8 patches
   const int n_cu = ca_cu_count() > 0 ? ca_cu_count() : 256;
-  const int per_pass = threads / 64 * 2;
-  int gx = ((cc == 4 ? 3 : 2) * n_cu + n_problems - 1) / n_problems;
-  gx = gx < (L + per_pass - 1) / per_pass ? gx : (L + per_pass - 1) / per_pass;
-  if (gx < 1) gx = 1;
-  if (cc == 4)
-    hipLaunchKernelGGL(ca_heatmap_fused_kernel<4>, dim3(gx, n_problems), dim3(threads), lds, (hipStream_t)stream, A);
-  else
-    hipLaunchKernelGGL(ca_heatmap_fused_kernel<8>, dim3(gx, n_problems), dim3(threads), lds, (hipStream_t)stream, A);
-  return ca_check_launch("ca_heatmap_fused");
+  const unsigned gx = grid_1d(L, threads / 64 * 2, ((cc == 4 ? 3 : 2) * n_cu + n_problems - 1) / n_problems);
+  return launch(cc == 4 ? ca_heatmap_fused_kernel<4> : ca_heatmap_fused_kernel<8>, dim3(gx, n_problems), threads, lds,
+                stream, "ca_heatmap_fused", A);
 }
-
-namespace {
-template <bool SILU>
-__global__ __launch_bounds__(256) void ca_silu_split_kernel(const float *__restrict__ x, int ldx, bf16 *__restrict__ hi,
-                                                            bf16 *__restrict__ lo, int ldo, int rows, int K) {
-  const long per_row = K >> 2;   // (64-bit: rows * per_row passes 2^31 long before the planes pass device memory)
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < rows * per_row; i += (long)gridDim.x * 256) {
-    const int r = (int)(i / per_row), k = (int)(i - r * per_row) << 2;
-    const f32x4 v = *(const f32x4 *)(x + (size_t)r * ldx + k);
-    bf16x4 h, l;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float s = SILU ? ca_silu(v[j]) : v[j];
-      h[j] = (bf16)s;
-      l[j] = (bf16)(s - (float)h[j]);
-    }
-    *(bf16x4 *)(hi + (size_t)r * ldo + k) = h;
-    *(bf16x4 *)(lo + (size_t)r * ldo + k) = l;
-  }
-}
-}  // namespace
 
 extern "C" int ca_silu_split_bf16(const float *x, int32_t ldx, void *hi, void *lo, int32_t ldo, int32_t rows, int32_t K,
                                   ca_stream_t stream) {
-  if (!x || !hi || !lo || rows < 1 || K < 4 || K % 4 || ldx < K || ldo < K || ldx % 4 || ldo % 4 ||
-      (((uintptr_t)x & 15) | (((uintptr_t)hi | (uintptr_t)lo) & 7))) {
-    ca_set_error("ca_silu_split_bf16: bad arguments (rows=%d K=%d ldx=%d ldo=%d)", rows, K, ldx, ldo);
-    return CA_ERR_ARG;
-  }
-  const long n = (long)rows * (K / 4);
-  const long blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
-  hipLaunchKernelGGL(ca_silu_split_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, ldx,
-                     (bf16 *)hi, (bf16 *)lo, ldo, rows, K);
-  return ca_check_launch("ca_silu_split_bf16");
+  return split_planes("ca_silu_split_bf16", ca_silu_split_kernel<true>, x, ldx, hi, lo, ldo, rows, K, stream);
 }
 
 extern "C" int ca_split_bf16(const float *x, int32_t ldx, void *hi, void *lo, int32_t ldo, int32_t rows, int32_t K,
                              ca_stream_t stream) {
-  if (!x || !hi || !lo || rows < 1 || K < 4 || K % 4 || ldx < K || ldo < K || ldx % 4 || ldo % 4 ||
-      (((uintptr_t)x & 15) | (((uintptr_t)hi | (uintptr_t)lo) & 7))) {
-    ca_set_error("ca_split_bf16: bad arguments (rows=%d K=%d ldx=%d ldo=%d)", rows, K, ldx, ldo);
-    return CA_ERR_ARG;
-  }
-  const long n = (long)rows * (K / 4);
-  const long blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
-  hipLaunchKernelGGL(ca_silu_split_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, ldx,
-                     (bf16 *)hi, (bf16 *)lo, ldo, rows, K);
-  return ca_check_launch("ca_split_bf16");
+  return split_planes("ca_split_bf16", ca_silu_split_kernel<false>, x, ldx, hi, lo, ldo, rows, K, stream);
 }
-
-namespace {
-__global__ __launch_bounds__(256) void ca_modulation_combine_kernel(const float *__restrict__ pair, int ldp,
-                                                                    const bf16 *__restrict__ bias, float *__restrict__ out,
-                                                                    int ldo, int nv, int N) {
-  const long per_row = N >> 2;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv * per_row; i += (long)gridDim.x * 256) {
-    const int v = (int)(i / per_row), n = (int)(i - v * per_row) << 2;
-    const f32x4 h = *(const f32x4 *)(pair + (size_t)v * ldp + n), l = *(const f32x4 *)(pair + (size_t)(nv + v) * ldp + n);
-    f32x4 b = {0.f, 0.f, 0.f, 0.f};
-    if (bias) {
-      const bf16x4 b4 = *(const bf16x4 *)(bias + n);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) b[j] = (float)b4[j];
-    }
-    f32x4 o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = (h[j] + b[j]) + l[j];
-    *(f32x4 *)(out + (size_t)v * ldo + n) = o;
-  }
-}
-}  // namespace
 
 extern "C" int ca_modulation_combine_f32(const float *pair, int32_t ldp, const void *bias, float *out, int32_t ldo,
                                          int32_t nv, int32_t N, ca_stream_t stream) {
@@ -1274,11 +1224,8 @@ extern "C" int ca_modulation_combine_f32(const float *pair, int32_t ldp, const v
     ca_set_error("ca_modulation_combine_f32: bad arguments (nv=%d N=%d ldp=%d ldo=%d)", nv, N, ldp, ldo);
     return CA_ERR_ARG;
   }
-  const long n = (long)nv * (N / 4);
-  const long blocks = (n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048;
-  hipLaunchKernelGGL(ca_modulation_combine_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, pair, ldp,
-                     (const bf16 *)bias, out, ldo, nv, N);
-  return ca_check_launch("ca_modulation_combine_f32");
+  return launch(ca_modulation_combine_kernel, grid_1d((long)nv * (N / 4), 256, 2048), 256, 0, stream,
+                "ca_modulation_combine_f32", pair, ldp, bias, out, ldo, nv, N);
 }
 
 extern "C" int ca_axpy_bf16(void *x, const void *y, float a, int64_t n, ca_stream_t stream) {
@@ -1286,10 +1233,7 @@ extern "C" int ca_axpy_bf16(void *x, const void *y, float a, int64_t n, ca_strea
     ca_set_error("ca_axpy_bf16: bad arguments (n=%lld)", (long long)n);
     return CA_ERR_ARG;
   }
-  const long blocks = (n + 2047) / 2048;
-  hipLaunchKernelGGL(ca_axpy_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (bf16 *)x,
-                     (const bf16 *)y, a, (long)n);
-  return ca_check_launch("ca_axpy_bf16");
+  return launch(ca_axpy_kernel, grid_1d(n, 2048), 256, 0, stream, "ca_axpy_bf16", x, y, a, n);
 }
 
 extern "C" int ca_axpy_f32(float *x, const void *y, int32_t y_is_f32, float a, int64_t n, ca_stream_t stream) {
@@ -1297,14 +1241,8 @@ extern "C" int ca_axpy_f32(float *x, const void *y, int32_t y_is_f32, float a, i
     ca_set_error("ca_axpy_f32: bad arguments (n=%lld)", (long long)n);
     return CA_ERR_ARG;
   }
-  const long blocks = (n + 2047) / 2048;
-  if (y_is_f32)
-    hipLaunchKernelGGL(ca_axpy_f32_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x,
-                       (const float *)y, a, (long)n);
-  else
-    hipLaunchKernelGGL(ca_axpy_f32_kernel<bf16>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x,
-                       (const bf16 *)y, a, (long)n);
-  return ca_check_launch("ca_axpy_f32");
+  if (y_is_f32) return launch(ca_axpy_f32_kernel<float>, grid_1d(n, 2048), 256, 0, stream, "ca_axpy_f32", x, y, a, n);
+  return launch(ca_axpy_f32_kernel<bf16>, grid_1d(n, 2048), 256, 0, stream, "ca_axpy_f32", x, y, a, n);
 }
 
 extern "C" int ca_timestep_embedding_f32(const float *t, int32_t nt, float *out, int32_t dim, float time_factor,
@@ -1313,9 +1251,6 @@ extern "C" int ca_timestep_embedding_f32(const float *t, int32_t nt, float *out,
     ca_set_error("ca_timestep_embedding_f32: bad arguments (nt=%d dim=%d)", nt, dim);
     return CA_ERR_ARG;
   }
-  const long n = (long)nt * (dim / 2);
-  const long blocks = (n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096;
-  hipLaunchKernelGGL(ca_timestep_embedding_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, t, nt,
-                     out, dim, time_factor, max_period);
-  return ca_check_launch("ca_timestep_embedding_f32");
+  return launch(ca_timestep_embedding_kernel, grid_1d((long)nt * (dim / 2), 256, 4096), 256, 0, stream,
+                "ca_timestep_embedding_f32", t, nt, out, dim, time_factor, max_period);
 }

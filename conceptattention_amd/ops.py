@@ -285,8 +285,7 @@ def attention(problems: Sequence[Attn], num_heads: int, scale: Optional[float] =
 
 def attention_stats(reset: bool = False) -> dict:
     """Counters of ca_attn4_kernel's rare softmax paths on the current device (blocking copy; diagnostics only)."""
-    import ctypes
-    c = (ctypes.c_ulonglong * 2)()
+    c = (C.c_ulonglong * 2)()
     L.check(L.load().ca_attn_stats(c, int(reset)), "ca_attn_stats")
     return {"recomputed_workgroups": int(c[0]), "rereference_events": int(c[1])}
 
@@ -318,24 +317,19 @@ def ln_modulate(x, out, segments, eps: float = 1e-6, out_scale=None, out_lo=None
         arr[i].row_end = row_end
         arr[i].shift = _chk(shift, torch.float32, "shift").data_ptr()
         arr[i].scale = _chk(scale, torch.float32, "scale").data_ptr()
-    if fp8:
-        fn = lib.ca_ln_modulate_f32in_fp8 if x32 else lib.ca_ln_modulate_fp8
-        L.check(fn(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), out_scale.data_ptr(),
-                   x.shape[0], x.shape[1], arr, len(segments), eps, _stream()), "ca_ln_modulate_fp8")
-        return
-    if out_lo is not None:
+    if out_lo is not None and not fp8:
         if not x32:
             raise ValueError("ln_modulate: out_lo needs an fp32 input")
         _chk(out_lo, torch.bfloat16, "out_lo")
         if out_lo.shape != out.shape:
             raise ValueError("ln_modulate: out_lo must have out's shape")
-        L.check(lib.ca_ln_modulate_f32in_split(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0),
-                                               out_lo.data_ptr(), out_lo.stride(0), x.shape[0], x.shape[1], arr,
-                                               len(segments), eps, _stream()), "ca_ln_modulate_f32in_split")
-        return
-    fn = lib.ca_ln_modulate_f32in if x32 else lib.ca_ln_modulate_bf16
-    L.check(fn(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), x.shape[0], x.shape[1],
-               arr, len(segments), eps, _stream()), "ca_ln_modulate_bf16")
+        name, extra = "ca_ln_modulate_f32in_split", (out_lo.data_ptr(), out_lo.stride(0))
+    elif fp8:
+        name, extra = "ca_ln_modulate_f32in_fp8" if x32 else "ca_ln_modulate_fp8", (out_scale.data_ptr(),)
+    else:
+        name, extra = "ca_ln_modulate_f32in" if x32 else "ca_ln_modulate_bf16", ()
+    L.check(getattr(lib, name)(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), *extra, x.shape[0], x.shape[1],
+                               arr, len(segments), eps, _stream()), name)
 
 
 def qpre_finish(x, d, norm_scale, num_heads: int, rope=None, q_out=None, q_out_scale: float = 0.0,
@@ -412,14 +406,23 @@ def gemv(x, w, bias, out, silu_input=False, accumulate=False) -> None:
                              w.shape[0], w.shape[1], int(silu_input), int(accumulate), _stream()), "ca_gemv_bf16")
 
 
-def silu_split(x, hi, lo) -> None:
-    """hi + lo = silu(x) to ~16 mantissa bits, as two bf16 planes (x fp32 [rows,K]; hi, lo bf16 [rows,K])."""
+def _split(what: str, symbol: str, x, hi, lo) -> None:
     lib = L.load()
     _chk(x, torch.float32, "x"), _chk(hi, torch.bfloat16, "hi"), _chk(lo, torch.bfloat16, "lo")
     if x.dim() != 2 or hi.shape != x.shape or lo.shape != x.shape or hi.stride(0) != lo.stride(0):
-        raise ValueError("silu_split: x, hi, lo must be [rows,K] of one shape (hi / lo of one row stride)")
-    L.check(lib.ca_silu_split_bf16(x.data_ptr(), x.stride(0), hi.data_ptr(), lo.data_ptr(), hi.stride(0), x.shape[0],
-                                   x.shape[1], _stream()), "ca_silu_split_bf16")
+        raise ValueError(f"{what}: x, hi, lo must be [rows,K] of one shape (hi / lo of one row stride)")
+    L.check(getattr(lib, symbol)(x.data_ptr(), x.stride(0), hi.data_ptr(), lo.data_ptr(), hi.stride(0), x.shape[0],
+                                 x.shape[1], _stream()), symbol)
+
+
+def silu_split(x, hi, lo) -> None:
+    """hi + lo = silu(x) to ~16 mantissa bits, as two bf16 planes (x fp32 [rows,K]; hi, lo bf16 [rows,K])."""
+    _split("silu_split", "ca_silu_split_bf16", x, hi, lo)
+
+
+def split_planes(x, hi, lo) -> None:
+    """hi = bf16(x), lo = bf16(x - hi): x fp32 [rows,K] as two bf16 planes (~16 mantissa bits)."""
+    _split("split_planes", "ca_split_bf16", x, hi, lo)
 
 
 def modulation_gemm(vecs, w, bias, out, ones) -> bool:
@@ -574,16 +577,6 @@ def axpy_f32(x, y, a: float) -> None:
         raise ValueError("axpy_f32: x,y must be contiguous with equal sizes")
     L.check(lib.ca_axpy_f32(x.data_ptr(), y.data_ptr(), int(y.dtype == torch.float32), float(a), x.numel(), _stream()),
             "ca_axpy_f32")
-
-
-def split_planes(x, hi, lo) -> None:
-    """hi = bf16(x), lo = bf16(x - hi): x fp32 [rows,K] as two bf16 planes (~16 mantissa bits)."""
-    lib = L.load()
-    _chk(x, torch.float32, "x"), _chk(hi, torch.bfloat16, "hi"), _chk(lo, torch.bfloat16, "lo")
-    if x.dim() != 2 or hi.shape != x.shape or lo.shape != x.shape or hi.stride(0) != lo.stride(0):
-        raise ValueError("split_planes: x, hi, lo must be [rows,K] of one shape (hi / lo of one row stride)")
-    L.check(lib.ca_split_bf16(x.data_ptr(), x.stride(0), hi.data_ptr(), lo.data_ptr(), hi.stride(0), x.shape[0],
-                              x.shape[1], _stream()), "ca_split_bf16")
 
 
 def timestep_embedding(t, out, time_factor: float = 1000.0, max_period: float = 10000.0) -> None:

@@ -6,7 +6,7 @@ slip).  Nothing here touches torch.cuda at import time; the reference and the bo
 inputs live on.
 
 Every case names the C entry point it calls and the kernel instantiation that entry point launches for its
-arguments, spelled as at the hipLaunchKernelGGL site (CASES; `kernel`).  A reference returns, per output,
+arguments, spelled as where ca_rowops.hip launches it (CASES; `kernel`).  A reference returns, per output,
 (fp64 value, bound before the output's own rounding, kind); `bound` adds the rounding of the kind.
 
 Bounds (elementwise, u = 2^-24 = fp32 unit roundoff; every fp32 operation is charged 2 u of its running magnitude, one
@@ -82,7 +82,7 @@ EPS = 1e-6
 class Case:
     name: str
     entry: str          # the C entry point (include/conceptattn.h)
-    kernel: str         # the instantiation it launches, spelled as at its hipLaunchKernelGGL site
+    kernel: str         # the instantiation it launches, spelled as where ca_rowops.hip launches it
     op: str             # reference family
     shape: dict = field(default_factory=dict, hash=False, compare=False)
     seed: int = 0

@@ -1,5 +1,6 @@
 """The row kernels' case table without a GPU (tests/rowop_cases.py): every launch form of ca_rowops.hip and every row
 entry point of include/conceptattn.h is named by a GPU case, and every bound rejects a named kernel slip."""
+import ctypes
 import os
 import re
 
@@ -18,19 +19,13 @@ def _norm(name: str) -> str:
 
 
 def launch_forms() -> list:
-    """The kernel of every hipLaunchKernelGGL site of ca_rowops.hip, CA_GEMV_LAUNCH(NV) expanded over its switch."""
+    """The kernel of every launch of ca_rowops.hip: each instantiation its host half (the unit's second anonymous
+    namespace and the entry points after it) hands to launch(), directly, through a dispatch lambda or from a table.
+    Not a launch: the kernels named for ca_raise_lds_limit (cast to const void *) and inside decltype."""
     src = open(SRC).read()
-    sites = re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_]\w*(?:<[^>]*>)?)", src)
-    forms = []
-    for s in sites:
-        s = _norm(s)
-        if s == "ca_gemv_kernel<NV>":
-            nvs = [int(n) for n in re.findall(r"CA_GEMV_LAUNCH\((\d+)\)", src)]
-            assert sorted(nvs) == list(range(1, 9)), nvs
-            forms += [f"ca_gemv_kernel<{n}>" for n in nvs]
-        else:
-            forms.append(s)
-    return forms
+    host = re.sub(r"//[^\n]*", "", src[src.rindex("\nnamespace {"):])
+    assert "launch(" in host and "__global__" not in host
+    return [_norm(s) for s in re.findall(r"(?<!\(const void \*\))(?<!decltype\(&)\b(ca_\w+_kernel\b(?:<[^>]*>)?)", host)]
 
 
 def row_entry_points() -> set:
@@ -61,6 +56,22 @@ def test_every_row_entry_point_has_a_case():
     covered = {c.entry for c in R.CASES}
     assert entries <= covered, f"row entry points without a case: {sorted(entries - covered)}"
     assert covered <= entries, sorted(covered - entries)
+
+
+@pytest.mark.parametrize("entry", sorted(row_entry_points()))
+def test_a_rejected_call_is_reported_under_the_called_entry_points_name(entry):
+    """Every row entry point refuses a NULL first pointer before it touches the GPU, and the text ca_last_error() then
+    returns begins with the name of the entry point that was CALLED -- also where two entry points share one body
+    (ca_qpre_finish_rope_f32 once reported as ca_qpre_finish_f32)."""
+    import __graft_entry__ as graft
+    from conceptattention_amd import _lib as L
+    graft.build()
+    lib = L.load()
+    args = [0.0 if t is ctypes.c_float else 0 if t in (ctypes.c_int32, ctypes.c_int64) else None
+            for t in L.SIGNATURES[entry][1]]
+    assert args[0] is None, entry
+    assert getattr(lib, entry)(*args) == -1, entry
+    assert lib.ca_last_error().decode().startswith(entry + ": "), lib.ca_last_error()
 
 
 def test_case_ids_are_unique_and_inputs_are_built_on_the_cpu():
