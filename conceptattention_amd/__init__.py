@@ -4,7 +4,7 @@ Public surface mirrors the reference package (`concept_attention/__init__.py:2`)
 ``from conceptattention_amd import ConceptAttentionFluxPipeline``.  Importing the package does not
 touch the GPU; the HIP library is loaded on first use and its absence is a hard error.
 """
-from .params import FluxParams, configs, tiny_params  # noqa: F401
+from .params import AutoEncoderParams, FluxParams, ae_params, configs, tiny_params  # noqa: F401
 
 
 def __getattr__(name):  # lazy: keep `import conceptattention_amd` light for host-only tools
@@ -17,6 +17,9 @@ def __getattr__(name):  # lazy: keep `import conceptattention_amd` light for hos
     if name in ("FluxGenerator", "load_flow_model"):
         from . import image_generator
         return getattr(image_generator, name)
+    if name in ("AutoEncoder", "load_ae", "synthetic_ae_state_dict", "ae_state_dict_spec"):
+        from . import vae
+        return getattr(vae, name)
     if name == "compute_heatmaps_from_vectors":
         from .heatmaps import compute_heatmaps_from_vectors
         return compute_heatmaps_from_vectors

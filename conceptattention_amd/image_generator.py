@@ -6,19 +6,22 @@ same ``generate_image(width, height, num_steps, guidance, seed, prompt, concepts
 ``(image, concept_attention_dict)`` contract, where the dict holds the four vector stacks
 ``[steps, 19, 1, ...]`` that ``compute_heatmaps_from_vectors`` consumes.  What is NOT re-stated: the
 HuggingFace downloads (`load_t5/load_clip/load_ae/hf_hub_download`, `:19-62`; unavailable offline) -- the
-text encoder and autoencoder are injectable, with synthetic stand-ins by default -- and the
+text encoder and autoencoder are injectable (``autoencoder`` also takes "synthetic" or a ``.safetensors`` path and
+then builds the HIP ``vae.AutoEncoder``); by default the text encoder is a synthetic stand-in and the unpacked latent
+is returned instead of an image -- and the
 `model.cpu()` / `.to(device)` round trip of the 23.8 GB weights on every call (`:183,194`), which a
 288 GB device does not need.
 """
 from __future__ import annotations
 
+import os
 import time
 
 import torch
 
 from . import sampling
 from .flux_dit import HipFluxDiT, on_own_device
-from .params import T5_TOKENS, configs
+from .params import T5_TOKENS, ae_params, configs
 
 
 def load_flow_model(name: str, device="cuda", hf_download: bool = True, attention_block_class=None,
@@ -62,6 +65,10 @@ class FluxGenerator:
                                                    self.device)
         self.text_encoder = enc
         self.t5, self.clip = enc.t5, enc.clip
+        if isinstance(autoencoder, (str, os.PathLike)):   # "synthetic" or a .safetensors path: the HIP autoencoder
+            from .vae import load_ae
+            autoencoder = load_ae(model_name if model_name in ae_params else "flux-schnell", self.device,
+                                  weights=str(autoencoder), seed=weight_seed)
         self.ae = autoencoder
         self.nsfw_classifier = None
 

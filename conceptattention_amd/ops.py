@@ -587,3 +587,97 @@ def timestep_embedding(t, out, time_factor: float = 1000.0, max_period: float = 
         raise ValueError("timestep_embedding: out must be contiguous [nt, dim]")
     L.check(lib.ca_timestep_embedding_f32(t.data_ptr(), t.shape[0], out.data_ptr(), out.shape[1], time_factor,
                                           max_period, _stream()), "ca_timestep_embedding_f32")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Autoencoder kernels (ca_vae.hip).  Activations are NHWC tensors whose last dimension is the channel row.
+
+def conv_out_hw(h: int, w: int, ksize: int = 3, stride: int = 1, upsample: bool = False):
+    """Output height and width of ``conv2d_nhwc`` (stride 2 = the (0,1,0,1) padding of the reference's Downsample)."""
+    if upsample:
+        return 2 * h, 2 * w
+    if stride == 2:
+        return (h - 2) // 2 + 1, (w - 2) // 2 + 1
+    return h, w
+
+
+def pack_conv_weight(w: torch.Tensor, cin_pad: Optional[int] = None) -> torch.Tensor:
+    """nn.Conv2d weight [Cout, Cin, k, k] -> the kernel's operand: bf16 [ceil16(Cout), k*k*cin_pad], tap-major and
+    K-contiguous (column (ky*k + kx) * cin_pad + c), zeros in the padding rows and columns."""
+    cout, cin, k, _ = w.shape
+    cin_pad = cin_pad or (cin + 31) // 32 * 32
+    out = torch.zeros((cout + 15) // 16 * 16, k * k, cin_pad, dtype=torch.bfloat16, device=w.device)
+    out[:cout, :, :cin] = w.permute(0, 2, 3, 1).reshape(cout, k * k, cin).to(torch.bfloat16)
+    return out.reshape(out.shape[0], k * k * cin_pad)
+
+
+def conv2d_nhwc(x, w_packed, bias, out, cout: int, ksize: int = 3, stride: int = 1, upsample: bool = False,
+                resid=None, cin: Optional[int] = None) -> None:
+    """x bf16 [B,H,W,>=cin] -> out fp32 / bf16 [B,Ho,Wo,>=cout]; bias fp32 [cout]; resid fp32 like out (may be out)."""
+    _chk(x, torch.bfloat16, "x"), _chk(w_packed, torch.bfloat16, "w")
+    if out.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("conv2d_nhwc: out must be fp32 or bf16")
+    _chk(out, out.dtype, "out")
+    B, H, W = x.shape[0], x.shape[1], x.shape[2]
+    cin = cin or w_packed.shape[1] // (ksize * ksize)
+    if x.dim() != 4 or out.dim() != 4 or not x.is_contiguous() or not out.is_contiguous() or \
+            w_packed.shape != ((cout + 15) // 16 * 16, ksize * ksize * cin) or not w_packed.is_contiguous():
+        raise ValueError(f"conv2d_nhwc: x{tuple(x.shape)} / out{tuple(out.shape)} must be contiguous NHWC, w "
+                         f"{tuple(w_packed.shape)} the packed [ceil16(cout), k*k*cin]")
+    if tuple(out.shape[:3]) != (B,) + conv_out_hw(H, W, ksize, stride, upsample):
+        raise ValueError(f"conv2d_nhwc: out{tuple(out.shape)} does not match the output size of x{tuple(x.shape)}")
+    if bias is not None and (_chk(bias, torch.float32, "bias").numel() != cout or not bias.is_contiguous()):
+        raise ValueError("conv2d_nhwc: bias must be contiguous fp32 [cout]")
+    if resid is not None and (_chk(resid, torch.float32, "resid").shape != out.shape or not resid.is_contiguous()):
+        raise ValueError("conv2d_nhwc: resid must be contiguous fp32 of out's shape")
+    L.check(L.load().ca_conv3x3_nhwc(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(resid), out.data_ptr(), B, H, W,
+                                     cin, cout, x.shape[3], out.shape[3], out.shape[3], ksize, stride, int(upsample),
+                                     int(out.dtype == torch.float32), _stream()), "ca_conv3x3_nhwc")
+
+
+def groupnorm_chunks(hw: int) -> int:
+    return max(1, min(128, hw // 512))
+
+
+def groupnorm_nhwc(x, gamma, beta, out, swish: bool, eps: float = 1e-6, part=None) -> None:
+    """x fp32 / bf16 [B, HW, C] (or [B,H,W,C]) -> out bf16 of the same shape; gamma / beta fp32 [C]; 32 groups."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("groupnorm_nhwc: x must be fp32 or bf16")
+    _chk(x, x.dtype, "x"), _chk(out, torch.bfloat16, "out")
+    _chk(gamma, torch.float32, "gamma"), _chk(beta, torch.float32, "beta")
+    C_ = x.shape[-1]
+    if not x.is_contiguous() or not out.is_contiguous() or out.shape != x.shape or gamma.numel() != C_ or beta.numel() != C_:
+        raise ValueError("groupnorm_nhwc: x and out must be contiguous and alike, gamma / beta [C]")
+    B, hw = x.shape[0], x.numel() // (x.shape[0] * C_)
+    n_chunks = groupnorm_chunks(hw)
+    if part is None:
+        part = torch.empty(B * n_chunks * 96, device=x.device, dtype=torch.float32)
+    if _chk(part, torch.float32, "part").numel() < B * n_chunks * 96:
+        raise ValueError("groupnorm_nhwc: part needs B * groupnorm_chunks(HW) * 96 floats")
+    L.check(L.load().ca_groupnorm_nhwc(x.data_ptr(), int(x.dtype == torch.float32), C_, gamma.data_ptr(), beta.data_ptr(),
+                                       out.data_ptr(), C_, B, hw, C_, eps, int(swish), part.data_ptr(), n_chunks,
+                                       _stream()), "ca_groupnorm_nhwc")
+
+
+def softmax_rows(s, p, n: int, scale: float) -> None:
+    """s fp32 [rows, >=n] -> p bf16 [rows, >=n]: p[:, :n] = softmax(scale * s[:, :n]), p[:, n:] = 0."""
+    _chk(s, torch.float32, "s"), _chk(p, torch.bfloat16, "p")
+    if s.dim() != 2 or p.dim() != 2 or s.shape[0] != p.shape[0]:
+        raise ValueError("softmax_rows: s and p must be 2-D with the same rows")
+    L.check(L.load().ca_softmax_rows_f32(s.data_ptr(), s.stride(0), p.data_ptr(), p.stride(0), s.shape[0], n, scale,
+                                         _stream()), "ca_softmax_rows_f32")
+
+
+def affine_rows(x, out, a: float = 1.0, b: float = 0.0, logvar=None, noise=None, cols: Optional[int] = None) -> None:
+    """out[:, :cols] = a * (x + exp(0.5 logvar) * noise) + b over 2-D row views (fp32 in, fp32 or bf16 out)."""
+    _chk(x, torch.float32, "x"), _chk(out, out.dtype, "out")
+    if out.dtype not in (torch.float32, torch.bfloat16) or x.dim() != 2 or out.dim() != 2 or x.shape[0] != out.shape[0]:
+        raise ValueError("affine_rows: 2-D fp32 x, 2-D fp32 / bf16 out with the same rows")
+    cols = cols or x.shape[1]
+    for t in (logvar, noise):
+        if t is not None and (_chk(t, torch.float32, "logvar/noise").dim() != 2 or t.shape[0] != x.shape[0]):
+            raise ValueError("affine_rows: logvar / noise must be 2-D fp32 with x's rows")
+    L.check(L.load().ca_affine_rows_f32(x.data_ptr(), x.stride(0), _ptr(logvar), 0 if logvar is None else logvar.stride(0),
+                                        _ptr(noise), 0 if noise is None else noise.stride(0), out.data_ptr(),
+                                        out.stride(0), int(out.dtype == torch.float32), x.shape[0], cols, a, b,
+                                        _stream()), "ca_affine_rows_f32")

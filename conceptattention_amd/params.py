@@ -47,6 +47,24 @@ configs = {
     "flux-dev": FluxParams(guidance_embed=True),
 }
 
+
+@dataclass(frozen=True)
+class AutoEncoderParams:
+    """Fields of the reference's AutoEncoderParams (flux/modules/autoencoder.py:8-18)."""
+    resolution: int = 256
+    in_channels: int = 3
+    ch: int = 128
+    out_ch: int = 3
+    ch_mult: tuple = (1, 2, 4, 4)
+    num_res_blocks: int = 2
+    z_channels: int = 16
+    scale_factor: float = 0.3611
+    shift_factor: float = 0.1159
+
+
+# flux/util.py:49-58,81-90: both models ship the same autoencoder
+ae_params = {"flux-schnell": AutoEncoderParams(), "flux-dev": AutoEncoderParams()}
+
 # T5 sequence length per model (reference concept_attention/image_generator.py:57)
 T5_TOKENS = {"flux-schnell": 256, "flux-dev": 512}
 

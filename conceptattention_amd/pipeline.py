@@ -4,7 +4,8 @@ and ``encode_image`` signatures and defaults, ``ConceptAttentionPipelineOutput``
 and the heat-map reduction in the gfx950 kernels.
 
 Out of scope: the T5/CLIP text encoders and the VAE need checkpoints that
-are not available offline.  They are injectable (``text_encoder`` / ``autoencoder``); without them
+are not available offline.  They are injectable (``text_encoder`` / ``autoencoder``; ``autoencoder="synthetic"`` or a
+``.safetensors`` path builds the HIP autoencoder of ``vae.py``); without them
 the pipeline runs in *synthetic conditioning* mode -- prompt and concept strings are mapped to
 seeded N(0,1) embeddings of the right shapes and ``image`` is returned as the unpacked latent --
 which is exactly the configuration BASELINE.json measures.
@@ -98,7 +99,7 @@ class ConceptAttentionFluxPipeline:
         self._replicas = [self.model]  # activation sets that share self.model's weights (one per stream)
         self._streams = []
         self.text_encoder = self.flux_generator.text_encoder
-        self.autoencoder = autoencoder
+        self.autoencoder = self.flux_generator.ae   # (a name or path was built into the HIP AutoEncoder there)
 
     # ------------------------------------------------------------------ conditioning
     def _embed(self, prompt: str, concepts: Sequence[str]):
@@ -345,7 +346,8 @@ class ConceptAttentionFluxPipeline:
                      seed: int = 0, cmap="plasma", stop_after_multi_modal_attentions=True,
                      attention_norm: str = "sparsemax", softmax=True,
                      joint_attention_kwargs=None, noise=None) -> ConceptAttentionPipelineOutput:
-        """``image``: a latent tensor (1,16,h/8,w/8), or a PIL image when an autoencoder was injected.
+        """``image``: a latent tensor (1,16,h/8,w/8), or a PIL image when the pipeline has an autoencoder
+        (``autoencoder="synthetic"``, a ``.safetensors`` path, or an injected object).
         One forward of the 19 double blocks per noise sample (stop_after_multimodal_attentions).
         ``joint_attention_kwargs`` (not in the reference's signature, which hard-codes None at :296) lets the
         segmentation harness select the concept cross/self-attention ablations; ``noise`` (a list of num_samples
@@ -360,7 +362,8 @@ class ConceptAttentionFluxPipeline:
             arr = torch.nn.functional.interpolate((2.0 * arr - 1.0)[None].to(self.device), (height, width))
             latent = self.autoencoder.encode(arr).to(torch.bfloat16)
         else:
-            raise ValueError("encode_image needs a latent tensor or an injected autoencoder")
+            raise ValueError("encode_image needs a latent tensor, or a pipeline built with autoencoder=\"synthetic\", a "
+                             ".safetensors path or an object with encode / decode")
         txt, vec, con, con_ids, con_vec = self._embed(prompt, concepts)
         out_space, cross_space = self._encode_maps(self.model, latent, txt, vec, con, con_ids, con_vec, layer_indices,
                                                    num_samples, num_steps, noise_timestep, seed,

@@ -10,7 +10,9 @@ import torch
 
 from conceptattention_amd import ConceptAttentionFluxPipeline
 
-pipeline = ConceptAttentionFluxPipeline(model_name="flux-schnell", device="cuda:0")
+# CA_AUTOENCODER=synthetic (or the path of an ae.safetensors) runs the HIP VAE: encode_image then takes a PIL image too
+pipeline = ConceptAttentionFluxPipeline(model_name="flux-schnell", device="cuda:0",
+                                        autoencoder=os.environ.get("CA_AUTOENCODER"))
 
 latent = torch.randn(1, 16, 128, 128, generator=torch.Generator().manual_seed(0))  # stand-in for ae.encode(image)
 concepts = ["dragon", "rock", "sky", "sun", "clouds"]

@@ -9,7 +9,9 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from conceptattention_amd import ConceptAttentionFluxPipeline
 
-pipeline = ConceptAttentionFluxPipeline(model_name="flux-schnell", device="cuda:0")
+# CA_AUTOENCODER=synthetic (or the path of an ae.safetensors) runs the HIP VAE: pipeline_output.image is then a PIL image
+pipeline = ConceptAttentionFluxPipeline(model_name="flux-schnell", device="cuda:0",
+                                        autoencoder=os.environ.get("CA_AUTOENCODER"))
 
 prompt = "A cat in a park on the grass by a tree"
 concepts = ["cat", "grass", "sky", "tree"]

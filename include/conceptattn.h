@@ -28,9 +28,10 @@
 extern "C" {
 #endif
 
-#define CA_VERSION 126 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
+#define CA_VERSION 127 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
                           CA_ATTN_Q_PRESCALED; .1: ca_axpy_f32, ca_split_bf16; .2: ca_attn_stats; .3: ca_gemm_problem.qk_f16,
-                          ca_attn_fwd_qk16; .4: ca_qpre_finish_rope_f32; .5: ca_heatmap_fused; .6: ca_gemm_plan */
+                          ca_attn_fwd_qk16; .4: ca_qpre_finish_rope_f32; .5: ca_heatmap_fused; .6: ca_gemm_plan;
+                          .7: the autoencoder kernels (conv3x3_nhwc, groupnorm_nhwc, softmax_rows_f32, affine_rows_f32) */
 
 #define CA_OK 0
 #define CA_ERR_ARG (-1)    /* bad shape / null pointer / misalignment */
@@ -399,6 +400,49 @@ int ca_silu_split_bf16(const float *x, int32_t ldx, void *hi, void *lo, int32_t 
  * bias bf16 [N] or NULL, out fp32 [nv, N] (row stride ldo), N % 4 == 0. */
 int ca_modulation_combine_f32(const float *pair, int32_t ldp, const void *bias, float *out, int32_t ldo, int32_t nv,
                               int32_t N, ca_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Flux autoencoder (concept_attention/flux/src/flux/modules/autoencoder.py).  Activations are NHWC: a pixel is a row of
+ * channels with a free row stride; every element offset is formed in 64 bits (a 1024 x 1024 fp32 activation of 256
+ * channels is 1 GiB).
+ *
+ * Implicit-GEMM convolution on v_mfma_f32_16x16x32_bf16, fp32 accumulation:
+ *   out[b, oy, ox, n] = bias[n] + sum_{ky, kx, c} x[b, sy, sx, c] * w[n, (ky * ksize + kx) * Cin + c]  (+ resid)
+ * One kernel for every nn.Conv2d of the encoder and decoder:
+ *   ksize 3, stride 1            padding 1 (ResnetBlock :63-65, conv_in / conv_out :126,157,208,235)
+ *   ksize 3, stride 2            the (0,1,0,1) zero padding of Downsample (:85-95): Ho = (Hin - 2) / 2 + 1
+ *   ksize 3, stride 1, upsample  the nearest 2x of Upsample (:98-106) folded into the index: (sy, sx) = (iy >> 1,
+ *                                ix >> 1), Ho = 2 Hin; no upsampled tensor exists
+ *   ksize 1                      nin_shortcut (:66-67)
+ * Padding pixels are zeros by predicate.  x: bf16 [B, Hin, Win, ldx], Cin % 32 == 0 channels read per pixel (a
+ * narrower tensor -- the 16-channel latent, the 3-channel image -- sits in a zero-padded row: ldx >= Cin, ldx % 8 == 0).
+ * w: bf16 [ceil16(Cout), ksize * ksize * Cin], tap-major and K-contiguous, zero rows / columns for the padding.
+ * bias: fp32 [Cout] or NULL.  resid: fp32 [pixels, ldr] or NULL, added in the epilogue; may alias an fp32 out.
+ * out: fp32 (out_f32) or bf16 [pixels, ldo], Cout channels stored per pixel.
+ */
+int ca_conv3x3_nhwc(const void *x, const void *w, const float *bias, const float *resid, void *out, int32_t B,
+                    int32_t Hin, int32_t Win, int32_t Cin, int32_t Cout, int32_t ldx, int32_t ldr, int32_t ldo,
+                    int32_t ksize, int32_t stride, int32_t upsample, int32_t out_f32, ca_stream_t stream);
+
+/* nn.GroupNorm(32, C, eps, affine) with optional swish (autoencoder.py:21-22,30,62,64,156,234): x fp32 (x_f32) or bf16
+ * [B, HW, ldx], y bf16 [B, HW, ldy], gamma / beta fp32 [C]; C a power of two in 32..1024.  Two launches: per-chunk
+ * (count, mean, M2) of every group by Welford / Chan into part (fp32 [B, n_chunks, 32, 3], caller's scratch), then the
+ * merge and the apply.  The variance is never formed as a difference of two large sums. */
+int ca_groupnorm_nhwc(const void *x, int32_t x_f32, int32_t ldx, const float *gamma, const float *beta, void *y,
+                      int32_t ldy, int32_t B, int64_t HW, int32_t C, float eps, int32_t swish, float *part,
+                      int32_t n_chunks, ca_stream_t stream);
+
+/* p[r, 0:n] = softmax(scale * s[r, 0:n]) as bf16, p[r, n:ldp] = 0: the probabilities of the one-head attention of
+ * AttnBlock (autoencoder.py:47) between its two GEMMs; any n. */
+int ca_softmax_rows_f32(const float *s, int32_t lds, void *p, int32_t ldp, int32_t rows, int32_t n, float scale,
+                        ca_stream_t stream);
+
+/* out[r, c] = a * (x[r, c] + exp(0.5 * logvar[r, c]) * noise[r, c]) + b for c < C; logvar and noise both given or both
+ * NULL.  DiagonalGaussian and the scale / shift of AutoEncoder (autoencoder.py:262-309); with a = 1, b = 0 the cast of an
+ * fp32 tensor to a bf16 convolution operand.  out fp32 (out_f32) or bf16, row stride ldo; columns >= C are not written. */
+int ca_affine_rows_f32(const float *x, int32_t ldx, const float *logvar, int32_t ldl, const float *noise, int32_t ldn,
+                       void *out, int32_t ldo, int32_t out_f32, int64_t rows, int32_t C, float a, float b,
+                       ca_stream_t stream);
 
 #ifdef __cplusplus
 }
