@@ -6,6 +6,7 @@ from __future__ import annotations
 import numpy as np
 
 import gemm_route_cases as G
+import vae_cases as V
 from conceptattention_amd import _lib as L
 
 LINE = 1 << 32
@@ -80,6 +81,40 @@ ROWOP_PAST = [("ln_rows6_split_seg15", "x"), ("ln_rows6_split_seg15", "out"), ("
               ("ln_bf16_H264_M8", "x"), ("ln_bf16_H264_M8", "out"), ("ln_fp8_f32_H4096_seg15", "out"),
               ("qk_h3_seg16_pre", "qkv"), ("logits_bf16_C5_L4352", "img"), ("logits_f32_C8_L257_dim4096", "img"),
               ("fused4_bf16_vectors", "img"), ("fused8_f32_vectors", "img")]
+
+# the autoencoder kernels (ca_vae.hip): one case of vae_cases.py per entry point in which every operand role exists
+VAE_PLACEMENT = {"ca_conv3x3_nhwc": "conv_5x7_c96_o48_s1_resid_f32", "ca_groupnorm_nhwc": "gn_C32_hw1025_f32",
+                 "ca_softmax_rows_f32": "softmax_n257", "ca_affine_rows_f32": "affine_sample_f32"}
+VAE_ROLES = {"ca_conv3x3_nhwc": ["x", "w", "bias", "resid", "out"],
+             "ca_groupnorm_nhwc": ["x", "gamma", "beta", "y", "part"],
+             "ca_softmax_rows_f32": ["s", "p"], "ca_affine_rows_f32": ["x", "logvar", "noise", "out"]}
+# one operand at a time with its last row more than 4 GiB from its base: conv on 5 x 7, B = 2 (out once fp32, once
+# bf16), GroupNorm with HW = 7, B = 2, softmax with 5 rows, affine with 70 rows.  The softmax p is run by a test of
+# its own: the kernel zeroes p[r, n:ldp], so a far ldp makes it write the whole extent.
+VAE_PAST = [("conv_5x7_c96_o48_s1_resid_f32", "x"), ("conv_5x7_c96_o48_s1_resid_f32", "resid"),
+            ("conv_5x7_c96_o48_s1_resid_f32", "out"), ("conv4_o36_partial_fragment_bf16", "out"),
+            ("gn_C64_hw7_f32", "x"), ("gn_C64_hw7_f32", "y"), ("softmax_n63", "s"), ("softmax_n63", "p"),
+            ("affine_decode_bf16", "x"), ("affine_decode_bf16", "out")]
+VAE_PAST_OWN_TEST = ("softmax_n63", "p")
+
+
+def vae_roles(case) -> list:
+    """The operand roles of one autoencoder case (the buffers the run helpers of test_vae_routes_gpu name)."""
+    s = case.shape
+    if case.op == "conv":
+        return ["x", "w", "out"] + (["bias"] if s["bias"] else []) + (["resid"] if s["resid"] == "separate" else [])
+    if case.op == "affine":
+        return ["x", "out"] + (["logvar", "noise"] if s["lv"] else [])
+    return {"gn": ["x", "gamma", "beta", "y", "part"], "softmax": ["s", "p"]}[case.op]
+
+
+def vae_far_rows(cid: str, role: str):
+    """(rows, bytes per element) of the 2-D buffer that carries `role` in case cid."""
+    case = V.BY_ID[cid]
+    inp = V.make_inputs(case)
+    buf = inp[{"out": "out0", "y": "y0", "p": "p0"}.get(role, role)]
+    assert buf.dim() == 2, (cid, role)
+    return buf.shape[0], buf.element_size()
 
 
 def far_ld(rows: int, itemsize: int, extent: int) -> int:

@@ -77,6 +77,44 @@ def test_every_rowop_form_and_plane_has_a_placement_case():
     assert R.BY_ID["temb_grid_stride"].shape["nt"] * 128 > 4096 * 256     # a second trip through the grid-stride loop
 
 
+def test_every_vae_entry_point_and_role_has_a_placement_and_a_far_case():
+    """The GPU file places VAE_PLACEMENT's case of every entry point of ca_vae.hip once per role of VAE_ROLES, and
+    runs VAE_PAST with one operand's row stride from far_ld."""
+    import vae_cases as V
+    want = {"ca_conv3x3_nhwc": {"x", "w", "bias", "resid", "out"}, "ca_groupnorm_nhwc": {"x", "gamma", "beta", "y", "part"},
+            "ca_softmax_rows_f32": {"s", "p"}, "ca_affine_rows_f32": {"x", "logvar", "noise", "out"}}
+    assert {c.entry for c in V.CASES} == set(C.VAE_PLACEMENT) == set(want)
+    for entry, cid in C.VAE_PLACEMENT.items():
+        case = V.BY_ID[cid]
+        assert case.entry == entry
+        roles = C.VAE_ROLES[entry]
+        assert len(roles) == len(set(roles)) and set(roles) == want[entry] == set(C.vae_roles(case)), entry
+        if case.op == "affine":
+            assert not case.shape["view"]        # four buffers of their own
+        if case.op == "gn":
+            assert (case.shape["n_chunks"] or V.groupnorm_chunks(case.shape["HW"])) > 1      # part: more than one chunk
+    past = {(V.BY_ID[cid].op, role, V.BY_ID[cid].shape.get("out")) for cid, role in C.VAE_PAST}
+    assert past >= {("conv", "x", "f32"), ("conv", "resid", "f32"), ("conv", "out", "f32"), ("conv", "out", "bf16"),
+                    ("gn", "x", None), ("gn", "y", None), ("softmax", "s", None), ("softmax", "p", None),
+                    ("affine", "x", "bf16"), ("affine", "out", "bf16")}
+    assert C.VAE_PAST_OWN_TEST in C.VAE_PAST
+    for cid, role in C.VAE_PAST:
+        s = V.BY_ID[cid].shape
+        assert role in C.vae_roles(V.BY_ID[cid]), (cid, role)
+        if V.BY_ID[cid].op == "conv":
+            assert (s["B"], s["H"], s["W"]) == (2, 5, 7), cid
+        if V.BY_ID[cid].op == "gn":
+            assert (s["B"], s["HW"]) == (2, 7), cid
+        if V.BY_ID[cid].op in ("softmax", "affine"):
+            assert s["rows"] == {"softmax": 5, "affine": 70}[V.BY_ID[cid].op], cid
+        rows, item = C.vae_far_rows(cid, role)
+        ld = C.far_ld(rows, item, C.PAST_4GIB)
+        assert ld < 1 << 31, (cid, role, ld)                       # the entry points take int32_t strides
+        assert (rows - 1) * ld * item >= LINE, (cid, role)         # the last row starts 2^32 bytes or more from the base
+        assert ((rows - 1) * ld + 1) * item > LINE, (cid, role)    # and the touched extent exceeds 2^32 bytes
+        assert rows * ld * item <= C.PAST_4GIB < PL.ARENA_BYTES - 2 * PL.GUARD - 256
+
+
 def test_no_role_is_left_out():
     assert not NEVER_DEREFERENCED
 

@@ -35,14 +35,16 @@ import test_gemm_routes_gpu as TG  # noqa: E402
 import address_range_cases as C  # noqa: E402
 import rowop_cases as R  # noqa: E402
 import test_rowop_routes_gpu as TR  # noqa: E402
+import test_vae_routes_gpu as TV  # noqa: E402
+import vae_cases as V  # noqa: E402
 from address_range_cases import (ATTN_FAR, ATTN_LIMITS, ATTN_PLACEMENT, ATTN_ROLES, GEMM_INPUT_FIELD,  # noqa: E402
                                  far_ldkv, gemm_epis_for)
 from conceptattention_amd import ops  # noqa: E402
 
 DEV = "cuda"
 NAN = float("nan")
-COUNTS = {"attention placement": 0, "gemm placement": 0, "rowop placement": 0, "attention far": 0, "gemm far": 0,
-          "past 4 GiB": 0}
+COUNTS = {"attention placement": 0, "gemm placement": 0, "rowop placement": 0, "vae placement": 0, "attention far": 0,
+          "gemm far": 0, "past 4 GiB": 0}
 
 
 def _bytes(t):
@@ -371,6 +373,75 @@ def test_rowop_operand_past_4_gib(arena, cid, role):
     assert fa.last_row_offset >= 1 << 32, fa.last_row_offset
     for k in plain:
         assert torch.equal(_bytes(plain[k]), _bytes(got[k])), f"{case.id} {k}: far {role} != plain"
+    COUNTS["past 4 GiB"] += 1
+
+
+# ------------------------------------------------------------------------------------ the autoencoder kernels
+@pytest.mark.parametrize("entry", list(C.VAE_PLACEMENT))
+def test_vae_placement(arena, entry):
+    """One case per entry point of ca_vae.hip with every operand role: all at bit31, then role by role across the
+    2^32 line mid-row of a middle row.  Bit-identical to ordinary allocations, inside the case's own bounds, canary
+    columns and guard bands intact."""
+    case = V.BY_ID[C.VAE_PLACEMENT[entry]]
+    inp = V.make_inputs(case)
+    plain = TV.run_checked(case, inp)
+    roles = C.VAE_ROLES[entry]
+    for role in [None] + roles:
+        pl = arena.placer(role)
+        got = TV.run_checked(case, inp, pl)
+        _assert_placed(pl, role)
+        assert set(pl.placed) == set(roles), set(pl.placed) ^ set(roles)
+        pl.check_guards()
+        for k in plain:
+            assert torch.equal(_bytes(plain[k]), _bytes(got[k])), f"{case.id} {k}: {role or 'bit31'} != plain"
+        COUNTS["vae placement"] += 1
+
+
+@pytest.mark.parametrize("cid,role", [v for v in C.VAE_PAST if v != C.VAE_PAST_OWN_TEST], ids=lambda v: str(v))
+def test_vae_operand_past_4_gib(arena, cid, role):
+    """One operand with its row stride from far_ld (its last row starts more than 4 GiB from its base), the others
+    small; only the touched columns are written.  Equal to the same case at its ordinary stride."""
+    case = V.BY_ID[cid]
+    inp = V.make_inputs(case)
+    plain = TV.run_checked(case, inp)
+    fa = FarAlloc(arena, role, C.PAST_4GIB)
+    got = TV.run_checked(case, inp, fa)
+    fa.check_guards()
+    assert fa.last_row_offset >= 1 << 32 and fa.ld < 1 << 31, (fa.last_row_offset, fa.ld)
+    print(f"\n  {cid} {role}: ld={fa.ld}, last row {fa.last_row_offset} bytes from the base")
+    for k in plain:
+        assert torch.equal(_bytes(plain[k]), _bytes(got[k])), f"{cid} {k}: far {role} != plain"
+    COUNTS["past 4 GiB"] += 1
+
+
+def test_softmax_p_past_4_gib(arena):
+    """ca_softmax_rows_f32 zeroes p[r, n:ldp]: with ldp from far_ld it owns, and writes, 5 rows of 1 GiB.  The test
+    fills only the first n + 1024 and the last 1024 columns of every row with NaN; afterwards the probabilities equal
+    the ordinary-stride run's, every other element of the extent is zero, and the guard bands are intact."""
+    cid, role = C.VAE_PAST_OWN_TEST
+    case = V.BY_ID[cid]
+    s, inp = case.shape, V.make_inputs(case)
+    rows, n = s["rows"], s["n"]
+    plain = TV.run_checked(case, inp)
+    ld = C.far_ld(rows, 2, C.PAST_4GIB)
+    assert ld < 1 << 31 and (rows - 1) * ld * 2 >= 1 << 32     # the last row starts 2^32 bytes or more from the base
+    start = (arena.base + PL.GUARD + 255) // 256 * 256
+    span = rows * ld * 2
+    for g in (start - PL.GUARD, start + span):
+        arena.window(g, PL.GUARD).fill_(PL.PATTERN)
+    full = arena.window(start, span).view(torch.bfloat16).view(rows, ld)
+    full[:, :n + 1024] = NAN
+    full[:, -1024:] = NAN
+    sc = inp["s"].to(DEV)
+    TV._call("ca_softmax_rows_f32", sc.data_ptr(), sc.stride(0), full.data_ptr(), ld, rows, n, s["scale"])
+    for g in (start - PL.GUARD, start + span):
+        assert bool((arena.window(g, PL.GUARD) == PL.PATTERN).all()), "guard band written"
+    assert torch.equal(_bytes(plain["p"]), _bytes(full[:, :n])), "far p != plain"
+    a = (n + 63) // 64 * 64                  # rows start 128-byte aligned: from column a on a row reads as int64
+    for r in range(rows):                    # (min / max reductions: no temporary of the extent's size)
+        body = full[r, a:].view(torch.int64)
+        assert bool((full[r, n:a].view(torch.int16) == 0).all()) and body.max().item() == 0 == body.min().item(), \
+            f"row {r}: padding not zero"
     COUNTS["past 4 GiB"] += 1
 
 
