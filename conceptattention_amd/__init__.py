@@ -4,7 +4,8 @@ Public surface mirrors the reference package (`concept_attention/__init__.py:2`)
 ``from conceptattention_amd import ConceptAttentionFluxPipeline``.  Importing the package does not
 touch the GPU; the HIP library is loaded on first use and its absence is a hard error.
 """
-from .params import AutoEncoderParams, FluxParams, ae_params, configs, tiny_params  # noqa: F401
+from .params import (AutoEncoderParams, FluxParams, T5Params, ae_params, configs, t5_params, tiny_params,  # noqa: F401
+                     tiny_t5_params)
 
 
 def __getattr__(name):  # lazy: keep `import conceptattention_amd` light for host-only tools
@@ -20,6 +21,9 @@ def __getattr__(name):  # lazy: keep `import conceptattention_amd` light for hos
     if name in ("AutoEncoder", "load_ae", "synthetic_ae_state_dict", "ae_state_dict_spec"):
         from . import vae
         return getattr(vae, name)
+    if name in ("T5Encoder", "HipTextEncoder", "ToyByteTokenizer", "load_t5", "synthetic_t5_state_dict", "t5_state_dict_spec"):
+        from . import t5
+        return getattr(t5, name)
     if name == "compute_heatmaps_from_vectors":
         from .heatmaps import compute_heatmaps_from_vectors
         return compute_heatmaps_from_vectors

@@ -8,10 +8,11 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 LIB = os.path.join(PKG, "libconceptattn.so")
-SOURCES = ["ca_api.hip", "ca_gemm.hip", "ca_attn.hip", "ca_attn4.hip", "ca_rowops.hip", "ca_vae.hip"]
+SOURCES = ["ca_api.hip", "ca_gemm.hip", "ca_attn.hip", "ca_attn4.hip", "ca_rowops.hip", "ca_vae.hip", "ca_t5.hip"]
 # ca_attn4.hip owns the AGPR file by hand (literal a[...] registers in its asm statements): hipcc must never park a
 # VGPR there (its default spill target), and the emitted code is audited for it below
-EXTRA_FLAGS = {"ca_attn4.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-save-temps=obj"]}
+EXTRA_FLAGS = {"ca_attn4.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-save-temps=obj"],
+               "ca_t5.hip": ["-save-temps=obj"]}   # (its assembly is read for spills below)
 HEADERS = ["ca_common.h", "ca_attn_common.h", "ca_attn4_sched.inc", "ca_attn4_kernel.inc"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function"]
@@ -52,6 +53,20 @@ def audit_attn4(asm_path: str) -> None:
                            f"{spills}, scratch {scratch} bytes")
     for tmp in os.listdir(HERE):   # -save-temps leftovers
         if tmp.startswith("ca_attn4-") and not tmp.endswith(".s"):
+            os.remove(os.path.join(HERE, tmp))
+
+
+def audit_t5(asm_path: str) -> None:
+    """ca_t5_attn_kernel holds a wave's whole score block in registers (L / 4 floats per lane, 128 at L = 512): a spill
+    there turns the softmax into scratch traffic.  Every kernel of the unit must report no spill and no scratch."""
+    import re
+    text = open(asm_path).read()
+    spills = [int(x) for x in re.findall(r"\.vgpr_spill_count:\s*(\d+)", text)]
+    scratch = [int(x) for x in re.findall(r"\.private_segment_fixed_size:\s*(\d+)", text)]
+    if any(spills) or any(scratch) or not spills:
+        raise RuntimeError(f"ca_t5.hip audit failed: vgpr spills {spills}, scratch {scratch} bytes")
+    for tmp in os.listdir(HERE):   # -save-temps leftovers
+        if tmp.startswith("ca_t5-") and not tmp.endswith(".s"):
             os.remove(os.path.join(HERE, tmp))
 
 
@@ -304,6 +319,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         if p.wait() != 0:
             raise RuntimeError("hipcc failed")
     audit_attn4(os.path.join(HERE, "ca_attn4-hip-amdgcn-amd-amdhsa-gfx950.s"))
+    audit_t5(os.path.join(HERE, "ca_t5-hip-amdgcn-amd-amdhsa-gfx950.s"))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
     if verbose:
         print(" ".join(cmd), flush=True)

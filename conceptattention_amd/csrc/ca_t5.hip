@@ -1,0 +1,312 @@
+// Kernels of the T5 encoder (transformers' T5Stack, encoder side): self-attention with the relative-position bias on
+// v_mfma_f32_16x16x32_bf16, the RMS layer norm of the fp32 residual stream, the gated-GELU product and the embedding
+// gather.  The projections run on the grouped GEMM of ca_gemm.hip.  Every element offset is formed in 64 bits.
+#include "ca_common.h"
+
+// ------------------------------------------------------------------------------------------------------------------
+// out = softmax(q k^T + bias) v per (sequence, head); head dim 64, no 1/sqrt(d) scale, no mask.
+//
+// A workgroup of 4 waves owns 64 query rows of one (sequence, head); a wave owns 16 of them.  K of the head sits in LDS
+// row-major ([key][64], rows of 72 bf16 so that the 16 rows of a ds_read_b128 fragment read fall on 16 distinct 16-byte
+// slots), V transposed ([d][key], rows of L + 16 bf16) because P V contracts over the keys and an MFMA operand wants its
+// 8 contraction elements contiguous in a lane; the head's bias row (2L - 1 floats) sits beside them.
+//
+// Scores are computed transposed, S^T = K Q^T: with K as the MFMA's A operand and Q as B, a lane ends up with ONE query
+// (lane & 15) and keys 16 t + 4 (lane >> 4) + 0..3 of every 16-key tile t.  All L scores of the wave's 16 queries are
+// held in registers (L / 4 floats per lane), so the softmax is the exact two-pass one: row maximum, then exp and sum,
+// each finished by two cross-lane exchanges over the 4 lanes of a query.  The same registers, rounded to bf16, are the
+// B operand of O^T = V^T P^T: the contraction slot (g, e) of 32-key step u stands for key 32 u + 4 g + e (e < 4) or
+// 32 u + 16 + 4 g + e - 4 (e >= 4), and the V^T fragment is read from LDS under the same permutation.  The lane's
+// query is the same in both products, so 1 / sum is a per-lane scalar.  P is rounded to bf16 unnormalised (in (0, 1]);
+// the sum is taken over the fp32 values.
+#define T5_D 64
+#define T5_LDK 72
+
+template <int NT>   // NT = L / 16 key tiles
+__global__ __launch_bounds__(256) void ca_t5_attn_kernel(const bf16 *q, const bf16 *k, const bf16 *v, const float *bias,
+                                                          bf16 *out, long ldq, long ldk, long ldv, long ldo, int heads) {
+  constexpr int L = NT * 16;
+  constexpr int LDV = L + 16;
+  extern __shared__ __attribute__((aligned(16))) unsigned char t5_smem[];
+  bf16 *sK = (bf16 *)t5_smem;                        // [L][T5_LDK]
+  bf16 *sV = sK + L * T5_LDK;                        // [64][LDV], transposed
+  float *sB = (float *)(sV + T5_D * LDV);            // [2 L] (2 L - 1 used)
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  constexpr int QT = L / 64;
+  const long blk = blockIdx.x;
+  const int qt = (int)(blk % QT);
+  const long sh = blk / QT;
+  const int h = (int)(sh % heads);
+  const long seq = sh / heads;
+  const long row0 = seq * L;                         // first token row of the sequence
+  const long col = (long)h * T5_D;
+
+  // ---- K, V^T and the bias row into LDS
+  {
+    const int c = tid & 7;
+#pragma unroll 4
+    for (int r = tid >> 3; r < L; r += 32) {
+      const uint4 x = *(const uint4 *)(k + (row0 + r) * ldk + col + c * 8);
+      *(uint4 *)(sK + r * T5_LDK + c * 8) = x;
+    }
+    const int kp0 = tid & 31, cv = tid >> 5;         // key pair within a 64-key slab, 8-column chunk
+#pragma unroll 2
+    for (int kp = kp0; kp < L / 2; kp += 32) {
+      const bf16x8 a = *(const bf16x8 *)(v + (row0 + 2 * kp) * ldv + col + cv * 8);
+      const bf16x8 b = *(const bf16x8 *)(v + (row0 + 2 * kp + 1) * ldv + col + cv * 8);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        bf16x2 pr = {a[i], b[i]};
+        *(bf16x2 *)(sV + (cv * 8 + i) * LDV + 2 * kp) = pr;
+      }
+    }
+    const float *bh = bias + (long)h * (2 * L - 1);
+    for (int i = tid; i < 2 * L - 1; i += 256) sB[i] = bh[i];
+  }
+
+  // ---- this lane's query row as the B operand of S^T = K Q^T
+  const int j = lane & 15, g = lane >> 4;
+  const int qpos = qt * 64 + wave * 16 + j;
+  bf16x8 qf[2];
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) qf[kk] = *(const bf16x8 *)(q + (row0 + qpos) * ldq + col + kk * 32 + g * 8);
+  __syncthreads();
+
+  f32x4 s[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      const bf16x8 kf = *(const bf16x8 *)(sK + (t * 16 + j) * T5_LDK + kk * 32 + g * 8);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], acc, 0, 0, 0);
+    }
+    s[t] = acc;
+  }
+
+  // ---- + bias[key - query + L - 1], row maximum
+  float mx = -INFINITY;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int b0 = t * 16 + g * 4 - qpos + L - 1;    // in [0, 2 L - 5]
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      s[t][r] += sB[b0 + r];
+      mx = fmaxf(mx, s[t][r]);
+    }
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 16));
+  mx = fmaxf(mx, __shfl_xor(mx, 32));
+
+  float sum = 0.f;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      s[t][r] = __builtin_amdgcn_exp2f((s[t][r] - mx) * 1.4426950409f);
+      sum += s[t][r];
+    }
+  }
+  sum += __shfl_xor(sum, 16);
+  sum += __shfl_xor(sum, 32);
+
+  // ---- O^T = V^T P^T: lane holds columns 16 dt + 4 g + 0..3 of query j
+  f32x4 o[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < NT / 2; ++u) {
+    bf16x8 pf;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      pf[r] = (bf16)s[2 * u][r];
+      pf[4 + r] = (bf16)s[2 * u + 1][r];
+    }
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      const bf16 *vr = sV + (dt * 16 + j) * LDV + u * 32 + g * 4;
+      const bf16x4 lo = *(const bf16x4 *)vr, hi = *(const bf16x4 *)(vr + 16);
+      const bf16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[dt], 0, 0, 0);
+    }
+  }
+
+  const float inv = 1.0f / sum;
+  bf16 *orow = out + (row0 + qpos) * ldo + col + g * 4;
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    const uint2 w = {ca_pack2(o[dt][0] * inv, o[dt][1] * inv), ca_pack2(o[dt][2] * inv, o[dt][3] * inv)};
+    *(uint2 *)(orow + dt * 16) = w;
+  }
+}
+
+static int t5_attn_lds_bytes(int L) { return L * T5_LDK * 2 + T5_D * (L + 16) * 2 + 2 * L * 4; }
+
+template <int NT>
+static int t5_attn_launch(const bf16 *q, const bf16 *k, const bf16 *v, const float *bias, bf16 *out, long ldq, long ldk,
+                          long ldv, long ldo, int heads, long blocks, hipStream_t st, const char *FN) {
+  static std::atomic<unsigned long long> raised{0};
+  const int lds = t5_attn_lds_bytes(NT * 16);
+  const int rc = ca_raise_lds_limit({(const void *)ca_t5_attn_kernel<NT>}, lds, raised, FN);
+  if (rc != CA_OK) return rc;
+  hipLaunchKernelGGL(ca_t5_attn_kernel<NT>, dim3((unsigned)blocks), dim3(256), lds, st, q, k, v, bias, out, ldq, ldk, ldv,
+                     ldo, heads);
+  return ca_check_launch(FN);
+}
+
+extern "C" int ca_t5_attn_bf16(const void *q, const void *k, const void *v, const float *bias, void *out, int32_t ldq,
+                               int32_t ldk, int32_t ldv, int32_t ldo, int32_t n_seq, int32_t heads, int32_t L,
+                               ca_stream_t stream) {
+  const char *FN = "ca_t5_attn_bf16";
+  if (!q || !k || !v || !bias || !out) {
+    ca_set_error("%s: null pointer", FN);
+    return CA_ERR_ARG;
+  }
+  const long width = (long)heads * T5_D;
+  if (n_seq < 1 || heads < 1 || L < 64 || L > 512 || L % 64 || ldq < width || ldk < width || ldv < width || ldo < width ||
+      ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8) {
+    ca_set_error("%s: bad sizes (n_seq=%d heads=%d L=%d [64..512, %% 64] ldq=%d ldk=%d ldv=%d ldo=%d [>= heads*64, %% 8])",
+                 FN, n_seq, heads, L, ldq, ldk, ldv, ldo);
+    return CA_ERR_ARG;
+  }
+  if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) || ((uintptr_t)bias & 3)) {
+    ca_set_error("%s: q, k, v and out must be 16-byte aligned, bias 4-byte", FN);
+    return CA_ERR_ARG;
+  }
+  const long blocks = (long)n_seq * heads * (L / 64);
+  if (blocks > 0x7fffffffL) {
+    ca_set_error("%s: %ld workgroups exceed the grid", FN, blocks);
+    return CA_ERR_ARG;
+  }
+  const bf16 *qp = (const bf16 *)q, *kp = (const bf16 *)k, *vp = (const bf16 *)v;
+  bf16 *op = (bf16 *)out;
+  hipStream_t st = (hipStream_t)stream;
+  switch (L / 64) {
+#define T5_CASE(n) \
+  case n: return t5_attn_launch<4 * n>(qp, kp, vp, bias, op, ldq, ldk, ldv, ldo, heads, blocks, st, FN);
+    T5_CASE(1) T5_CASE(2) T5_CASE(3) T5_CASE(4) T5_CASE(5) T5_CASE(6) T5_CASE(7) T5_CASE(8)
+#undef T5_CASE
+  }
+  ca_set_error("%s: L=%d", FN, L);
+  return CA_ERR_ARG;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// T5LayerNorm: out[r, :] = bf16(x[r, :] * rsqrt(mean(x[r, :]^2) + eps) * w[:]); no mean subtraction, no bias.  A
+// workgroup per row (rows walked with the grid's stride), two passes over the row (the second hits the cache).
+__device__ __forceinline__ float t5_block_sum(float v, float *red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(256) void ca_t5_rmsnorm_kernel(const float *x, long ldx, const float *w, bf16 *out, long ldo,
+                                                             long rows, int H, float eps) {
+  __shared__ float red[4];
+  for (long r = blockIdx.x; r < rows; r += gridDim.x) {
+    const float *xr = x + r * ldx;
+    bf16 *orow = out + r * ldo;
+    float ss = 0.f;
+    for (int i = threadIdx.x * 4; i < H; i += 1024) {
+      const f32x4 a = *(const f32x4 *)(xr + i);
+      ss += (a[0] * a[0] + a[1] * a[1]) + (a[2] * a[2] + a[3] * a[3]);
+    }
+    ss = t5_block_sum(ss, red);
+    const float rs = 1.0f / sqrtf(ss / (float)H + eps);
+    for (int i = threadIdx.x * 4; i < H; i += 1024) {
+      const f32x4 a = *(const f32x4 *)(xr + i), g = *(const f32x4 *)(w + i);
+      const uint2 o = {ca_pack2(a[0] * rs * g[0], a[1] * rs * g[1]), ca_pack2(a[2] * rs * g[2], a[3] * rs * g[3])};
+      *(uint2 *)(orow + i) = o;
+    }
+  }
+}
+
+extern "C" int ca_t5_rmsnorm_f32in(const float *x, int32_t ldx, const float *w, void *out, int32_t ldo, int64_t rows,
+                                   int32_t H, float eps, ca_stream_t stream) {
+  const char *FN = "ca_t5_rmsnorm_f32in";
+  if (!x || !w || !out || rows < 1 || H < 4 || H % 4 || ldx < H || ldo < H || ldx % 4 || ldo % 4 || !(eps > 0.f)) {
+    ca_set_error("%s: bad arguments (rows=%lld H=%d [%% 4] ldx=%d ldo=%d [>= H, %% 4] eps=%g [> 0])", FN, (long long)rows,
+                 H, ldx, ldo, (double)eps);
+    return CA_ERR_ARG;
+  }
+  if ((((uintptr_t)x | (uintptr_t)w) & 15) || ((uintptr_t)out & 7)) {
+    ca_set_error("%s: x and w must be 16-byte aligned, out 8-byte", FN);
+    return CA_ERR_ARG;
+  }
+  const long blocks = rows < 65536 ? rows : 65536;
+  hipLaunchKernelGGL(ca_t5_rmsnorm_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, w,
+                     (bf16 *)out, (long)ldo, (long)rows, H, eps);
+  return ca_check_launch(FN);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// out = bf16(float(g) * float(u)): the gelu(wi_0 x) * (wi_1 x) product of T5DenseGatedActDense, 8 elements per thread.
+__global__ __launch_bounds__(256) void ca_gated_mul_kernel(const bf16 *g, long ldg, const bf16 *u, long ldu, bf16 *out,
+                                                            long ldo, long rows, int C) {
+  const int cq = C / 8;
+  const long total = rows * cq;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long r = i / cq;
+    const int c = (int)(i - r * cq) * 8;
+    const bf16x8 a = *(const bf16x8 *)(g + r * ldg + c), b = *(const bf16x8 *)(u + r * ldu + c);
+    uint4 o;
+    o.x = ca_pack2((float)a[0] * (float)b[0], (float)a[1] * (float)b[1]);
+    o.y = ca_pack2((float)a[2] * (float)b[2], (float)a[3] * (float)b[3]);
+    o.z = ca_pack2((float)a[4] * (float)b[4], (float)a[5] * (float)b[5]);
+    o.w = ca_pack2((float)a[6] * (float)b[6], (float)a[7] * (float)b[7]);
+    *(uint4 *)(out + r * ldo + c) = o;
+  }
+}
+
+extern "C" int ca_gated_mul_bf16(const void *g, int32_t ldg, const void *u, int32_t ldu, void *out, int32_t ldo,
+                                 int64_t rows, int32_t C, ca_stream_t stream) {
+  const char *FN = "ca_gated_mul_bf16";
+  if (!g || !u || !out || rows < 1 || C < 8 || C % 8 || ldg < C || ldu < C || ldo < C || ldg % 8 || ldu % 8 || ldo % 8 ||
+      (((uintptr_t)g | (uintptr_t)u | (uintptr_t)out) & 15)) {
+    ca_set_error("%s: bad arguments (rows=%lld C=%d [%% 8] ldg=%d ldu=%d ldo=%d [>= C, %% 8]; 16-byte aligned pointers)",
+                 FN, (long long)rows, C, ldg, ldu, ldo);
+    return CA_ERR_ARG;
+  }
+  long blocks = (rows * (C / 8) + 255) / 256;
+  if (blocks > 65536) blocks = 65536;
+  hipLaunchKernelGGL(ca_gated_mul_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16 *)g,
+                     (long)ldg, (const bf16 *)u, (long)ldu, (bf16 *)out, (long)ldo, (long)rows, C);
+  return ca_check_launch(FN);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// out[r, :] = float(table[ids[r], :]): the token embedding into the fp32 residual stream.  The ids are the caller's
+// responsibility (the Python wrapper rejects any outside [0, vocab) before the launch).
+__global__ __launch_bounds__(256) void ca_embed_rows_kernel(const bf16 *table, long ldt, const int32_t *ids, float *out,
+                                                             long ldo, long rows, int H) {
+  const int cq = H / 8;
+  const long total = rows * cq;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long r = i / cq;
+    const int c = (int)(i - r * cq) * 8;
+    const bf16x8 a = *(const bf16x8 *)(table + (long)ids[r] * ldt + c);
+    float *o = out + r * ldo + c;
+    *(f32x4 *)o = f32x4{(float)a[0], (float)a[1], (float)a[2], (float)a[3]};
+    *(f32x4 *)(o + 4) = f32x4{(float)a[4], (float)a[5], (float)a[6], (float)a[7]};
+  }
+}
+
+extern "C" int ca_embed_rows_f32(const void *table, int32_t ldt, const int32_t *ids, float *out, int32_t ldo, int64_t rows,
+                                 int32_t H, ca_stream_t stream) {
+  const char *FN = "ca_embed_rows_f32";
+  if (!table || !ids || !out || rows < 1 || H < 8 || H % 8 || ldt < H || ldo < H || ldt % 8 || ldo % 4 ||
+      (((uintptr_t)table | (uintptr_t)out) & 15) || ((uintptr_t)ids & 3)) {
+    ca_set_error("%s: bad arguments (rows=%lld H=%d [%% 8] ldt=%d [>= H, %% 8] ldo=%d [>= H, %% 4]; table and out 16-byte "
+                 "aligned, ids 4-byte)", FN, (long long)rows, H, ldt, ldo);
+    return CA_ERR_ARG;
+  }
+  long blocks = (rows * (H / 8) + 255) / 256;
+  if (blocks > 65536) blocks = 65536;
+  hipLaunchKernelGGL(ca_embed_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16 *)table,
+                     (long)ldt, ids, out, (long)ldo, (long)rows, H);
+  return ca_check_launch(FN);
+}

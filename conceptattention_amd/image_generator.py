@@ -7,8 +7,10 @@ same ``generate_image(width, height, num_steps, guidance, seed, prompt, concepts
 ``[steps, 19, 1, ...]`` that ``compute_heatmaps_from_vectors`` consumes.  What is NOT re-stated: the
 HuggingFace downloads (`load_t5/load_clip/load_ae/hf_hub_download`, `:19-62`; unavailable offline) -- the
 text encoder and autoencoder are injectable (``autoencoder`` also takes "synthetic" or a ``.safetensors`` path and
-then builds the HIP ``vae.AutoEncoder``); by default the text encoder is a synthetic stand-in and the unpacked latent
-is returned instead of an image -- and the
+then builds the HIP ``vae.AutoEncoder``; ``text_encoder`` takes a ``t5.HipTextEncoder``, whose T5 side is the HIP
+encoder of ``t5.py`` on local weights, or "synthetic-t5", the same encoder on synthetic weights behind a toy tokenizer).
+By default the text encoder is still the seeded-noise stand-in and the unpacked latent is returned instead of an image.
+CLIP (the pooled ``vec``) has no HIP encoder yet and stays a stand-in or an injected callable.  Also not re-stated: the
 `model.cpu()` / `.to(device)` round trip of the 23.8 GB weights on every call (`:183,194`), which a
 288 GB device does not need.
 """
@@ -61,6 +63,12 @@ class FluxGenerator:
                                      dit_class=dit_class, weights=weights, weight_seed=weight_seed,
                                      params=self.params, residual_dtype=residual_dtype)
         n_tok = n_text_tokens or T5_TOKENS.get(model_name, 256)
+        if isinstance(text_encoder, str):
+            if text_encoder != "synthetic-t5":
+                raise ValueError(f"text_encoder: unknown name {text_encoder!r} (\"synthetic-t5\", or an encoder object)")
+            from .t5 import synthetic_text_encoder
+            text_encoder = synthetic_text_encoder(self.params.context_in_dim, n_tok, self.device,
+                                                  self.params.vec_in_dim, weight_seed)
         enc = text_encoder or SyntheticTextEncoder(n_tok, self.params.context_in_dim, self.params.vec_in_dim,
                                                    self.device)
         self.text_encoder = enc
@@ -73,9 +81,16 @@ class FluxGenerator:
         self.nsfw_classifier = None
 
     def embed(self, prompt: str, concepts):
-        """prepare()'s text side + embed_concepts (flux/sampling.py:47-55, concept_attention/utils.py:6-33)."""
-        txt, vec = self.t5(prompt), self.clip(prompt)
-        con = torch.stack([self.t5(c)[0, 0, :] for c in concepts]).unsqueeze(0)
+        """prepare()'s text side + embed_concepts (flux/sampling.py:47-55, concept_attention/utils.py:6-33).  A text
+        encoder with ``t5_many`` encodes the prompt and every concept in ONE forward; any other one is called once per
+        string, as the reference does."""
+        many = getattr(self.text_encoder, "t5_many", None)
+        if many is not None:
+            both, vec = many([prompt, *concepts]), self.clip(prompt)
+            txt, con = both[:1], both[1:, 0, :].unsqueeze(0)
+        else:
+            txt, vec = self.t5(prompt), self.clip(prompt)
+            con = torch.stack([self.t5(c)[0, 0, :] for c in concepts]).unsqueeze(0)
         con, con_ids, con_vec = sampling.concept_inputs(con, vec)
         return txt, vec, con, con_ids, con_vec
 

@@ -681,3 +681,60 @@ def affine_rows(x, out, a: float = 1.0, b: float = 0.0, logvar=None, noise=None,
                                         _ptr(noise), 0 if noise is None else noise.stride(0), out.data_ptr(),
                                         out.stride(0), int(out.dtype == torch.float32), x.shape[0], cols, a, b,
                                         _stream()), "ca_affine_rows_f32")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# T5 encoder kernels (ca_t5.hip).  Rows are tokens; q / k / v are 2-D views with free row strides.
+
+def t5_attention(q, k, v, bias, out, n_seq: int, num_heads: int) -> None:
+    """out = softmax(q k^T + bias) v per (sequence, head); head dim 64, no 1/sqrt(d) scale, no mask.  q, k, v, out bf16
+    [n_seq * L, num_heads * 64] views (row stride free, e.g. column slices of one projection output); bias fp32
+    [num_heads, 2 L - 1] contiguous, indexed by key_pos - query_pos + L - 1."""
+    for n, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        _chk(t, torch.bfloat16, n)
+        if t.dim() != 2 or t.shape[1] != num_heads * 64 or t.shape[0] != q.shape[0]:
+            raise ValueError(f"t5_attention: {n} must be 2-D [n_seq * L, num_heads*64 = {num_heads * 64}], got {tuple(t.shape)}")
+    _chk(bias, torch.float32, "bias")
+    if n_seq < 1 or q.shape[0] % n_seq:
+        raise ValueError(f"t5_attention: {q.shape[0]} rows are not n_seq = {n_seq} sequences of one length")
+    Lq = q.shape[0] // n_seq
+    if tuple(bias.shape) != (num_heads, 2 * Lq - 1) or not bias.is_contiguous():
+        raise ValueError(f"t5_attention: bias must be contiguous fp32 [num_heads, 2 L - 1] = [{num_heads}, {2 * Lq - 1}], "
+                         f"got {tuple(bias.shape)}")
+    L.check(L.load().ca_t5_attn_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                                     q.stride(0), k.stride(0), v.stride(0), out.stride(0), n_seq, num_heads, Lq,
+                                     _stream()), "ca_t5_attn_bf16")
+
+
+def t5_rmsnorm(x, weight, out, eps: float = 1e-6) -> None:
+    """out = bf16(x * rsqrt(mean(x^2) + eps) * weight): x fp32 [rows, H], weight fp32 [H], out bf16 [rows, H]."""
+    _chk(x, torch.float32, "x"), _chk(weight, torch.float32, "weight"), _chk(out, torch.bfloat16, "out")
+    if x.dim() != 2 or out.shape != x.shape or weight.numel() != x.shape[1] or not weight.is_contiguous():
+        raise ValueError("t5_rmsnorm: x and out must be 2-D of one shape, weight contiguous [H]")
+    L.check(L.load().ca_t5_rmsnorm_f32in(x.data_ptr(), x.stride(0), weight.data_ptr(), out.data_ptr(), out.stride(0),
+                                         x.shape[0], x.shape[1], eps, _stream()), "ca_t5_rmsnorm_f32in")
+
+
+def gated_mul(g, u, out) -> None:
+    """out = bf16(float(g) * float(u)) over 2-D bf16 row views of one shape."""
+    _chk(g, torch.bfloat16, "g"), _chk(u, torch.bfloat16, "u"), _chk(out, torch.bfloat16, "out")
+    if g.dim() != 2 or u.shape != g.shape or out.shape != g.shape:
+        raise ValueError("gated_mul: g, u and out must be 2-D of one shape")
+    L.check(L.load().ca_gated_mul_bf16(g.data_ptr(), g.stride(0), u.data_ptr(), u.stride(0), out.data_ptr(), out.stride(0),
+                                       g.shape[0], g.shape[1], _stream()), "ca_gated_mul_bf16")
+
+
+def embed_rows(table, ids, out) -> None:
+    """out[r, :] = float(table[ids[r], :]): table bf16 [vocab, H], ids int32 [rows] (host or device), out fp32 [rows, H].
+    An id outside [0, vocab) is a ValueError here, before anything is launched (the kernel cannot check it)."""
+    _chk(table, torch.bfloat16, "table"), _chk(out, torch.float32, "out")
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous():
+        raise ValueError("embed_rows: ids must be a contiguous 1-D int32 tensor")
+    if table.dim() != 2 or out.dim() != 2 or out.shape[0] != ids.shape[0] or out.shape[1] != table.shape[1] or ids.numel() < 1:
+        raise ValueError("embed_rows: table [vocab, H], ids [rows >= 1], out [rows, H]")
+    lo, hi = int(ids.min()), int(ids.max())
+    if lo < 0 or hi >= table.shape[0]:
+        raise ValueError(f"embed_rows: ids span [{lo}, {hi}], outside the vocabulary [0, {table.shape[0]})")
+    ids = ids.to(table.device)
+    L.check(L.load().ca_embed_rows_f32(table.data_ptr(), table.stride(0), ids.data_ptr(), out.data_ptr(), out.stride(0),
+                                       ids.shape[0], table.shape[1], _stream()), "ca_embed_rows_f32")

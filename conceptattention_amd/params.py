@@ -65,6 +65,37 @@ class AutoEncoderParams:
 # flux/util.py:49-58,81-90: both models ship the same autoencoder
 ae_params = {"flux-schnell": AutoEncoderParams(), "flux-dev": AutoEncoderParams()}
 
+@dataclass(frozen=True)
+class T5Params:
+    """The encoder-side fields of transformers' T5Config; the defaults are google/t5-v1_1-xxl, the checkpoint the
+    reference loads (flux/util.py load_t5, flux/modules/conditioner.py:6-38): gated GELU (tanh form), RMS layer norm
+    without bias, no bias in any projection, relative-position buckets shared by all blocks."""
+    vocab_size: int = 32128
+    d_model: int = 4096
+    d_kv: int = 64
+    num_heads: int = 64
+    d_ff: int = 10240
+    num_layers: int = 24
+    relative_attention_num_buckets: int = 32
+    relative_attention_max_distance: int = 128
+    layer_norm_epsilon: float = 1e-6
+
+    @property
+    def inner_dim(self) -> int:
+        return self.num_heads * self.d_kv
+
+
+t5_params = {"t5-v1_1-xxl": T5Params()}
+
+
+def tiny_t5_params(**kw) -> T5Params:
+    """The smallest geometry that still has every structure of the encoder (two blocks, several heads, d_ff != d_model)
+    and meets the GEMM's rules (every projection width a multiple of 256, every depth a multiple of 64)."""
+    base = dict(vocab_size=512, d_model=256, num_heads=4, d_ff=512, num_layers=2)
+    base.update(kw)
+    return replace(T5Params(), **base)
+
+
 # T5 sequence length per model (reference concept_attention/image_generator.py:57)
 T5_TOKENS = {"flux-schnell": 256, "flux-dev": 512}
 

@@ -3,12 +3,13 @@
 and ``encode_image`` signatures and defaults, ``ConceptAttentionPipelineOutput``), running the DiT
 and the heat-map reduction in the gfx950 kernels.
 
-Out of scope: the T5/CLIP text encoders and the VAE need checkpoints that
-are not available offline.  They are injectable (``text_encoder`` / ``autoencoder``; ``autoencoder="synthetic"`` or a
-``.safetensors`` path builds the HIP autoencoder of ``vae.py``); without them
-the pipeline runs in *synthetic conditioning* mode -- prompt and concept strings are mapped to
-seeded N(0,1) embeddings of the right shapes and ``image`` is returned as the unpacked latent --
-which is exactly the configuration BASELINE.json measures.
+Text and image plumbing.  The autoencoder (``vae.py``) and the T5 encoder (``t5.py``) run in HIP and are opt-in:
+``autoencoder="synthetic"`` or a ``.safetensors`` path; ``text_encoder`` = a ``t5.HipTextEncoder`` (T5 weights from a local
+file, any tokenizer callable) or ``"synthetic-t5"`` (the same encoder on synthetic weights behind a toy byte tokenizer).
+No checkpoint or vocabulary file is available offline, so the default is still *synthetic conditioning*: prompt and
+concept strings are mapped to seeded N(0,1) embeddings of the right shapes (``SyntheticTextEncoder``) and ``image`` is
+returned as the unpacked latent -- exactly the configuration BASELINE.json measures.  Still out of scope: the CLIP
+encoder behind the pooled ``vec`` (a stand-in or an injected callable) and tokenizer vocabularies.
 """
 from __future__ import annotations
 
@@ -76,6 +77,8 @@ class ConceptAttentionFluxPipeline:
         "synthetic" (seeded random init), a path to a flux1-*.safetensors file, or a state dict.
         ``precision="fp8"`` runs the large projections on e4m3 operands (HipFluxDiT.set_precision);
         ``residual_dtype`` is the storage type of the residual streams (fp32 by default, HipFluxDiT.__init__);
+        ``text_encoder``: None (seeded-noise stand-in), "synthetic-t5", or an object with ``t5`` / ``clip`` (a
+        ``t5.HipTextEncoder``; one with ``t5_many`` encodes prompt and concepts in one forward).
         ``capture_independent_image=True`` makes the returned latent (and every map) independent of ``layer_indices``
         bit for bit, as in the reference, for the image rows' attention twice in the captured layers
         (HipFluxDiT.capture_independent_image; INTEGRATION.md)."""

@@ -2,16 +2,20 @@
 
 Without Flux/T5/CLIP/VAE checkpoints (none can be fetched here) the pipeline runs on seeded random-init weights
 and synthetic text embeddings, so the pictures are noise; the call sequence, shapes and outputs are the real ones.
-Pass weights="/path/to/flux1-schnell.safetensors" plus text_encoder= / autoencoder= objects to run the real model."""
+Pass weights="/path/to/flux1-schnell.safetensors", autoencoder="/path/to/ae.safetensors" and
+text_encoder=HipTextEncoder(load_t5(weights="/path/to/t5"), tokenizer, 256, clip=...) to run the real model (CLIP and the
+tokenizer are not built here)."""
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from conceptattention_amd import ConceptAttentionFluxPipeline
 
+# CA_TEXT_ENCODER=synthetic-t5 sends prompt and concepts through the HIP T5 encoder (synthetic weights, toy tokenizer)
 # CA_AUTOENCODER=synthetic (or the path of an ae.safetensors) runs the HIP VAE: pipeline_output.image is then a PIL image
 pipeline = ConceptAttentionFluxPipeline(model_name="flux-schnell", device="cuda:0",
-                                        autoencoder=os.environ.get("CA_AUTOENCODER"))
+                                        autoencoder=os.environ.get("CA_AUTOENCODER"),
+                                        text_encoder=os.environ.get("CA_TEXT_ENCODER"))
 
 prompt = "A cat in a park on the grass by a tree"
 concepts = ["cat", "grass", "sky", "tree"]

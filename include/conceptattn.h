@@ -28,10 +28,11 @@
 extern "C" {
 #endif
 
-#define CA_VERSION 127 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
+#define CA_VERSION 128 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
                           CA_ATTN_Q_PRESCALED; .1: ca_axpy_f32, ca_split_bf16; .2: ca_attn_stats; .3: ca_gemm_problem.qk_f16,
                           ca_attn_fwd_qk16; .4: ca_qpre_finish_rope_f32; .5: ca_heatmap_fused; .6: ca_gemm_plan;
-                          .7: the autoencoder kernels (conv3x3_nhwc, groupnorm_nhwc, softmax_rows_f32, affine_rows_f32) */
+                          .7: the autoencoder kernels (conv3x3_nhwc, groupnorm_nhwc, softmax_rows_f32, affine_rows_f32);
+                          128: the T5 encoder kernels (t5_attn_bf16, t5_rmsnorm_f32in, gated_mul_bf16, embed_rows_f32) */
 
 #define CA_OK 0
 #define CA_ERR_ARG (-1)    /* bad shape / null pointer / misalignment */
@@ -443,6 +444,38 @@ int ca_softmax_rows_f32(const float *s, int32_t lds, void *p, int32_t ldp, int32
 int ca_affine_rows_f32(const float *x, int32_t ldx, const float *logvar, int32_t ldl, const float *noise, int32_t ldn,
                        void *out, int32_t ldo, int32_t out_f32, int64_t rows, int32_t C, float a, float b,
                        ca_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * T5 encoder (transformers' modeling_t5.py, encoder side, as flux/modules/conditioner.py:6-38 loads and calls it:
+ * every string padded to max_length, attention_mask = None, so padding tokens take part in attention).  The q / k / v /
+ * o and wi / wo projections run on ca_gemm_bf16; the kernels below are the rest of a block.
+ *
+ * T5Attention.forward: scores = q k^T (NO 1 / sqrt(d) scale) + position_bias; softmax in fp32; out = P v.
+ * q, k, v: bf16 [n_seq * L, heads * 64] views with free row strides (column slices of one fused projection output);
+ * head h at columns h * 64.  bias: fp32 [heads, 2 L - 1], bias[h, key_pos - query_pos + L - 1] =
+ * relative_attention_bias[bucket(key_pos - query_pos), h], built by the caller.  out: bf16, same form.  Scores, softmax
+ * and the P v accumulation are fp32; P is rounded to bf16 (unnormalised, in (0, 1]) only as an MFMA operand.
+ * L % 64 == 0, 64 <= L <= 512, heads >= 1, n_seq >= 1, n_seq * heads * L / 64 workgroups < 2^31; row strides % 8;
+ * q, k, v, out 16-byte aligned.  One launch. */
+int ca_t5_attn_bf16(const void *q, const void *k, const void *v, const float *bias, void *out, int32_t ldq, int32_t ldk,
+                    int32_t ldv, int32_t ldo, int32_t n_seq, int32_t heads, int32_t L, ca_stream_t stream);
+
+/* T5LayerNorm.forward: out[r, :] = bf16(x[r, :] * rsqrt(mean(x[r, :]^2) + eps) * w[:]) -- no mean subtraction, no bias.
+ * x fp32 [rows, ldx] (the residual stream), w fp32 [H], out bf16 [rows, ldo]; H % 4 == 0, ldx / ldo >= H and % 4. */
+int ca_t5_rmsnorm_f32in(const float *x, int32_t ldx, const float *w, void *out, int32_t ldo, int64_t rows, int32_t H,
+                        float eps, ca_stream_t stream);
+
+/* T5DenseGatedActDense.forward: out = bf16(float(g) * float(u)) with g = gelu_new(wi_0 x) (the out2 of a
+ * CA_EPI_SPLIT_GELU launch on the stacked [wi_1 ; wi_0] weight) and u = wi_1 x.  bf16 rows of C columns, C % 8 == 0,
+ * row strides >= C and % 8, 16-byte aligned. */
+int ca_gated_mul_bf16(const void *g, int32_t ldg, const void *u, int32_t ldu, void *out, int32_t ldo, int64_t rows,
+                      int32_t C, ca_stream_t stream);
+
+/* nn.Embedding into the fp32 residual stream: out[r, :] = float(table[ids[r], :]).  table bf16 [vocab, ldt], ids int32
+ * [rows] on the device, out fp32 [rows, ldo]; H % 8 == 0.  The library cannot see the ids: the caller guarantees
+ * 0 <= ids[r] < vocab (the Python wrapper checks before the launch). */
+int ca_embed_rows_f32(const void *table, int32_t ldt, const int32_t *ids, float *out, int32_t ldo, int64_t rows,
+                      int32_t H, ca_stream_t stream);
 
 #ifdef __cplusplus
 }
