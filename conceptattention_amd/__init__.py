@@ -4,8 +4,8 @@ Public surface mirrors the reference package (`concept_attention/__init__.py:2`)
 ``from conceptattention_amd import ConceptAttentionFluxPipeline``.  Importing the package does not
 touch the GPU; the HIP library is loaded on first use and its absence is a hard error.
 """
-from .params import (AutoEncoderParams, FluxParams, T5Params, ae_params, configs, t5_params, tiny_params,  # noqa: F401
-                     tiny_t5_params)
+from .params import (AutoEncoderParams, ClipTextParams, FluxParams, T5Params, ae_params, clip_params, configs,  # noqa: F401
+                     t5_params, tiny_clip_params, tiny_params, tiny_t5_params)
 
 
 def __getattr__(name):  # lazy: keep `import conceptattention_amd` light for host-only tools
@@ -24,6 +24,10 @@ def __getattr__(name):  # lazy: keep `import conceptattention_amd` light for hos
     if name in ("T5Encoder", "HipTextEncoder", "ToyByteTokenizer", "load_t5", "synthetic_t5_state_dict", "t5_state_dict_spec"):
         from . import t5
         return getattr(t5, name)
+    if name in ("ClipTextEncoder", "HipClipEmbedder", "ToyClipTokenizer", "load_clip", "synthetic_clip_state_dict",
+                "clip_state_dict_spec"):
+        from . import clip
+        return getattr(clip, name)
     if name == "compute_heatmaps_from_vectors":
         from .heatmaps import compute_heatmaps_from_vectors
         return compute_heatmaps_from_vectors

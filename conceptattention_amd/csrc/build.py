@@ -8,11 +8,13 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 LIB = os.path.join(PKG, "libconceptattn.so")
-SOURCES = ["ca_api.hip", "ca_gemm.hip", "ca_attn.hip", "ca_attn4.hip", "ca_rowops.hip", "ca_vae.hip", "ca_t5.hip"]
+SOURCES = ["ca_api.hip", "ca_gemm.hip", "ca_attn.hip", "ca_attn4.hip", "ca_rowops.hip", "ca_vae.hip", "ca_t5.hip",
+           "ca_clip.hip"]
 # ca_attn4.hip owns the AGPR file by hand (literal a[...] registers in its asm statements): hipcc must never park a
 # VGPR there (its default spill target), and the emitted code is audited for it below
 EXTRA_FLAGS = {"ca_attn4.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-save-temps=obj"],
-               "ca_t5.hip": ["-save-temps=obj"]}   # (its assembly is read for spills below)
+               "ca_t5.hip": ["-save-temps=obj"],    # (its assembly is read for spills below)
+               "ca_clip.hip": ["-save-temps=obj"]}  # (the same)
 HEADERS = ["ca_common.h", "ca_attn_common.h", "ca_attn4_sched.inc", "ca_attn4_kernel.inc"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function"]
@@ -56,18 +58,29 @@ def audit_attn4(asm_path: str) -> None:
             os.remove(os.path.join(HERE, tmp))
 
 
-def audit_t5(asm_path: str) -> None:
-    """ca_t5_attn_kernel holds a wave's whole score block in registers (L / 4 floats per lane, 128 at L = 512): a spill
-    there turns the softmax into scratch traffic.  Every kernel of the unit must report no spill and no scratch."""
+def _audit_no_spill(unit: str, asm_path: str) -> None:
+    """Every kernel of ``unit``.hip must report no VGPR spill and no scratch; removes the -save-temps leftovers."""
     import re
     text = open(asm_path).read()
     spills = [int(x) for x in re.findall(r"\.vgpr_spill_count:\s*(\d+)", text)]
     scratch = [int(x) for x in re.findall(r"\.private_segment_fixed_size:\s*(\d+)", text)]
     if any(spills) or any(scratch) or not spills:
-        raise RuntimeError(f"ca_t5.hip audit failed: vgpr spills {spills}, scratch {scratch} bytes")
+        raise RuntimeError(f"{unit}.hip audit failed: vgpr spills {spills}, scratch {scratch} bytes")
     for tmp in os.listdir(HERE):   # -save-temps leftovers
-        if tmp.startswith("ca_t5-") and not tmp.endswith(".s"):
+        if tmp.startswith(unit + "-") and not tmp.endswith(".s"):
             os.remove(os.path.join(HERE, tmp))
+
+
+def audit_t5(asm_path: str) -> None:
+    """ca_t5_attn_kernel holds a wave's whole score block in registers (L / 4 floats per lane, 128 at L = 512): a spill
+    there turns the softmax into scratch traffic.  Every kernel of the unit must report no spill and no scratch."""
+    _audit_no_spill("ca_t5", asm_path)
+
+
+def audit_clip(asm_path: str) -> None:
+    """ca_clip_attn_kernel keeps its scores in registers as well (at most 32 floats per lane), indexed by unrolled loops
+    under wave-uniform branches: an index hipcc could not resolve would put the block into scratch."""
+    _audit_no_spill("ca_clip", asm_path)
 
 
 def audit_sgpr_hazards(text: str) -> list:
@@ -320,6 +333,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             raise RuntimeError("hipcc failed")
     audit_attn4(os.path.join(HERE, "ca_attn4-hip-amdgcn-amd-amdhsa-gfx950.s"))
     audit_t5(os.path.join(HERE, "ca_t5-hip-amdgcn-amd-amdhsa-gfx950.s"))
+    audit_clip(os.path.join(HERE, "ca_clip-hip-amdgcn-amd-amdhsa-gfx950.s"))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
     if verbose:
         print(" ".join(cmd), flush=True)

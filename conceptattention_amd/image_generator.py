@@ -8,9 +8,10 @@ same ``generate_image(width, height, num_steps, guidance, seed, prompt, concepts
 HuggingFace downloads (`load_t5/load_clip/load_ae/hf_hub_download`, `:19-62`; unavailable offline) -- the
 text encoder and autoencoder are injectable (``autoencoder`` also takes "synthetic" or a ``.safetensors`` path and
 then builds the HIP ``vae.AutoEncoder``; ``text_encoder`` takes a ``t5.HipTextEncoder``, whose T5 side is the HIP
-encoder of ``t5.py`` on local weights, or "synthetic-t5", the same encoder on synthetic weights behind a toy tokenizer).
-By default the text encoder is still the seeded-noise stand-in and the unpacked latent is returned instead of an image.
-CLIP (the pooled ``vec``) has no HIP encoder yet and stays a stand-in or an injected callable.  Also not re-stated: the
+encoder of ``t5.py`` on local weights and whose CLIP side may be the HIP encoder of ``clip.py``, or "synthetic-t5", the
+T5 encoder on synthetic weights behind a toy tokenizer, or "synthetic-t5-clip", that plus a synthetic CLIP text encoder
+for the pooled ``vec``).  By default the text encoder is still the seeded-noise stand-in and the unpacked latent is
+returned instead of an image.  Also not re-stated: the
 `model.cpu()` / `.to(device)` round trip of the 23.8 GB weights on every call (`:183,194`), which a
 288 GB device does not need.
 """
@@ -64,11 +65,16 @@ class FluxGenerator:
                                      params=self.params, residual_dtype=residual_dtype)
         n_tok = n_text_tokens or T5_TOKENS.get(model_name, 256)
         if isinstance(text_encoder, str):
-            if text_encoder != "synthetic-t5":
-                raise ValueError(f"text_encoder: unknown name {text_encoder!r} (\"synthetic-t5\", or an encoder object)")
+            if text_encoder not in ("synthetic-t5", "synthetic-t5-clip"):
+                raise ValueError(f"text_encoder: unknown name {text_encoder!r} (\"synthetic-t5\", \"synthetic-t5-clip\", "
+                                 "or an encoder object)")
             from .t5 import synthetic_text_encoder
+            clip = None
+            if text_encoder == "synthetic-t5-clip":
+                from .clip import synthetic_clip_embedder
+                clip = synthetic_clip_embedder(self.params.vec_in_dim, self.device, weight_seed)
             text_encoder = synthetic_text_encoder(self.params.context_in_dim, n_tok, self.device,
-                                                  self.params.vec_in_dim, weight_seed)
+                                                  self.params.vec_in_dim, weight_seed, clip=clip)
         enc = text_encoder or SyntheticTextEncoder(n_tok, self.params.context_in_dim, self.params.vec_in_dim,
                                                    self.device)
         self.text_encoder = enc

@@ -738,3 +738,74 @@ def embed_rows(table, ids, out) -> None:
     ids = ids.to(table.device)
     L.check(L.load().ca_embed_rows_f32(table.data_ptr(), table.stride(0), ids.data_ptr(), out.data_ptr(), out.stride(0),
                                        ids.shape[0], table.shape[1], _stream()), "ca_embed_rows_f32")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# CLIP text encoder kernels (ca_clip.hip).  Rows are tokens; q / k / v are 2-D views with free row strides.
+
+def clip_attention(q, k, v, out, n_seq: int, num_heads: int, scale: float = 0.125) -> None:
+    """out = softmax(scale q k^T + causal mask) v per (sequence, head); head dim 64.  q, k, v, out bf16
+    [n_seq * L, num_heads * 64] views (row stride free), L = rows / n_seq any value in 1..128; a query at position i
+    sees keys 0..i of its own sequence."""
+    for n, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        _chk(t, torch.bfloat16, n)
+        if t.dim() != 2 or t.shape[1] != num_heads * 64 or t.shape[0] != q.shape[0]:
+            raise ValueError(f"clip_attention: {n} must be 2-D [n_seq * L, num_heads*64 = {num_heads * 64}], got {tuple(t.shape)}")
+    if n_seq < 1 or q.shape[0] % n_seq:
+        raise ValueError(f"clip_attention: {q.shape[0]} rows are not n_seq = {n_seq} sequences of one length")
+    L.check(L.load().ca_clip_attn_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), q.stride(0), k.stride(0),
+                                       v.stride(0), out.stride(0), n_seq, num_heads, q.shape[0] // n_seq, float(scale),
+                                       _stream()), "ca_clip_attn_bf16")
+
+
+def layernorm(x, weight, bias, out, eps: float = 1e-5, row_idx=None) -> None:
+    """out[r] = bf16((x[src] - mean) * rsqrt(var + eps) * weight + bias), src = row_idx[r] or r: x fp32 [n, H], weight and
+    bias fp32 [H], out bf16 [rows, H]; ``row_idx`` an int32 tensor [rows] (host or device) of rows of x, checked here."""
+    _chk(x, torch.float32, "x"), _chk(weight, torch.float32, "weight"), _chk(bias, torch.float32, "bias")
+    _chk(out, torch.bfloat16, "out")
+    if x.dim() != 2 or out.dim() != 2 or out.shape[1] != x.shape[1] or weight.numel() != x.shape[1] or \
+            bias.numel() != x.shape[1] or not weight.is_contiguous() or not bias.is_contiguous():
+        raise ValueError("layernorm: x [n, H], out [rows, H], weight and bias contiguous [H]")
+    idx = None
+    if row_idx is None:
+        if out.shape[0] != x.shape[0]:
+            raise ValueError("layernorm: without row_idx, out has as many rows as x")
+    else:
+        if not isinstance(row_idx, torch.Tensor) or row_idx.dtype != torch.int32 or row_idx.dim() != 1 or \
+                not row_idx.is_contiguous() or row_idx.shape[0] != out.shape[0] or row_idx.numel() < 1:
+            raise ValueError("layernorm: row_idx must be a contiguous int32 tensor with one entry per row of out")
+        lo, hi = int(row_idx.min()), int(row_idx.max())
+        if lo < 0 or hi >= x.shape[0]:
+            raise ValueError(f"layernorm: row_idx spans [{lo}, {hi}], outside the rows of x [0, {x.shape[0]})")
+        idx = row_idx.to(x.device)
+    L.check(L.load().ca_layernorm_f32in(x.data_ptr(), x.stride(0), _ptr(idx), weight.data_ptr(), bias.data_ptr(),
+                                        out.data_ptr(), out.stride(0), out.shape[0], x.shape[1], eps, _stream()),
+            "ca_layernorm_f32in")
+
+
+def quick_gelu(x, out) -> None:
+    """out = bf16(x * sigmoid(1.702 x)) over 2-D bf16 row views of one shape; out may be x."""
+    _chk(x, torch.bfloat16, "x"), _chk(out, torch.bfloat16, "out")
+    if x.dim() != 2 or out.shape != x.shape:
+        raise ValueError("quick_gelu: x and out must be 2-D of one shape")
+    L.check(L.load().ca_quick_gelu_bf16(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), x.shape[0], x.shape[1],
+                                        _stream()), "ca_quick_gelu_bf16")
+
+
+def clip_embed(tok, pos, ids, out, length: int) -> None:
+    """out[r, :] = float(tok[ids[r], :]) + float(pos[r % length, :]): tok bf16 [vocab, H], pos bf16 [>= length, H], ids
+    int32 [rows] (host or device), out fp32 [rows, H].  An id outside [0, vocab) is a ValueError here, before anything is
+    launched (the kernel cannot check it)."""
+    _chk(tok, torch.bfloat16, "tok"), _chk(pos, torch.bfloat16, "pos"), _chk(out, torch.float32, "out")
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous():
+        raise ValueError("clip_embed: ids must be a contiguous 1-D int32 tensor")
+    if tok.dim() != 2 or pos.dim() != 2 or out.dim() != 2 or out.shape[0] != ids.shape[0] or ids.numel() < 1 or \
+            out.shape[1] != tok.shape[1] or pos.shape[1] != tok.shape[1] or not 1 <= length <= pos.shape[0]:
+        raise ValueError("clip_embed: tok [vocab, H], pos [>= length, H], ids [rows >= 1], out [rows, H]")
+    lo, hi = int(ids.min()), int(ids.max())
+    if lo < 0 or hi >= tok.shape[0]:
+        raise ValueError(f"clip_embed: ids span [{lo}, {hi}], outside the vocabulary [0, {tok.shape[0]})")
+    ids = ids.to(tok.device)
+    L.check(L.load().ca_clip_embed_f32(tok.data_ptr(), tok.stride(0), pos.data_ptr(), pos.stride(0), ids.data_ptr(),
+                                       out.data_ptr(), out.stride(0), ids.shape[0], length, tok.shape[1], _stream()),
+            "ca_clip_embed_f32")

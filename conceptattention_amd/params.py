@@ -96,6 +96,38 @@ def tiny_t5_params(**kw) -> T5Params:
     return replace(T5Params(), **base)
 
 
+@dataclass(frozen=True)
+class ClipTextParams:
+    """The text-model fields of transformers' CLIPTextConfig; the defaults are openai/clip-vit-large-patch14, the
+    checkpoint the reference loads (flux/util.py load_clip, max_length 77): pre-norm blocks, LayerNorm with bias, a bias
+    in every projection, quick_gelu, learned position embeddings, a causal mask.  ``eos_token_id`` is 2 in the published
+    config (the end-of-text token is 49407): transformers then pools at the first arg-max of the ids, and at the first
+    position equal to ``eos_token_id`` for any other value."""
+    vocab_size: int = 49408
+    hidden_size: int = 768
+    num_attention_heads: int = 12
+    intermediate_size: int = 3072
+    num_hidden_layers: int = 12
+    max_position_embeddings: int = 77
+    layer_norm_eps: float = 1e-5
+    eos_token_id: int = 2
+
+    @property
+    def head_dim(self) -> int:
+        return self.hidden_size // self.num_attention_heads
+
+
+clip_params = {"clip-vit-large-patch14": ClipTextParams()}
+
+
+def tiny_clip_params(**kw) -> ClipTextParams:
+    """The smallest geometry that still has every structure of the text model (two layers, several heads of 64,
+    intermediate != hidden) and meets the GEMM's rules (every projection width a multiple of 256)."""
+    base = dict(vocab_size=512, hidden_size=256, num_attention_heads=4, intermediate_size=512, num_hidden_layers=2)
+    base.update(kw)
+    return replace(ClipTextParams(), **base)
+
+
 # T5 sequence length per model (reference concept_attention/image_generator.py:57)
 T5_TOKENS = {"flux-schnell": 256, "flux-dev": 512}
 

@@ -3,13 +3,15 @@
 and ``encode_image`` signatures and defaults, ``ConceptAttentionPipelineOutput``), running the DiT
 and the heat-map reduction in the gfx950 kernels.
 
-Text and image plumbing.  The autoencoder (``vae.py``) and the T5 encoder (``t5.py``) run in HIP and are opt-in:
-``autoencoder="synthetic"`` or a ``.safetensors`` path; ``text_encoder`` = a ``t5.HipTextEncoder`` (T5 weights from a local
-file, any tokenizer callable) or ``"synthetic-t5"`` (the same encoder on synthetic weights behind a toy byte tokenizer).
+Text and image plumbing.  The autoencoder (``vae.py``), the T5 encoder (``t5.py``) and the CLIP text encoder (``clip.py``)
+run in HIP and are opt-in: ``autoencoder="synthetic"`` or a ``.safetensors`` path; ``text_encoder`` = a
+``t5.HipTextEncoder`` (T5 weights from a local file, any tokenizer callable, ``clip=`` a ``clip.HipClipEmbedder``),
+``"synthetic-t5"`` (the T5 encoder on synthetic weights behind a toy byte tokenizer) or ``"synthetic-t5-clip"`` (that plus
+a synthetic CLIP text encoder for the pooled ``vec``).
 No checkpoint or vocabulary file is available offline, so the default is still *synthetic conditioning*: prompt and
 concept strings are mapped to seeded N(0,1) embeddings of the right shapes (``SyntheticTextEncoder``) and ``image`` is
-returned as the unpacked latent -- exactly the configuration BASELINE.json measures.  Still out of scope: the CLIP
-encoder behind the pooled ``vec`` (a stand-in or an injected callable) and tokenizer vocabularies.
+returned as the unpacked latent -- exactly the configuration BASELINE.json measures.  Still out of scope: tokenizer
+vocabularies.
 """
 from __future__ import annotations
 
@@ -77,7 +79,7 @@ class ConceptAttentionFluxPipeline:
         "synthetic" (seeded random init), a path to a flux1-*.safetensors file, or a state dict.
         ``precision="fp8"`` runs the large projections on e4m3 operands (HipFluxDiT.set_precision);
         ``residual_dtype`` is the storage type of the residual streams (fp32 by default, HipFluxDiT.__init__);
-        ``text_encoder``: None (seeded-noise stand-in), "synthetic-t5", or an object with ``t5`` / ``clip`` (a
+        ``text_encoder``: None (seeded-noise stand-in), "synthetic-t5", "synthetic-t5-clip", or an object with ``t5`` / ``clip`` (a
         ``t5.HipTextEncoder``; one with ``t5_many`` encodes prompt and concepts in one forward).
         ``capture_independent_image=True`` makes the returned latent (and every map) independent of ``layer_indices``
         bit for bit, as in the reference, for the image rows' attention twice in the captured layers

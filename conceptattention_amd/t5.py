@@ -333,8 +333,9 @@ class HipTextEncoder:
     local directory path builds ``T5Tokenizer.from_pretrained(path)`` on first use; that branch has never been
     exercised, because no sentencepiece vocabulary file is available to this repository's tests.
 
-    ``clip``: the pooled CLIP embedding is NOT built in HIP yet.  ``clip(text)`` delegates to the injected ``clip``
-    callable, and without one to ``SyntheticTextEncoder.clip``: seeded noise keyed by the text, still a stand-in."""
+    ``clip``: ``clip(text)`` delegates to the injected ``clip`` -- a callable ``text -> [1, vec_dim]``, or an object with
+    such a ``clip`` method (``clip.HipClipEmbedder``, the CLIP text encoder on HIP; kept as ``clip_embedder``) -- and
+    without one to ``SyntheticTextEncoder.clip``: seeded noise keyed by the text, a stand-in."""
 
     def __init__(self, t5_encoder: T5Encoder, tokenizer, max_length: int = 256, clip=None, vec_dim: int = 768):
         if max_length % 64 or not 64 <= max_length <= 512:
@@ -342,6 +343,9 @@ class HipTextEncoder:
         self.encoder, self.max_length = t5_encoder, int(max_length)
         self._tokenizer = tokenizer
         self.device = t5_encoder.device
+        self.clip_embedder = clip if hasattr(clip, "clip") else None
+        if self.clip_embedder is not None:
+            clip = self.clip_embedder.clip
         if clip is None:
             from .pipeline import SyntheticTextEncoder
             clip = SyntheticTextEncoder(self.max_length, t5_encoder.params.d_model, vec_dim, self.device).clip
@@ -376,9 +380,11 @@ class HipTextEncoder:
         return self._clip(text)
 
 
-def synthetic_text_encoder(context_dim: int, max_length: int, device, vec_dim: int = 768, seed: int = 0) -> HipTextEncoder:
+def synthetic_text_encoder(context_dim: int, max_length: int, device, vec_dim: int = 768, seed: int = 0,
+                           clip=None) -> HipTextEncoder:
     """``text_encoder="synthetic-t5"``: a two-block T5Encoder of d_model = ``context_dim`` (4 heads, d_ff 512) with
     synthetic weights behind the toy byte tokenizer.  Real arithmetic on meaningless weights: prompts and concepts reach
-    the DiT through the encoder's kernels, and equal strings give equal bits."""
+    the DiT through the encoder's kernels, and equal strings give equal bits.  ``clip``: as for HipTextEncoder (None: the
+    seeded-noise stand-in; "synthetic-t5-clip" passes ``clip.synthetic_clip_embedder``)."""
     p = tiny_t5_params(d_model=context_dim, vocab_size=ToyByteTokenizer.vocab_size + 253)
-    return HipTextEncoder(load_t5(p, device, "synthetic", seed), ToyByteTokenizer(), max_length, vec_dim=vec_dim)
+    return HipTextEncoder(load_t5(p, device, "synthetic", seed), ToyByteTokenizer(), max_length, clip=clip, vec_dim=vec_dim)

@@ -28,11 +28,13 @@
 extern "C" {
 #endif
 
-#define CA_VERSION 128 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
+#define CA_VERSION 129 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
                           CA_ATTN_Q_PRESCALED; .1: ca_axpy_f32, ca_split_bf16; .2: ca_attn_stats; .3: ca_gemm_problem.qk_f16,
                           ca_attn_fwd_qk16; .4: ca_qpre_finish_rope_f32; .5: ca_heatmap_fused; .6: ca_gemm_plan;
                           .7: the autoencoder kernels (conv3x3_nhwc, groupnorm_nhwc, softmax_rows_f32, affine_rows_f32);
-                          128: the T5 encoder kernels (t5_attn_bf16, t5_rmsnorm_f32in, gated_mul_bf16, embed_rows_f32) */
+                          128: the T5 encoder kernels (t5_attn_bf16, t5_rmsnorm_f32in, gated_mul_bf16, embed_rows_f32);
+                          129: the CLIP text encoder kernels (clip_attn_bf16, layernorm_f32in, quick_gelu_bf16,
+                          clip_embed_f32) */
 
 #define CA_OK 0
 #define CA_ERR_ARG (-1)    /* bad shape / null pointer / misalignment */
@@ -476,6 +478,38 @@ int ca_gated_mul_bf16(const void *g, int32_t ldg, const void *u, int32_t ldu, vo
  * 0 <= ids[r] < vocab (the Python wrapper checks before the launch). */
 int ca_embed_rows_f32(const void *table, int32_t ldt, const int32_t *ids, float *out, int32_t ldo, int64_t rows,
                       int32_t H, ca_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * CLIP text encoder (transformers' modeling_clip.py, CLIPTextModel, as flux/modules/conditioner.py loads and calls it:
+ * every string padded to 77 tokens, attention_mask = None, so the mask is causal only and padding tokens are keys like
+ * any other).  The q|k|v, out_proj, fc1 and fc2 projections run on ca_gemm_bf16; the kernels below are the rest.
+ *
+ * CLIPAttention.forward: out = softmax(scale * q k^T + causal mask) v per (sequence, head), head dim 64.  q, k, v, out:
+ * bf16 [n_seq * L, heads * 64] views with free row strides (column slices of one fused projection output); head h at
+ * columns h * 64; sequence s owns rows s * L .. s * L + L - 1; a query at position i sees keys 0 .. i.  Scores, softmax
+ * and the P v accumulation are fp32; P is rounded to bf16 (unnormalised, in [0, 1]) only as an MFMA operand.
+ * 1 <= L <= 128, any value: a sequence need not fill a tile.  No row at or beyond n_seq * L is read or written (the
+ * places of such rows in the last tile hold zeros).  heads >= 1, n_seq >= 1, scale > 0 and finite; row strides
+ * >= heads * 64 and % 8; q, k, v, out 16-byte aligned.  One launch. */
+int ca_clip_attn_bf16(const void *q, const void *k, const void *v, void *out, int32_t ldq, int32_t ldk, int32_t ldv,
+                      int32_t ldo, int32_t n_seq, int32_t heads, int32_t L, float scale, ca_stream_t stream);
+
+/* nn.LayerNorm on the fp32 stream: out[r, :] = bf16((x[src, :] - mean) * rsqrt(var + eps) * w[:] + b[:]), var the biased
+ * variance about the mean, statistics in fp32; src = row_idx ? row_idx[r] : r (int32 on the device; the caller
+ * guarantees 0 <= row_idx[r] < the rows of x).  x fp32 [*, ldx], w and b fp32 [H], out bf16 [rows, ldo]; H % 4 == 0,
+ * ldx / ldo >= H and % 4. */
+int ca_layernorm_f32in(const float *x, int32_t ldx, const int32_t *row_idx, const float *w, const float *b, void *out,
+                       int32_t ldo, int64_t rows, int32_t H, float eps, ca_stream_t stream);
+
+/* quick_gelu: out = bf16(x * sigmoid(1.702 x)), computed in fp32; bf16 rows of C columns, C % 8 == 0, row strides >= C
+ * and % 8, 16-byte aligned; out may be x.  Finite for every finite x; -inf gives -0, +inf gives +inf, NaN stays NaN. */
+int ca_quick_gelu_bf16(const void *x, int32_t ldx, void *out, int32_t ldo, int64_t rows, int32_t C, ca_stream_t stream);
+
+/* CLIPTextEmbeddings: out[r, :] = float(tok[ids[r], :]) + float(pos[r % L, :]), one fp32 addition.  tok bf16
+ * [vocab, ldt], pos bf16 [>= L, ldp], ids int32 [rows] on the device, out fp32 [rows, ldo]; H % 8 == 0, 1 <= L <= 128.
+ * The library cannot see the ids: the caller guarantees 0 <= ids[r] < vocab (the Python wrapper checks). */
+int ca_clip_embed_f32(const void *tok, int32_t ldt, const void *pos, int32_t ldp, const int32_t *ids, float *out,
+                      int32_t ldo, int64_t rows, int32_t L, int32_t H, ca_stream_t stream);
 
 #ifdef __cplusplus
 }
