@@ -16,12 +16,16 @@ norm statistics are fp32.  The projection biases are bf16 (the GEMM's bias opera
 fp32.  ``out_proj`` and ``fc2`` add into the stream in the GEMM epilogue (EPI_GATE_RESIDUAL with a ones gate), q | k | v
 are one ``[3 hidden, hidden]`` weight under EPI_BIAS, ``fc1`` is EPI_BIAS followed by ``ca_quick_gelu_bf16`` in place.
 
-Batching: ONE SEQUENCE PER PASS.  A sequence's bits must not depend on what else is in the call.  At most 77 rows fill
-no 256-row tile of the GEMM: two or more sequences in one launch would share a row tile, and which rows ride in a full
-256 x 256 tile and which in the thin-row kernel (a last row tile of at most 128 rows) would depend on the batch.  With
-one sequence per pass every GEMM has at most 77 rows and always takes the thin-row route; the whole network is 250 MB of
-weights, so the price is launches, not bandwidth.  Batching the row kernels alone was not done.  The workspace is
-resident and reused across calls.
+Batching: up to ``MAX_SEGMENTS`` (16) sequences per pass, every sequence with the bits of its own one-sequence pass.
+The sequences of a pass are stacked as rows (sequence s owns rows s * L .. s * L + L - 1).  The row kernels -- embedding,
+LayerNorm, quick_gelu -- work row by row, and the attention kernel takes ``n_seq`` and never looks across a sequence's
+rows.  Each projection is ONE GEMM problem over the stacked rows, always under the 256 x 256 ping-pong tile: the grouped
+launch holds at most ``GEMM_MAX_PROBLEMS`` (2) problems, so one problem per sequence would not fit sixteen of them, and
+it is not needed -- the GEMM's contract is one k order per accumulator, whichever way a row is computed (a full 256-row
+tile, a thin last row tile inside the walk, or the thin-row kernel that a lone sequence's 77 rows take;
+tests/test_kernels_gpu.py::test_gemm_thin_last_row_tile_is_bit_identical pins it for every epilogue used here, and
+tests/test_clip_model_gpu.py pins the encoder's bits against one-sequence calls).  A call with more sequences runs in
+several passes.  The workspace is resident, sized once for a full pass and reused across calls.
 """
 from __future__ import annotations
 
@@ -114,8 +118,10 @@ def pooled_positions(ids: torch.Tensor, eos_token_id: int) -> torch.Tensor:
 class ClipTextEncoder:
     """``encode_ids(ids[n, L]) -> [n, hidden]`` bf16, the ``pooler_output`` of CLIPTextModel with
     ``attention_mask=None``; ``hidden_states(ids) -> [n, L, hidden]`` bf16, its ``last_hidden_state`` (after the final
-    norm).  L any value in 1..max_position_embeddings (at most 128, the attention kernel's limit).  One sequence per pass:
-    see the module docstring."""
+    norm).  L any value in 1..max_position_embeddings (at most 128, the attention kernel's limit).  Up to SEQS_PER_PASS
+    sequences share every launch: see the module docstring."""
+
+    SEQS_PER_PASS = L.MAX_SEGMENTS
 
     def __init__(self, params: ClipTextParams, device="cuda"):
         p = params
@@ -186,9 +192,10 @@ class ClipTextEncoder:
 
     # ------------------------------------------------------------------ workspace
     def _workspace(self) -> dict:
-        """Resident buffers of one pass (one sequence of at most max_position_embeddings rows), made on first use."""
+        """Resident buffers of one full pass (SEQS_PER_PASS sequences of at most max_position_embeddings rows), made on
+        first use: calls of any size share them."""
         if self._ws is None:
-            p, dev, rows = self.params, self.device, self.params.max_position_embeddings
+            p, dev, rows = self.params, self.device, self.SEQS_PER_PASS * self.params.max_position_embeddings
             self._ws = {"x": torch.empty(rows, p.hidden_size, device=dev, dtype=torch.float32),
                         "hn": torch.empty(rows, p.hidden_size, device=dev, dtype=torch.bfloat16),
                         "qkv": torch.empty(rows, 3 * p.hidden_size, device=dev, dtype=torch.bfloat16),
@@ -216,35 +223,42 @@ class ClipTextEncoder:
     @torch.no_grad()
     def encode_ids(self, ids: torch.Tensor) -> torch.Tensor:
         host = self._check_ids(ids, "encode_ids")
+        n, length = host.shape
+        # the pooled row of sequence s within its pass: (s - s0) * L + position
         pooled = pooled_positions(host, self.params.eos_token_id).to(torch.int32)
         dev_ids = host.to(torch.int32).to(self.device)
-        out = torch.empty(host.shape[0], self.params.hidden_size, device=self.device, dtype=torch.bfloat16)
-        for s in range(host.shape[0]):
-            self._pass(dev_ids[s], out[s:s + 1], pooled[s:s + 1])
+        out = torch.empty(n, self.params.hidden_size, device=self.device, dtype=torch.bfloat16)
+        for s0 in range(0, n, self.SEQS_PER_PASS):
+            s1 = min(n, s0 + self.SEQS_PER_PASS)
+            rows = pooled[s0:s1] + torch.arange(s1 - s0, dtype=torch.int32) * length
+            self._pass(dev_ids[s0:s1].reshape(-1), s1 - s0, length, out[s0:s1], rows.contiguous())
         return out
 
     @torch.no_grad()
     def hidden_states(self, ids: torch.Tensor) -> torch.Tensor:
         host = self._check_ids(ids, "hidden_states")
+        n = host.shape[0]
         dev_ids = host.to(torch.int32).to(self.device)
         out = torch.empty(*host.shape, self.params.hidden_size, device=self.device, dtype=torch.bfloat16)
-        for s in range(host.shape[0]):
-            self._pass(dev_ids[s], out[s], None)
+        for s0 in range(0, n, self.SEQS_PER_PASS):
+            s1 = min(n, s0 + self.SEQS_PER_PASS)
+            self._pass(dev_ids[s0:s1].reshape(-1), s1 - s0, host.shape[1], out[s0:s1].view(-1, self.params.hidden_size), None)
         return out
 
-    def _pass(self, ids, out, pooled) -> None:
-        """One sequence through the network; the final norm on all rows, or on the rows ``pooled`` names alone."""
+    def _pass(self, ids, n_seq: int, length: int, out, pooled) -> None:
+        """``n_seq`` stacked sequences of ``length`` rows through the network; the final norm on all rows, or on the
+        rows ``pooled`` names alone."""
         p, w = self.params, self.w
-        rows, d = ids.shape[0], p.hidden_size
+        rows, d = n_seq * length, p.hidden_size
         ws = self._workspace()
         x, hn, qkv, ao, u = (ws[k][:rows] for k in ("x", "hn", "qkv", "ao", "u"))
-        tile = L.TILE_PP_256x256   # at most 77 rows: always the thin-row kernel behind this tile
+        tile = L.TILE_PP_256x256   # one tile for every row count: a row's bits must not depend on the batch
         scale = p.head_dim ** -0.5
-        ops.clip_embed(w["tok"], w["pos"], ids, x, rows)
+        ops.clip_embed(w["tok"], w["pos"], ids, x, length)
         for i in range(p.num_hidden_layers):
             ops.layernorm(x, w[f"{i}.ln1.w"], w[f"{i}.ln1.b"], hn, p.layer_norm_eps)
             ops.gemm([ops.Gemm(hn, w[f"{i}.qkv"], w[f"{i}.qkv.b"], qkv)], tile)
-            ops.clip_attention(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], ao, 1, p.num_attention_heads, scale)
+            ops.clip_attention(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], ao, n_seq, p.num_attention_heads, scale)
             ops.gemm([ops.Gemm(ao, w[f"{i}.o"], w[f"{i}.o.b"], x, epilogue=L.EPI_GATE_RESIDUAL, resid=x, gate=w["ones"])], tile)
             ops.layernorm(x, w[f"{i}.ln2.w"], w[f"{i}.ln2.b"], hn, p.layer_norm_eps)
             ops.gemm([ops.Gemm(hn, w[f"{i}.fc1"], w[f"{i}.fc1.b"], u)], tile)

@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import os
 import time
+from collections import OrderedDict
 
 import torch
 
@@ -48,6 +49,41 @@ def load_flow_model(name: str, device="cuda", hf_download: bool = True, attentio
     elif weights is not None:
         model.load_state_dict(weights, strict=False)
     return model
+
+
+class ConceptCache:
+    """Bounded LRU of concept first-token vectors (bf16 [context_dim] on the device, 8 KB each at 4096), keyed by the
+    concept string.  It belongs to one encoder object: ``bind`` drops every entry when another one shows up."""
+
+    def __init__(self, max_entries: int = 4096):
+        if max_entries < 1:
+            raise ValueError("ConceptCache: max_entries must be >= 1")
+        self.max_entries = int(max_entries)
+        self._entries: OrderedDict = OrderedDict()
+        self._owner = None
+
+    def bind(self, encoder) -> None:
+        if encoder is not self._owner:
+            self._entries.clear()
+            self._owner = encoder
+
+    def get(self, text: str):
+        v = self._entries.get(text)
+        if v is not None:
+            self._entries.move_to_end(text)
+        return v
+
+    def put(self, text: str, vector) -> None:
+        self._entries[text] = vector
+        self._entries.move_to_end(text)
+        while len(self._entries) > self.max_entries:
+            self._entries.popitem(last=False)
+
+    def __len__(self):
+        return len(self._entries)
+
+    def __contains__(self, text):
+        return text in self._entries
 
 
 class FluxGenerator:
@@ -85,6 +121,8 @@ class FluxGenerator:
                                   weights=str(autoencoder), seed=weight_seed)
         self.ae = autoencoder
         self.nsfw_classifier = None
+        self.concept_cache = ConceptCache()
+        self.t5_sequences_encoded = 0     # sequences embed_many actually sent through the T5 encoder (for tests)
 
     def embed(self, prompt: str, concepts):
         """prepare()'s text side + embed_concepts (flux/sampling.py:47-55, concept_attention/utils.py:6-33).  A text
@@ -100,15 +138,62 @@ class FluxGenerator:
         con, con_ids, con_vec = sampling.concept_inputs(con, vec)
         return txt, vec, con, con_ids, con_vec
 
+    def embed_many(self, prompts, concepts_per_item):
+        """``embed`` for several items: [(txt, vec, con, con_ids, con_vec), ...], each entry bit for bit what
+        ``embed(prompt, concepts)`` returns for that item.  ONE T5 call over the distinct strings that are needed --
+        every distinct prompt, and the concepts ``concept_cache`` does not hold yet -- and one ``clip_many`` call over
+        the distinct prompts.  (The T5 encoder gives a sequence the same bits whatever else is in the call.)  A text
+        encoder without ``t5_many`` is called through ``embed`` per item."""
+        prompts, concepts_per_item = list(prompts), [list(c) for c in concepts_per_item]
+        if len(prompts) != len(concepts_per_item):
+            raise ValueError("embed_many: one concept list per prompt")
+        many = getattr(self.text_encoder, "t5_many", None)
+        if many is None:
+            return [self.embed(p, c) for p, c in zip(prompts, concepts_per_item)]
+        cache = self.concept_cache
+        cache.bind(self.text_encoder)
+        uniq_prompts = list(dict.fromkeys(prompts))
+        concepts = list(dict.fromkeys(c for cs in concepts_per_item for c in cs))
+        # read every cached vector BEFORE anything is inserted: an insertion may evict an entry this call still needs
+        con_vecs = {c: cache.get(c) for c in concepts}
+        new = [c for c in concepts if con_vecs[c] is None]
+        both = many(uniq_prompts + new)
+        self.t5_sequences_encoded += len(uniq_prompts) + len(new)
+        txts = {p: both[i:i + 1] for i, p in enumerate(uniq_prompts)}
+        for j, c in enumerate(new):
+            con_vecs[c] = both[len(uniq_prompts) + j, 0, :].clone()     # (a copy: the entry must not pin the whole batch)
+            cache.put(c, con_vecs[c])
+        clip_many = getattr(getattr(self.text_encoder, "clip_embedder", None), "clip_many", None)
+        if clip_many is not None:
+            pooled = clip_many(uniq_prompts)
+            vecs = {p: pooled[i:i + 1] for i, p in enumerate(uniq_prompts)}
+        else:
+            vecs = {p: self.clip(p) for p in uniq_prompts}
+        out = []
+        for p, cs in zip(prompts, concepts_per_item):
+            con = torch.stack([con_vecs[c] for c in cs]).unsqueeze(0)
+            out.append((txts[p], vecs[p], *sampling.concept_inputs(con, vecs[p])))
+        return out
+
     def decode(self, x: torch.Tensor, height: int, width: int):
         """unpack + VAE decode + PIL (image_generator.py:189-204); without an autoencoder the unpacked
         latent is returned as a numpy array."""
+        return self.decode_many(x, height, width)[0]
+
+    def decode_many(self, x: torch.Tensor, height: int, width: int) -> list:
+        """``decode`` for the B items of ``x``: one image (or latent array) per item.  The HIP autoencoder makes the
+        bytes on the device (``AutoEncoder.decode_pixels``) and only they come back; an injected object that has
+        ``decode`` alone goes the reference's way through an fp32 image."""
         lat = sampling.unpack(x.float(), height, width)
         if self.ae is None:
-            return lat[0].cpu().numpy()
+            return [lat[k].cpu().numpy() for k in range(lat.shape[0])]
         import PIL.Image
-        img = self.ae.decode(lat.to(torch.float32)).clamp(-1, 1)[0].permute(1, 2, 0)
-        return PIL.Image.fromarray((127.5 * (img + 1.0)).cpu().byte().numpy())
+        if hasattr(self.ae, "decode_pixels"):
+            pix = self.ae.decode_pixels(lat.to(torch.float32)).cpu().numpy()
+        else:
+            img = self.ae.decode(lat.to(torch.float32)).clamp(-1, 1).permute(0, 2, 3, 1)
+            pix = (127.5 * (img + 1.0)).cpu().byte().numpy()
+        return [PIL.Image.fromarray(pix[k]) for k in range(pix.shape[0])]
 
     @torch.no_grad()  # (the reference uses inference_mode; the resident workspace is reused across calls)
     @on_own_device

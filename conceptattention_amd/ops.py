@@ -684,6 +684,34 @@ def affine_rows(x, out, a: float = 1.0, b: float = 0.0, logvar=None, noise=None,
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Pixel I/O kernels (ca_pixels.hip): image bytes into the autoencoder's input plane, its output plane to bytes.
+
+def pixels_to_nhwc32(src, dst) -> None:
+    """dst[y, x, :3] = bf16(2 * (src[sy, sx] / 255) - 1) at the nearest source pixel of torch's interpolate, dst[y, x, 3:]
+    = 0: src uint8 [H0, W0, 3] on the device (row stride free, the pixel's 3 bytes adjacent), dst bf16 [H, W, 32]
+    contiguous -- one image slot of the zero-padded input plane."""
+    _chk(src, torch.uint8, "src"), _chk(dst, torch.bfloat16, "dst")
+    if src.dim() != 3 or src.shape[2] != 3 or src.stride(2) != 1 or src.stride(1) != 3 or dst.dim() != 3 or dst.shape[2] != 32 or \
+            not dst.is_contiguous() or src.device != dst.device:
+        raise ValueError(f"pixels_to_nhwc32: src{tuple(src.shape)} must be uint8 [H0, W0, 3] with adjacent pixels, dst"
+                         f"{tuple(dst.shape)} contiguous bf16 [H, W, 32] on the same device")
+    L.check(L.load().ca_pixels_u8_to_nhwc32_bf16(src.data_ptr(), src.stride(0), dst.data_ptr(), src.shape[0], src.shape[1],
+                                                 dst.shape[0], dst.shape[1], _stream()), "ca_pixels_u8_to_nhwc32_bf16")
+
+
+def nhwc_to_pixels(src, dst) -> None:
+    """dst = (127.5 * (src[..., :3].clamp(-1, 1) + 1.0)).byte(): src fp32 [..., ld >= 3] contiguous (NHWC), dst uint8
+    [..., 3] contiguous with the same leading dimensions.  A NaN gives 0."""
+    _chk(src, torch.float32, "src"), _chk(dst, torch.uint8, "dst")
+    if src.dim() < 2 or src.shape[-1] < 3 or dst.shape[-1] != 3 or tuple(src.shape[:-1]) != tuple(dst.shape[:-1]) or \
+            not src.is_contiguous() or not dst.is_contiguous() or src.device != dst.device:
+        raise ValueError(f"nhwc_to_pixels: src{tuple(src.shape)} must be contiguous fp32 [..., ld >= 3], dst"
+                         f"{tuple(dst.shape)} contiguous uint8 [..., 3] of the same pixels on the same device")
+    L.check(L.load().ca_nhwc_f32_to_pixels_u8(src.data_ptr(), src.shape[-1], dst.data_ptr(), dst.numel() // 3, _stream()),
+            "ca_nhwc_f32_to_pixels_u8")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # T5 encoder kernels (ca_t5.hip).  Rows are tokens; q / k / v are 2-D views with free row strides.
 
 def t5_attention(q, k, v, bias, out, n_seq: int, num_heads: int) -> None:

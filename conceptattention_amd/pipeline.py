@@ -70,6 +70,31 @@ def colorize_heatmaps(heatmaps: np.ndarray, cmap: str = "plasma") -> list:
     return out
 
 
+MAX_ITEMS_PER_FORWARD = min(_lib.ATTN_MAX_PROBLEMS // 2, _lib.MAX_SEGMENTS // 3)   # launch limits: 5 items
+
+
+def plan_batches(keys: Sequence, batch: int) -> list:
+    """The forwards of a batched call, as lists of item indices.  ``keys[i]`` is whatever item i must share with the
+    others of its forward -- (latent shape, concept count, text length).  Items of one key form a group, the groups in the
+    order of their first item; a group is cut into chunks of at most min(batch, MAX_ITEMS_PER_FORWARD) items in their
+    original order.  Pure: no device, no tensors."""
+    size = max(1, min(int(batch), MAX_ITEMS_PER_FORWARD))
+    groups: dict = {}
+    for i, k in enumerate(keys):
+        groups.setdefault(k, []).append(i)
+    return [idx[c0:c0 + size] for idx in groups.values() for c0 in range(0, len(idx), size)]
+
+
+def _per_item(value, n: int, what: str) -> list:
+    """``concepts``-style argument: one list of strings for all n items, or one list per item."""
+    value = list(value)
+    if value and all(isinstance(v, str) for v in value):
+        return [value] * n
+    if len(value) != n:
+        raise ValueError(f"{what}: one list for all items, or one list per item ({n} items, got {len(value)})")
+    return [list(v) for v in value]
+
+
 class ConceptAttentionFluxPipeline:
     def __init__(self, model_name: str = "flux-schnell", offload_model: bool = False, device="cuda:0",
                  weights="synthetic", weight_seed: int = 0, text_encoder=None, autoencoder=None,
@@ -350,31 +375,45 @@ class ConceptAttentionFluxPipeline:
                      noise_timestep: int = 2, device: str = "cuda:0", return_pil_heatmaps: bool = True,
                      seed: int = 0, cmap="plasma", stop_after_multi_modal_attentions=True,
                      attention_norm: str = "sparsemax", softmax=True,
-                     joint_attention_kwargs=None, noise=None) -> ConceptAttentionPipelineOutput:
+                     joint_attention_kwargs=None, noise=None, vae_noise=None) -> ConceptAttentionPipelineOutput:
         """``image``: a latent tensor (1,16,h/8,w/8), or a PIL image when the pipeline has an autoencoder
         (``autoencoder="synthetic"``, a ``.safetensors`` path, or an injected object).
         One forward of the 19 double blocks per noise sample (stop_after_multimodal_attentions).
         ``joint_attention_kwargs`` (not in the reference's signature, which hard-codes None at :296) lets the
         segmentation harness select the concept cross/self-attention ablations; ``noise`` (a list of num_samples
-        tensors shaped like the latent) overrides get_noise, whose device RNG stream differs between platforms."""
+        tensors shaped like the latent) overrides get_noise, whose device RNG stream differs between platforms;
+        ``vae_noise`` (1,16,h/8,w/8) is the autoencoder's sampling noise for a PIL image (drawn on the device when not
+        given), so that a call is reproducible."""
         assert all([0 <= li < self.params.depth for li in layer_indices]), "Invalid layer index"
         assert height == width, "Height and width must be the same for now"
         norm = resolve_norm(softmax, attention_norm)
         if isinstance(image, torch.Tensor):
             latent = image.to(self.device, torch.bfloat16)
-        elif self.autoencoder is not None:
-            arr = torch.from_numpy(np.asarray(image.convert("RGB"))).permute(2, 0, 1).float() / 255.0
-            arr = torch.nn.functional.interpolate((2.0 * arr - 1.0)[None].to(self.device), (height, width))
-            latent = self.autoencoder.encode(arr).to(torch.bfloat16)
         else:
-            raise ValueError("encode_image needs a latent tensor, or a pipeline built with autoencoder=\"synthetic\", a "
-                             ".safetensors path or an object with encode / decode")
+            latent = self._encode_pixels([image], height, width, vae_noise)
         txt, vec, con, con_ids, con_vec = self._embed(prompt, concepts)
         out_space, cross_space = self._encode_maps(self.model, latent, txt, vec, con, con_ids, con_vec, layer_indices,
                                                    num_samples, num_steps, noise_timestep, seed,
                                                    stop_after_multi_modal_attentions, joint_attention_kwargs, norm,
                                                    noise=noise)
         return self._finish(image, out_space, cross_space, return_pil_heatmaps, cmap)
+
+    def _encode_pixels(self, images, height: int, width: int, vae_noise=None) -> torch.Tensor:
+        """PIL images -> bf16 latents (B,16,h/8,w/8).  The HIP autoencoder takes the bytes (``encode_pixels``: resize,
+        scaling and cast in one kernel per image); an injected object with ``encode`` alone gets the reference's fp32
+        image tensor."""
+        if self.autoencoder is None:
+            raise ValueError("encode_image needs a latent tensor, or a pipeline built with autoencoder=\"synthetic\", a "
+                             ".safetensors path or an object with encode / decode")
+        arrays = [np.asarray(im.convert("RGB")) for im in images]
+        if hasattr(self.autoencoder, "encode_pixels"):
+            return self.autoencoder.encode_pixels(arrays, height, width, noise=vae_noise).to(torch.bfloat16)
+        xs = []
+        for a in arrays:
+            arr = torch.from_numpy(a).permute(2, 0, 1).float() / 255.0
+            xs.append(torch.nn.functional.interpolate((2.0 * arr - 1.0)[None].to(self.device), (height, width)))
+        kw = {} if vae_noise is None else {"noise": vae_noise}
+        return self.autoencoder.encode(torch.cat(xs), **kw).to(torch.bfloat16)
 
     def _encode_maps(self, model, latent, txt, vec, con, con_ids, con_vec, layer_indices, num_samples, num_steps,
                      noise_timestep, seed, stop_after_multi_modal_attentions=True, joint_attention_kwargs=None,
@@ -410,6 +449,99 @@ class ConceptAttentionFluxPipeline:
                   joint_attention_kwargs=joint_attention_kwargs, return_vectors=False, heatmaps=req)
         side = int(round(n_patches ** 0.5))
         return acc_o.view(B, C, side, side), acc_c.view(B, C, side, side)
+
+    # ------------------------------------------------------------------ batched calls from pixels and text
+    def _text_length(self) -> int:
+        enc = self.text_encoder
+        return int(getattr(enc, "max_length", getattr(enc, "n_tokens", 0)))
+
+    @torch.no_grad()
+    @on_own_device
+    def encode_images(self, images, concepts, prompts, width: int = 1024, height: int = 1024,
+                      layer_indices=list(range(15, 19)), num_samples: int = 1, num_steps: int = 4,
+                      noise_timestep: int = 2, seed: int = 0, batch: int = 5, noise=None, vae_noise=None,
+                      return_pil_heatmaps: bool = True, cmap="plasma", stop_after_multi_modal_attentions=True,
+                      attention_norm: str = "sparsemax", softmax=True, joint_attention_kwargs=None) -> list:
+        """``encode_image`` for a list of images: a list of ConceptAttentionPipelineOutput in item order, every item with
+        the maps of its own ``encode_image`` call.  ``images``: PIL images and / or latents (1,16,h/8,w/8);
+        ``concepts``: one list for all items or one list per item; ``prompts``: one string per item (or one for all).
+        Items that share a latent shape and a concept count go ``batch`` (at most 5) at a time through one text-encoder
+        call (``FluxGenerator.embed_many``), one autoencoder pass (``AutoEncoder.encode_pixels``) and one forward.
+        ``noise``: per item, what ``encode_image`` takes (a list of num_samples tensors); ``vae_noise``: per item, a
+        tensor (1,16,h/8,w/8) -- without it the autoencoder draws one batch of noise per forward, so PIL items are then
+        reproducible per call of this method, not against single calls."""
+        assert all([0 <= li < self.params.depth for li in layer_indices]), "Invalid layer index"
+        assert height == width, "Height and width must be the same for now"
+        norm = resolve_norm(softmax, attention_norm)
+        images = list(images)
+        n = len(images)
+        prompts = [prompts] * n if isinstance(prompts, str) else list(prompts)
+        concepts = _per_item(concepts, n, "encode_images: concepts")
+        for name, v in (("prompts", prompts), ("noise", noise), ("vae_noise", vae_noise)):
+            if v is not None and len(v) != n:
+                raise ValueError(f"encode_images: {name} has {len(v)} entries for {n} images")
+        shapes = [tuple(im.shape[1:]) if isinstance(im, torch.Tensor) else (16, height // 8, width // 8) for im in images]
+        results = [None] * n
+        for idx in plan_batches([(shapes[i], len(concepts[i]), self._text_length()) for i in range(n)], batch):
+            emb = self.flux_generator.embed_many([prompts[i] for i in idx], [concepts[i] for i in idx])
+            txt, vec, con, con_ids, con_vec = (torch.cat([e[k] for e in emb], 0) if len(idx) > 1 else emb[0][k]
+                                               for k in range(5))
+            pil = [i for i in idx if not isinstance(images[i], torch.Tensor)]
+            lat = {}
+            if pil:
+                vn = None if vae_noise is None else torch.cat([vae_noise[i].to(self.device, torch.float32) for i in pil], 0)
+                enc = self._encode_pixels([images[i] for i in pil], height, width, vn)
+                lat = {i: enc[k:k + 1] for k, i in enumerate(pil)}
+            latent = torch.cat([lat[i] if i in lat else images[i].to(self.device, torch.bfloat16) for i in idx], 0)
+            if noise is not None and any(len(noise[i]) != num_samples for i in idx):
+                raise ValueError("noise: one tensor per noise sample")
+            nz = None if noise is None else [torch.cat([noise[i][s_].to(self.device, torch.bfloat16) for i in idx], 0)
+                                             for s_ in range(num_samples)]
+            ho, hc = self._encode_maps(self.model, latent, txt, vec, con, con_ids, con_vec, layer_indices, num_samples,
+                                       num_steps, noise_timestep, seed, stop_after_multi_modal_attentions,
+                                       joint_attention_kwargs, norm, noise=nz)
+            for k, i in enumerate(idx):
+                results[i] = self._finish(images[i], ho[k:k + 1], hc[k:k + 1], return_pil_heatmaps, cmap)
+        return results
+
+    @torch.no_grad()
+    @on_own_device
+    def generate_images(self, prompts, concepts, seeds=None, latents=None, width: int = 1024, height: int = 1024,
+                        return_cross_attention=False, layer_indices=list(range(15, 19)), return_pil_heatmaps=True,
+                        num_inference_steps: int = 4, guidance: float = 0.0, timesteps=None, softmax: bool = True,
+                        attention_norm: str = "sparsemax", cmap="plasma", batch: int = 5) -> list:
+        """``generate_image`` for a list of prompts: a list of ConceptAttentionPipelineOutput in item order, every item
+        with the image and maps of its own ``generate_image(prompt, concepts, seed=seeds[i], latent=latents[i])`` call on
+        the fused route.  ``concepts``: one list for all items or one list per item; ``seeds``: one per item (default
+        0, 1, 2, ...).  Items with one concept count go ``batch`` (at most 5) at a time through one text-encoder call,
+        one denoising loop and one autoencoder pass whose bytes are made on the device."""
+        assert return_cross_attention is False, "Not supported yet"
+        assert all([0 <= li < self.params.depth for li in layer_indices]), "Invalid layer index"
+        assert height == width, "Height and width must be the same for now"
+        norm = resolve_norm(softmax, attention_norm)
+        prompts = list(prompts)
+        n = len(prompts)
+        concepts = _per_item(concepts, n, "generate_images: concepts")
+        seeds = list(range(n)) if seeds is None else list(seeds)
+        for name, v in (("seeds", seeds), ("latents", latents)):
+            if v is not None and len(v) != n:
+                raise ValueError(f"generate_images: {name} has {len(v)} entries for {n} prompts")
+        if timesteps is None:
+            timesteps = list(range(num_inference_steps))
+        shapes = [(16, height // 8, width // 8) if latents is None else tuple(latents[i].shape[1:]) for i in range(n)]
+        results = [None] * n
+        for idx in plan_batches([(shapes[i], len(concepts[i]), self._text_length()) for i in range(n)], batch):
+            emb = self.flux_generator.embed_many([prompts[i] for i in idx], [concepts[i] for i in idx])
+            txt, vec, con = (torch.cat([e[k] for e in emb], 0) if len(idx) > 1 else emb[0][k] for k in range(3))
+            x = torch.cat([latents[i].to(self.device, torch.bfloat16) if latents is not None else
+                           sampling.get_noise(1, height, width, self.device, torch.bfloat16, seeds[i]) for i in idx], 0)
+            img, ho, hc = self.generate_on_device(x, txt, vec, con, layer_indices=layer_indices,
+                                                  num_inference_steps=num_inference_steps, guidance=guidance,
+                                                  timesteps=timesteps, fused=True, norm=norm)
+            pictures = self.flux_generator.decode_many(img, height, width)
+            for k, i in enumerate(idx):
+                results[i] = self._finish(pictures[k], ho[k:k + 1], hc[k:k + 1], return_pil_heatmaps, cmap)
+        return results
 
     @torch.no_grad()
     @on_own_device

@@ -192,14 +192,32 @@ class ConceptAttentionSegmentationModel:
         maps = out.concept_heatmaps if target_space == "output" else out.cross_attention_maps
         return torch.as_tensor(np.asarray(maps), dtype=torch.float32), None
 
+    @torch.no_grad()
+    def segment_images(self, images, concepts, captions, layers=list(range(15, 19)), num_samples: int = 1,
+                       num_steps: int = 4, noise_timestep: int = 2, seed: int = 0, height: int = 1024,
+                       width: int = 1024, target_space: str = "output", joint_attention_kwargs=None, batch: int = 5,
+                       **_unused):
+        """``segment_individual_image`` for a list of images through ``pipeline.encode_images``: up to ``batch`` images
+        per forward, every image with the coefficients of its own call."""
+        outs = self.pipeline.encode_images(images, concepts, list(captions[:len(images)]), width=width, height=height,
+                                           layer_indices=layers, num_samples=num_samples, num_steps=num_steps,
+                                           noise_timestep=noise_timestep, seed=seed, batch=batch,
+                                           return_pil_heatmaps=False, joint_attention_kwargs=joint_attention_kwargs)
+        return [(torch.as_tensor(np.asarray(o.concept_heatmaps if target_space == "output" else o.cross_attention_maps),
+                                 dtype=torch.float32), None) for o in outs]
+
     def __call__(self, images, target_concepts, concepts, captions, mean_value_threshold: bool = True,
                  joint_attention_kwargs=None, apply_blur: bool = False, **kwargs):
         if not isinstance(images, (list, tuple)):
             images = [images]
         all_masks, all_coefficients, reconstructed = [], [], []
+        batched = None
+        if len(images) > 1 and hasattr(self.pipeline, "encode_images"):   # several images share every forward
+            batched = self.segment_images(images, concepts, captions, joint_attention_kwargs=joint_attention_kwargs,
+                                          **kwargs)
         for i, image in enumerate(images):
-            coeff, recon = self.segment_individual_image(image, concepts, captions[i],
-                                                         joint_attention_kwargs=joint_attention_kwargs, **kwargs)
+            coeff, recon = batched[i] if batched is not None else self.segment_individual_image(
+                image, concepts, captions[i], joint_attention_kwargs=joint_attention_kwargs, **kwargs)
             if apply_blur:
                 coeff = gaussian_blur3(coeff)
             if target_concepts is None:

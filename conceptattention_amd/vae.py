@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import math
 import os
+import warnings
 from typing import Optional
 
 import torch
@@ -347,10 +348,16 @@ class AutoEncoder:
         if H % m or W % m:
             raise ValueError(f"encode: H and W must be multiples of {m}")
         ws = self._workspace(B, H, W)
-        f = [0, 1, 2]
         xin = x.to(self.device, torch.float32).permute(0, 2, 3, 1).contiguous()
         xb = self._resident(ws, "x32", (B, H, W, 32), torch.bfloat16, self.device, zero=True)   # channels 3.. stay zero
         ops.affine_rows(xin.view(-1, p.in_channels), xb.view(-1, 32), cols=p.in_channels)
+        return self._moments_net(ws, xb)
+
+    def _moments_net(self, ws, xb):
+        """The encoder from its zero-padded bf16 input plane ``xb`` [B, H, W, 32] (the workspace's "x32") on."""
+        p = self.params
+        B, H, W, _ = xb.shape
+        f = [0, 1, 2]
         h = self._conv(xb, "encoder.conv_in", self._view(ws["f"][f[0]], B, H, W, p.ch))
         n = len(p.ch_mult)
         for lv in range(n):
@@ -369,8 +376,13 @@ class AutoEncoder:
     def encode(self, x: torch.Tensor, sample: bool = True, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         """scale * (mean + exp(0.5 logvar) * noise - shift) (autoencoder.py:262-305); ``sample=False``: the scaled mean.
         ``noise`` [B, z, H/8, W/8] is drawn with torch.randn on the device when not given."""
+        mom, dims = self._moments_nhwc(x)
+        return self._latent(mom, dims, sample, noise)
+
+    def _latent(self, mom, dims, sample, noise):
+        """DiagonalGaussian and the scale / shift on the NHWC moments; the caller's own NCHW tensor."""
         z = self.params.z_channels
-        mom, (B, h, w_) = self._moments_nhwc(x)
+        B, h, w_ = dims
         out = torch.empty(B, h, w_, z, device=self.device, dtype=torch.float32)
         m2 = mom.view(-1, 2 * z)
         a, b = self.scale_factor, -self.scale_factor * self.shift_factor
@@ -384,14 +396,66 @@ class AutoEncoder:
         return out.permute(0, 3, 1, 2).contiguous()
 
     @torch.no_grad()
+    def encode_pixels(self, images, height: int, width: int, sample: bool = True,
+                      noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``encode`` from image bytes: ``images`` is a list of uint8 [H0, W0, 3] tensors or arrays of any sizes.  Each is
+        uploaded as bytes and written by ``ops.pixels_to_nhwc32`` (nearest resize to height x width, 2 x / 255 - 1, bf16)
+        straight into its slot of the zero-padded input plane: no fp32 image, no layout copy, no cast launch.  The result
+        is bit for bit ``encode(x)`` of x = interpolate(2 * (img.float() / 255) - 1, (height, width)) with the same
+        ``noise``; the batch runs in the same passes of at most MAX_PIXELS pixels."""
+        if not self.loaded:
+            raise RuntimeError("AutoEncoder: no weights loaded")
+        m = 2 ** (len(self.params.ch_mult) - 1)
+        if height % m or width % m:
+            raise ValueError(f"encode_pixels: height and width must be multiples of {m}")
+        srcs = []
+        for im in images:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", UserWarning)      # a read-only array (a PIL image's buffer) is only read here
+                t = torch.as_tensor(im)
+            if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+                raise ValueError(f"encode_pixels: every image must be uint8 [H0, W0, 3], got {t.dtype} {tuple(t.shape)}")
+            srcs.append(t.contiguous().to(self.device))
+        if not srcs:
+            raise ValueError("encode_pixels: no images")
+        n = self._items_per_pass(height, width, "encode_pixels")
+        parts, dims = [], None
+        for i in range(0, len(srcs), n):
+            chunk = srcs[i:i + n]
+            ws = self._workspace(len(chunk), height, width)
+            xb = self._resident(ws, "x32", (len(chunk), height, width, 32), torch.bfloat16, self.device, zero=True)
+            for j, src in enumerate(chunk):
+                ops.pixels_to_nhwc32(src, xb[j])
+            mom, dims = self._moments_net(ws, xb)
+            parts.append(mom if len(srcs) <= n else mom.clone())      # (the NHWC buffer is reused by the next pass)
+        if len(parts) > 1:
+            mom = torch.cat(parts)
+            dims = tuple(mom.shape[:3])
+        return self._latent(mom, dims, sample, noise)
+
+    @torch.no_grad()
     def decode(self, z: torch.Tensor) -> torch.Tensor:
         m = self._check(z, self.params.z_channels, "decode")
         n = self._items_per_pass(z.shape[2] * m, z.shape[3] * m, "decode")
-        if z.shape[0] <= n:
-            return self._decode_pass(z, m)
-        return torch.cat([self._decode_pass(z[i:i + n], m) for i in range(0, z.shape[0], n)])
+        parts = [self._decode_pass(z[i:i + n], m).permute(0, 3, 1, 2).contiguous()   # the caller's own NCHW tensor:
+                 for i in range(0, z.shape[0], n)]                                    # the NHWC buffer is reused
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    @torch.no_grad()
+    def decode_pixels(self, z: torch.Tensor) -> torch.Tensor:
+        """uint8 [B, H, W, 3] on the device, made from the decoder's NHWC buffer by ``ops.nhwc_to_pixels``: bit for bit
+        ``(127.5 * (decode(z).clamp(-1, 1) + 1.0)).byte()`` in HWC order, with no fp32 image leaving the workspace."""
+        m = self._check(z, self.params.z_channels, "decode_pixels")
+        n = self._items_per_pass(z.shape[2] * m, z.shape[3] * m, "decode_pixels")
+        if self.params.out_ch != 3:
+            raise ValueError("decode_pixels: the byte image has 3 channels")
+        out = torch.empty(z.shape[0], z.shape[2] * m, z.shape[3] * m, 3, device=self.device, dtype=torch.uint8)
+        for i in range(0, z.shape[0], n):
+            ops.nhwc_to_pixels(self._decode_pass(z[i:i + n], m), out[i:i + n])
+        return out
 
     def _decode_pass(self, z, m):
+        """One pass of the decoder; returns the workspace's fp32 NHWC image buffer [B, H, W, out_ch]."""
         p = self.params
         B, _, h, w_ = z.shape
         ws = self._workspace(B, h * m, w_ * m)
@@ -411,7 +475,7 @@ class AutoEncoder:
         _, H, W, _ = t.shape
         img = self._resident(ws, "img", (B, H, W, p.out_ch), torch.float32, self.device)
         self._conv(t, "decoder.conv_out", img)
-        return img.permute(0, 3, 1, 2).contiguous()      # the caller's own NCHW tensor; the NHWC buffer is reused
+        return img
 
     # the reference's callers move the module around and switch modes; resident here
     def to(self, *a, **k):

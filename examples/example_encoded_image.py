@@ -1,7 +1,12 @@
 """Concept heat maps of an existing image -- the reference's example_encoded_image.py on the MI355X path.
 
 The image is given as a VAE latent (1, 16, H/8, W/8); with an autoencoder injected into the pipeline a PIL image
-works as in the reference.  One forward of the 19 double blocks per noise sample."""
+works as in the reference.  One forward of the 19 double blocks per noise sample.
+
+Several images at once: ``pipeline.encode_images(images, concepts, prompts, batch=5)`` takes a list of PIL images or
+latents (one concept list for all, or one per image) and returns one output per image, each with the maps of its own
+``encode_image`` call; up to five images share every launch, their bytes go straight into the autoencoder's input plane
+and a concept string is sent through T5 once, however many images name it."""
 import os
 import sys
 

@@ -4,7 +4,11 @@ Without Flux/T5/CLIP/VAE checkpoints (none can be fetched here) the pipeline run
 and synthetic text embeddings, so the pictures are noise; the call sequence, shapes and outputs are the real ones.
 Pass weights="/path/to/flux1-schnell.safetensors", autoencoder="/path/to/ae.safetensors" and
 text_encoder=HipTextEncoder(load_t5(weights="/path/to/t5"), tokenizer, 256, clip=...) to run the real model (CLIP and the
-tokenizer are not built here)."""
+tokenizer are not built here).
+
+Several prompts at once: ``pipeline.generate_images(prompts, concepts, seeds=[...], batch=5)`` returns one output per
+prompt, each with the image and maps of its own ``generate_image`` call; up to five prompts share every launch, and with
+an autoencoder the image bytes are made on the device."""
 import os
 import sys
 

@@ -28,13 +28,13 @@
 extern "C" {
 #endif
 
-#define CA_VERSION 129 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
+#define CA_VERSION 130 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
                           CA_ATTN_Q_PRESCALED; .1: ca_axpy_f32, ca_split_bf16; .2: ca_attn_stats; .3: ca_gemm_problem.qk_f16,
                           ca_attn_fwd_qk16; .4: ca_qpre_finish_rope_f32; .5: ca_heatmap_fused; .6: ca_gemm_plan;
                           .7: the autoencoder kernels (conv3x3_nhwc, groupnorm_nhwc, softmax_rows_f32, affine_rows_f32);
                           128: the T5 encoder kernels (t5_attn_bf16, t5_rmsnorm_f32in, gated_mul_bf16, embed_rows_f32);
                           129: the CLIP text encoder kernels (clip_attn_bf16, layernorm_f32in, quick_gelu_bf16,
-                          clip_embed_f32) */
+                          clip_embed_f32); 130: the pixel I/O kernels (pixels_u8_to_nhwc32_bf16, nhwc_f32_to_pixels_u8) */
 
 #define CA_OK 0
 #define CA_ERR_ARG (-1)    /* bad shape / null pointer / misalignment */
@@ -510,6 +510,23 @@ int ca_quick_gelu_bf16(const void *x, int32_t ldx, void *out, int32_t ldo, int64
  * The library cannot see the ids: the caller guarantees 0 <= ids[r] < vocab (the Python wrapper checks). */
 int ca_clip_embed_f32(const void *tok, int32_t ldt, const void *pos, int32_t ldp, const int32_t *ids, float *out,
                       int32_t ldo, int64_t rows, int32_t L, int32_t H, ca_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Pixel I/O of the autoencoder: image bytes in, image bytes out, with no fp32 image tensor in between.
+ *
+ * One image into one slot of the zero-padded input plane of encoder.conv_in, resized with the index rule of
+ * torch.nn.functional.interpolate(mode="nearest"):
+ *   dst[y, x, c] = bf16_rne(2.0f * (float(src[sy, sx, c]) / 255.0f) - 1.0f) for c < 3, dst[y, x, 3..31] = 0,
+ *   sy = min((int)floorf(y * ((float)H0 / H)), H0 - 1), sx likewise; the division by 255 correctly rounded.
+ * src: uint8 [H0, W0, 3], rows src_stride BYTES apart (>= 3 W0; unused when H0 = 1); dst: bf16 [H, W, 32], 16-byte aligned.  Bit-identical
+ * to float() / 255, 2 x - 1, interpolate and the bf16 cast of ca_affine_rows_f32.  One launch per image. */
+int ca_pixels_u8_to_nhwc32_bf16(const void *src, int64_t src_stride, void *dst, int32_t H0, int32_t W0, int32_t H,
+                                int32_t W, ca_stream_t stream);
+
+/* The decoder's NHWC output to bytes: dst[p, c] = (uint8)truncf(127.5f * (min(max(src[p, c], -1), 1) + 1.0f)) for c < 3,
+ * the sum and the product rounded separately: (127.5 * (img.clamp(-1, 1) + 1.0)).byte().  A NaN gives 0.  src: fp32
+ * [pixels, ld >= 3]; dst: uint8 [pixels, 3], 16-byte aligned; pixels counts every pixel of the batch. */
+int ca_nhwc_f32_to_pixels_u8(const float *src, int32_t ld, void *dst, int64_t pixels, ca_stream_t stream);
 
 #ifdef __cplusplus
 }
