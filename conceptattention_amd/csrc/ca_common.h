@@ -83,6 +83,21 @@ __device__ __forceinline__ uint32_t ca_pack2_f16(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, v);
 }
 
+// 8 floats (already divided by the row scale) -> 8 OCP e4m3 bytes (v_cvt_pk_fp8_f32, RNE; inputs clamped to
+// the largest finite e4m3 value so nothing overflows to NaN)
+constexpr float E4M3_MAX = 448.0f;
+__device__ __forceinline__ uint2 ca_pack_fp8x8(const float *y) {
+  float c[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) c[j] = fminf(fmaxf(y[j], -E4M3_MAX), E4M3_MAX);
+  int lo = 0, hi = 0;
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(c[0], c[1], lo, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(c[2], c[3], lo, true);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(c[4], c[5], hi, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(c[6], c[7], hi, true);
+  return make_uint2((uint32_t)lo, (uint32_t)hi);
+}
+
 __device__ __forceinline__ float ca_gelu_tanh(float x) {
   // nn.GELU(approximate="tanh"): 0.5 x (1 + tanh(u)), u = sqrt(2/pi) (x + 0.044715 x^3).  With
   // 0.5 (1 + tanh(u)) = sigmoid(2u) this is x / (1 + exp(-2u)); exp(-2u) = exp2(x (k0 + k1 x^2)),

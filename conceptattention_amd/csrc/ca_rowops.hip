@@ -53,20 +53,7 @@ __device__ __forceinline__ uint4 pack8_bf16_residual(const float *y) {
   return pack8_bf16(r);
 }
 
-// 8 floats (already divided by the row scale) -> 8 OCP e4m3 bytes (v_cvt_pk_fp8_f32, RNE; inputs clamped to
-// the largest finite e4m3 value so nothing overflows to NaN)
-constexpr float E4M3_MAX = 448.0f;
-__device__ __forceinline__ uint2 ca_pack_fp8x8(const float *y) {
-  float c[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) c[j] = fminf(fmaxf(y[j], -E4M3_MAX), E4M3_MAX);
-  int lo = 0, hi = 0;
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(c[0], c[1], lo, false);
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(c[2], c[3], lo, true);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(c[4], c[5], hi, false);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(c[6], c[7], hi, true);
-  return make_uint2((uint32_t)lo, (uint32_t)hi);
-}
+// (E4M3_MAX and ca_pack_fp8x8, the e4m3 store of the FP8 forms below, live in ca_common.h: ca_t5.hip packs with them too)
 
 // ------------------------------------------------------------------------------------------
 // out = (1 + scale) * LayerNorm(x) + shift ; one wave per row, row kept in registers.

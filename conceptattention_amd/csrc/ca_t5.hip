@@ -1,6 +1,7 @@
 // Kernels of the T5 encoder (transformers' T5Stack, encoder side): self-attention with the relative-position bias on
-// v_mfma_f32_16x16x32_bf16, the RMS layer norm of the fp32 residual stream, the gated-GELU product and the embedding
-// gather.  The projections run on the grouped GEMM of ca_gemm.hip.  Every element offset is formed in 64 bits.
+// v_mfma_f32_16x16x32_bf16, the RMS layer norm of the fp32 residual stream, the gated-GELU product (each also as a
+// producer of e4m3 rows with one scale per row, for the fp8 mode) and the embedding gather.  The projections run on
+// the grouped GEMM of ca_gemm.hip.  Every element offset is formed in 64 bits.
 #include "ca_common.h"
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -244,6 +245,87 @@ extern "C" int ca_t5_rmsnorm_f32in(const float *x, int32_t ldx, const float *w, 
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// The e4m3 producers of the fp8 mode: a row leaves as e4m3 bytes plus one fp32 scale (amax / 448, or 1 for a zero row;
+// the rule of ca_quantize_rows_fp8_kernel), the A operand of ca_gemm_fp8.  A workgroup owns a whole row, so the row
+// maximum is known before the store and the row never exists in bf16.
+__device__ __forceinline__ float t5_block_max(float v, float *red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+// y[0..8) = x[i..i+8) * rs * w[i..i+8): products only, so the pass that takes the maximum and the pass that stores
+// form the same bits
+__device__ __forceinline__ void t5_norm8(const float *xr, const float *w, int i, float rs, float *y) {
+  const f32x4 a0 = *(const f32x4 *)(xr + i), a1 = *(const f32x4 *)(xr + i + 4);
+  const f32x4 g0 = *(const f32x4 *)(w + i), g1 = *(const f32x4 *)(w + i + 4);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    y[j] = a0[j] * rs * g0[j];
+    y[4 + j] = a1[j] * rs * g1[j];
+  }
+}
+
+// T5LayerNorm into e4m3: three passes over the row (sum of squares, maximum, store; the last two hit the cache).
+__global__ __launch_bounds__(256) void ca_t5_rmsnorm_fp8_kernel(const float *x, long ldx, const float *w, uint8_t *out,
+                                                                 long ldo, float *out_scale, long rows, int H,
+                                                                 float eps) {
+  __shared__ float red[4];
+  for (long r = blockIdx.x; r < rows; r += gridDim.x) {
+    const float *xr = x + r * ldx;
+    uint8_t *orow = out + r * ldo;
+    float ss = 0.f;
+    for (int i = threadIdx.x * 8; i < H; i += 2048) {
+      const f32x4 a = *(const f32x4 *)(xr + i), b = *(const f32x4 *)(xr + i + 4);
+      ss += ((a[0] * a[0] + a[1] * a[1]) + (a[2] * a[2] + a[3] * a[3])) +
+            ((b[0] * b[0] + b[1] * b[1]) + (b[2] * b[2] + b[3] * b[3]));
+    }
+    ss = t5_block_sum(ss, red);
+    const float rs = 1.0f / sqrtf(ss / (float)H + eps);
+    float amax = 0.f;
+    for (int i = threadIdx.x * 8; i < H; i += 2048) {
+      float y[8];
+      t5_norm8(xr, w, i, rs, y);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(y[j]));
+    }
+    amax = t5_block_max(amax, red);
+    const float sc = amax > 0.f ? amax * (1.0f / E4M3_MAX) : 1.0f;
+    const float inv = 1.0f / sc;
+    if (threadIdx.x == 0) out_scale[r] = sc;
+    for (int i = threadIdx.x * 8; i < H; i += 2048) {
+      float y[8];
+      t5_norm8(xr, w, i, rs, y);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) y[j] *= inv;
+      *(uint2 *)(orow + i) = ca_pack_fp8x8(y);
+    }
+  }
+}
+
+extern "C" int ca_t5_rmsnorm_f32in_fp8(const float *x, int32_t ldx, const float *w, void *out8, int32_t ldo,
+                                       float *out_scale, int64_t rows, int32_t H, float eps, ca_stream_t stream) {
+  const char *FN = "ca_t5_rmsnorm_f32in_fp8";
+  if (!x || !w || !out8 || !out_scale || rows < 1 || H < 8 || H % 8 || ldx < H || ldo < H || ldx % 4 || ldo % 8 ||
+      !(eps > 0.f)) {
+    ca_set_error("%s: bad arguments (rows=%lld H=%d [%% 8] ldx=%d [>= H, %% 4] ldo=%d [>= H, %% 8] eps=%g [> 0])", FN,
+                 (long long)rows, H, ldx, ldo, (double)eps);
+    return CA_ERR_ARG;
+  }
+  if ((((uintptr_t)x | (uintptr_t)w) & 15) || ((uintptr_t)out8 & 7) || ((uintptr_t)out_scale & 3)) {
+    ca_set_error("%s: x and w must be 16-byte aligned, out8 8-byte, out_scale 4-byte", FN);
+    return CA_ERR_ARG;
+  }
+  const long blocks = rows < 65536 ? rows : 65536;
+  hipLaunchKernelGGL(ca_t5_rmsnorm_fp8_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, w,
+                     (uint8_t *)out8, (long)ldo, out_scale, (long)rows, H, eps);
+  return ca_check_launch(FN);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // out = bf16(float(g) * float(u)): the gelu(wi_0 x) * (wi_1 x) product of T5DenseGatedActDense, 8 elements per thread.
 __global__ __launch_bounds__(256) void ca_gated_mul_kernel(const bf16 *g, long ldg, const bf16 *u, long ldu, bf16 *out,
                                                             long ldo, long rows, int C) {
@@ -275,6 +357,54 @@ extern "C" int ca_gated_mul_bf16(const void *g, int32_t ldg, const void *u, int3
   if (blocks > 65536) blocks = 65536;
   hipLaunchKernelGGL(ca_gated_mul_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16 *)g,
                      (long)ldg, (const bf16 *)u, (long)ldu, (bf16 *)out, (long)ldo, (long)rows, C);
+  return ca_check_launch(FN);
+}
+
+// The gate product into e4m3: y = float(g) * float(u) is exact in fp32, so the two passes over a row (maximum, store;
+// the second hits the cache) see the same values.  A workgroup per row, rows walked with the grid's stride.
+__global__ __launch_bounds__(256) void ca_gated_mul_fp8_kernel(const bf16 *g, long ldg, const bf16 *u, long ldu,
+                                                                uint8_t *out, long ldo, float *out_scale, long rows,
+                                                                int C) {
+  __shared__ float red[4];
+  for (long r = blockIdx.x; r < rows; r += gridDim.x) {
+    const bf16 *gr = g + r * ldg, *ur = u + r * ldu;
+    uint8_t *orow = out + r * ldo;
+    float amax = 0.f;
+    for (int i = threadIdx.x * 8; i < C; i += 2048) {
+      const bf16x8 a = *(const bf16x8 *)(gr + i), b = *(const bf16x8 *)(ur + i);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf((float)a[j] * (float)b[j]));
+    }
+    amax = t5_block_max(amax, red);
+    const float sc = amax > 0.f ? amax * (1.0f / E4M3_MAX) : 1.0f;
+    const float inv = 1.0f / sc;
+    if (threadIdx.x == 0) out_scale[r] = sc;
+    for (int i = threadIdx.x * 8; i < C; i += 2048) {
+      const bf16x8 a = *(const bf16x8 *)(gr + i), b = *(const bf16x8 *)(ur + i);
+      float y[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) y[j] = (float)a[j] * (float)b[j] * inv;
+      *(uint2 *)(orow + i) = ca_pack_fp8x8(y);
+    }
+  }
+}
+
+extern "C" int ca_gated_mul_fp8(const void *g, int32_t ldg, const void *u, int32_t ldu, void *out8, int32_t ldo,
+                                float *out_scale, int64_t rows, int32_t C, ca_stream_t stream) {
+  const char *FN = "ca_gated_mul_fp8";
+  if (!g || !u || !out8 || !out_scale || rows < 1 || C < 8 || C % 8 || ldg < C || ldu < C || ldo < C || ldg % 8 ||
+      ldu % 8 || ldo % 8) {
+    ca_set_error("%s: bad arguments (rows=%lld C=%d [%% 8] ldg=%d ldu=%d ldo=%d [>= C, %% 8])", FN, (long long)rows, C,
+                 ldg, ldu, ldo);
+    return CA_ERR_ARG;
+  }
+  if ((((uintptr_t)g | (uintptr_t)u) & 15) || ((uintptr_t)out8 & 7) || ((uintptr_t)out_scale & 3)) {
+    ca_set_error("%s: g and u must be 16-byte aligned, out8 8-byte, out_scale 4-byte", FN);
+    return CA_ERR_ARG;
+  }
+  const long blocks = rows < 65536 ? rows : 65536;
+  hipLaunchKernelGGL(ca_gated_mul_fp8_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16 *)g,
+                     (long)ldg, (const bf16 *)u, (long)ldu, (uint8_t *)out8, (long)ldo, out_scale, (long)rows, C);
   return ca_check_launch(FN);
 }
 

@@ -89,8 +89,15 @@ class ConceptCache:
 class FluxGenerator:
     def __init__(self, model_name: str, device, offload: bool = False, attention_block_class=None,
                  dit_class=HipFluxDiT, weights="synthetic", weight_seed: int = 0, text_encoder=None,
-                 autoencoder=None, params=None, n_text_tokens=None, residual_dtype=torch.float32):
+                 autoencoder=None, params=None, n_text_tokens=None, residual_dtype=torch.float32,
+                 t5_precision: str = "bf16"):
+        """``t5_precision``: the precision of the T5 encoder built for ``text_encoder="synthetic-t5"`` /
+        ``"synthetic-t5-clip"`` ("bf16", or "fp8": t5.T5Encoder's opt-in e4m3 projections); an encoder object passed in
+        carries its own precision and must be left at the default here."""
         from .pipeline import SyntheticTextEncoder
+        if t5_precision != "bf16" and not isinstance(text_encoder, str):
+            raise ValueError("t5_precision applies to the T5 encoder built from a text_encoder name; an encoder object "
+                             "(or the seeded-noise stand-in) has none to set")
         self.device = torch.device(device)
         self.offload = offload
         self.model_name = model_name
@@ -110,7 +117,8 @@ class FluxGenerator:
                 from .clip import synthetic_clip_embedder
                 clip = synthetic_clip_embedder(self.params.vec_in_dim, self.device, weight_seed)
             text_encoder = synthetic_text_encoder(self.params.context_in_dim, n_tok, self.device,
-                                                  self.params.vec_in_dim, weight_seed, clip=clip)
+                                                  self.params.vec_in_dim, weight_seed, clip=clip,
+                                                  t5_precision=t5_precision)
         enc = text_encoder or SyntheticTextEncoder(n_tok, self.params.context_in_dim, self.params.vec_in_dim,
                                                    self.device)
         self.text_encoder = enc

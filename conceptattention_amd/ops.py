@@ -752,6 +752,39 @@ def gated_mul(g, u, out) -> None:
                                        g.shape[0], g.shape[1], _stream()), "ca_gated_mul_bf16")
 
 
+def _chk_fp8_out(what: str, out, out_scale, shape) -> None:
+    """The e4m3 plane and the scale vector of an fp8 producer: uint8 of ``shape``, contiguous fp32 [rows]."""
+    _chk(out, torch.uint8, "out"), _chk(out_scale, torch.float32, "out_scale")
+    if tuple(out.shape) != tuple(shape) or out_scale.dim() != 1 or out_scale.numel() != shape[0] or \
+            not out_scale.is_contiguous():
+        raise ValueError(f"{what}: out must be uint8 {tuple(shape)}, out_scale contiguous fp32 [{shape[0]}]")
+
+
+def t5_rmsnorm_fp8(x, weight, out, out_scale, eps: float = 1e-6) -> None:
+    """t5_rmsnorm written as an fp8 GEMM operand: with y = x * rsqrt(mean(x^2) + eps) * weight in fp32 (never rounded to
+    bf16), out_scale[r] = max|y[r]| / 448 (1 for a zero row) and out[r] = e4m3(y[r] / out_scale[r]).  x fp32 [rows, H],
+    weight fp32 [H], out uint8 [rows, H] (row stride free), out_scale fp32 [rows] contiguous."""
+    _chk(x, torch.float32, "x"), _chk(weight, torch.float32, "weight")
+    if x.dim() != 2 or weight.numel() != x.shape[1] or not weight.is_contiguous():
+        raise ValueError("t5_rmsnorm_fp8: x must be 2-D, weight contiguous [H]")
+    _chk_fp8_out("t5_rmsnorm_fp8", out, out_scale, x.shape)
+    L.check(L.load().ca_t5_rmsnorm_f32in_fp8(x.data_ptr(), x.stride(0), weight.data_ptr(), out.data_ptr(), out.stride(0),
+                                             out_scale.data_ptr(), x.shape[0], x.shape[1], eps, _stream()),
+            "ca_t5_rmsnorm_f32in_fp8")
+
+
+def gated_mul_fp8(g, u, out, out_scale) -> None:
+    """gated_mul written as an fp8 GEMM operand: y = float(g) * float(u) (exact), out_scale[r] = max|y[r]| / 448 (1 for
+    a zero row), out[r] = e4m3(y[r] / out_scale[r]).  g, u bf16 [rows, C] row views, out uint8 [rows, C] (row stride
+    free), out_scale fp32 [rows] contiguous."""
+    _chk(g, torch.bfloat16, "g"), _chk(u, torch.bfloat16, "u")
+    if g.dim() != 2 or u.shape != g.shape:
+        raise ValueError("gated_mul_fp8: g and u must be 2-D of one shape")
+    _chk_fp8_out("gated_mul_fp8", out, out_scale, g.shape)
+    L.check(L.load().ca_gated_mul_fp8(g.data_ptr(), g.stride(0), u.data_ptr(), u.stride(0), out.data_ptr(), out.stride(0),
+                                      out_scale.data_ptr(), g.shape[0], g.shape[1], _stream()), "ca_gated_mul_fp8")
+
+
 def embed_rows(table, ids, out) -> None:
     """out[r, :] = float(table[ids[r], :]): table bf16 [vocab, H], ids int32 [rows] (host or device), out fp32 [rows, H].
     An id outside [0, vocab) is a ValueError here, before anything is launched (the kernel cannot check it)."""

@@ -99,13 +99,15 @@ class ConceptAttentionFluxPipeline:
     def __init__(self, model_name: str = "flux-schnell", offload_model: bool = False, device="cuda:0",
                  weights="synthetic", weight_seed: int = 0, text_encoder=None, autoencoder=None,
                  params=None, n_text_tokens: Optional[int] = None, precision: str = "bf16",
-                 residual_dtype=torch.float32, capture_independent_image: bool = False):
+                 residual_dtype=torch.float32, capture_independent_image: bool = False, t5_precision: str = "bf16"):
         """model_name / offload_model / device as in the reference (:100-113).  ``weights`` is
         "synthetic" (seeded random init), a path to a flux1-*.safetensors file, or a state dict.
         ``precision="fp8"`` runs the large projections on e4m3 operands (HipFluxDiT.set_precision);
         ``residual_dtype`` is the storage type of the residual streams (fp32 by default, HipFluxDiT.__init__);
         ``text_encoder``: None (seeded-noise stand-in), "synthetic-t5", "synthetic-t5-clip", or an object with ``t5`` / ``clip`` (a
         ``t5.HipTextEncoder``; one with ``t5_many`` encodes prompt and concepts in one forward).
+        ``t5_precision``: "bf16" (default) or "fp8", the precision of the T5 encoder a ``text_encoder`` NAME builds
+        (t5.T5Encoder: e4m3 projections, opt-in; independent of ``precision``, which is the DiT's).
         ``capture_independent_image=True`` makes the returned latent (and every map) independent of ``layer_indices``
         bit for bit, as in the reference, for the image rows' attention twice in the captured layers
         (HipFluxDiT.capture_independent_image; INTEGRATION.md)."""
@@ -121,7 +123,8 @@ class ConceptAttentionFluxPipeline:
         self.flux_generator = FluxGenerator(model_name=model_name, offload=offload_model, device=self.device,
                                             weights=weights, weight_seed=weight_seed, text_encoder=text_encoder,
                                             autoencoder=autoencoder, params=self.params,
-                                            n_text_tokens=n_text_tokens, residual_dtype=residual_dtype)
+                                            n_text_tokens=n_text_tokens, residual_dtype=residual_dtype,
+                                            t5_precision=t5_precision)
         self.model = self.flux_generator.model
         self.model.set_precision(precision)
         self.model.capture_independent_image = bool(capture_independent_image)

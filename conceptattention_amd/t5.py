@@ -23,6 +23,17 @@ Batching.  All sequences of a call go through every launch together (rows = n_se
 tiles, so a sequence's bits do not depend on what else is in the batch; for another L (a multiple of 64) a sequence
 would share a row tile with its neighbour or fall to the thin-row kernel depending on the batch, so those lengths run
 one sequence per pass.
+
+fp8 mode (``precision="fp8"``, opt-in; bf16 is the default and its bits are what they were).  The projections named in
+``fp8_projections`` (of ``qkv``, ``o``, ``wi``, ``wo``) run on ``ca_gemm_fp8``: e4m3 operands with one fp32 scale per
+row on both sides (activation row, weight output row), fp32 accumulation, the same epilogues.  The A operands are
+written as e4m3 by their producers: the RMS norm in front of ``qkv`` and ``wi`` (``ca_t5_rmsnorm_f32in_fp8``) and the
+gate product in front of ``wo`` (``ca_gated_mul_fp8``) own a whole row per workgroup, so the row never exists in bf16;
+the attention output has 64 writers per row and goes through ``ca_quantize_rows_fp8``.  Weights: a checkpoint tensor
+that arrives as ``torch.float8_e4m3fn`` is used byte for byte with unit scales; any other is rounded to bf16 as in the
+bf16 mode and then quantised per output row (scale = row amax / 448).  Everything else -- the fp32 stream, attention,
+the embedding, the norm weights, the bias table, the final norm and the bf16 output -- is unchanged.  A row's scale
+depends on that row alone and the tile is the same one, so the batching guarantee above holds in fp8 as well.
 """
 from __future__ import annotations
 
@@ -38,9 +49,12 @@ from .params import T5Params, t5_params, tiny_t5_params
 from .weights import _gen
 
 __all__ = ["T5Encoder", "T5Params", "HipTextEncoder", "ToyByteTokenizer", "load_t5", "synthetic_t5_state_dict",
-           "t5_state_dict_spec", "relative_position_bucket", "relative_bias_table"]
+           "t5_state_dict_spec", "relative_position_bucket", "relative_bias_table", "FP8_PROJECTIONS"]
 
 TIED_EMBEDDING = "encoder.embed_tokens.weight"   # transformers lists the tied input embedding under both names
+PRECISIONS = ("bf16", "fp8")
+FP8_PROJECTIONS = ("qkv", "o", "wi", "wo")       # the four GEMMs of a block, as packed
+SCALE_KEY_SUFFIXES = (".scale_weight", ".weight_scale")   # per-tensor scales of scaled-fp8 checkpoints: not supported
 
 
 # ---------------------------------------------------------------------------------------------------------- layout
@@ -123,12 +137,28 @@ def relative_bias_table(weight: torch.Tensor, length: int, num_buckets: int = 32
 # ---------------------------------------------------------------------------------------------------------- the model
 class T5Encoder:
     """``encode_ids(ids[n_seq, L]) -> [n_seq, L, d_model]`` bf16: the ``last_hidden_state`` of T5EncoderModel with
-    ``attention_mask=None``.  L a multiple of 64 up to 512."""
+    ``attention_mask=None``.  L a multiple of 64 up to 512.
+
+    ``precision``: "bf16" (default) or "fp8" (the module docstring's fp8 mode).  ``fp8_projections``: which of the four
+    projections of a block run in e4m3 in fp8 mode; the others keep the bf16 route and its bf16 producer.  The list
+    exists because real T5-XXL is known for large activation outliers in front of ``wo``: a user with real weights can
+    keep that projection in bf16 (``("qkv", "o", "wi")``) without giving up the rest.  The accuracy of the fp8 mode has
+    been measured on this repository's synthetic weights only; real-weight accuracy is UNMEASURED."""
 
     MAX_ROWS = 8192   # token rows of one pass: 16 sequences of 512; bounds the workspace and every GEMM operand (< 4 GiB)
 
-    def __init__(self, params: T5Params, device="cuda"):
+    def __init__(self, params: T5Params, device="cuda", precision: str = "bf16",
+                 fp8_projections: Sequence[str] = FP8_PROJECTIONS):
         p = params
+        if precision not in PRECISIONS:
+            raise ValueError(f"T5Encoder: precision must be one of {PRECISIONS}, got {precision!r}")
+        if isinstance(fp8_projections, str):
+            fp8_projections = (fp8_projections,)
+        names = tuple(fp8_projections)
+        if not names or any(n not in FP8_PROJECTIONS for n in names):
+            raise ValueError(f"T5Encoder: fp8_projections must be a non-empty selection of {FP8_PROJECTIONS}, got {names!r}")
+        self.precision = precision
+        self.fp8 = frozenset(names) if precision == "fp8" else frozenset()   # the projections that run in e4m3
         if p.d_kv != 64:
             raise ValueError("T5Encoder: d_kv must be 64 (ca_t5_attn_bf16)")
         if p.d_model % 256 or (3 * p.inner_dim) % 256 or p.d_ff % 256:
@@ -140,6 +170,7 @@ class T5Encoder:
         self.device = torch.device(device)
         self.spec = dict(t5_state_dict_spec(p))
         self.tensors: dict = {}      # name -> fp32 host copy as loaded
+        self.e4m3: set = set()       # names that arrived as torch.float8_e4m3fn (their fp32 copy holds e4m3 values exactly)
         self.w: dict = {}            # packed device operands
         self._ws: Optional[dict] = None
         self._bias: dict = {}        # L -> device table
@@ -149,8 +180,19 @@ class T5Encoder:
     def load_state_dict(self, sd, strict: bool = True, assign: bool = False):
         """Same (missing, unexpected) semantics as nn.Module.load_state_dict; a shape mismatch always raises.
         ``encoder.embed_tokens.weight`` is the tied twin of ``shared.weight``: either name (or both) fills it.  The
-        operands are packed here, once; ``assign`` is accepted and changes nothing (the tensors are always copied)."""
+        operands are packed here, once; ``assign`` is accepted and changes nothing (the tensors are always copied).
+
+        A ``torch.float8_e4m3fn`` tensor is widened exactly (every e4m3 value is a bf16 value) and remembered by name:
+        the fp8 mode packs its bytes unchanged with unit scales.  In fp8 mode a per-tensor scale key
+        (``*.scale_weight`` / ``*.weight_scale``) next to e4m3 weights is a RuntimeError: such files store
+        weight / scale and are not supported; in bf16 mode such a key is an unexpected key like any other."""
         sd = dict(sd)
+        if self.precision == "fp8":
+            is_e4m3 = any(k in self.spec and getattr(v, "dtype", None) == torch.float8_e4m3fn for k, v in sd.items())
+            scaled = [k for k in sd if k.endswith(SCALE_KEY_SUFFIXES)]
+            if is_e4m3 and scaled:
+                raise RuntimeError(f"load_state_dict: {scaled[0]} is a per-tensor scale next to e4m3 weights; per-tensor-"
+                                   "scaled fp8 checkpoints are not supported (the e4m3 bytes are used with unit scales)")
         if TIED_EMBEDDING in sd:
             twin = sd.pop(TIED_EMBEDDING)
             sd.setdefault("shared.weight", twin)
@@ -163,6 +205,10 @@ class T5Encoder:
                 if tuple(sd[k].shape) != tuple(shape):
                     raise RuntimeError(f"load_state_dict: {k} has shape {tuple(sd[k].shape)}, expected {tuple(shape)}")
                 self.tensors[k] = sd[k].detach().to("cpu", torch.float32)
+                if sd[k].dtype == torch.float8_e4m3fn:
+                    self.e4m3.add(k)
+                else:
+                    self.e4m3.discard(k)
         if not missing:
             self._pack()
         return missing, unexpected
@@ -175,19 +221,41 @@ class T5Encoder:
 
         def bf(x):
             return x.to(dev, torch.bfloat16).contiguous()
+
+        def e4m3(name):
+            """(e4m3 bytes [N, K], fp32 scale [N]) of one checkpoint tensor: its own bytes with unit scales if it
+            arrived as e4m3, else the bf16 rounding of the bf16 mode quantised per output row."""
+            if name in self.e4m3:
+                return (t[name].to(torch.float8_e4m3fn).view(torch.uint8).to(dev).contiguous(),
+                        torch.ones(t[name].shape[0], device=dev, dtype=torch.float32))
+            return ops.quantize_rows_fp8(bf(t[name]))
+
+        def put(key, names):
+            """The packed operand of projection ``key`` from the row concatenation of the tensors ``names``."""
+            if key.split(".")[1] not in self.fp8:
+                w[key] = bf(torch.cat([t[n] for n in names]))
+                return
+            parts = [e4m3(n) for n in names]     # per-row scales: piecewise == the quantised concatenation
+            w[key] = torch.cat([q for q, _ in parts]).contiguous()
+            w[key + ".scale"] = torch.cat([s for _, s in parts]).contiguous()
         w = {"shared": bf(t["shared.weight"]), "ones": torch.ones(p.d_model, device=dev, dtype=torch.float32),
              "final_ln": t["encoder.final_layer_norm.weight"].to(dev)}
         for i in range(p.num_layers):
             a, f = f"encoder.block.{i}.layer.0", f"encoder.block.{i}.layer.1.DenseReluDense"
-            w[f"{i}.qkv"] = bf(torch.cat([t[f"{a}.SelfAttention.{n}.weight"] for n in ("q", "k", "v")]))
-            w[f"{i}.o"] = bf(t[f"{a}.SelfAttention.o.weight"])
+            put(f"{i}.qkv", [f"{a}.SelfAttention.{n}.weight" for n in ("q", "k", "v")])
+            put(f"{i}.o", [f"{a}.SelfAttention.o.weight"])
             w[f"{i}.ln0"] = t[f"{a}.layer_norm.weight"].to(dev)
-            w[f"{i}.wi"] = bf(torch.cat([t[f"{f}.wi_1.weight"], t[f"{f}.wi_0.weight"]]))   # [plain ; GELU]
-            w[f"{i}.wo"] = bf(t[f"{f}.wo.weight"])
+            put(f"{i}.wi", [f"{f}.wi_1.weight", f"{f}.wi_0.weight"])   # [plain ; GELU]
+            put(f"{i}.wo", [f"{f}.wo.weight"])
             w[f"{i}.ln1"] = t[f"encoder.block.{i}.layer.1.layer_norm.weight"].to(dev)
         self.w = w
         self._bias = {}
         self.loaded = True
+
+    def weight_bytes(self, embedding: bool = True) -> int:
+        """Device bytes of the packed operands (e4m3 planes and their scale vectors included); ``embedding=False``
+        leaves the token table out, which no precision mode changes."""
+        return sum(v.numel() * v.element_size() for k, v in self.w.items() if embedding or k != "shared")
 
     def bias_table(self, length: int) -> torch.Tensor:
         """Host table fp32 [heads, 2 length - 1] of the loaded relative_attention_bias."""
@@ -209,11 +277,18 @@ class T5Encoder:
         p, dev = self.params, self.device
         ws = {"rows": rows,
               "x": torch.empty(rows, p.d_model, device=dev, dtype=torch.float32),
-              "hn": torch.empty(rows, p.d_model, device=dev, dtype=torch.bfloat16),
               "qkv": torch.empty(rows, 3 * p.inner_dim, device=dev, dtype=torch.bfloat16),
               "ao": torch.empty(rows, p.inner_dim, device=dev, dtype=torch.bfloat16),
               "u": torch.empty(rows, p.d_ff, device=dev, dtype=torch.bfloat16),
               "g": torch.empty(rows, p.d_ff, device=dev, dtype=torch.bfloat16)}
+        if not {"qkv", "wi"} <= self.fp8:     # a bf16 norm output is read only by a bf16 qkv or wi projection
+            ws["hn"] = torch.empty(rows, p.d_model, device=dev, dtype=torch.bfloat16)
+        # fp8 mode: the e4m3 plane and the row scales in front of each quantised projection (hn8: qkv and wi)
+        for key, cols, used in (("hn8", p.d_model, self.fp8 & {"qkv", "wi"}), ("ao8", p.inner_dim, self.fp8 & {"o"}),
+                                ("p8", p.d_ff, self.fp8 & {"wo"})):
+            if used:
+                ws[key] = torch.empty(rows, cols, device=dev, dtype=torch.uint8)
+                ws[key + ".scale"] = torch.empty(rows, device=dev, dtype=torch.float32)
         self._ws = ws
         return ws
 
@@ -248,20 +323,50 @@ class T5Encoder:
         p, w = self.params, self.w
         rows, inner = n_seq * length, p.inner_dim
         ws = self._workspace(rows)
-        x, hn, qkv, ao, u, g = (ws[k][:rows] for k in ("x", "hn", "qkv", "ao", "u", "g"))
+        x, qkv, ao, u, g = (ws[k][:rows] for k in ("x", "qkv", "ao", "u", "g"))
         bias = self._device_bias(length)
         tile = L.TILE_PP_256x256   # one tile for every row count: a row's bits must not depend on the batch
+        eps = p.layer_norm_epsilon
+
+        def planes(key):           # the e4m3 plane and the row scales of an fp8 producer
+            return ws[key][:rows], ws[key + ".scale"][:rows]
+
+        def project(name, i, a, out_, **epi):
+            """out_ = epi(a @ w[name]^T): ``a`` is the bf16 operand, or (e4m3 plane, row scales) where ``name`` is fp8."""
+            key = f"{i}.{name}"
+            if name in self.fp8:
+                ops.gemm([ops.Gemm(a[0], w[key], None, out_, a_scale=a[1], w_scale=w[key + ".scale"], **epi)], tile)
+            else:
+                ops.gemm([ops.Gemm(a, w[key], None, out_, **epi)], tile)
+
+        def normed(name, weight):  # the RMS norm of the stream as the A operand of projection ``name``
+            if name in self.fp8:
+                h8 = planes("hn8")
+                ops.t5_rmsnorm_fp8(x, weight, h8[0], h8[1], eps)
+                return h8
+            hn = ws["hn"][:rows]
+            ops.t5_rmsnorm(x, weight, hn, eps)
+            return hn
+        into_stream = dict(epilogue=L.EPI_GATE_RESIDUAL, resid=x, gate=w["ones"])
         ops.embed_rows(w["shared"], ids, x)
         for i in range(p.num_layers):
-            ops.t5_rmsnorm(x, w[f"{i}.ln0"], hn, p.layer_norm_epsilon)
-            ops.gemm([ops.Gemm(hn, w[f"{i}.qkv"], None, qkv)], tile)
+            project("qkv", i, normed("qkv", w[f"{i}.ln0"]), qkv)
             ops.t5_attention(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], bias, ao, n_seq, p.num_heads)
-            ops.gemm([ops.Gemm(ao, w[f"{i}.o"], None, x, epilogue=L.EPI_GATE_RESIDUAL, resid=x, gate=w["ones"])], tile)
-            ops.t5_rmsnorm(x, w[f"{i}.ln1"], hn, p.layer_norm_epsilon)
-            ops.gemm([ops.Gemm(hn, w[f"{i}.wi"], None, u, epilogue=L.EPI_SPLIT_GELU, out2=g, n_split=p.d_ff)], tile)
-            ops.gated_mul(g, u, u)
-            ops.gemm([ops.Gemm(u, w[f"{i}.wo"], None, x, epilogue=L.EPI_GATE_RESIDUAL, resid=x, gate=w["ones"])], tile)
-        ops.t5_rmsnorm(x, w["final_ln"], out, p.layer_norm_epsilon)
+            if "o" in self.fp8:    # 64 workgroups (one per head) write a row of ao: no kernel knows its maximum
+                a = planes("ao8")
+                ops.quantize_rows_fp8(ao, a[0], a[1])
+            else:
+                a = ao
+            project("o", i, a, x, **into_stream)
+            project("wi", i, normed("wi", w[f"{i}.ln1"]), u, epilogue=L.EPI_SPLIT_GELU, out2=g, n_split=p.d_ff)
+            if "wo" in self.fp8:
+                a = planes("p8")
+                ops.gated_mul_fp8(g, u, a[0], a[1])
+            else:
+                ops.gated_mul(g, u, u)
+                a = u
+            project("wo", i, a, x, **into_stream)
+        ops.t5_rmsnorm(x, w["final_ln"], out, eps)
 
     # the reference's callers move the module around and switch modes; resident here
     def to(self, *a, **k):
@@ -285,13 +390,16 @@ def _read_safetensors(path: str) -> dict:
     return sd
 
 
-def load_t5(params="t5-v1_1-xxl", device="cuda", weights="synthetic", seed: int = 0) -> T5Encoder:
+def load_t5(params="t5-v1_1-xxl", device="cuda", weights="synthetic", seed: int = 0, precision: str = "bf16",
+            fp8_projections: Sequence[str] = FP8_PROJECTIONS) -> T5Encoder:
     """``params``: a T5Params or a name of ``params.t5_params``.  ``weights``: "synthetic", a state dict, or a local
     ``.safetensors`` file or a directory of shards (transformers' names; a full T5 checkpoint's decoder and lm_head
     keys are ignored, a missing encoder key is an error).  The ``T5`` environment variable names the checkpoint when the
-    caller gives none ("synthetic"), as ``AE`` does for the autoencoder; nothing is ever downloaded."""
+    caller gives none ("synthetic"), as ``AE`` does for the autoencoder; nothing is ever downloaded.
+    ``precision``, ``fp8_projections``: as for ``T5Encoder``; an e4m3fn ``.safetensors`` file loads as stored (its bytes
+    become the fp8 operands unchanged; in bf16 mode they are widened exactly)."""
     p = t5_params[params] if isinstance(params, str) else params
-    enc = T5Encoder(p, device)
+    enc = T5Encoder(p, device, precision=precision, fp8_projections=fp8_projections)
     if isinstance(weights, str) and weights == "synthetic" and os.environ.get("T5"):
         weights = os.environ["T5"]
     if isinstance(weights, dict):
@@ -381,10 +489,12 @@ class HipTextEncoder:
 
 
 def synthetic_text_encoder(context_dim: int, max_length: int, device, vec_dim: int = 768, seed: int = 0,
-                           clip=None) -> HipTextEncoder:
+                           clip=None, t5_precision: str = "bf16") -> HipTextEncoder:
     """``text_encoder="synthetic-t5"``: a two-block T5Encoder of d_model = ``context_dim`` (4 heads, d_ff 512) with
     synthetic weights behind the toy byte tokenizer.  Real arithmetic on meaningless weights: prompts and concepts reach
     the DiT through the encoder's kernels, and equal strings give equal bits.  ``clip``: as for HipTextEncoder (None: the
-    seeded-noise stand-in; "synthetic-t5-clip" passes ``clip.synthetic_clip_embedder``)."""
+    seeded-noise stand-in; "synthetic-t5-clip" passes ``clip.synthetic_clip_embedder``).  ``t5_precision``: the
+    T5Encoder's ``precision`` ("fp8": all four projections in e4m3)."""
     p = tiny_t5_params(d_model=context_dim, vocab_size=ToyByteTokenizer.vocab_size + 253)
-    return HipTextEncoder(load_t5(p, device, "synthetic", seed), ToyByteTokenizer(), max_length, clip=clip, vec_dim=vec_dim)
+    return HipTextEncoder(load_t5(p, device, "synthetic", seed, precision=t5_precision), ToyByteTokenizer(), max_length,
+                          clip=clip, vec_dim=vec_dim)

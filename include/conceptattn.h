@@ -28,13 +28,14 @@
 extern "C" {
 #endif
 
-#define CA_VERSION 130 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
+#define CA_VERSION 131 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
                           CA_ATTN_Q_PRESCALED; .1: ca_axpy_f32, ca_split_bf16; .2: ca_attn_stats; .3: ca_gemm_problem.qk_f16,
                           ca_attn_fwd_qk16; .4: ca_qpre_finish_rope_f32; .5: ca_heatmap_fused; .6: ca_gemm_plan;
                           .7: the autoencoder kernels (conv3x3_nhwc, groupnorm_nhwc, softmax_rows_f32, affine_rows_f32);
                           128: the T5 encoder kernels (t5_attn_bf16, t5_rmsnorm_f32in, gated_mul_bf16, embed_rows_f32);
                           129: the CLIP text encoder kernels (clip_attn_bf16, layernorm_f32in, quick_gelu_bf16,
-                          clip_embed_f32); 130: the pixel I/O kernels (pixels_u8_to_nhwc32_bf16, nhwc_f32_to_pixels_u8) */
+                          clip_embed_f32); 130: the pixel I/O kernels (pixels_u8_to_nhwc32_bf16, nhwc_f32_to_pixels_u8);
+                          131: the T5 encoder's e4m3 producers (t5_rmsnorm_f32in_fp8, gated_mul_fp8) */
 
 #define CA_OK 0
 #define CA_ERR_ARG (-1)    /* bad shape / null pointer / misalignment */
@@ -472,6 +473,18 @@ int ca_t5_rmsnorm_f32in(const float *x, int32_t ldx, const float *w, void *out, 
  * row strides >= C and % 8, 16-byte aligned. */
 int ca_gated_mul_bf16(const void *g, int32_t ldg, const void *u, int32_t ldu, void *out, int32_t ldo, int64_t rows,
                       int32_t C, ca_stream_t stream);
+
+/* The two above as producers of ca_gemm_fp8's A operand (the T5 encoder's fp8 mode): the fp32 row y (the norm's
+ * x * rsqrt(mean(x^2) + eps) * w, not rounded to bf16; the exact product float(g) * float(u)) leaves as OCP e4m3 bytes
+ * and one fp32 scale per row: out_scale[r] = max|y| / 448, or 1 for an all-zero row (which stores zero bytes);
+ * out8[r, :] = e4m3(y / out_scale[r]), round-to-nearest-even, saturating at +-448 -- the rule of ca_quantize_rows_fp8.
+ * out8 uint8 [rows, ldo] with ldo in bytes, >= the row length and % 8 (ca_gemm_fp8 itself wants lda % 16), 8-byte
+ * aligned; out_scale fp32 [rows] contiguous.  H % 8 == 0 / C % 8 == 0; inputs as for the bf16 forms (x, w, g, u
+ * 16-byte aligned, ldx % 4, ldg / ldu % 8).  One workgroup owns a row. */
+int ca_t5_rmsnorm_f32in_fp8(const float *x, int32_t ldx, const float *w, void *out8, int32_t ldo, float *out_scale,
+                            int64_t rows, int32_t H, float eps, ca_stream_t stream);
+int ca_gated_mul_fp8(const void *g, int32_t ldg, const void *u, int32_t ldu, void *out8, int32_t ldo, float *out_scale,
+                     int64_t rows, int32_t C, ca_stream_t stream);
 
 /* nn.Embedding into the fp32 residual stream: out[r, :] = float(table[ids[r], :]).  table bf16 [vocab, ldt], ids int32
  * [rows] on the device, out fp32 [rows, ldo]; H % 8 == 0.  The library cannot see the ids: the caller guarantees

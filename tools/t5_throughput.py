@@ -5,6 +5,10 @@ drawn on the device straight into the packed operands (the CPU generator would h
 then the median of the repeats.  Each step is a process of its own under its own time limit:
     python tools/t5_throughput.py          # runs every step: `timeout ... python tools/t5_throughput.py L`
     python tools/t5_throughput.py 256      # one step, one JSON line
+    python tools/t5_throughput.py --precision fp8          # 1 x 256, 5 x 256 and 5 x 512 tokens, each its own process
+    python tools/t5_throughput.py --precision fp8 1x256    # one step: the fp8 mode beside the bf16 mode, same process
+With ``--precision fp8`` a step times ``T5Encoder(precision="fp8")`` (the same weights, quantised per output row)
+against the bf16 encoder in one process and prints both family breakdowns; the plain torch network is not run.
 No number printed here is a gate."""
 import json
 import math
@@ -90,7 +94,8 @@ def family_shares(enc, ids):
     from conceptattention_amd import ops
     marks = []
     names = {"gemm": "gemm", "t5_attention": "attention", "t5_rmsnorm": "rmsnorm", "gated_mul": "gated_mul",
-             "embed_rows": "embed"}
+             "embed_rows": "embed", "t5_rmsnorm_fp8": "rmsnorm_fp8", "gated_mul_fp8": "gated_mul_fp8",
+             "quantize_rows_fp8": "quantize_rows_fp8"}
     saved = {n: getattr(ops, n) for n in names}
 
     def wrap(n):
@@ -116,6 +121,42 @@ def family_shares(enc, ids):
     return {k: round(v / total, 3) for k, v in sorted(ms.items(), key=lambda kv: -kv[1])}
 
 
+def fp8_encoder(bf):
+    """The fp8-mode twin of a bf16 encoder: the same operands, quantised per output row as T5Encoder._pack does."""
+    from conceptattention_amd import ops
+    from conceptattention_amd.t5 import FP8_PROJECTIONS, T5Encoder
+    enc = T5Encoder(bf.params, "cuda", precision="fp8")
+    w = {}
+    for k, t in bf.w.items():
+        if k.split(".")[-1] in FP8_PROJECTIONS:
+            w[k], w[k + ".scale"] = ops.quantize_rows_fp8(t)
+        else:
+            w[k] = t
+    enc.w, enc.tensors, enc.loaded = w, bf.tensors, True
+    return enc
+
+
+def step_fp8(n_seq, L):
+    import torch
+    from conceptattention_amd.params import t5_params
+    p = t5_params["t5-v1_1-xxl"]
+    bf = device_encoder(p)
+    f8 = fp8_encoder(bf)
+    ids = torch.zeros(n_seq, L, dtype=torch.long)
+    ids[:, :12] = torch.randint(2, p.vocab_size, (n_seq, 12), generator=torch.Generator().manual_seed(1))
+    with torch.no_grad():
+        ms = {"bf16": timed(lambda: bf.encode_ids(ids)), "fp8": timed(lambda: f8.encode_ids(ids))}
+        ms["bf16_again"] = timed(lambda: bf.encode_ids(ids))        # the drift of the box between the two measurements
+        a, b = f8.encode_ids(ids).float(), bf.encode_ids(ids).float()
+        shares = {"bf16": family_shares(bf, ids), "fp8": family_shares(f8, ids)}
+    print(json.dumps({"tokens": f"{n_seq}x{L}", "bf16_ms": round(ms["bf16"], 2), "fp8_ms": round(ms["fp8"], 2),
+                      "bf16_again_ms": round(ms["bf16_again"], 2), "fp8_over_bf16": round(ms["fp8"] / ms["bf16"], 3),
+                      "weights_gb": {"bf16": round(bf.weight_bytes(False) / 1e9, 2), "fp8": round(f8.weight_bytes(False) / 1e9, 2)},
+                      "workspace_mb": {"bf16": round(bf.workspace_bytes() / 1e6, 1), "fp8": round(f8.workspace_bytes() / 1e6, 1)},
+                      "rel_rms_fp8_vs_bf16": round(float(((a - b).pow(2).mean() / b.pow(2).mean()).sqrt()), 5),
+                      "share_of_hip_time": shares}), flush=True)
+
+
 def step(L):
     import torch
     from conceptattention_amd.params import t5_params
@@ -137,10 +178,23 @@ def step(L):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) == 2:
-        step(int(sys.argv[1]))
+    args = sys.argv[1:]
+    precision = "bf16"
+    if "--precision" in args:
+        i = args.index("--precision")
+        precision = args[i + 1]
+        del args[i:i + 2]
+    if precision not in ("bf16", "fp8") or len(args) > 1:
+        sys.exit("usage: t5_throughput.py [--precision bf16|fp8] [L | NxL]")
+    if args and precision == "fp8":
+        n, _, L = args[0].rpartition("x")
+        step_fp8(int(n or N_SEQ), int(L))
+    elif args:
+        step(int(args[0]))
     else:
-        for L in (256, 512):
-            rc = subprocess.call(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), str(L)])
+        steps = ("256", "512") if precision == "bf16" else ("1x256", "5x256", "5x512")
+        for s in steps:
+            rc = subprocess.call(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--precision",
+                                  precision, s])
             if rc != 0:
-                sys.exit(f"L={L} ended with {rc}")   # nothing more is started on the GPU
+                sys.exit(f"{s} ended with {rc}")   # nothing more is started on the GPU
