@@ -712,6 +712,72 @@ def nhwc_to_pixels(src, dst) -> None:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Segmentation scoring (ca_seg.hip): heat maps against label images, one workgroup per item.
+
+SEG_RECORD_BYTES = C.sizeof(L.SegRecord)   # 40
+
+
+def seg_blur_weights(sigma: float = 1.0) -> list:
+    """The nine fp32 weights of segmentation.gaussian_blur3 in row-major order, formed as it forms them."""
+    k = torch.exp(-0.5 * (torch.tensor([-1.0, 0.0, 1.0]) / sigma) ** 2)
+    k = k / k.sum()
+    return [float(v) for v in (k[:, None] * k[None, :]).reshape(-1)]
+
+
+def seg_score(maps, labels, results, mean_value_threshold: bool = True, downscale_for_eval: bool = False,
+              blur_weights=None, mask_out=None, coeff_out=None) -> None:
+    """Score n heat maps against n label images (ca_seg_score; include/conceptattn.h states the arithmetic).
+    maps: n fp32 [h, w] contiguous tensors (a list, or one [n, h, w] tensor), h * w <= 4096; labels: n uint8 [Hl, Wl]
+    contiguous tensors, nonzero = positive, Hl * Wl <= 2^24; results: uint8 [n, 40] contiguous, one ca_seg_record per
+    item (L.SegRecord); mask_out: optional uint8 [n, h, w], coeff_out: optional fp32 [n, h, w], both at map resolution.
+    ``blur_weights``: nine numbers (seg_blur_weights) to blur the map first, None for no blur.  More than
+    L.SEG_MAX_PROBLEMS items go in several launches."""
+    lib = L.load()
+    maps, labels = list(maps), list(labels)
+    n = len(maps)
+    if n < 1 or len(labels) != n:
+        raise ValueError(f"seg_score: {n} maps and {len(labels)} labels; need the same number, at least 1")
+    _chk(results, torch.uint8, "results")
+    if tuple(results.shape) != (n, SEG_RECORD_BYTES) or not results.is_contiguous():
+        raise ValueError(f"seg_score: results{tuple(results.shape)} must be contiguous uint8 [{n}, {SEG_RECORD_BYTES}]")
+    h, w = (int(v) for v in maps[0].shape) if maps[0].dim() == 2 else (0, 0)
+    Hl, Wl = (int(v) for v in labels[0].shape) if labels[0].dim() == 2 else (0, 0)
+    for i in range(n):
+        _chk(maps[i], torch.float32, "maps"), _chk(labels[i], torch.uint8, "labels")
+        if tuple(maps[i].shape) != (h, w) or not maps[i].is_contiguous() or tuple(labels[i].shape) != (Hl, Wl) or \
+                not labels[i].is_contiguous() or maps[i].device != results.device or labels[i].device != results.device:
+            raise ValueError(f"seg_score[{i}]: maps are contiguous fp32 [h, w] and labels contiguous uint8 [Hl, Wl], all "
+                             "items of one shape and on the device of results")
+    for name, t, dt in (("mask_out", mask_out, torch.uint8), ("coeff_out", coeff_out, torch.float32)):
+        if t is not None:
+            _chk(t, dt, name)
+            if tuple(t.shape) != (n, h, w) or not t.is_contiguous() or t.device != results.device:
+                raise ValueError(f"seg_score: {name}{tuple(t.shape)} must be contiguous [{n}, {h}, {w}] on the same device")
+    if not 1 <= h * w <= L.SEG_MAX_CELLS:
+        raise ValueError(f"seg_score: a map of {h} x {w} cells; ca_seg_score takes 1..{L.SEG_MAX_CELLS} (larger maps are "
+                         "scored on the host: segmentation.SegmentationScores)")
+    if not 1 <= Hl * Wl <= L.SEG_MAX_LABEL_PIXELS:
+        raise ValueError(f"seg_score: a label of {Hl} x {Wl} pixels; ca_seg_score takes 1..2^24")
+    flags = (L.SEG_MEAN_THRESHOLD if mean_value_threshold else 0) | (L.SEG_DOWNSCALE if downscale_for_eval else 0)
+    bw = None
+    if blur_weights is not None:
+        blur_weights = [float(v) for v in blur_weights]
+        if len(blur_weights) != 9:
+            raise ValueError("seg_score: blur_weights are the nine weights of the 3x3 blur")
+        flags |= L.SEG_BLUR
+        bw = (C.c_float * 9)(*blur_weights)
+    for c0 in range(0, n, L.SEG_MAX_PROBLEMS):
+        m = min(L.SEG_MAX_PROBLEMS, n - c0)
+        arr = (L.SegProblem * m)()
+        for k in range(m):
+            p, i = arr[k], c0 + k
+            p.map, p.label, p.result = maps[i].data_ptr(), labels[i].data_ptr(), results[i].data_ptr()
+            p.mask_out = None if mask_out is None else mask_out[i].data_ptr()
+            p.coeff_out = None if coeff_out is None else coeff_out[i].data_ptr()
+        L.check(lib.ca_seg_score(arr, m, h, w, Hl, Wl, flags, bw, _stream()), "ca_seg_score")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # T5 encoder kernels (ca_t5.hip).  Rows are tokens; q / k / v are 2-D views with free row strides.
 
 def t5_attention(q, k, v, bias, out, n_seq: int, num_heads: int) -> None:

@@ -458,25 +458,14 @@ class ConceptAttentionFluxPipeline:
         enc = self.text_encoder
         return int(getattr(enc, "max_length", getattr(enc, "n_tokens", 0)))
 
-    @torch.no_grad()
-    @on_own_device
-    def encode_images(self, images, concepts, prompts, width: int = 1024, height: int = 1024,
-                      layer_indices=list(range(15, 19)), num_samples: int = 1, num_steps: int = 4,
-                      noise_timestep: int = 2, seed: int = 0, batch: int = 5, noise=None, vae_noise=None,
-                      return_pil_heatmaps: bool = True, cmap="plasma", stop_after_multi_modal_attentions=True,
-                      attention_norm: str = "sparsemax", softmax=True, joint_attention_kwargs=None) -> list:
-        """``encode_image`` for a list of images: a list of ConceptAttentionPipelineOutput in item order, every item with
-        the maps of its own ``encode_image`` call.  ``images``: PIL images and / or latents (1,16,h/8,w/8);
-        ``concepts``: one list for all items or one list per item; ``prompts``: one string per item (or one for all).
-        Items that share a latent shape and a concept count go ``batch`` (at most 5) at a time through one text-encoder
-        call (``FluxGenerator.embed_many``), one autoencoder pass (``AutoEncoder.encode_pixels``) and one forward.
-        ``noise``: per item, what ``encode_image`` takes (a list of num_samples tensors); ``vae_noise``: per item, a
-        tensor (1,16,h/8,w/8) -- without it the autoencoder draws one batch of noise per forward, so PIL items are then
-        reproducible per call of this method, not against single calls."""
+    def _encode_chunks(self, images, concepts, prompts, width, height, layer_indices, num_samples, num_steps,
+                       noise_timestep, seed, batch, noise, vae_noise, stop_after_multi_modal_attentions, attention_norm,
+                       softmax, joint_attention_kwargs):
+        """The forwards of ``encode_images``, one at a time: yields (item indices, acc_o, acc_c) with the two fp32 maps
+        [len(indices), C, side, side] of the chunk still on the device (``_encode_maps``).  ``images`` is a list."""
         assert all([0 <= li < self.params.depth for li in layer_indices]), "Invalid layer index"
         assert height == width, "Height and width must be the same for now"
         norm = resolve_norm(softmax, attention_norm)
-        images = list(images)
         n = len(images)
         prompts = [prompts] * n if isinstance(prompts, str) else list(prompts)
         concepts = _per_item(concepts, n, "encode_images: concepts")
@@ -484,7 +473,6 @@ class ConceptAttentionFluxPipeline:
             if v is not None and len(v) != n:
                 raise ValueError(f"encode_images: {name} has {len(v)} entries for {n} images")
         shapes = [tuple(im.shape[1:]) if isinstance(im, torch.Tensor) else (16, height // 8, width // 8) for im in images]
-        results = [None] * n
         for idx in plan_batches([(shapes[i], len(concepts[i]), self._text_length()) for i in range(n)], batch):
             emb = self.flux_generator.embed_many([prompts[i] for i in idx], [concepts[i] for i in idx])
             txt, vec, con, con_ids, con_vec = (torch.cat([e[k] for e in emb], 0) if len(idx) > 1 else emb[0][k]
@@ -503,6 +491,29 @@ class ConceptAttentionFluxPipeline:
             ho, hc = self._encode_maps(self.model, latent, txt, vec, con, con_ids, con_vec, layer_indices, num_samples,
                                        num_steps, noise_timestep, seed, stop_after_multi_modal_attentions,
                                        joint_attention_kwargs, norm, noise=nz)
+            yield idx, ho, hc
+
+    @torch.no_grad()
+    @on_own_device
+    def encode_images(self, images, concepts, prompts, width: int = 1024, height: int = 1024,
+                      layer_indices=list(range(15, 19)), num_samples: int = 1, num_steps: int = 4,
+                      noise_timestep: int = 2, seed: int = 0, batch: int = 5, noise=None, vae_noise=None,
+                      return_pil_heatmaps: bool = True, cmap="plasma", stop_after_multi_modal_attentions=True,
+                      attention_norm: str = "sparsemax", softmax=True, joint_attention_kwargs=None) -> list:
+        """``encode_image`` for a list of images: a list of ConceptAttentionPipelineOutput in item order, every item with
+        the maps of its own ``encode_image`` call.  ``images``: PIL images and / or latents (1,16,h/8,w/8);
+        ``concepts``: one list for all items or one list per item; ``prompts``: one string per item (or one for all).
+        Items that share a latent shape and a concept count go ``batch`` (at most 5) at a time through one text-encoder
+        call (``FluxGenerator.embed_many``), one autoencoder pass (``AutoEncoder.encode_pixels``) and one forward.
+        ``noise``: per item, what ``encode_image`` takes (a list of num_samples tensors); ``vae_noise``: per item, a
+        tensor (1,16,h/8,w/8) -- without it the autoencoder draws one batch of noise per forward, so PIL items are then
+        reproducible per call of this method, not against single calls."""
+        images = list(images)
+        results = [None] * len(images)
+        for idx, ho, hc in self._encode_chunks(images, concepts, prompts, width, height, layer_indices, num_samples,
+                                               num_steps, noise_timestep, seed, batch, noise, vae_noise,
+                                               stop_after_multi_modal_attentions, attention_norm, softmax,
+                                               joint_attention_kwargs):
             for k, i in enumerate(idx):
                 results[i] = self._finish(images[i], ho[k:k + 1], hc[k:k + 1], return_pil_heatmaps, cmap)
         return results

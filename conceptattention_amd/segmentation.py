@@ -10,7 +10,9 @@ What is mirrored
                                    experiments/imagenet_segmentation/run_experiment.py:166-235
 The heat maps themselves come from ``ConceptAttentionFluxPipeline.encode_image`` (one forward of the 19
 double blocks on the HIP path); everything in this file is small host-side arithmetic on (C, side, side)
-maps.  The image loop of the harness (`run_experiment.py:137`) is the natural multi-GPU shard: every rank
+maps -- except ``DeviceSegmentationScores`` and ``ConceptAttentionSegmentationModel.score_images``, which score the maps
+where they are: one ca_seg_score workgroup per image (csrc/ca_seg.hip) computes the mask, the counts and the exact AP from
+the device accumulators, and only the 40-byte records come back, once.  The image loop of the harness (`run_experiment.py:137`) is the natural multi-GPU shard: every rank
 scores its own images and ``SegmentationScores.all_reduce`` sums the five counters once at the end.
 """
 from __future__ import annotations
@@ -170,6 +172,65 @@ class SegmentationScores:
                 "mAP": float(self.ap_sum / max(self.n, 1)), "n": self.n}
 
 
+# ------------------------------------------------------------------------------------------ scores on the device
+SEG_RECORD = np.dtype([("n11", "<i4"), ("n10", "<i4"), ("n01", "<i4"), ("n00", "<i4"), ("ap", "<f8"), ("mean", "<f4"),
+                       ("lo", "<f4"), ("hi", "<f4"), ("thresholds", "<i4")])   # ca_seg_record (include/conceptattn.h)
+
+
+class DeviceSegmentationScores:
+    """``SegmentationScores`` whose per-image records stay on the device until somebody asks: ``reserve`` hands
+    ``ops.seg_score`` the next records of a buffer that grows by ``chunk`` records, and ``to_host`` / ``result`` /
+    ``all_reduce`` download the records written so far ONCE (and not again until new ones were reserved)."""
+
+    def __init__(self, device="cuda:0", chunk: int = 256):
+        self.device = torch.device(device)
+        self.chunk = max(1, int(chunk))
+        self.n = 0
+        self._pixels: list = []      # label pixels per item (host)
+        self._buf = torch.zeros(self.chunk, SEG_RECORD.itemsize, dtype=torch.uint8, device=self.device)
+        self._host = None            # (n, records) of the last download
+
+    def reserve(self, n: int, label_pixels: int) -> torch.Tensor:
+        """uint8 [n, 40]: the records of the next n items (each scored against ``label_pixels`` label pixels)."""
+        need = self.n + n
+        if need > self._buf.shape[0]:
+            cap = -(-need // self.chunk) * self.chunk
+            grown = torch.zeros(cap, SEG_RECORD.itemsize, dtype=torch.uint8, device=self.device)
+            grown[:self.n] = self._buf[:self.n]      # (stream-ordered behind the launches that wrote them)
+            self._buf = grown
+        out = self._buf[self.n:need]
+        self.n = need
+        self._pixels += [int(label_pixels)] * n
+        return out
+
+    def records(self) -> np.ndarray:
+        """The n records as a numpy array of SEG_RECORD, in item order: the one download."""
+        if self._host is None or self._host[0] != self.n:
+            self._host = (self.n, self._buf[:self.n].cpu().numpy().view(SEG_RECORD).reshape(self.n))
+        return self._host[1]
+
+    def to_host(self) -> SegmentationScores:
+        """The counters the host path would hold after ``update`` on the same items: its (1 - m, m) against (1 - y, y)
+        stacking counts every pixel where mask and label agree once per class plane."""
+        rec = self.records()
+        out = SegmentationScores()
+        for r, n_px in zip(rec, self._pixels):
+            agree = int(r["n11"]) + int(r["n00"])
+            out.correct += 2 * agree
+            out.labelled += 2 * n_px
+            out.inter = out.inter + np.array([agree, agree])
+            out.union = out.union + np.array([2 * n_px - agree, 2 * n_px - agree])
+            out.ap_sum += float(r["ap"])
+            out.n += 1
+        return out
+
+    def all_reduce(self) -> SegmentationScores:
+        return self.to_host().all_reduce()
+
+    def result(self) -> dict:
+        return self.to_host().result()
+
+
 # ------------------------------------------------------------------------------------------ model wrapper
 class ConceptAttentionSegmentationModel:
     """Callable with the reference's segmentation-model contract (segmentation.py:34-81):
@@ -205,6 +266,70 @@ class ConceptAttentionSegmentationModel:
                                            return_pil_heatmaps=False, joint_attention_kwargs=joint_attention_kwargs)
         return [(torch.as_tensor(np.asarray(o.concept_heatmaps if target_space == "output" else o.cross_attention_maps),
                                  dtype=torch.float32), None) for o in outs]
+
+    @torch.no_grad()
+    def score_images(self, images, target_concepts, concepts, captions, labels, scores, size: int = 224,
+                     downscale_for_eval: bool = False, apply_blur: bool = False, mean_value_threshold: bool = True,
+                     target_space: str = "output", return_masks: bool = False, **encode_kwargs):
+        """Encode ``images`` and score every target concept's map against its label without leaving the device: the
+        chunks of ``pipeline.encode_images`` (``batch`` images per forward), each chunk's target planes straight from the
+        device accumulators into ``ops.seg_score``, the records into ``scores`` (a ``DeviceSegmentationScores``).
+        ``labels``: per image a uint8 / bool array (size, size), nonzero = positive (resizing label files stays the
+        caller's job, as in the harness).  ``encode_kwargs``: what ``segment_images`` takes (layers, num_samples,
+        num_steps, noise_timestep, seed, height, width, batch, joint_attention_kwargs) and ``noise`` / ``vae_noise`` /
+        ``attention_norm`` / ``softmax`` of ``encode_images``.  Nothing per image comes back unless ``return_masks``:
+        then ``(all_masks, all_coefficients)`` as ``__call__`` returns them, at map resolution (one download at the end).
+        Maps of more than 4096 cells raise a ValueError: ``__call__`` + ``prepare_for_scoring`` +
+        ``SegmentationScores.update`` remain for them, and for ``target_concepts=None``."""
+        from . import ops
+        if target_concepts is None:
+            raise ValueError("score_images scores one target concept per image; multi-class masks go through __call__")
+        images = list(images)
+        n = len(images)
+        if not (len(target_concepts) == len(labels) == n and len(captions) >= n):
+            raise ValueError(f"score_images: {n} images need {n} target concepts, labels and captions")
+        if target_space not in ("output", "cross_attention"):
+            raise ValueError("target_space: 'output' or 'cross_attention'")
+        pipe = self.pipeline
+        per_item = list(concepts) if concepts and not isinstance(concepts[0], str) else [list(concepts)] * n
+        target = [per_item[i].index(target_concepts[i]) for i in range(n)]
+        lab = []
+        for i, y in enumerate(labels):
+            y = np.asarray(_np(y))
+            if y.shape != (size, size) or y.dtype not in (np.uint8, np.bool_):
+                raise ValueError(f"labels[{i}]: expected a uint8 / bool array ({size}, {size}), got {y.dtype} {y.shape}")
+            lab.append(y.astype(np.uint8, copy=False))
+        kw = dict(encode_kwargs)
+        unknown = set(kw) - {"layers", "num_samples", "num_steps", "noise_timestep", "seed", "height", "width", "batch",
+                             "joint_attention_kwargs", "noise", "vae_noise", "attention_norm", "softmax"}
+        if unknown:
+            raise TypeError(f"score_images: unexpected arguments {sorted(unknown)}")
+        blur = ops.seg_blur_weights() if apply_blur else None
+        masks, planes, order = [], [], []
+        with torch.cuda.device(pipe.device):
+            chunks = pipe._encode_chunks(images, concepts, list(captions[:n]), kw.get("width", 1024), kw.get("height", 1024),
+                                         kw.get("layers", list(range(15, 19))), kw.get("num_samples", 1),
+                                         kw.get("num_steps", 4), kw.get("noise_timestep", 2), kw.get("seed", 0),
+                                         kw.get("batch", 5), kw.get("noise"), kw.get("vae_noise"), True,
+                                         kw.get("attention_norm", "sparsemax"), kw.get("softmax", True),
+                                         kw.get("joint_attention_kwargs"))
+            for idx, acc_o, acc_c in chunks:
+                acc = acc_o if target_space == "output" else acc_c
+                maps = [acc[k, target[i]] for k, i in enumerate(idx)]
+                y = torch.from_numpy(np.stack([lab[i] for i in idx])).pin_memory().to(pipe.device, non_blocking=True)
+                m_out = torch.empty(len(idx), *maps[0].shape, dtype=torch.uint8, device=pipe.device) if return_masks else None
+                ops.seg_score(maps, list(y), scores.reserve(len(idx), size * size), mean_value_threshold=mean_value_threshold,
+                              downscale_for_eval=downscale_for_eval, blur_weights=blur, mask_out=m_out)
+                if return_masks:
+                    masks.append(m_out), planes.append(torch.stack(maps)), order.extend(idx)
+        if not return_masks:
+            return None
+        masks, planes = torch.cat(masks).cpu().numpy().astype(bool), torch.cat(planes).cpu()
+        if apply_blur:
+            planes = gaussian_blur3(planes)      # (what __call__ hands out; the kernel's mask is of its own blur)
+        planes = planes.numpy()
+        back = {i: k for k, i in enumerate(order)}
+        return [masks[back[i]] for i in range(n)], [planes[back[i]] for i in range(n)]
 
     def __call__(self, images, target_concepts, concepts, captions, mean_value_threshold: bool = True,
                  joint_attention_kwargs=None, apply_blur: bool = False, **kwargs):

@@ -28,14 +28,15 @@
 extern "C" {
 #endif
 
-#define CA_VERSION 131 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
+#define CA_VERSION 132 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
                           CA_ATTN_Q_PRESCALED; .1: ca_axpy_f32, ca_split_bf16; .2: ca_attn_stats; .3: ca_gemm_problem.qk_f16,
                           ca_attn_fwd_qk16; .4: ca_qpre_finish_rope_f32; .5: ca_heatmap_fused; .6: ca_gemm_plan;
                           .7: the autoencoder kernels (conv3x3_nhwc, groupnorm_nhwc, softmax_rows_f32, affine_rows_f32);
                           128: the T5 encoder kernels (t5_attn_bf16, t5_rmsnorm_f32in, gated_mul_bf16, embed_rows_f32);
                           129: the CLIP text encoder kernels (clip_attn_bf16, layernorm_f32in, quick_gelu_bf16,
                           clip_embed_f32); 130: the pixel I/O kernels (pixels_u8_to_nhwc32_bf16, nhwc_f32_to_pixels_u8);
-                          131: the T5 encoder's e4m3 producers (t5_rmsnorm_f32in_fp8, gated_mul_fp8) */
+                          131: the T5 encoder's e4m3 producers (t5_rmsnorm_f32in_fp8, gated_mul_fp8);
+                          132: segmentation scoring on the device (seg_score) */
 
 #define CA_OK 0
 #define CA_ERR_ARG (-1)    /* bad shape / null pointer / misalignment */
@@ -540,6 +541,48 @@ int ca_pixels_u8_to_nhwc32_bf16(const void *src, int64_t src_stride, void *dst, 
  * the sum and the product rounded separately: (127.5 * (img.clamp(-1, 1) + 1.0)).byte().  A NaN gives 0.  src: fp32
  * [pixels, ld >= 3]; dst: uint8 [pixels, 3], 16-byte aligned; pixels counts every pixel of the batch. */
 int ca_nhwc_f32_to_pixels_u8(const float *src, int32_t ld, void *dst, int64_t pixels, ca_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Segmentation scoring (experiments/imagenet_segmentation/run_experiment.py:166-222 with batch_pix_accuracy,
+ * batch_intersection_union and get_ap_scores of concept_attention/utils.py:48-108; the mean-threshold mask of
+ * concept_attention/segmentation.py:55-81): one workgroup per item scores the target concept's heat map against a
+ * label image without leaving the device.  Per item, every step one fp32 rounding unless it says fp64:
+ *   x     = map, or with CA_SEG_BLUR its 3x3 blur with reflect padding: the nine products blur_weights[3 i + j] *
+ *           map[y + i - 1, x + j - 1], each rounded, added in row-major order
+ *   lo, hi = min x, max x;  mean = (float)(fp64 sum of x / (h w))   (a fixed summation tree)
+ *   mask  = x > mean  with CA_SEG_MEAN_THRESHOLD, else x > 0
+ *   c     = (x - lo) / (hi - lo), the division correctly rounded; a constant map gives NaN, as on the host
+ *   label pixel (Y, X) reads the mask at cell (near(Y; Hl, h), near(X; Wl, w)) and the coefficient at the same cell,
+ *   or with CA_SEG_DOWNSCALE at (near(near(Y; Hl, 14); 14, h), near(near(X; Wl, 14); 14, w));
+ *   near(i; n_out, n_in) = min((int)floorf(i * ((float)n_in / (float)n_out)), n_in - 1), the rule of
+ *   torch.nn.functional.interpolate(mode="nearest")
+ *   n11, n10, n01, n00 = pixels by (mask, label != 0)
+ *   ap    = the average precision of the 2 Hl Wl stacked scores (1 - c, c) (NaN -> 0) against the one-hot label:
+ *           sum over the distinct scores, descending, of (R_k - R_{k-1}) P_k with P_k = tp_k / n_k and
+ *           R_k = tp_k / (Hl Wl) in fp64, tp_k and n_k exact integers; the sum over a fixed tree (the same bits
+ *           every run)
+ * All problems of a call share h, w, Hl, Wl and flags.  Limits: 1 <= h w <= 4096, 1 <= Hl Wl <= 2^24,
+ * 1 <= n_problems <= CA_SEG_MAX_PROBLEMS, CA_SEG_BLUR needs h, w >= 2 and blur_weights (nine floats on the HOST, read
+ * during the call; unused and may be NULL otherwise); CA_ERR_ARG otherwise.  Needs up to 112.5 KB of LDS. */
+#define CA_SEG_MAX_PROBLEMS 16
+#define CA_SEG_MEAN_THRESHOLD 1
+#define CA_SEG_DOWNSCALE 2
+#define CA_SEG_BLUR 4
+typedef struct {
+  const float *map;   /* fp32 [h, w] contiguous: the target concept's accumulated heat map                             */
+  const void *label;  /* uint8 [Hl, Wl] contiguous: nonzero = positive                                                 */
+  void *result;       /* one ca_seg_record, 40 bytes, 8-byte aligned                                                    */
+  void *mask_out;     /* uint8 [h, w], or NULL: the mask at map resolution (0 / 1)                                     */
+  float *coeff_out;   /* fp32 [h, w], or NULL: c at map resolution                                                     */
+} ca_seg_problem;
+typedef struct {
+  int32_t n11, n10, n01, n00;
+  double ap;
+  float mean, lo, hi;
+  int32_t thresholds; /* the number of distinct scores among the pixels */
+} ca_seg_record;
+int ca_seg_score(const ca_seg_problem *problems, int32_t n_problems, int32_t h, int32_t w, int32_t Hl, int32_t Wl,
+                 int32_t flags, const float *blur_weights, ca_stream_t stream);
 
 #ifdef __cplusplus
 }
