@@ -301,7 +301,7 @@ extern "C" int ca_seg_score(const ca_seg_problem *problems, int32_t n_problems, 
   if (flags & CA_SEG_BLUR)
     for (int i = 0; i < 9; ++i) A.blur[i] = blur_weights[i];
   const size_t lds = (size_t)npad * 8 + (size_t)((hw + 3) & ~3) * 12 + SEG_SCRATCH_BYTES;
-  if (lds > 64 * 1024) {   // maps above 48 x 48: above the default dynamic LDS limit
+  if (lds > 64 * 1024) {   // above 2048 cells (npad 8192: 57 856 -> 90 672 bytes): above the default dynamic LDS limit
     static std::atomic<unsigned long long> attr_done{0};
     const int rc = ca_raise_lds_limit({(const void *)ca_seg_score_kernel},
                                       SEG_MAX_CELLS * 2 * 8 + SEG_MAX_CELLS * 12 + SEG_SCRATCH_BYTES, attr_done, FN);

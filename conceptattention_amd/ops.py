@@ -46,6 +46,20 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+INT32_MAX = 2 ** 31 - 1
+
+
+def _i32(value, name: str) -> int:
+    """A stride or size on its way to an ``int32_t`` parameter or struct field of the library.  ctypes keeps the low 32
+    bits of a larger integer without a word (2^32 + 256 arrives as 256, which passes every ``ld >= H`` check and makes the
+    kernel read and write other rows), so every such value goes through here: ValueError naming the argument when it is
+    not in 0 .. 2^31 - 1."""
+    v = int(value)
+    if not 0 <= v <= INT32_MAX:
+        raise ValueError(f"{name} = {v} does not fit the library's int32_t argument (0 .. 2^31 - 1)")
+    return v
+
+
 @dataclass
 class Gemm:
     """One problem of a grouped GEMM launch: out = epi(a @ w.T + bias)."""
@@ -98,18 +112,19 @@ def _gemm_problems(problems: Sequence[Gemm]):
         p = arr[i]
         p.A, p.W, p.out = a.data_ptr(), w.data_ptr(), out.data_ptr()
         p.bias = _ptr(None if g.bias is None else _chk(g.bias, torch.bfloat16, "bias"))
-        p.M, p.N, p.K = a.shape[0], w.shape[0], a.shape[1]
-        p.lda, p.ldw, p.ldc = a.stride(0), w.stride(0), out.stride(0)
+        p.M, p.N, p.K = _i32(a.shape[0], "M"), _i32(w.shape[0], "N"), _i32(a.shape[1], "K")
+        p.lda, p.ldw, p.ldc = _i32(a.stride(0), "lda"), _i32(w.stride(0), "ldw"), _i32(out.stride(0), "ldc")
         p.epilogue = g.epilogue
         p.out_f32 = int(f32o)
-        p.gate_rows = p.M if g.gate_rows is None else g.gate_rows
+        p.gate_rows = p.M if g.gate_rows is None else _i32(g.gate_rows, "gate_rows")
         if g.epilogue == L.EPI_GATE_RESIDUAL:
             if g.resid is None or g.gate is None:
                 raise ValueError(f"gemm[{i}]: GATE_RESIDUAL needs resid and gate")
-            p.resid, p.ldr = _chk(g.resid, out.dtype, "resid").data_ptr(), g.resid.stride(0)
+            p.resid, p.ldr = _chk(g.resid, out.dtype, "resid").data_ptr(), _i32(g.resid.stride(0), "ldr")
             p.gate = _chk(g.gate, torch.float32, "gate").data_ptr()
             p.gate2 = _ptr(None if g.gate2 is None else _chk(g.gate2, torch.float32, "gate2"))
-            p.gate_stride, p.gate_item_rows, p.gate2_item_rows = g.gate_stride, g.gate_item_rows, g.gate2_item_rows
+            p.gate_stride, p.gate_item_rows = _i32(g.gate_stride, "gate_stride"), _i32(g.gate_item_rows, "gate_item_rows")
+            p.gate2_item_rows = _i32(g.gate2_item_rows, "gate2_item_rows")
         elif g.epilogue == L.EPI_QKV_NORM_ROPE:
             if g.norm_q is None or g.norm_k is None or g.rope is None:
                 raise ValueError(f"gemm[{i}]: QKV_NORM_ROPE needs norm_q, norm_k, rope")
@@ -118,24 +133,26 @@ def _gemm_problems(problems: Sequence[Gemm]):
             rope = _chk(g.rope, torch.float32, "rope")
             if tuple(rope.shape) != (p.M, 64, 2) or not rope.is_contiguous():
                 raise ValueError(f"gemm[{i}]: rope must be contiguous [M,64,2]")
-            p.rope, p.n_split = rope.data_ptr(), g.n_split
+            p.rope, p.n_split = rope.data_ptr(), _i32(g.n_split, "n_split")
             p.q_out_scale = float(g.q_out_scale)
             p.qk_f16 = int(bool(g.qk_f16))
             if g.q_prerope is not None:
                 if g.q_prerope.dtype not in (torch.bfloat16, torch.float32):
                     raise ValueError(f"gemm[{i}]: q_prerope must be bf16 or fp32")
-                p.q_prerope, p.ldp = _chk(g.q_prerope, g.q_prerope.dtype, "q_prerope").data_ptr(), g.q_prerope.stride(0)
+                p.q_prerope = _chk(g.q_prerope, g.q_prerope.dtype, "q_prerope").data_ptr()
+                p.ldp = _i32(g.q_prerope.stride(0), "ldp")
                 p.qpre_f32 = int(g.q_prerope.dtype == torch.float32)
                 if g.qpre_raw or g.qpre_add:
                     if not p.qpre_f32 or (g.qpre_raw and g.qpre_add):
                         raise ValueError(f"gemm[{i}]: qpre_raw / qpre_add (one of them) need an fp32 q_prerope")
                     p.qpre_f32 = 2 if g.qpre_raw else 3
             if g.out2 is not None:
-                p.out2, p.ld2 = _chk(g.out2, torch.bfloat16, "out2").data_ptr(), g.out2.stride(0)
+                p.out2, p.ld2 = _chk(g.out2, torch.bfloat16, "out2").data_ptr(), _i32(g.out2.stride(0), "ld2")
         elif g.epilogue == L.EPI_SPLIT_GELU:
             if g.out2 is None:
                 raise ValueError(f"gemm[{i}]: SPLIT_GELU needs out2")
-            p.out2, p.ld2, p.n_split = _chk(g.out2, torch.bfloat16, "out2").data_ptr(), g.out2.stride(0), g.n_split
+            p.out2, p.ld2 = _chk(g.out2, torch.bfloat16, "out2").data_ptr(), _i32(g.out2.stride(0), "ld2")
+            p.n_split = _i32(g.n_split, "n_split")
     return arr, fp8
 
 
@@ -230,8 +247,8 @@ def attention(problems: Sequence[Attn], num_heads: int, scale: Optional[float] =
                                  f"got {tuple(t.shape)}")
         p = arr[i]
         p.q, p.out, p.k0, p.v0 = a.q.data_ptr(), a.out.data_ptr(), a.k0.data_ptr(), a.v0.data_ptr()
-        p.nq, p.n0 = a.q.shape[0], a.k0.shape[0]
-        p.ldq, p.ldo, p.ldkv = a.q.stride(0), a.out.stride(0), a.k0.stride(0)
+        p.nq, p.n0 = _i32(a.q.shape[0], "nq"), _i32(a.k0.shape[0], "n0")
+        p.ldq, p.ldo, p.ldkv = _i32(a.q.stride(0), "ldq"), _i32(a.out.stride(0), "ldo"), _i32(a.k0.stride(0), "ldkv")
         if a.v0.stride(0) != p.ldkv or a.v0.shape[0] != p.n0 or a.out.shape[0] != p.nq:
             raise ValueError(f"attention[{i}]: k0/v0/out row mismatch")
         p.nq0 = p.nq
@@ -240,12 +257,12 @@ def attention(problems: Sequence[Attn], num_heads: int, scale: Optional[float] =
             if a.q1.stride(0) != p.ldq or a.out1.stride(0) != p.ldo or a.out1.shape[0] != a.q1.shape[0]:
                 raise ValueError(f"attention[{i}]: both query / output segments must share one row stride")
             p.q1, p.out1 = a.q1.data_ptr(), a.out1.data_ptr()
-            p.nq = p.nq0 + a.q1.shape[0]
+            p.nq = _i32(p.nq0 + a.q1.shape[0], "nq")
         if a.k1 is not None and a.k1.shape[0] > 0:
             _chk(a.k1, torch.bfloat16, "k1"), _chk(a.v1, torch.bfloat16, "v1")
             if a.k1.stride(0) != p.ldkv or a.v1.stride(0) != p.ldkv or a.v1.shape[0] != a.k1.shape[0]:
                 raise ValueError(f"attention[{i}]: both key/value segments must share one row stride")
-            p.k1, p.v1, p.n1 = a.k1.data_ptr(), a.v1.data_ptr(), a.k1.shape[0]
+            p.k1, p.v1, p.n1 = a.k1.data_ptr(), a.v1.data_ptr(), _i32(a.k1.shape[0], "n1")
         if a.hm_con is not None or a.hm_part is not None:
             if a.hm_con is None or a.hm_part is None or a.q1 is None:
                 raise ValueError(f"attention[{i}]: hm_con, hm_part and a second query segment go together")
@@ -255,12 +272,12 @@ def attention(problems: Sequence[Attn], num_heads: int, scale: Optional[float] =
                 raise ValueError(f"attention[{i}]: hm_con must be fp32 [C <= 8, heads*128], hm_part contiguous fp32 "
                                  "[heads, rows of q1, 8]")
             p.hm_con, p.hm_part = a.hm_con.data_ptr(), a.hm_part.data_ptr()
-            p.hm_C, p.ldhc = a.hm_con.shape[0], a.hm_con.stride(0)
+            p.hm_C, p.ldhc = a.hm_con.shape[0], _i32(a.hm_con.stride(0), "ldhc")
         if a.out_f32 is not None:
             _chk(a.out_f32, torch.float32, "out_f32")
             if a.out_f32.shape[0] != p.nq:
                 raise ValueError(f"attention[{i}]: out_f32 row mismatch")
-            p.out_f32, p.ldo32 = a.out_f32.data_ptr(), a.out_f32.stride(0)
+            p.out_f32, p.ldo32 = a.out_f32.data_ptr(), _i32(a.out_f32.stride(0), "ldo32")
     if qk_f16 and not q_prescaled:
         raise ValueError("attention: qk_f16 needs q_prescaled (ca_attn_fwd_qk16)")
     if q_prescaled:
@@ -271,6 +288,7 @@ def attention(problems: Sequence[Attn], num_heads: int, scale: Optional[float] =
         scale = 1.0 / math.sqrt(128.0)
     elif not scale > 0:
         raise ValueError("attention: scale must be > 0")
+    num_heads = _i32(num_heads, "num_heads")
     if qk_f16:
         def launch():
             L.check(lib.ca_attn_fwd_qk16(arr, len(problems), num_heads, _stream()), "ca_attn_fwd_qk16")
@@ -314,7 +332,7 @@ def ln_modulate(x, out, segments, eps: float = 1e-6, out_scale=None, out_lo=None
         raise ValueError("ln_modulate: too many segments")
     arr = (L.ModSegment * len(segments))()
     for i, (row_end, shift, scale) in enumerate(segments):
-        arr[i].row_end = row_end
+        arr[i].row_end = _i32(row_end, "row_end")
         arr[i].shift = _chk(shift, torch.float32, "shift").data_ptr()
         arr[i].scale = _chk(scale, torch.float32, "scale").data_ptr()
     if out_lo is not None and not fp8:
@@ -323,13 +341,13 @@ def ln_modulate(x, out, segments, eps: float = 1e-6, out_scale=None, out_lo=None
         _chk(out_lo, torch.bfloat16, "out_lo")
         if out_lo.shape != out.shape:
             raise ValueError("ln_modulate: out_lo must have out's shape")
-        name, extra = "ca_ln_modulate_f32in_split", (out_lo.data_ptr(), out_lo.stride(0))
+        name, extra = "ca_ln_modulate_f32in_split", (out_lo.data_ptr(), _i32(out_lo.stride(0), "ld_lo"))
     elif fp8:
         name, extra = "ca_ln_modulate_f32in_fp8" if x32 else "ca_ln_modulate_fp8", (out_scale.data_ptr(),)
     else:
         name, extra = "ca_ln_modulate_f32in" if x32 else "ca_ln_modulate_bf16", ()
-    L.check(getattr(lib, name)(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), *extra, x.shape[0], x.shape[1],
-                               arr, len(segments), eps, _stream()), name)
+    L.check(getattr(lib, name)(x.data_ptr(), _i32(x.stride(0), "ldx"), out.data_ptr(), _i32(out.stride(0), "ldo"), *extra,
+                               _i32(x.shape[0], "M"), _i32(x.shape[1], "H"), arr, len(segments), eps, _stream()), name)
 
 
 def qpre_finish(x, d, norm_scale, num_heads: int, rope=None, q_out=None, q_out_scale: float = 0.0,
@@ -346,15 +364,18 @@ def qpre_finish(x, d, norm_scale, num_heads: int, rope=None, q_out=None, q_out_s
     if x.dim() != 2 or x.shape[1] != num_heads * 128 or norm_scale.numel() != 128:
         raise ValueError("qpre_finish: x must be [M, heads*128], norm_scale [128]")
     if q_out is None:
-        L.check(lib.ca_qpre_finish_f32(x.data_ptr(), x.stride(0), _ptr(d), 0 if d is None else d.stride(0),
-                                       norm_scale.data_ptr(), x.shape[0], num_heads, _stream()), "ca_qpre_finish_f32")
+        L.check(lib.ca_qpre_finish_f32(x.data_ptr(), _i32(x.stride(0), "ldx"), _ptr(d),
+                                       0 if d is None else _i32(d.stride(0), "ldd"), norm_scale.data_ptr(),
+                                       _i32(x.shape[0], "M"), _i32(num_heads, "num_heads"), _stream()), "ca_qpre_finish_f32")
         return
     _chk(q_out, torch.bfloat16, "q_out"), _chk(rope, torch.float32, "rope")
     if tuple(q_out.shape) != tuple(x.shape) or tuple(rope.shape) != (x.shape[0], 64, 2) or not rope.is_contiguous():
         raise ValueError("qpre_finish: q_out must have x's shape, rope must be contiguous [M,64,2]")
-    L.check(lib.ca_qpre_finish_rope_f32(x.data_ptr(), x.stride(0), _ptr(d), 0 if d is None else d.stride(0),
-                                        norm_scale.data_ptr(), rope.data_ptr(), q_out.data_ptr(), q_out.stride(0),
-                                        float(q_out_scale), int(bool(q_f16)), x.shape[0], num_heads, _stream()),
+    L.check(lib.ca_qpre_finish_rope_f32(x.data_ptr(), _i32(x.stride(0), "ldx"), _ptr(d),
+                                        0 if d is None else _i32(d.stride(0), "ldd"), norm_scale.data_ptr(),
+                                        rope.data_ptr(), q_out.data_ptr(), _i32(q_out.stride(0), "ldq"),
+                                        float(q_out_scale), int(bool(q_f16)), _i32(x.shape[0], "M"),
+                                        _i32(num_heads, "num_heads"), _stream()),
             "ca_qpre_finish_rope_f32")
 
 
@@ -371,8 +392,9 @@ def quantize_rows_fp8(x, out=None, out_scale=None):
     _chk(out, torch.uint8, "out"), _chk(out_scale, torch.float32, "out_scale")
     if tuple(out.shape) != tuple(x.shape) or out_scale.numel() != x.shape[0] or not out_scale.is_contiguous():
         raise ValueError("quantize_rows_fp8: out must match x, out_scale must be contiguous [M]")
-    L.check(lib.ca_quantize_rows_fp8(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), out_scale.data_ptr(),
-                                     x.shape[0], x.shape[1], _stream()), "ca_quantize_rows_fp8")
+    L.check(lib.ca_quantize_rows_fp8(x.data_ptr(), _i32(x.stride(0), "ldx"), out.data_ptr(), _i32(out.stride(0), "ldo"),
+                                     out_scale.data_ptr(), _i32(x.shape[0], "M"), _i32(x.shape[1], "K"), _stream()),
+            "ca_quantize_rows_fp8")
     return out, out_scale
 
 
@@ -386,12 +408,13 @@ def qknorm_rope(qkv, num_heads, segments, rope_cos_sin, q_prerope=None) -> None:
         raise ValueError(f"qknorm_rope: rope table must be contiguous [M,64,2], got {tuple(rope_cos_sin.shape)}")
     arr = (L.NormSegment * len(segments))()
     for i, (row_end, qs, ks) in enumerate(segments):
-        arr[i].row_end = row_end
+        arr[i].row_end = _i32(row_end, "row_end")
         arr[i].q_scale = _chk(qs, torch.bfloat16, "q_scale").data_ptr()
         arr[i].k_scale = _chk(ks, torch.bfloat16, "k_scale").data_ptr()
     pp, ldp = (None, 0) if q_prerope is None else (_chk(q_prerope, torch.bfloat16, "q_prerope").data_ptr(),
-                                                   q_prerope.stride(0))
-    L.check(lib.ca_qknorm_rope_bf16(qkv.data_ptr(), qkv.stride(0), M, num_heads, arr, len(segments),
+                                                   _i32(q_prerope.stride(0), "ldp"))
+    L.check(lib.ca_qknorm_rope_bf16(qkv.data_ptr(), _i32(qkv.stride(0), "ld"), _i32(M, "M"), _i32(num_heads, "num_heads"),
+                                    arr, len(segments),
                                     rope_cos_sin.data_ptr(), pp, ldp, _stream()), "ca_qknorm_rope_bf16")
 
 
@@ -402,8 +425,9 @@ def gemv(x, w, bias, out, silu_input=False, accumulate=False) -> None:
     if not w.is_contiguous():
         raise ValueError("gemv: w must be contiguous")
     b = _ptr(None if bias is None else _chk(bias, torch.bfloat16, "bias"))
-    L.check(lib.ca_gemv_bf16(x.data_ptr(), x.shape[0], x.stride(0), w.data_ptr(), b, out.data_ptr(), out.stride(0),
-                             w.shape[0], w.shape[1], int(silu_input), int(accumulate), _stream()), "ca_gemv_bf16")
+    L.check(lib.ca_gemv_bf16(x.data_ptr(), _i32(x.shape[0], "nv"), _i32(x.stride(0), "ldx"), w.data_ptr(), b, out.data_ptr(),
+                             _i32(out.stride(0), "ldo"), _i32(w.shape[0], "N"), _i32(w.shape[1], "K"), int(silu_input),
+                             int(accumulate), _stream()), "ca_gemv_bf16")
 
 
 def _split(what: str, symbol: str, x, hi, lo) -> None:
@@ -411,8 +435,9 @@ def _split(what: str, symbol: str, x, hi, lo) -> None:
     _chk(x, torch.float32, "x"), _chk(hi, torch.bfloat16, "hi"), _chk(lo, torch.bfloat16, "lo")
     if x.dim() != 2 or hi.shape != x.shape or lo.shape != x.shape or hi.stride(0) != lo.stride(0):
         raise ValueError(f"{what}: x, hi, lo must be [rows,K] of one shape (hi / lo of one row stride)")
-    L.check(getattr(lib, symbol)(x.data_ptr(), x.stride(0), hi.data_ptr(), lo.data_ptr(), hi.stride(0), x.shape[0],
-                                 x.shape[1], _stream()), symbol)
+    L.check(getattr(lib, symbol)(x.data_ptr(), _i32(x.stride(0), "ldx"), hi.data_ptr(), lo.data_ptr(),
+                                 _i32(hi.stride(0), "ldo"), _i32(x.shape[0], "rows"), _i32(x.shape[1], "K"), _stream()),
+            symbol)
 
 
 def silu_split(x, hi, lo) -> None:
@@ -459,8 +484,9 @@ def modulation_gemm(vecs, w, bias, out, ones) -> bool:
         gemm([Gemm(lo, w[c0:c1], None, o, L.EPI_GATE_RESIDUAL, resid=o, gate=ones[c0:c1])], L.TILE_PP_256x256)
     if pair is not None:
         _chk(out, torch.float32, "out")
-        L.check(lib.ca_modulation_combine_f32(pair.data_ptr(), pair.stride(0), _ptr(bias), out.data_ptr(), out.stride(0),
-                                              nv, N, _stream()), "ca_modulation_combine_f32")
+        L.check(lib.ca_modulation_combine_f32(pair.data_ptr(), _i32(pair.stride(0), "ldp"), _ptr(bias), out.data_ptr(),
+                                              _i32(out.stride(0), "ldo"), _i32(nv, "nv"), _i32(N, "N"), _stream()),
+                "ca_modulation_combine_f32")
     return True
 
 
@@ -476,9 +502,10 @@ def heatmap_logits(img_vec, con_vec, logits) -> None:
     Lp, dim, Cc = img_vec.shape[0], img_vec.shape[1], con_vec.shape[0]
     if tuple(logits.shape) != (Cc, Lp) or not logits.is_contiguous() or con_vec.shape[1] != dim:
         raise ValueError("heatmap_logits: shape mismatch")
-    L.check(lib.ca_heatmap_logits_bf16(img_vec.data_ptr(), img_vec.stride(0), con_vec.data_ptr(), con_vec.stride(0),
+    L.check(lib.ca_heatmap_logits_bf16(img_vec.data_ptr(), _i32(img_vec.stride(0), "ldi"), con_vec.data_ptr(),
+                                       _i32(con_vec.stride(0), "ldc"),
                                        int(con_vec.dtype == torch.float32) | 2 * int(img_vec.dtype == torch.float32),
-                                       Lp, Cc, dim, logits.data_ptr(),
+                                       _i32(Lp, "L"), _i32(Cc, "C"), _i32(dim, "dim"), logits.data_ptr(),
                                        _stream()), "ca_heatmap_logits_bf16")
 
 
@@ -489,10 +516,12 @@ def heatmap_softmax_accumulate(logits, acc, weight: float, norm: int = L.NORM_SO
     if logits.shape != acc.shape or not logits.is_contiguous() or not acc.is_contiguous():
         raise ValueError("heatmap_softmax_accumulate: logits/acc must be contiguous [C,L]")
     if norm == L.NORM_SOFTMAX:
-        L.check(lib.ca_heatmap_softmax_accumulate(logits.data_ptr(), logits.shape[0], logits.shape[1], weight,
+        L.check(lib.ca_heatmap_softmax_accumulate(logits.data_ptr(), _i32(logits.shape[0], "C"),
+                                                  _i32(logits.shape[1], "L"), weight,
                                                   acc.data_ptr(), _stream()), "ca_heatmap_softmax_accumulate")
         return
-    L.check(lib.ca_heatmap_norm_accumulate(logits.data_ptr(), logits.shape[0], logits.shape[1], int(norm), weight,
+    L.check(lib.ca_heatmap_norm_accumulate(logits.data_ptr(), _i32(logits.shape[0], "C"), _i32(logits.shape[1], "L"),
+                                           int(norm), weight,
                                            acc.data_ptr(), _stream()), "ca_heatmap_norm_accumulate")
 
 
@@ -537,14 +566,15 @@ def heatmap_fused(problems: Sequence[Heatmap], norm: int = L.NORM_SOFTMAX) -> No
             _chk(h.part, torch.float32, "part")
             if h.part.dim() != 3 or tuple(h.part.shape[1:]) != (Lp, 8) or not h.part.is_contiguous():
                 raise ValueError(f"heatmap_fused[{i}]: part must be contiguous fp32 [heads, L, 8]")
-            p.img_vec, p.ldi, p.img_f32 = h.part.data_ptr(), h.part.shape[0], 2
+            p.img_vec, p.ldi, p.img_f32 = h.part.data_ptr(), _i32(h.part.shape[0], "heads"), 2
         else:
             if h.img_vec.dtype not in (torch.bfloat16, torch.float32) or h.con_vec.dtype not in (torch.bfloat16, torch.float32):
                 raise ValueError(f"heatmap_fused[{i}]: img_vec and con_vec must be bf16 or fp32")
             _chk(h.img_vec, h.img_vec.dtype, "img_vec"), _chk(h.con_vec, h.con_vec.dtype, "con_vec")
             if tuple(h.img_vec.shape) != (Lp, dim) or tuple(h.con_vec.shape) != (Cc, dim):
                 raise ValueError(f"heatmap_fused[{i}]: all problems of a launch share L, C and dim")
-            p.img_vec, p.con_vec, p.ldi, p.ldc = h.img_vec.data_ptr(), h.con_vec.data_ptr(), h.img_vec.stride(0), h.con_vec.stride(0)
+            p.img_vec, p.con_vec = h.img_vec.data_ptr(), h.con_vec.data_ptr()
+            p.ldi, p.ldc = _i32(h.img_vec.stride(0), "ldi"), _i32(h.con_vec.stride(0), "ldc")
             p.img_f32, p.con_f32 = int(h.img_vec.dtype == torch.float32), int(h.con_vec.dtype == torch.float32)
         for name in ("acc", "acc2", "logits"):
             t = getattr(h, name)
@@ -554,7 +584,8 @@ def heatmap_fused(problems: Sequence[Heatmap], norm: int = L.NORM_SOFTMAX) -> No
                     raise ValueError(f"heatmap_fused[{i}]: {name} must be contiguous fp32 [C,L]")
                 setattr(p, name, t.data_ptr())
         p.weight, p.weight2 = float(h.weight), float(h.weight2)
-    L.check(lib.ca_heatmap_fused(arr, len(problems), Lp, Cc, dim, int(norm), _stream()), "ca_heatmap_fused")
+    L.check(lib.ca_heatmap_fused(arr, len(problems), _i32(Lp, "L"), _i32(Cc, "C"), _i32(dim, "dim"), int(norm), _stream()),
+            "ca_heatmap_fused")
 
 
 def axpy(x, y, a: float) -> None:
@@ -585,7 +616,8 @@ def timestep_embedding(t, out, time_factor: float = 1000.0, max_period: float = 
     _chk(t, torch.float32, "t"), _chk(out, torch.float32, "out")
     if out.dim() != 2 or out.shape[0] != t.shape[0] or not out.is_contiguous():
         raise ValueError("timestep_embedding: out must be contiguous [nt, dim]")
-    L.check(lib.ca_timestep_embedding_f32(t.data_ptr(), t.shape[0], out.data_ptr(), out.shape[1], time_factor,
+    L.check(lib.ca_timestep_embedding_f32(t.data_ptr(), _i32(t.shape[0], "nt"), out.data_ptr(),
+                                          _i32(out.shape[1], "dim"), time_factor,
                                           max_period, _stream()), "ca_timestep_embedding_f32")
 
 
@@ -630,8 +662,10 @@ def conv2d_nhwc(x, w_packed, bias, out, cout: int, ksize: int = 3, stride: int =
         raise ValueError("conv2d_nhwc: bias must be contiguous fp32 [cout]")
     if resid is not None and (_chk(resid, torch.float32, "resid").shape != out.shape or not resid.is_contiguous()):
         raise ValueError("conv2d_nhwc: resid must be contiguous fp32 of out's shape")
-    L.check(L.load().ca_conv3x3_nhwc(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(resid), out.data_ptr(), B, H, W,
-                                     cin, cout, x.shape[3], out.shape[3], out.shape[3], ksize, stride, int(upsample),
+    L.check(L.load().ca_conv3x3_nhwc(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(resid), out.data_ptr(),
+                                     _i32(B, "B"), _i32(H, "H"), _i32(W, "W"), _i32(cin, "cin"), _i32(cout, "cout"),
+                                     _i32(x.shape[3], "ldx"), _i32(out.shape[3], "ldo"), _i32(out.shape[3], "ldr"),
+                                     _i32(ksize, "ksize"), _i32(stride, "stride"), int(upsample),
                                      int(out.dtype == torch.float32), _stream()), "ca_conv3x3_nhwc")
 
 
@@ -654,8 +688,9 @@ def groupnorm_nhwc(x, gamma, beta, out, swish: bool, eps: float = 1e-6, part=Non
         part = torch.empty(B * n_chunks * 96, device=x.device, dtype=torch.float32)
     if _chk(part, torch.float32, "part").numel() < B * n_chunks * 96:
         raise ValueError("groupnorm_nhwc: part needs B * groupnorm_chunks(HW) * 96 floats")
+    C_ = _i32(C_, "C")
     L.check(L.load().ca_groupnorm_nhwc(x.data_ptr(), int(x.dtype == torch.float32), C_, gamma.data_ptr(), beta.data_ptr(),
-                                       out.data_ptr(), C_, B, hw, C_, eps, int(swish), part.data_ptr(), n_chunks,
+                                       out.data_ptr(), C_, _i32(B, "B"), hw, C_, eps, int(swish), part.data_ptr(), n_chunks,
                                        _stream()), "ca_groupnorm_nhwc")
 
 
@@ -664,7 +699,8 @@ def softmax_rows(s, p, n: int, scale: float) -> None:
     _chk(s, torch.float32, "s"), _chk(p, torch.bfloat16, "p")
     if s.dim() != 2 or p.dim() != 2 or s.shape[0] != p.shape[0]:
         raise ValueError("softmax_rows: s and p must be 2-D with the same rows")
-    L.check(L.load().ca_softmax_rows_f32(s.data_ptr(), s.stride(0), p.data_ptr(), p.stride(0), s.shape[0], n, scale,
+    L.check(L.load().ca_softmax_rows_f32(s.data_ptr(), _i32(s.stride(0), "lds"), p.data_ptr(), _i32(p.stride(0), "ldp"),
+                                         _i32(s.shape[0], "rows"), _i32(n, "n"), scale,
                                          _stream()), "ca_softmax_rows_f32")
 
 
@@ -677,9 +713,11 @@ def affine_rows(x, out, a: float = 1.0, b: float = 0.0, logvar=None, noise=None,
     for t in (logvar, noise):
         if t is not None and (_chk(t, torch.float32, "logvar/noise").dim() != 2 or t.shape[0] != x.shape[0]):
             raise ValueError("affine_rows: logvar / noise must be 2-D fp32 with x's rows")
-    L.check(L.load().ca_affine_rows_f32(x.data_ptr(), x.stride(0), _ptr(logvar), 0 if logvar is None else logvar.stride(0),
-                                        _ptr(noise), 0 if noise is None else noise.stride(0), out.data_ptr(),
-                                        out.stride(0), int(out.dtype == torch.float32), x.shape[0], cols, a, b,
+    L.check(L.load().ca_affine_rows_f32(x.data_ptr(), _i32(x.stride(0), "ldx"), _ptr(logvar),
+                                        0 if logvar is None else _i32(logvar.stride(0), "ldl"), _ptr(noise),
+                                        0 if noise is None else _i32(noise.stride(0), "ldn"), out.data_ptr(),
+                                        _i32(out.stride(0), "ldo"), int(out.dtype == torch.float32), x.shape[0],
+                                        _i32(cols, "cols"), a, b,
                                         _stream()), "ca_affine_rows_f32")
 
 
@@ -695,8 +733,10 @@ def pixels_to_nhwc32(src, dst) -> None:
             not dst.is_contiguous() or src.device != dst.device:
         raise ValueError(f"pixels_to_nhwc32: src{tuple(src.shape)} must be uint8 [H0, W0, 3] with adjacent pixels, dst"
                          f"{tuple(dst.shape)} contiguous bf16 [H, W, 32] on the same device")
-    L.check(L.load().ca_pixels_u8_to_nhwc32_bf16(src.data_ptr(), src.stride(0), dst.data_ptr(), src.shape[0], src.shape[1],
-                                                 dst.shape[0], dst.shape[1], _stream()), "ca_pixels_u8_to_nhwc32_bf16")
+    src_stride = int(src.stride(0))   # bytes, an int64_t of the entry point: the only stride that is not an int32_t
+    L.check(L.load().ca_pixels_u8_to_nhwc32_bf16(src.data_ptr(), src_stride, dst.data_ptr(), _i32(src.shape[0], "H0"),
+                                                 _i32(src.shape[1], "W0"), _i32(dst.shape[0], "H"), _i32(dst.shape[1], "W"),
+                                                 _stream()), "ca_pixels_u8_to_nhwc32_bf16")
 
 
 def nhwc_to_pixels(src, dst) -> None:
@@ -707,7 +747,8 @@ def nhwc_to_pixels(src, dst) -> None:
             not src.is_contiguous() or not dst.is_contiguous() or src.device != dst.device:
         raise ValueError(f"nhwc_to_pixels: src{tuple(src.shape)} must be contiguous fp32 [..., ld >= 3], dst"
                          f"{tuple(dst.shape)} contiguous uint8 [..., 3] of the same pixels on the same device")
-    L.check(L.load().ca_nhwc_f32_to_pixels_u8(src.data_ptr(), src.shape[-1], dst.data_ptr(), dst.numel() // 3, _stream()),
+    L.check(L.load().ca_nhwc_f32_to_pixels_u8(src.data_ptr(), _i32(src.shape[-1], "ld"), dst.data_ptr(), dst.numel() // 3,
+                                              _stream()),
             "ca_nhwc_f32_to_pixels_u8")
 
 
@@ -796,8 +837,9 @@ def t5_attention(q, k, v, bias, out, n_seq: int, num_heads: int) -> None:
         raise ValueError(f"t5_attention: bias must be contiguous fp32 [num_heads, 2 L - 1] = [{num_heads}, {2 * Lq - 1}], "
                          f"got {tuple(bias.shape)}")
     L.check(L.load().ca_t5_attn_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), bias.data_ptr(), out.data_ptr(),
-                                     q.stride(0), k.stride(0), v.stride(0), out.stride(0), n_seq, num_heads, Lq,
-                                     _stream()), "ca_t5_attn_bf16")
+                                     _i32(q.stride(0), "ldq"), _i32(k.stride(0), "ldk"), _i32(v.stride(0), "ldv"),
+                                     _i32(out.stride(0), "ldo"), _i32(n_seq, "n_seq"), _i32(num_heads, "num_heads"),
+                                     _i32(Lq, "L"), _stream()), "ca_t5_attn_bf16")
 
 
 def t5_rmsnorm(x, weight, out, eps: float = 1e-6) -> None:
@@ -805,8 +847,9 @@ def t5_rmsnorm(x, weight, out, eps: float = 1e-6) -> None:
     _chk(x, torch.float32, "x"), _chk(weight, torch.float32, "weight"), _chk(out, torch.bfloat16, "out")
     if x.dim() != 2 or out.shape != x.shape or weight.numel() != x.shape[1] or not weight.is_contiguous():
         raise ValueError("t5_rmsnorm: x and out must be 2-D of one shape, weight contiguous [H]")
-    L.check(L.load().ca_t5_rmsnorm_f32in(x.data_ptr(), x.stride(0), weight.data_ptr(), out.data_ptr(), out.stride(0),
-                                         x.shape[0], x.shape[1], eps, _stream()), "ca_t5_rmsnorm_f32in")
+    L.check(L.load().ca_t5_rmsnorm_f32in(x.data_ptr(), _i32(x.stride(0), "ldx"), weight.data_ptr(), out.data_ptr(),
+                                         _i32(out.stride(0), "ldo"), x.shape[0], _i32(x.shape[1], "H"), eps, _stream()),
+            "ca_t5_rmsnorm_f32in")
 
 
 def gated_mul(g, u, out) -> None:
@@ -814,8 +857,9 @@ def gated_mul(g, u, out) -> None:
     _chk(g, torch.bfloat16, "g"), _chk(u, torch.bfloat16, "u"), _chk(out, torch.bfloat16, "out")
     if g.dim() != 2 or u.shape != g.shape or out.shape != g.shape:
         raise ValueError("gated_mul: g, u and out must be 2-D of one shape")
-    L.check(L.load().ca_gated_mul_bf16(g.data_ptr(), g.stride(0), u.data_ptr(), u.stride(0), out.data_ptr(), out.stride(0),
-                                       g.shape[0], g.shape[1], _stream()), "ca_gated_mul_bf16")
+    L.check(L.load().ca_gated_mul_bf16(g.data_ptr(), _i32(g.stride(0), "ldg"), u.data_ptr(), _i32(u.stride(0), "ldu"),
+                                       out.data_ptr(), _i32(out.stride(0), "ldo"), g.shape[0], _i32(g.shape[1], "C"),
+                                       _stream()), "ca_gated_mul_bf16")
 
 
 def _chk_fp8_out(what: str, out, out_scale, shape) -> None:
@@ -834,8 +878,9 @@ def t5_rmsnorm_fp8(x, weight, out, out_scale, eps: float = 1e-6) -> None:
     if x.dim() != 2 or weight.numel() != x.shape[1] or not weight.is_contiguous():
         raise ValueError("t5_rmsnorm_fp8: x must be 2-D, weight contiguous [H]")
     _chk_fp8_out("t5_rmsnorm_fp8", out, out_scale, x.shape)
-    L.check(L.load().ca_t5_rmsnorm_f32in_fp8(x.data_ptr(), x.stride(0), weight.data_ptr(), out.data_ptr(), out.stride(0),
-                                             out_scale.data_ptr(), x.shape[0], x.shape[1], eps, _stream()),
+    L.check(L.load().ca_t5_rmsnorm_f32in_fp8(x.data_ptr(), _i32(x.stride(0), "ldx"), weight.data_ptr(), out.data_ptr(),
+                                             _i32(out.stride(0), "ldo"), out_scale.data_ptr(), x.shape[0],
+                                             _i32(x.shape[1], "H"), eps, _stream()),
             "ca_t5_rmsnorm_f32in_fp8")
 
 
@@ -847,8 +892,9 @@ def gated_mul_fp8(g, u, out, out_scale) -> None:
     if g.dim() != 2 or u.shape != g.shape:
         raise ValueError("gated_mul_fp8: g and u must be 2-D of one shape")
     _chk_fp8_out("gated_mul_fp8", out, out_scale, g.shape)
-    L.check(L.load().ca_gated_mul_fp8(g.data_ptr(), g.stride(0), u.data_ptr(), u.stride(0), out.data_ptr(), out.stride(0),
-                                      out_scale.data_ptr(), g.shape[0], g.shape[1], _stream()), "ca_gated_mul_fp8")
+    L.check(L.load().ca_gated_mul_fp8(g.data_ptr(), _i32(g.stride(0), "ldg"), u.data_ptr(), _i32(u.stride(0), "ldu"),
+                                      out.data_ptr(), _i32(out.stride(0), "ldo"), out_scale.data_ptr(), g.shape[0],
+                                      _i32(g.shape[1], "C"), _stream()), "ca_gated_mul_fp8")
 
 
 def embed_rows(table, ids, out) -> None:
@@ -863,8 +909,9 @@ def embed_rows(table, ids, out) -> None:
     if lo < 0 or hi >= table.shape[0]:
         raise ValueError(f"embed_rows: ids span [{lo}, {hi}], outside the vocabulary [0, {table.shape[0]})")
     ids = ids.to(table.device)
-    L.check(L.load().ca_embed_rows_f32(table.data_ptr(), table.stride(0), ids.data_ptr(), out.data_ptr(), out.stride(0),
-                                       ids.shape[0], table.shape[1], _stream()), "ca_embed_rows_f32")
+    L.check(L.load().ca_embed_rows_f32(table.data_ptr(), _i32(table.stride(0), "ldt"), ids.data_ptr(), out.data_ptr(),
+                                       _i32(out.stride(0), "ldo"), ids.shape[0], _i32(table.shape[1], "H"), _stream()),
+            "ca_embed_rows_f32")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -880,9 +927,10 @@ def clip_attention(q, k, v, out, n_seq: int, num_heads: int, scale: float = 0.12
             raise ValueError(f"clip_attention: {n} must be 2-D [n_seq * L, num_heads*64 = {num_heads * 64}], got {tuple(t.shape)}")
     if n_seq < 1 or q.shape[0] % n_seq:
         raise ValueError(f"clip_attention: {q.shape[0]} rows are not n_seq = {n_seq} sequences of one length")
-    L.check(L.load().ca_clip_attn_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), q.stride(0), k.stride(0),
-                                       v.stride(0), out.stride(0), n_seq, num_heads, q.shape[0] // n_seq, float(scale),
-                                       _stream()), "ca_clip_attn_bf16")
+    L.check(L.load().ca_clip_attn_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _i32(q.stride(0), "ldq"),
+                                       _i32(k.stride(0), "ldk"), _i32(v.stride(0), "ldv"), _i32(out.stride(0), "ldo"),
+                                       _i32(n_seq, "n_seq"), _i32(num_heads, "num_heads"), _i32(q.shape[0] // n_seq, "L"),
+                                       float(scale), _stream()), "ca_clip_attn_bf16")
 
 
 def layernorm(x, weight, bias, out, eps: float = 1e-5, row_idx=None) -> None:
@@ -905,8 +953,9 @@ def layernorm(x, weight, bias, out, eps: float = 1e-5, row_idx=None) -> None:
         if lo < 0 or hi >= x.shape[0]:
             raise ValueError(f"layernorm: row_idx spans [{lo}, {hi}], outside the rows of x [0, {x.shape[0]})")
         idx = row_idx.to(x.device)
-    L.check(L.load().ca_layernorm_f32in(x.data_ptr(), x.stride(0), _ptr(idx), weight.data_ptr(), bias.data_ptr(),
-                                        out.data_ptr(), out.stride(0), out.shape[0], x.shape[1], eps, _stream()),
+    L.check(L.load().ca_layernorm_f32in(x.data_ptr(), _i32(x.stride(0), "ldx"), _ptr(idx), weight.data_ptr(),
+                                        bias.data_ptr(), out.data_ptr(), _i32(out.stride(0), "ldo"), out.shape[0],
+                                        _i32(x.shape[1], "H"), eps, _stream()),
             "ca_layernorm_f32in")
 
 
@@ -915,8 +964,8 @@ def quick_gelu(x, out) -> None:
     _chk(x, torch.bfloat16, "x"), _chk(out, torch.bfloat16, "out")
     if x.dim() != 2 or out.shape != x.shape:
         raise ValueError("quick_gelu: x and out must be 2-D of one shape")
-    L.check(L.load().ca_quick_gelu_bf16(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), x.shape[0], x.shape[1],
-                                        _stream()), "ca_quick_gelu_bf16")
+    L.check(L.load().ca_quick_gelu_bf16(x.data_ptr(), _i32(x.stride(0), "ldx"), out.data_ptr(), _i32(out.stride(0), "ldo"),
+                                        x.shape[0], _i32(x.shape[1], "C"), _stream()), "ca_quick_gelu_bf16")
 
 
 def clip_embed(tok, pos, ids, out, length: int) -> None:
@@ -933,6 +982,8 @@ def clip_embed(tok, pos, ids, out, length: int) -> None:
     if lo < 0 or hi >= tok.shape[0]:
         raise ValueError(f"clip_embed: ids span [{lo}, {hi}], outside the vocabulary [0, {tok.shape[0]})")
     ids = ids.to(tok.device)
-    L.check(L.load().ca_clip_embed_f32(tok.data_ptr(), tok.stride(0), pos.data_ptr(), pos.stride(0), ids.data_ptr(),
-                                       out.data_ptr(), out.stride(0), ids.shape[0], length, tok.shape[1], _stream()),
+    L.check(L.load().ca_clip_embed_f32(tok.data_ptr(), _i32(tok.stride(0), "ldt"), pos.data_ptr(),
+                                       _i32(pos.stride(0), "ldp"), ids.data_ptr(), out.data_ptr(),
+                                       _i32(out.stride(0), "ldo"), ids.shape[0],
+                                       _i32(length, "length"), _i32(tok.shape[1], "H"), _stream()),
             "ca_clip_embed_f32")

@@ -5,7 +5,9 @@ from __future__ import annotations
 
 import numpy as np
 
+import clip_cases as CL
 import gemm_route_cases as G
+import t5_cases as T5
 import vae_cases as V
 from conceptattention_amd import _lib as L
 
@@ -96,6 +98,74 @@ VAE_PAST = [("conv_5x7_c96_o48_s1_resid_f32", "x"), ("conv_5x7_c96_o48_s1_resid_
             ("gn_C64_hw7_f32", "x"), ("gn_C64_hw7_f32", "y"), ("softmax_n63", "s"), ("softmax_n63", "p"),
             ("affine_decode_bf16", "x"), ("affine_decode_bf16", "out")]
 VAE_PAST_OWN_TEST = ("softmax_n63", "p")
+
+
+# the text, pixel and scoring kernels (ca_t5.hip, ca_clip.hip, ca_pixels.hip, ca_seg.hip): per entry point one small case
+# of its case table in which every operand role is present, as the argument of the run helper of its kernel test file
+# (tests/test_address_range_gpu.TEXT_RUN), and the roles that helper names
+TEXT_PLACEMENT = {
+    "ca_t5_attn_bf16": T5.AttnCase(2, 3, 192, "contig", "std8"),
+    "ca_t5_rmsnorm_f32in": (256, 7, True),
+    "ca_t5_rmsnorm_f32in_fp8": (256, 5, True),
+    "ca_gated_mul_bf16": (512, 7, True),
+    "ca_gated_mul_fp8": (512, 3),
+    "ca_embed_rows_f32": (256, 7, True),
+    "ca_clip_attn_bf16": CL.AttnCase(3, 2, 77, "apart"),
+    "ca_layernorm_f32in": (256, CL.LN_ROWS, True),          # run with the row_idx gather
+    "ca_quick_gelu_bf16": (512, 7, True),
+    "ca_clip_embed_f32": 256,
+    "ca_pixels_u8_to_nhwc32_bf16": (5, 7, 16, 24),
+    "ca_nhwc_f32_to_pixels_u8": (2, 3, 5, 32),
+    "ca_seg_score": "map16x16-label64x64",
+}
+TEXT_ROLES = {
+    "ca_t5_attn_bf16": ["q", "k", "v", "bias", "out"],
+    "ca_t5_rmsnorm_f32in": ["x", "w", "out"],
+    "ca_t5_rmsnorm_f32in_fp8": ["x", "w", "out", "out_scale"],
+    "ca_gated_mul_bf16": ["g", "u", "out"],
+    "ca_gated_mul_fp8": ["g", "u", "out", "out_scale"],     # (g and u: the two halves of one SPLIT_GELU buffer)
+    "ca_embed_rows_f32": ["table", "ids", "out"],
+    "ca_clip_attn_bf16": ["q", "k", "v", "out"],
+    "ca_layernorm_f32in": ["x", "row_idx", "w", "b", "out"],
+    "ca_quick_gelu_bf16": ["x", "out"],
+    "ca_clip_embed_f32": ["tok", "pos", "ids", "out"],
+    "ca_pixels_u8_to_nhwc32_bf16": ["src", "dst"],
+    "ca_nhwc_f32_to_pixels_u8": ["src", "dst"],
+    "ca_seg_score": ["map", "label", "result", "mask_out", "coeff_out"],
+}
+# the operands with a free row stride, each run once with its last row more than 4 GiB from its base:
+# (entry point, the run helper's case, role, rows of the far buffer, bytes per element).  64 rows for the attention
+# kernels (one tile of T5's, L = 64 of CLIP's; no guard rows), 5 to 9 elsewhere (tok: a vocabulary of 8, pos: its 77 rows)
+T5_FAR_ATTN, CLIP_FAR_ATTN = T5.AttnCase(1, 1, 64, "contig", "std1"), CL.AttnCase(1, 2, 64, "apart")
+TEXT_PAST = [("ca_t5_attn_bf16", T5_FAR_ATTN, role, 64, 2) for role in ("q", "k", "v", "out")] + \
+            [("ca_clip_attn_bf16", CLIP_FAR_ATTN, role, 64, 2) for role in ("q", "k", "v", "out")] + [
+    ("ca_t5_rmsnorm_f32in", (256, 7, True), "x", 7, 4), ("ca_t5_rmsnorm_f32in", (256, 7, True), "out", 7, 2),
+    ("ca_t5_rmsnorm_f32in_fp8", (256, 5, True), "x", 5, 4), ("ca_t5_rmsnorm_f32in_fp8", (256, 5, True), "out", 5, 1),
+    ("ca_gated_mul_bf16", (512, 7, True), "g", 7, 2), ("ca_gated_mul_bf16", (512, 7, True), "u", 7, 2),
+    ("ca_gated_mul_bf16", (512, 7, True), "out", 7, 2),
+    ("ca_gated_mul_fp8", (512, 7), "g", 7, 2), ("ca_gated_mul_fp8", (512, 7), "out", 7, 1),
+    ("ca_embed_rows_f32", (256, 7, True), "table", 8, 2), ("ca_embed_rows_f32", (256, 7, True), "out", 7, 4),
+    ("ca_layernorm_f32in", (256, CL.LN_ROWS, True), "x", 9, 4), ("ca_layernorm_f32in", (256, CL.LN_ROWS, True), "out", 6, 2),
+    ("ca_layernorm_f32in", (256, CL.LN_ROWS, False), "x", 9, 4),         # row by row, without the gather
+    ("ca_layernorm_f32in", (256, CL.LN_ROWS, False), "out", 9, 2),
+    ("ca_quick_gelu_bf16", (512, 7, True), "x", 7, 2), ("ca_quick_gelu_bf16", (512, 7, True), "out", 7, 2),
+    ("ca_clip_embed_f32", 256, "tok", 8, 2), ("ca_clip_embed_f32", 256, "pos", 77, 2),
+    ("ca_clip_embed_f32", 256, "out", 231, 4),
+]
+# the operands of these entry points that have a free row stride (the others are contiguous by contract: bias, weights,
+# ids, row_idx, out_scale, the pixel planes, everything of ca_seg_score).  The src of ca_pixels_u8_to_nhwc32_bf16 has a
+# free BYTE stride (an int64_t) over a 3-D buffer: a test of its own.
+TEXT_FREE_STRIDES = {
+    "ca_t5_attn_bf16": {"q", "k", "v", "out"}, "ca_clip_attn_bf16": {"q", "k", "v", "out"},
+    "ca_t5_rmsnorm_f32in": {"x", "out"}, "ca_t5_rmsnorm_f32in_fp8": {"x", "out"},
+    "ca_gated_mul_bf16": {"g", "u", "out"}, "ca_gated_mul_fp8": {"g", "out"},      # (g: the buffer that holds g and u)
+    "ca_embed_rows_f32": {"table", "out"}, "ca_layernorm_f32in": {"x", "out"}, "ca_quick_gelu_bf16": {"x", "out"},
+    "ca_clip_embed_f32": {"tok", "pos", "out"}, "ca_pixels_u8_to_nhwc32_bf16": {"src"},
+    "ca_nhwc_f32_to_pixels_u8": set(), "ca_seg_score": set(),
+}
+TEXT_PAST_OWN_TEST = ("ca_pixels_u8_to_nhwc32_bf16", "src")
+PIXEL_FAR = (5, 7, 16, 24)              # five source rows, their byte stride from far_ld(5, 1, PAST_4GIB)
+BAD_STRIDE = (1 << 32) + 256            # a row stride whose low 32 bits pass `ld >= H`: ops._i32 refuses it
 
 
 def vae_roles(case) -> list:

@@ -68,6 +68,9 @@ MODEL_REL_RMS = 1e-2
 # Measured on MI355X, tests/test_clip_kernels_gpu.py (largest printed max err / bound per kernel): attention 0.713
 # (L = 15), 0.702 (L = 64), 0.689 (L = 77); layernorm 0.965 and quick_gelu 0.981 (both the bf16 store's half ulp next to a
 # power of two); embed exact.  No constant above was changed after a measurement.
+# With the later cases: layernorm 0.980 (65541 x 264, the grid wrap, row by row and gathered), 0.975 (H = 1032); quick_gelu
+# 0.981 (43692 x 3072, the grid wrap, and C = 2056); embed exact, H = 8 and the 174790 x 768 wrap included; attention
+# unchanged at 0.713.
 
 
 def _gen(tag: str) -> torch.Generator:
@@ -180,8 +183,34 @@ def attn_emulated(q, k, v, n_seq, heads, scale=SCALE, slip=None):
 # ---------------------------------------------------------------------------------------------------------- LayerNorm
 LN_H = (64, 256, 768)
 LN_ROWS = 9
-LN_CASES = [(H, strided) for H in LN_H for strided in (False, True)]
+# (H, rows, strided).  The column loop steps 1024 elements per pass: 1032 is one whole pass and a second one that two of
+# the 256 threads enter; 4 is the entry point's minimum width (one thread works, 255 bring 0 to the reductions)
+WIDTH_ROWS = (1, 7)
+LN_CASES = [(H, LN_ROWS, strided) for H in LN_H for strided in (False, True)] + \
+           [(H, rows, strided) for H in (1032, 4) for rows in WIDTH_ROWS for strided in (False, True)]
 LN_GATHER = (5, 0, 8, 5, 2, 2)     # out of order and repeated
+
+
+def ln_id(case) -> str:
+    H, rows, strided = case
+    return f"{H}-{strided}" if rows == LN_ROWS else f"{H}-{rows}-{strided}"
+
+
+def ln_gather(rows: int) -> tuple:
+    """Rows of x to read, out of order and repeated, the last row among them."""
+    return tuple(min(i, rows - 1) for i in LN_GATHER)
+
+
+# ---- grid wrap: the capped grids of ca_clip.hip, restated
+ROW_GRID_CAP = 65536                 # workgroups, one row each: `rows < 65536 ? rows : 65536` (ca_clip.hip:256)
+ELEM_GRID_CAP = 65536 * 256          # threads, 8 elements each: `if (blocks > 65536) blocks = 65536` (ca_clip.hip:298, 335)
+WRAP_ROWS, WRAP_H = ROW_GRID_CAP + 5, 264
+# op -> (units of work: rows or threads, the cap in the same units, units per workgroup, the case itself)
+WRAP_CASES = {
+    "layernorm": (WRAP_ROWS, ROW_GRID_CAP, 1, dict(H=WRAP_H, rows=WRAP_ROWS)),
+    "quick_gelu": (43692 * (3072 // 8), ELEM_GRID_CAP, 256, dict(C=3072, rows=43692)),
+    "clip_embed": (77 * 2270 * (768 // 8), ELEM_GRID_CAP, 256, dict(H=768, rows=77 * 2270)),   # rows a multiple of 77
+}
 
 
 def ln_inputs(H, rows=LN_ROWS):
@@ -230,6 +259,8 @@ def layernorm_emulated(x, w, b, eps=EPS, slip=None):
 
 # ---------------------------------------------------------------------------------------------------------- quick_gelu
 QG_CASES = [(C, rows, strided) for (C, rows) in ((512, 7), (3072, 3)) for strided in (False, True)]
+# 8 elements per thread: 2056 is 257 threads' worth per row (no multiple of the wave), 8 the entry point's minimum width
+QG_CASES += [(C, rows, strided) for C in (2056, 8) for rows in WIDTH_ROWS for strided in (False, True)]
 
 
 def quick_gelu_inputs(C, rows):
@@ -261,7 +292,7 @@ def quick_gelu_emulated(x, slip=None):
 
 # ---------------------------------------------------------------------------------------------------------- embedding
 EMBED_L, EMBED_SEQ = 77, 3
-EMBED_H = (64, 256)
+EMBED_H = (64, 256, 8)             # 8: the entry point's minimum width
 
 
 def embed_inputs(H, vocab=512, L=EMBED_L, n_seq=EMBED_SEQ):

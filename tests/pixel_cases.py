@@ -27,6 +27,18 @@ RESIZE_CASES = [
 ]
 
 
+# ---- grid wrap: both kernels launch at most PIX_MAX_BLOCKS = 2048 workgroups (ca_pixels.hip:8, 54, 124) of 256 threads and
+# walk the rest with the grid's stride.  A thread of the input kernel owns a quarter of a pixel (one 16-byte store), a
+# thread of the output kernel 16 output bytes.
+PIXEL_GRID_CAP = 2048 * 256
+# op -> (threads' worth of work, the cap in threads, threads per workgroup, the case itself)
+WRAP_CASES = {
+    "pixels_to_nhwc32": (514 * 257 * 4, PIXEL_GRID_CAP, 256, dict(h0=37, w0=53, h=514, w=257)),     # non-integer factors
+    "nhwc_to_pixels": ((2797571 * 3 + 15) // 16, PIXEL_GRID_CAP, 256, dict(pixels=2797571)),         # 9 bytes behind the last unit
+}
+PRODUCT_RESIZE = (375, 500, 1024, 1024)      # an evaluation image into the product's size: eight trips through the loop
+
+
 def nearest_index(n_out: int, n_in: int) -> np.ndarray:
     """int64 [n_out]: the source index of every destination index, in fp32 as torch computes it."""
     scale = np.float32(n_in) / np.float32(n_out)

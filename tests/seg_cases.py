@@ -21,6 +21,7 @@ import torch
 ENTRY = "ca_seg_score"
 MAX_CELLS = 4096
 MAX_PROBLEMS = 16
+MAX_LABEL_PIXELS = 1 << 24
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "metrics.npz")
 f32 = np.float32
 
@@ -210,11 +211,29 @@ def _cases() -> list:
         Case("labels-all-negative", 16, 16, 64, 64, seed=7, label="zeros"),
         Case("full-sort-4096-distinct", 64, 64, 224, 224, seed=8, kind="distinct"),
         Case("three-cells", 1, 3, 5, 7, seed=9),
+        # label sizes beyond 224 x 224: score_images' own, an ordinary evaluation label, the entry point's limit (2^24
+        # pixels on four cells: every count of the record and of the two tables reaches 2^22 .. 2^24)
+        Case("map64x64-label1024x1024", 64, 64, 1024, 1024, seed=1),
+        Case("map48x64-label375x500", 48, 64, 375, 500, seed=1),      # rectangular; 6144 entries sorted as 8192
+        Case("map2x2-label4096x4096", 2, 2, 4096, 4096, seed=1),
+        # the dynamic-LDS request crosses 64 KiB where the padded sort size jumps from 4096 to 8192 entries: 2048 cells
+        # (57 856 bytes) are the largest launch inside the default limit, 2049 (90 672 bytes) the smallest that raises it
+        Case("map32x64-label224x224", 32, 64, 224, 224, seed=1),
+        Case("map3x683-label224x224", 3, 683, 224, 224, seed=1),
     ]
     return out
 
 
 CASES = _cases()
+LDS_DEFAULT_LIMIT = 64 * 1024
+
+
+def lds_bytes(cells: int) -> int:
+    """The dynamic LDS ca_seg_score asks for (ca_seg.hip: sort entries, x, tot, pos, scratch)."""
+    npad = 2
+    while npad < 2 * cells:
+        npad <<= 1
+    return npad * 8 + (cells + 3) // 4 * 4 * 12 + 512
 
 
 def cap_launch_inputs():

@@ -55,6 +55,10 @@ EPS = 1e-6
 # Measured on MI355X, tests/test_t5_kernels_gpu.py (largest printed max err / bound per kernel): attention 0.750 (std8),
 # 0.696 (far), 0.562 (std1); rmsnorm 0.980 and gated_mul 0.988 (both the bf16 store's half ulp next to a power of two);
 # embed exact.  No constant above was changed after a measurement.
+# With the later cases (same file, largest per kernel): attention 0.811 (2x3x192 std8), 0.804 (L = 320), 0.793 (L = 448);
+# rmsnorm 0.980 (65541 x 264, the grid wrap), 0.975 (H = 1032), 0.808 (H = 4); gated_mul 0.988 (13108 x 10240, the grid
+# wrap, and C = 2056); embed exact, the 32769 x 4096 wrap included.  The same cases at bit 31, across a 2^32 line and with
+# far rows (tests/test_address_range_gpu.py) give the bits of the plain run.
 
 
 def _gen(tag: str) -> torch.Generator:
@@ -87,6 +91,9 @@ ATTN_SHAPES = [(1, 1, 64),      # one tile
                (2, 3, 192),     # odd head count, L no power of two
                (1, 64, 64),     # the real head count
                (5, 4, 256),
+               (1, 2, 320),     # NT = 20, 24, 28: with 64 .. 256 and 512 every instantiation of ca_t5_attn_kernel<NT>, each
+               (2, 1, 384),     # with its own LDS carve (rows of L + 16), score-register count and unroll
+               (1, 3, 448),
                (1, 2, 512)]     # the maximum: offsets beyond the 128 clamp on both sides
 ATTN_CASES = [AttnCase(n, h, L, layout, fam) for (n, h, L) in ATTN_SHAPES for layout in ("contig", "sliced")
               for fam in ("std1", "std8", "far")]
@@ -182,7 +189,25 @@ def attn_emulated(q, k, v, bias, n_seq, heads, slip=None, weight=None, n_real=No
 # ---------------------------------------------------------------------------------------------------------- row kernels
 ROW_H = (256, 4096)
 ROW_ROWS = (1, 7, 1280)
-ROW_CASES = [(H, rows, strided) for H in ROW_H for rows in ROW_ROWS for strided in (False, True)]
+EMBED_CASES = [(H, rows, strided) for H in ROW_H for rows in ROW_ROWS for strided in (False, True)]
+# the column loops step 1024 elements per pass (2048 in the e4m3 producers, t5_fp8_cases.py): 1032 and 2056 are one whole
+# pass and a second one that two (one) of the 256 threads enter; 4 and 8 are the entry points' minimum widths
+WIDTH_ROWS = (1, 7)
+ROW_CASES = EMBED_CASES + [(H, rows, strided) for H in (1032, 4) for rows in WIDTH_ROWS for strided in (False, True)]
+EMBED_CASES = EMBED_CASES + [(8, rows, strided) for rows in WIDTH_ROWS for strided in (False, True)]
+GATE_CASES = [(C, rows, strided) for C in (512, 10240) for rows in ROW_ROWS for strided in (False, True)] + \
+             [(C, rows, strided) for C in (2056, 8) for rows in WIDTH_ROWS for strided in (False, True)]
+# ---- grid wrap: the capped grids of ca_t5.hip, restated.  A case that exceeds its cap sends workgroups through a second
+# iteration of the kernel's stride loop (in the row kernels with the 4-float `red` array reused across iterations).
+ROW_GRID_CAP = 65536                 # workgroups, one row each: `rows < 65536 ? rows : 65536` (ca_t5.hip:241, 322, 405)
+ELEM_GRID_CAP = 65536 * 256          # threads, 8 elements each: `if (blocks > 65536) blocks = 65536` (ca_t5.hip:357, 438)
+WRAP_ROWS, WRAP_H = ROW_GRID_CAP + 5, 264
+# op -> (units of work: rows or threads, the cap in the same units, units per workgroup, the case itself)
+WRAP_CASES = {
+    "t5_rmsnorm": (WRAP_ROWS, ROW_GRID_CAP, 1, dict(H=WRAP_H, rows=WRAP_ROWS)),
+    "gated_mul": (13108 * (10240 // 8), ELEM_GRID_CAP, 256, dict(C=10240, rows=13108)),
+    "embed_rows": (32769 * (4096 // 8), ELEM_GRID_CAP, 256, dict(H=4096, rows=32769)),
+}
 ROW_MAGNITUDES = (1.0, 1e-2, 1e4, 3.0)    # row r is scaled by ROW_MAGNITUDES[r % 4]: 1e-2 makes eps matter, 1e4 is large
 
 

@@ -59,9 +59,22 @@ HALF_STEP_SUB = 2.0 ** -10       # half an e4m3 step in the subnormal range (tim
 # Measured on MI355X, tests/test_t5_fp8_kernels_gpu.py (largest printed error / bound): rmsnorm scale 0.112, value 0.985;
 # gated product scale 0.398, value 0.985 (an e4m3 tie: half a step, under the second-order factor).  No constant above was
 # changed after a measurement.
+# With the later cases: the grid wrap (65541 x 264) rmsnorm scale 0.147, value 0.985 (4 of 17 302 824 bytes differ from the
+# CPU emulation, inside the bound), gated product scale 0.422, value 0.985 (no byte differs); widths 2056 and 8: scale at
+# most 0.420, value at most 0.984.
 
 RMS_CASES = [(H, rows, strided) for H in (256, 4096) for rows in (1, 5, 257) for strided in (False, True)]
 GATE_CASES = [(C, rows) for C in (512, 10240) for rows in (1, 3, 130)]
+# the column loops step 2048 elements per pass: 2056 is one whole pass and a second one that thread 0 alone enters; 8 is
+# the entry points' minimum width (one thread works, 255 bring 0 to the reductions)
+RMS_CASES += [(H, rows, strided) for H in (2056, 8) for rows in (1, 7) for strided in (False, True)]
+GATE_CASES += [(C, rows) for C in (2056, 8) for rows in (1, 7)]
+# grid wrap: both producers launch one workgroup per row up to 65536 (`rows < 65536 ? rows : 65536`, ca_t5.hip:322, 405) and
+# walk the rest with the grid's stride, with the 4-float `red` array of t5_block_sum / t5_block_max reused
+ROW_GRID_CAP = 65536
+WRAP_ROWS, WRAP_WIDTH = ROW_GRID_CAP + 5, 264
+WRAP_CASES = {"t5_rmsnorm_fp8": (WRAP_ROWS, ROW_GRID_CAP, 1, dict(H=WRAP_WIDTH, rows=WRAP_ROWS)),
+              "gated_mul_fp8": (WRAP_ROWS, ROW_GRID_CAP, 1, dict(C=WRAP_WIDTH, rows=WRAP_ROWS))}
 FAMILIES = ("normal", "zero", "outlier")   # row r belongs to FAMILIES[r % 3]; a one-row case runs once per family
 OUTLIER = 1e4
 SLIPS = ("scale_from_bf16", "amax_over_240", "truncate")

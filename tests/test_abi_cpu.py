@@ -153,6 +153,49 @@ def test_auto_tile_picks_the_256x256_ping_pong_tile_for_the_models_launches(lib)
     assert tile([(4096, 128, 3072, L.EPI_BIAS, 0)]) in (L.TILE_PP_256x128, L.TILE_256x64)
 
 
+def test_i32_helper_refuses_what_ctypes_would_truncate():
+    """ctypes keeps the low 32 bits of an integer given to a c_int32 parameter without a word; ops._i32 is what stands
+    in front of every such parameter."""
+    from conceptattention_amd import ops
+    assert ctypes.c_int32(2 ** 32 + 256).value == 256                  # the silent truncation itself
+    assert ops._i32(2 ** 31 - 1, "ld") == 2 ** 31 - 1 and ops._i32(0, "ld") == 0
+    for bad in (2 ** 31, 2 ** 32 + 256, -1):
+        with pytest.raises(ValueError, match="ldo"):
+            ops._i32(bad, "ldo")
+
+
+def test_no_stride_reaches_the_library_except_through_the_i32_helper():
+    """Every ``.stride(`` of ops.py is the argument of ops._i32 or one side of a comparison.  The one exception is the
+    byte stride of pixels_to_nhwc32, an int64_t of its entry point."""
+    import ast
+    path = os.path.join(ROOT, "conceptattention_amd", "ops.py")
+    tree = ast.parse(open(path).read())
+    parent = {}
+    for node in ast.walk(tree):
+        for child in ast.iter_child_nodes(node):
+            parent[child] = node
+    INT64 = {("pixels_to_nhwc32", "src")}
+    seen = helped = 0
+    for node in ast.walk(tree):
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == "stride":
+            seen += 1
+            up = parent[node]
+            if isinstance(up, ast.Compare):
+                continue
+            if isinstance(up, ast.Call) and isinstance(up.func, ast.Name) and up.func.id == "_i32" and up.args[0] is node:
+                helped += 1
+                continue
+            fn = up
+            while not isinstance(fn, ast.FunctionDef):
+                fn = parent[fn]
+            assert (fn.name, ast.unparse(node.func.value)) in INT64, f"ops.py:{node.lineno}: {ast.unparse(up)}"
+            assert L.SIGNATURES["ca_pixels_u8_to_nhwc32_bf16"][1][1] is ctypes.c_int64
+    assert seen > 60 and helped > 50, (seen, helped)
+    # and the strides of the four new units' entry points are int32_t: what the helper is there for
+    for name in ("ca_t5_attn_bf16", "ca_t5_rmsnorm_f32in_fp8", "ca_clip_attn_bf16", "ca_layernorm_f32in"):
+        assert ctypes.c_int32 in L.SIGNATURES[name][1]
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(L, "_lib", None)
     monkeypatch.setattr(L, "LIB_PATH", str(tmp_path / "nope.so"))

@@ -2,6 +2,8 @@
 role of the attention and GEMM case tables has a placement case, the limits DESIGN.md ("Address arithmetic") states
 are the ones at which the kernels' 32-bit expressions stop equalling the 64-bit address, the GEMM limit goes through
 ca_gemm_plan, and named slips move at least one touched 16-byte access on the chosen placements."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -113,6 +115,57 @@ def test_every_vae_entry_point_and_role_has_a_placement_and_a_far_case():
         assert (rows - 1) * ld * item >= LINE, (cid, role)         # the last row starts 2^32 bytes or more from the base
         assert ((rows - 1) * ld + 1) * item > LINE, (cid, role)    # and the touched extent exceeds 2^32 bytes
         assert rows * ld * item <= C.PAST_4GIB < PL.ARENA_BYTES - 2 * PL.GUARD - 256
+
+
+def test_every_text_pixel_and_scoring_entry_point_and_role_has_a_placement_and_a_far_case():
+    """The GPU file places TEXT_PLACEMENT's case of every entry point of ca_t5.hip, ca_clip.hip, ca_pixels.hip and
+    ca_seg.hip once per role of TEXT_ROLES, and runs TEXT_PAST (and the pixel source) with one operand's row stride
+    from far_ld."""
+    import os
+    import re
+
+    import clip_cases as CL
+    import pixel_cases as P
+    import seg_cases as S
+    import t5_cases as T5
+    import t5_fp8_cases as F8
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    entries = set()
+    for unit in ("ca_t5.hip", "ca_clip.hip", "ca_pixels.hip", "ca_seg.hip"):
+        src = open(os.path.join(root, "conceptattention_amd", "csrc", unit)).read()
+        entries |= set(re.findall(r'extern "C" int (ca_\w+)\(', src))
+    assert entries == set(C.TEXT_PLACEMENT) == set(C.TEXT_ROLES) == set(C.TEXT_FREE_STRIDES), entries ^ set(C.TEXT_PLACEMENT)
+    # the roles are the pointer parameters of the entry point (ca_seg_score: the pointers of its problem struct)
+    pointers = {name: sum(a is ctypes.c_void_p for a in L.SIGNATURES[name][1]) - 1 for name in entries}     # - the stream
+    pointers["ca_seg_score"] = len(L.SegProblem._fields_)
+    for name, roles in C.TEXT_ROLES.items():
+        assert len(roles) == len(set(roles)) == pointers[name], (name, roles, pointers[name])
+    # existing cases of the tables
+    assert C.TEXT_PLACEMENT["ca_t5_attn_bf16"] in T5.ATTN_CASES and C.TEXT_PLACEMENT["ca_clip_attn_bf16"] in CL.ATTN_CASES
+    assert C.TEXT_PLACEMENT["ca_clip_attn_bf16"].layout == "apart" and C.TEXT_PLACEMENT["ca_t5_attn_bf16"].layout == "contig"
+    assert C.TEXT_PLACEMENT["ca_t5_rmsnorm_f32in"] in T5.ROW_CASES and C.TEXT_PLACEMENT["ca_embed_rows_f32"] in T5.EMBED_CASES
+    assert C.TEXT_PLACEMENT["ca_gated_mul_bf16"] in T5.GATE_CASES and C.TEXT_PLACEMENT["ca_gated_mul_fp8"] in F8.GATE_CASES
+    assert C.TEXT_PLACEMENT["ca_t5_rmsnorm_f32in_fp8"] in F8.RMS_CASES and C.TEXT_PLACEMENT["ca_layernorm_f32in"] in CL.LN_CASES
+    assert C.TEXT_PLACEMENT["ca_quick_gelu_bf16"] in CL.QG_CASES and C.TEXT_PLACEMENT["ca_clip_embed_f32"] in CL.EMBED_H
+    assert C.TEXT_PLACEMENT["ca_pixels_u8_to_nhwc32_bf16"] in P.RESIZE_CASES
+    assert C.TEXT_PLACEMENT["ca_seg_score"] in {c.name for c in S.CASES}
+    # far rows: every operand with a free row stride, at a stride the int32_t parameters take
+    far = {}
+    for entry, case, role, rows, item in C.TEXT_PAST:
+        assert role in C.TEXT_ROLES[entry], (entry, role)
+        far.setdefault(entry, set()).add(role)
+        ld = C.far_ld(rows, item, C.PAST_4GIB)
+        assert ld < 1 << 31, (entry, role, ld)
+        assert (rows - 1) * ld * item >= LINE, (entry, role)             # the last row starts 2^32 bytes or more from the base
+        assert rows * ld * item <= C.PAST_4GIB < PL.ARENA_BYTES - 2 * PL.GUARD - 256
+        assert rows == 64 if "attn" in entry else rows in (5, 6, 7, 8, 9, 77, 231), (entry, role, rows)
+    far.setdefault(C.TEXT_PAST_OWN_TEST[0], set()).add(C.TEXT_PAST_OWN_TEST[1])
+    for entry, roles in C.TEXT_FREE_STRIDES.items():
+        assert far.get(entry, set()) == roles, (entry, far.get(entry), roles)
+    assert any(e == "ca_layernorm_f32in" and c[2] and r == "x" for e, c, r, _, _ in C.TEXT_PAST)      # the gathered x
+    h0 = C.PIXEL_FAR[0]
+    assert (h0 - 1) * C.far_ld(h0, 1, C.PAST_4GIB) >= LINE and L.SIGNATURES["ca_pixels_u8_to_nhwc32_bf16"][1][1] is ctypes.c_int64
+    assert ctypes.c_int32(C.BAD_STRIDE).value == 256                     # what ctypes would hand the library
 
 
 def test_no_role_is_left_out():

@@ -37,14 +37,23 @@ import rowop_cases as R  # noqa: E402
 import test_rowop_routes_gpu as TR  # noqa: E402
 import test_vae_routes_gpu as TV  # noqa: E402
 import vae_cases as V  # noqa: E402
+import clip_cases as CL  # noqa: E402
+import pixel_cases as PX  # noqa: E402
+import seg_cases as SG  # noqa: E402
+import t5_fp8_cases as F8  # noqa: E402
+import test_clip_kernels_gpu as TC  # noqa: E402
+import test_pixel_kernels_gpu as TP  # noqa: E402
+import test_seg_kernels_gpu as TS  # noqa: E402
+import test_t5_fp8_kernels_gpu as TF  # noqa: E402
+import test_t5_kernels_gpu as TT  # noqa: E402
 from address_range_cases import (ATTN_FAR, ATTN_LIMITS, ATTN_PLACEMENT, ATTN_ROLES, GEMM_INPUT_FIELD,  # noqa: E402
                                  far_ldkv, gemm_epis_for)
 from conceptattention_amd import ops  # noqa: E402
 
 DEV = "cuda"
 NAN = float("nan")
-COUNTS = {"attention placement": 0, "gemm placement": 0, "rowop placement": 0, "vae placement": 0, "attention far": 0,
-          "gemm far": 0, "past 4 GiB": 0}
+COUNTS = {"attention placement": 0, "gemm placement": 0, "rowop placement": 0, "vae placement": 0, "text placement": 0,
+          "attention far": 0, "gemm far": 0, "past 4 GiB": 0}
 
 
 def _bytes(t):
@@ -443,6 +452,108 @@ def test_softmax_p_past_4_gib(arena):
         assert bool((full[r, n:a].view(torch.int16) == 0).all()) and body.max().item() == 0 == body.min().item(), \
             f"row {r}: padding not zero"
     COUNTS["past 4 GiB"] += 1
+
+
+# ------------------------------------------------------------ the text, pixel and scoring kernels
+LN_IDX = torch.tensor(CL.LN_GATHER, dtype=torch.int32)
+# entry point -> the run helper of its kernel test file: (case, allocator, **kw) -> {name: a clone of the output}.  Every
+# helper checks its case against the case table's own reference and bound, padding and guard rows included.
+TEXT_RUN = {
+    "ca_t5_attn_bf16": TT.run_attention,
+    "ca_t5_rmsnorm_f32in": TT.run_rmsnorm,
+    "ca_t5_rmsnorm_f32in_fp8": TF.run_rmsnorm_fp8,
+    "ca_gated_mul_bf16": TT.run_gated_mul,
+    "ca_gated_mul_fp8": TF.run_gated_mul_fp8,
+    "ca_embed_rows_f32": lambda case, alloc=None, **kw: TT.run_embed_rows(case, alloc, **kw)[0],
+    "ca_clip_attn_bf16": TC.run_attention,
+    # (strided cases with the row_idx gather, the others row by row)
+    "ca_layernorm_f32in": lambda case, alloc=None: TC.run_layernorm(case, alloc, gather=LN_IDX if case[2] else None)[0],
+    "ca_quick_gelu_bf16": TC.run_quick_gelu,
+    "ca_clip_embed_f32": lambda case, alloc=None, **kw: TC.run_clip_embed(case, alloc, **kw)[0],
+    "ca_pixels_u8_to_nhwc32_bf16": TP.run_to_nhwc32,
+    "ca_nhwc_f32_to_pixels_u8": TP.run_to_pixels,
+    "ca_seg_score": lambda name, alloc=None: TS.run_case(next(c for c in SG.CASES if c.name == name), alloc or PL.Plain(DEV)),
+}
+
+
+@pytest.mark.parametrize("entry", list(C.TEXT_PLACEMENT))
+def test_text_placement(arena, entry):
+    """One case per entry point of ca_t5.hip, ca_clip.hip, ca_pixels.hip and ca_seg.hip with every operand role: plain,
+    all at bit31, then role by role across the 2^32 line mid-row of a middle row.  Bit-identical to ordinary
+    allocations, inside the case's own bound, padding columns, guard rows and guard bands intact."""
+    case, roles, run = C.TEXT_PLACEMENT[entry], C.TEXT_ROLES[entry], TEXT_RUN[entry]
+    plain = run(case)
+    for role in [None] + roles:
+        pl = arena.placer(role)
+        got = run(case, pl)
+        _assert_placed(pl, role)
+        assert set(pl.placed) == set(roles), set(pl.placed) ^ set(roles)
+        pl.check_guards()
+        for k in plain:
+            assert torch.equal(_bytes(plain[k]), _bytes(got[k])), f"{entry} {k}: {role or 'bit31'} != plain"
+        COUNTS["text placement"] += 1
+
+
+@pytest.mark.parametrize("entry,case,role,rows,item", C.TEXT_PAST, ids=lambda v: str(v))
+def test_text_operand_past_4_gib(arena, entry, case, role, rows, item):
+    """One operand with its row stride from far_ld (its last row starts more than 4 GiB from its base, the stride below
+    2^31), the others small; only the touched columns are written.  Equal to the same case at its ordinary stride."""
+    run = TEXT_RUN[entry]
+    kw = dict(guard=0) if "attn" in entry else dict(vocab=8) if role in ("table", "tok") else {}
+    plain = run(case, **kw)
+    fa = FarAlloc(arena, role, C.PAST_4GIB)
+    got = run(case, fa, **kw)
+    fa.check_guards()
+    assert tuple(fa.view.shape)[0] == rows and fa.view.element_size() == item, (fa.view.shape, rows, item)
+    assert fa.last_row_offset >= 1 << 32 and fa.ld < 1 << 31, (fa.last_row_offset, fa.ld)
+    print(f"\n  {entry} {role}: ld={fa.ld}, last row {fa.last_row_offset} bytes from the base")
+    for k in plain:
+        assert torch.equal(_bytes(plain[k]), _bytes(got[k])), f"{entry} {k}: far {role} != plain"
+    COUNTS["past 4 GiB"] += 1
+
+
+def test_pixel_source_past_4_gib(arena):
+    """ca_pixels_u8_to_nhwc32_bf16 takes the source's row stride in bytes as an int64_t: five rows 2^30 bytes apart, the
+    last one 2^32 bytes from the first.  The plane equals the contiguous source's."""
+    h0, w0, h, w = C.PIXEL_FAR
+    plain = TP.run_to_nhwc32(C.PIXEL_FAR)
+    ld = C.far_ld(h0, 1, C.PAST_4GIB)
+    assert (h0 - 1) * ld >= 1 << 32
+    start = (arena.base + PL.GUARD + 255) // 256 * 256
+    span = ((h0 - 1) * ld + w0 * 3 + 255) // 256 * 256
+    for g in (start - PL.GUARD, start + span):
+        arena.window(g, PL.GUARD).fill_(PL.PATTERN)
+    src = arena.window(start, span).as_strided((h0, w0, 3), (ld, 3, 1))
+    host = torch.from_numpy(PX.source_image(h0, w0))
+    src.copy_(host)
+    dst = torch.full((h, w, 32), TP.POISON, device=DEV, dtype=torch.bfloat16)
+    ops.pixels_to_nhwc32(src, dst)
+    torch.cuda.synchronize()
+    assert torch.equal(_bytes(dst), _bytes(plain["dst"])), "far src != plain"
+    assert torch.equal(src.cpu(), host), "the source changed"
+    for g in (start - PL.GUARD, start + span):
+        assert bool((arena.window(g, PL.GUARD) == PL.PATTERN).all()), "guard band written"
+    COUNTS["past 4 GiB"] += 1
+
+
+def test_a_row_stride_beyond_int32_is_refused_before_any_launch(arena):
+    """A uint8 [2, 256] view whose rows are 2^32 + 256 bytes apart, as the out of t5_rmsnorm_fp8: ctypes would hand the
+    library ldo = 256, which passes its ldo >= H check, and row 1 would land 256 bytes behind row 0.  ops._i32 raises,
+    naming the argument; nothing is launched: both rows, the bytes a truncated stride would have hit and the scales
+    still hold what they held."""
+    H = 256
+    x, w, _ = F8.rms_inputs(H, 2)
+    start = (arena.base + PL.GUARD + 255) // 256 * 256
+    plane = arena.window(start, C.BAD_STRIDE + H).as_strided((2, H), (C.BAD_STRIDE, 1))
+    near = arena.window(start, 4 * H)                       # row 0 and where ldo = 256 would put the rows behind it
+    near.fill_(TF.NAN_BYTE)
+    plane.fill_(TF.NAN_BYTE)
+    scale = torch.full((2,), NAN, device=DEV)
+    assert plane.stride(0) == C.BAD_STRIDE and plane.stride(0) % (1 << 32) == H
+    with pytest.raises(ValueError, match="ldo"):
+        ops.t5_rmsnorm_fp8(x.to(DEV), w.to(DEV), plane, scale, F8.EPS)
+    torch.cuda.synchronize()
+    assert bool((plane == TF.NAN_BYTE).all()) and bool((near == TF.NAN_BYTE).all()) and bool(scale.isnan().all())
 
 
 # ---------------------------------------------------------------------------------------------- c. rejection

@@ -56,13 +56,15 @@ def test_query_zero_returns_value_zero_and_the_sequences_have_their_own_v():
     assert not torch.equal(v[:77], v[77:154])
 
 
-@pytest.mark.parametrize("H,strided", T.LN_CASES)
-def test_layernorm_emulation_sits_inside_the_bound_and_the_slips_leave_it(H, strided):
-    x, w, b = T.ln_inputs(H)
+@pytest.mark.parametrize("H,rows,strided", T.LN_CASES, ids=[T.ln_id(c) for c in T.LN_CASES])
+def test_layernorm_emulation_sits_inside_the_bound_and_the_slips_leave_it(H, rows, strided):
+    x, w, b = T.ln_inputs(H, rows)
     ref, bound = T.layernorm_reference(x, w, b)
     assert _ratio(T.layernorm_emulated(x, w, b), ref, bound) <= 1.0
     assert _ratio(T.layernorm_emulated(x, w, b, slip="no_mean"), ref, bound) > 4.0
     assert _ratio(T.layernorm_emulated(x, w, b, slip="no_bias"), ref, bound) > 4.0
+    if rows != T.LN_ROWS:      # (the statements below are about the nine-row table)
+        return
     odd = x[1::2].double()                                            # the rows with a large mean
     assert (odd.mean(-1).abs() > 50 * odd.std(-1)).all()
     # the one-pass variance, in fp32, is NOT inside the bound on those rows: the bound tells the two forms apart
@@ -71,6 +73,22 @@ def test_layernorm_emulation_sits_inside_the_bound_and_the_slips_leave_it(H, str
     var = ((xf * xf).sum(-1, keepdim=True) / H - m * m).clamp_min(0)
     onepass = T.bf16r((xf - m) / torch.sqrt(var + T.EPS) * w + b)
     assert _ratio(onepass, ref[1::2], bound[1::2]) > 1.0
+
+
+def test_the_ragged_and_minimum_widths_are_cases_and_the_wrap_cases_exceed_their_caps():
+    for rows in T.WIDTH_ROWS:
+        for s in (False, True):
+            assert {(1032, rows, s), (4, rows, s)} <= set(T.LN_CASES) and {(2056, rows, s), (8, rows, s)} <= set(T.QG_CASES)
+    assert 8 in T.EMBED_H and [T.ln_id(c) for c in T.LN_CASES][:2] == ["64-False", "64-True"]
+    assert all(max(T.ln_gather(r)) == r - 1 and len(T.ln_gather(r)) == 6 for r in (1, 7, 9)) and T.ln_gather(9) == T.LN_GATHER
+    src = open(os.path.join(ROOT, "conceptattention_amd", "csrc", "ca_clip.hip")).read()      # the caps, as the source has them
+    assert src.count("rows < 65536 ? rows : 65536") == 1 and src.count("if (blocks > 65536) blocks = 65536;") == 2
+    assert T.ROW_GRID_CAP == 65536 and T.ELEM_GRID_CAP == 65536 * 256
+    assert set(T.WRAP_CASES) == {"layernorm", "quick_gelu", "clip_embed"}
+    for op, (units, cap, per_wg, case) in T.WRAP_CASES.items():
+        assert cap + per_wg <= units < cap + cap // 4, (op, units, cap)
+    assert (43692 - 1) * 384 < T.ELEM_GRID_CAP + 256                      # the smallest row count that wraps by a workgroup
+    assert T.WRAP_CASES["clip_embed"][3]["rows"] % 77 == 0 and 77 * 2269 * 96 < T.ELEM_GRID_CAP + 256
 
 
 @pytest.mark.parametrize("C,rows,strided", T.QG_CASES)

@@ -23,7 +23,21 @@ def test_the_table_holds_the_cases_the_kernel_can_go_wrong_at():
         assert sorted(img[:, :, c].reshape(-1).tolist()) == list(range(256))
 
 
-@pytest.mark.parametrize("h0,w0,h,w", T.RESIZE_CASES)
+def test_wrap_cases_exceed_the_cap_by_a_workgroup_and_by_less_than_a_quarter():
+    src = open(os.path.join(ROOT, "conceptattention_amd", "csrc", "ca_pixels.hip")).read()
+    assert "#define PIX_MAX_BLOCKS 2048" in src and src.count("if (blocks > PIX_MAX_BLOCKS) blocks = PIX_MAX_BLOCKS;") == 2
+    assert T.PIXEL_GRID_CAP == 2048 * 256 and set(T.WRAP_CASES) == {"pixels_to_nhwc32", "nhwc_to_pixels"}
+    for op, (units, cap, per_wg, case) in T.WRAP_CASES.items():
+        assert cap + per_wg <= units < cap + cap // 4, (op, units, cap)
+    c = T.WRAP_CASES["pixels_to_nhwc32"][3]
+    assert c["h"] * c["w"] > 131072 and c["h"] % c["h0"] and c["w"] % c["w0"]              # a non-integer resize
+    n = T.WRAP_CASES["nhwc_to_pixels"][3]["pixels"]
+    assert n > 2796203 and (n * 3) % 16 == 9                                                 # a tail behind the last unit
+    h0, w0, h, w = T.PRODUCT_RESIZE
+    assert h * w * 4 == 8 * T.PIXEL_GRID_CAP
+
+
+@pytest.mark.parametrize("h0,w0,h,w", T.RESIZE_CASES + [(37, 53, 514, 257), T.PRODUCT_RESIZE])
 def test_nearest_index_rule_is_interpolates(h0, w0, h, w):
     """An image that holds its own pixel indices, resized by torch on the CPU, names the source pixel of every
     destination pixel."""

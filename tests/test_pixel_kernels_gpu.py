@@ -7,6 +7,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import pixel_cases as T  # noqa: E402
+import placement  # noqa: E402
 from conceptattention_amd import ops  # noqa: E402
 
 DEV = "cuda"
@@ -17,6 +18,35 @@ def _run(src_dev, h, w):
     dst = torch.full((h, w, 32), POISON, device=DEV, dtype=torch.bfloat16)
     ops.pixels_to_nhwc32(src_dev, dst)
     return dst.cpu()
+
+
+def run_to_nhwc32(case, alloc=None):
+    """One resize case with its two buffers from an optional allocator (tests/placement.py), checked bit for bit;
+    returns a clone of the plane.  tests/test_address_range_gpu.py runs it at chosen addresses."""
+    h0, w0, h, w = case
+    al = alloc or placement.Plain(DEV)
+    src = T.source_image(h0, w0)
+    sd = al.to(torch.from_numpy(src), {"src": None})
+    dst = al.full((h, w, 32), POISON, torch.bfloat16, {"dst": None})
+    ops.pixels_to_nhwc32(sd, dst)
+    torch.cuda.synchronize()
+    assert torch.equal(dst.cpu(), T.u8_to_nhwc32_reference(src, h, w)), case
+    assert np.array_equal(sd.cpu().numpy(), src), "the source changed"
+    return {"dst": dst.clone()}
+
+
+def run_to_pixels(case, alloc=None):
+    """(b, h, w, ld): the decoder's plane to bytes, the buffers from an optional allocator, checked bit for bit."""
+    b, h, w, ld = case
+    al = alloc or placement.Plain(DEV)
+    x = T.f32_values(b, h, w, ld)
+    xd = al.to(torch.from_numpy(x), {"src": None})
+    out = al.full((b, h, w, 3), 77, torch.uint8, {"dst": None})
+    ops.nhwc_to_pixels(xd, out)
+    torch.cuda.synchronize()
+    assert np.array_equal(out.cpu().numpy(), T.f32_to_u8_reference(x)), case
+    assert np.array_equal(xd.cpu().numpy(), x), "the source changed"
+    return {"dst": out.clone()}
 
 
 @pytest.mark.parametrize("h0,w0,h,w", T.RESIZE_CASES)
@@ -90,3 +120,41 @@ def test_f32_to_u8_full_units_of_sixteen_bytes_and_the_tail_behind_them():
             got = buf.cpu().numpy()
             assert np.array_equal(got[: n * 3].reshape(n, 3), T.f32_to_u8_reference(x)), (n, shift)
             assert (got[n * 3:] == 77).all(), (n, shift)
+
+
+def test_u8_to_nhwc32_grid_wrap_between_two_poisoned_neighbours():
+    """514 x 257 pixels are 16 workgroups more than the 2048 of the capped grid: their threads take a second 16-byte unit.
+    37 x 53 -> 514 x 257 are non-integer factors both ways.  The slot in the middle of three: the wrap writes nothing of
+    the neighbours."""
+    c = T.WRAP_CASES["pixels_to_nhwc32"][3]
+    h0, w0, h, w = c["h0"], c["w0"], c["h"], c["w"]
+    src = T.source_image(h0, w0)
+    ref = T.u8_to_nhwc32_reference(src, h, w)
+    assert torch.equal(_run(torch.from_numpy(src).to(DEV), h, w), ref)
+    plane = torch.full((3, h, w, 32), POISON, device=DEV, dtype=torch.bfloat16)
+    ops.pixels_to_nhwc32(torch.from_numpy(src).to(DEV), plane[1])
+    assert (plane[0] == POISON).all() and (plane[2] == POISON).all()
+    assert torch.equal(plane[1].cpu(), ref)
+
+
+def test_u8_to_nhwc32_at_the_products_size():
+    """375 x 500 into 1024 x 1024: every thread walks the loop eight times."""
+    h0, w0, h, w = T.PRODUCT_RESIZE
+    run_to_nhwc32((h0, w0, h, w))
+
+
+@pytest.mark.parametrize("ld", [3, 32])
+def test_f32_to_u8_grid_wrap(ld):
+    """2 797 571 pixels are 524 545 units of 16 bytes, 257 more than the capped grid's threads, and 9 bytes behind the
+    last unit.  ld = 3 and an aligned source: the packed kernel; ld = 32: the pixel-by-pixel walk.  The bytes behind the
+    last pixel stay as they were."""
+    n = T.WRAP_CASES["nhwc_to_pixels"][3]["pixels"]
+    x = T.f32_values(1, 1, n, 3).reshape(n, 3)
+    src = torch.full((n, ld), 0.123, device=DEV)
+    src[:, :3] = torch.from_numpy(x).to(DEV)
+    assert src.data_ptr() % 16 == 0
+    buf = torch.full((n * 3 + 16,), 77, device=DEV, dtype=torch.uint8)
+    ops.nhwc_to_pixels(src, buf[: n * 3].view(n, 3))
+    got = buf.cpu().numpy()
+    assert np.array_equal(got[: n * 3].reshape(n, 3), T.f32_to_u8_reference(x))
+    assert (got[n * 3:] == 77).all()

@@ -1,6 +1,8 @@
 """The numpy restatement of ca_seg_score (tests/seg_cases.py) against the host scoring path it replaces
 (conceptattention_amd.segmentation): integer counters equal, AP within 1e-12 (the bound is derived in seg_cases.py).
 This pins the restatement, and through tests/test_seg_kernels_gpu.py the kernel's definition."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -73,6 +75,24 @@ def test_special_cases_are_what_their_names_say():
     amap, _ = by["signed-zero-threshold"].inputs()
     assert (amap < 0).any() and (amap > 0).any()
     assert len(T.cap_launch_inputs()[0]) == T.MAX_PROBLEMS
+
+
+def test_large_labels_and_the_lds_limit_boundary_are_cases():
+    by = {c.name: c for c in T.CASES}
+    for name, cells, pixels in (("map64x64-label1024x1024", 4096, 1 << 20), ("map48x64-label375x500", 3072, 187500),
+                                ("map32x64-label224x224", 2048, 50176), ("map3x683-label224x224", 2049, 50176),
+                                ("map2x2-label4096x4096", 4, 1 << 24)):
+        assert by[name].h * by[name].w == cells and by[name].Hl * by[name].Wl == pixels, name
+    # the request crosses the default limit between 2048 and 2049 cells, where the padded sort doubles
+    assert T.lds_bytes(2048) == 57856 <= T.LDS_DEFAULT_LIMIT < T.lds_bytes(2049) == 90672
+    assert T.lds_bytes(48 * 48) > T.LDS_DEFAULT_LIMIT and T.lds_bytes(T.MAX_CELLS) == 115200
+    assert 2 * 3072 < 8192                                     # the rectangular map sorts more slots than it has entries
+    ref = T.reference(*by["map2x2-label4096x4096"].inputs())   # the entry point's limit: 2^24 pixels, counts up to 2^24
+    assert ref["n11"] + ref["n10"] + ref["n01"] + ref["n00"] == 1 << 24 == T.MAX_LABEL_PIXELS
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "conceptattention_amd", "csrc",
+                            "ca_seg.hip")).read()
+    assert "(size_t)npad * 8 + (size_t)((hw + 3) & ~3) * 12 + SEG_SCRATCH_BYTES" in src and "if (lds > 64 * 1024)" in src
+    assert "48 x 48" not in src
 
 
 def test_mean_tree_is_the_rounded_fp64_mean():

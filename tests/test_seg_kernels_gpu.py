@@ -8,6 +8,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import placement  # noqa: E402
 import seg_cases as T  # noqa: E402
 from conceptattention_amd import _lib as L  # noqa: E402
 from conceptattention_amd import ops  # noqa: E402
@@ -19,16 +20,22 @@ RECORD = np.dtype([("n11", "<i4"), ("n10", "<i4"), ("n01", "<i4"), ("n00", "<i4"
 assert RECORD.itemsize == ctypes.sizeof(L.SegRecord) == 40
 
 
-def _launch(maps, labels, mean_value_threshold=True, downscale_for_eval=False, apply_blur=False, outputs=True):
-    """(records, masks, coefficients) of one ops.seg_score call; poisoned outputs show what nobody wrote."""
+def _launch(maps, labels, mean_value_threshold=True, downscale_for_eval=False, apply_blur=False, outputs=True, alloc=None):
+    """(records, masks, coefficients) of one ops.seg_score call; poisoned outputs show what nobody wrote.  ``alloc``: an
+    allocator of tests/placement.py for the five operand roles (one item)."""
     n, (h, w) = len(maps), maps[0].shape
-    md = [torch.from_numpy(m).to(DEV) for m in maps]
-    ld = [torch.from_numpy(l).to(DEV) for l in labels]
-    res = torch.full((n, 40), 0xAB, device=DEV, dtype=torch.uint8)
-    mask = torch.full((n, h, w), 77, device=DEV, dtype=torch.uint8) if outputs else None
-    coeff = torch.full((n, h, w), -3.0, device=DEV) if outputs else None
+    al = alloc or placement.Plain(DEV)
+    assert alloc is None or n == 1
+    md = [al.to(torch.from_numpy(m), {"map": None}) for m in maps]
+    ld = [al.to(torch.from_numpy(l), {"label": None}) for l in labels]
+    res = al.full((n, 40), 0xAB, torch.uint8, {"result": None})
+    mask = al.full((n, h, w), 77, torch.uint8, {"mask_out": None}) if outputs else None
+    coeff = al.full((n, h, w), -3.0, torch.float32, {"coeff_out": None}) if outputs else None
     ops.seg_score(md, ld, res, mean_value_threshold=mean_value_threshold, downscale_for_eval=downscale_for_eval,
                   blur_weights=ops.seg_blur_weights() if apply_blur else None, mask_out=mask, coeff_out=coeff)
+    torch.cuda.synchronize()
+    for d, t in list(zip(md, maps)) + list(zip(ld, labels)):
+        assert np.array_equal(d.cpu().numpy(), t), "an input changed"
     rec = res.cpu().numpy().view(RECORD).reshape(n)
     return rec, (mask.cpu().numpy() if outputs else None), (coeff.cpu().numpy() if outputs else None)
 
@@ -49,10 +56,19 @@ def _check(rec, mask, coeff, ref, what):
 
 @pytest.mark.parametrize("case", T.CASES, ids=repr)
 def test_every_case_equals_the_restatement(case):
+    run_case(case)
+
+
+def run_case(case, alloc=None):
+    """One case of seg_cases.CASES, its five buffers from an optional allocator, checked against the restatement;
+    returns the record, the mask and the coefficient as tensors of bytes."""
     amap, label = case.inputs()
     ref = T.reference(amap, label, **case.flags)
-    rec, mask, coeff = _launch([amap], [label], **case.flags)
+    rec, mask, coeff = _launch([amap], [label], alloc=alloc, **case.flags)
     _check(rec[0], mask[0], coeff[0], ref, case.name)
+    if alloc is not None:
+        return {"result": torch.from_numpy(rec[:1].copy().view(np.uint8)), "mask_out": torch.from_numpy(mask.copy()),
+                "coeff_out": torch.from_numpy(coeff.copy())}
     again, _, _ = _launch([amap], [label], outputs=False, **case.flags)     # (and without the optional outputs)
     assert rec[0].tobytes() == again[0].tobytes(), "two launches of one input differ"
 

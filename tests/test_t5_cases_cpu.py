@@ -55,14 +55,41 @@ def test_rmsnorm_emulation_sits_inside_the_bound_and_the_slips_leave_it(H, rows,
         assert _ratio(T.rmsnorm_emulated(x, w, slip="eps_1e-5"), ref, bound) > 4.0
 
 
-@pytest.mark.parametrize("C,rows", [(512, 7), (10240, 3)])
+@pytest.mark.parametrize("C,rows", [(512, 7), (10240, 3)] + [(C, rows) for C in (2056, 8) for rows in T.WIDTH_ROWS])
 def test_gate_emulations_sit_inside_their_bounds_and_erf_gelu_leaves(C, rows):
     g, u = T.gate_inputs(C, rows)
     ref, bound = T.gated_mul_reference(g, u)
     assert _ratio(T.gated_mul_emulated(g, u), ref, bound) <= 1.0
     ref, bound = T.gate_path_reference(g, u)        # the same values as fp32 pre-activations
     assert _ratio(T.gate_path_emulated(g, u), ref, bound) <= 1.0
-    assert _ratio(T.gate_path_emulated(g, u, slip="erf_gelu"), ref, bound) > 4.0
+    if C >= 512:     # (a row of 8 values need not hold one where the two GELUs differ by more than a bf16 step)
+        assert _ratio(T.gate_path_emulated(g, u, slip="erf_gelu"), ref, bound) > 4.0
+
+
+def test_every_attention_instantiation_and_the_ragged_and_minimum_widths_are_cases():
+    assert {c.L for c in T.ATTN_CASES} == {64 * n for n in range(1, 9)}        # NT = 4, 8, ..., 32
+    for L in (320, 384, 448):
+        assert {(c.layout, c.family) for c in T.ATTN_CASES if c.L == L} == \
+            {(lay, fam) for lay in ("contig", "sliced") for fam in ("std1", "std8", "far")}
+    for rows in T.WIDTH_ROWS:
+        for s in (False, True):
+            assert {(1032, rows, s), (4, rows, s)} <= set(T.ROW_CASES) and (8, rows, s) in T.EMBED_CASES
+            assert {(2056, rows, s), (8, rows, s)} <= set(T.GATE_CASES)
+    assert 1032 % 1024 == 8 and 1032 > 1024 and min(H for H, _, _ in T.ROW_CASES) == 4       # a partial second pass; the minimum
+
+
+def test_wrap_cases_exceed_their_caps_by_a_workgroup_and_by_less_than_a_quarter():
+    """The caps are restated from ca_t5.hip; the source must still hold them."""
+    import os
+    src = open(os.path.join(os.path.dirname(os.path.abspath(entry.__file__)), "conceptattention_amd", "csrc", "ca_t5.hip")).read()
+    assert src.count("rows < 65536 ? rows : 65536") == 3 and src.count("if (blocks > 65536) blocks = 65536;") == 2
+    assert src.count("dim3(256)") == 6
+    assert T.ROW_GRID_CAP == 65536 and T.ELEM_GRID_CAP == 65536 * 256
+    assert set(T.WRAP_CASES) == {"t5_rmsnorm", "gated_mul", "embed_rows"}
+    for op, (units, cap, per_wg, case) in T.WRAP_CASES.items():
+        assert cap + per_wg <= units < cap + cap // 4, (op, units, cap)
+    assert T.WRAP_CASES["gated_mul"][0] == 13108 * 1280 and (13108 - 1) * 1280 < T.ELEM_GRID_CAP + 256    # the smallest row count
+    assert T.WRAP_CASES["embed_rows"][0] == 32769 * 512 and (32769 - 1) * 512 < T.ELEM_GRID_CAP + 256
 
 
 def test_split_gelu_boundary_is_a_multiple_of_the_tile_for_both_geometries():

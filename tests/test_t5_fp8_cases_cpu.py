@@ -30,7 +30,9 @@ def _check_inside(q, s, y64, y_rel, fam):
         if f == "zero":
             assert float(s[r]) == 1.0 and not (q[r] & 0x7F).any()        # scale 1, bytes +-0
         if f == "outlier":   # the case is what it says: one byte at the maximum, a good part of the rest subnormal or 0
-            assert int(((q[r] & 0x7F) == 0x7E).sum()) == 1 and float(((q[r] & 0x78) == 0).double().mean()) > 0.15
+            assert int(((q[r] & 0x7F) == 0x7E).sum()) == 1
+            if q.shape[1] >= 256:    # (a share of the 7 other bytes of a minimum-width row is no statistic)
+                assert float(((q[r] & 0x78) == 0).double().mean()) > 0.15
 
 
 @pytest.mark.parametrize("H,rows", sorted({(H, rows) for H, rows, _ in F.RMS_CASES}))
@@ -43,6 +45,16 @@ def test_rmsnorm_emulation_sits_inside_the_bounds(H, rows):
 def test_gated_mul_emulation_sits_inside_the_bounds(C, rows):
     for first in ((0, 1, 2) if rows == 1 else (0,)):
         _check_inside(*_gate(C, rows, first))
+
+
+def test_the_ragged_and_minimum_widths_are_cases_and_the_wrap_cases_exceed_their_cap():
+    for rows in (1, 7):
+        assert {(2056, rows), (8, rows)} <= set(F.GATE_CASES)
+        assert {(H, rows, s) for H in (2056, 8) for s in (False, True)} <= set(F.RMS_CASES)
+    assert 2056 % 2048 == 8 and 2056 > 2048
+    assert F.ROW_GRID_CAP == 65536 and set(F.WRAP_CASES) == {"t5_rmsnorm_fp8", "gated_mul_fp8"}
+    for op, (units, cap, per_wg, case) in F.WRAP_CASES.items():
+        assert cap + per_wg <= units < cap + cap // 4 and case["rows"] == units, op
 
 
 @pytest.mark.parametrize("slip", F.SLIPS)
