@@ -28,6 +28,10 @@ def __getattr__(name):  # lazy: keep `import conceptattention_amd` light for hos
                 "clip_state_dict_spec"):
         from . import clip
         return getattr(clip, name)
+    if name in ("ConceptAttentionSegmentationModel", "MultiClassScores", "DeviceMultiClassScores",
+                "map_predictions_to_class_indices", "multiclass_table"):
+        from . import segmentation
+        return getattr(segmentation, name)
     if name == "compute_heatmaps_from_vectors":
         from .heatmaps import compute_heatmaps_from_vectors
         return compute_heatmaps_from_vectors

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CA_LIB_PATH: another build of the same library (an A/B against another source tree); still no fallback
 LIB_PATH = os.environ.get("CA_LIB_PATH") or os.path.join(_HERE, "libconceptattn.so")
 
-CA_VERSION = 132
+CA_VERSION = 133
 EPI_BIAS, EPI_GELU_TANH, EPI_GATE_RESIDUAL, EPI_SPLIT_GELU, EPI_QKV_NORM_ROPE = 0, 1, 2, 3, 4
 TILE_AUTO, TILE_256x256, TILE_256x192, TILE_256x128, TILE_256x64 = 0, 1, 2, 3, 4
 TILE_PP_256x256, TILE_PP_256x128, TILE_PP_256x192 = 5, 6, 7
@@ -27,6 +27,12 @@ SEG_MAX_PROBLEMS = 16
 SEG_MAX_CELLS = 4096                # ca_seg_score: h * w of the map
 SEG_MAX_LABEL_PIXELS = 1 << 24      # ca_seg_score: Hl * Wl of the label
 SEG_MEAN_THRESHOLD, SEG_DOWNSCALE, SEG_BLUR = 1, 2, 4
+MSEG_MAX_PROBLEMS = 16
+MSEG_MAX_CONCEPTS = 32              # ca_mseg_score: K, the maps of an item
+MSEG_MAX_CLASSES = 256              # ca_mseg_score: nclass
+MSEG_MAX_CELLS = 16384              # ca_mseg_score: h * w of the maps
+MSEG_MAX_LABEL_PIXELS = 1 << 24     # ca_mseg_score: Hl * Wl of the label
+MSEG_BLUR = 4
 ATTN_Q_PRESCALED = 0.0   # ca_attn_fwd_bf16(scale=...): the q rows already carry softmax_scale * log2(e)
 
 
@@ -72,6 +78,11 @@ class SegProblem(C.Structure):
 class SegRecord(C.Structure):
     _fields_ = [("n11", C.c_int32), ("n10", C.c_int32), ("n01", C.c_int32), ("n00", C.c_int32), ("ap", C.c_double),
                 ("mean", C.c_float), ("lo", C.c_float), ("hi", C.c_float), ("thresholds", C.c_int32)]
+
+
+class MsegProblem(C.Structure):
+    _fields_ = [("maps", C.c_void_p), ("label", C.c_void_p), ("counts", C.c_void_p), ("class_out", C.c_void_p),
+                ("index_out", C.c_void_p)]
 
 
 class ModSegment(C.Structure):
@@ -164,6 +175,9 @@ SIGNATURES = {
     "ca_nhwc_f32_to_pixels_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "ca_seg_score": (C.c_int, [C.POINTER(SegProblem), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                C.POINTER(C.c_float), C.c_void_p]),
+    "ca_mseg_score": (C.c_int, [C.POINTER(MsegProblem), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                C.c_void_p]),
 }
 
 _lib = None

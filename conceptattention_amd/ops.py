@@ -819,6 +819,87 @@ def seg_score(maps, labels, results, mean_value_threshold: bool = True, downscal
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Multi-class segmentation scoring (ca_mseg.hip): an item's K maps against a label image of class ids.
+
+def mseg_score(maps, labels, counts, class_of, nclass: int, ignore_index: Optional[int] = None, scale=None,
+               blur_weights=None, class_out=None, index_out=None) -> None:
+    """Argmax over every item's K maps, the winning concept's class, and its counts against a label image of class ids
+    (ca_mseg_score; include/conceptattn.h states the arithmetic).
+    maps: n fp32 [K, h, w] contiguous tensors (a list, or one [n, K, h, w] tensor), K <= 32, h * w <= 16384; labels: n
+    uint8 [Hl, Wl] contiguous tensors of class ids, Hl * Wl <= 2^24; counts: int32 [n, 2 + 2 nclass] contiguous, per item
+    correct, labelled, inter[nclass], union[nclass]; class_of: per item the K class ids of its concepts (host integers,
+    each below nclass <= 256); ignore_index: the label value that is skipped, None for none; scale: K host numbers that
+    multiply the planes before the argmax, None for none; blur_weights: nine numbers (seg_blur_weights) to blur the
+    planes first, None for no blur; class_out / index_out: optional uint8 [n, h, w], the class and the winning concept
+    per map cell.  More than L.MSEG_MAX_PROBLEMS items go in several launches."""
+    lib = L.load()
+    maps, labels = list(maps), list(labels)
+    n = len(maps)
+    if n < 1 or len(labels) != n:
+        raise ValueError(f"mseg_score: {n} maps and {len(labels)} labels; need the same number, at least 1")
+    nclass = int(nclass)
+    if not 1 <= nclass <= L.MSEG_MAX_CLASSES:
+        raise ValueError(f"mseg_score: nclass = {nclass}; ca_mseg_score takes 1..{L.MSEG_MAX_CLASSES}")
+    _chk(counts, torch.int32, "counts")
+    if tuple(counts.shape) != (n, 2 + 2 * nclass) or not counts.is_contiguous():
+        raise ValueError(f"mseg_score: counts{tuple(counts.shape)} must be contiguous int32 [{n}, {2 + 2 * nclass}]")
+    K, h, w = (int(v) for v in maps[0].shape) if maps[0].dim() == 3 else (0, 0, 0)
+    Hl, Wl = (int(v) for v in labels[0].shape) if labels[0].dim() == 2 else (0, 0)
+    for i in range(n):
+        _chk(maps[i], torch.float32, "maps"), _chk(labels[i], torch.uint8, "labels")
+        if tuple(maps[i].shape) != (K, h, w) or not maps[i].is_contiguous() or tuple(labels[i].shape) != (Hl, Wl) or \
+                not labels[i].is_contiguous() or maps[i].device != counts.device or labels[i].device != counts.device:
+            raise ValueError(f"mseg_score[{i}]: maps are contiguous fp32 [K, h, w] and labels contiguous uint8 [Hl, Wl], "
+                             "all items of one shape and on the device of counts")
+    for name, t in (("class_out", class_out), ("index_out", index_out)):
+        if t is not None:
+            _chk(t, torch.uint8, name)
+            if tuple(t.shape) != (n, h, w) or not t.is_contiguous() or t.device != counts.device:
+                raise ValueError(f"mseg_score: {name}{tuple(t.shape)} must be contiguous [{n}, {h}, {w}] on the same device")
+    if not 1 <= K <= L.MSEG_MAX_CONCEPTS:
+        raise ValueError(f"mseg_score: maps of K = {K} concepts; ca_mseg_score takes 1..{L.MSEG_MAX_CONCEPTS}")
+    if not 1 <= h * w <= L.MSEG_MAX_CELLS:
+        raise ValueError(f"mseg_score: maps of {h} x {w} cells; ca_mseg_score takes 1..{L.MSEG_MAX_CELLS} (larger maps are "
+                         "scored on the host: segmentation.MultiClassScores)")
+    if not 1 <= Hl * Wl <= L.MSEG_MAX_LABEL_PIXELS:
+        raise ValueError(f"mseg_score: a label of {Hl} x {Wl} pixels; ca_mseg_score takes 1..2^24")
+    ignore = -1 if ignore_index is None else int(ignore_index)
+    if not -1 <= ignore <= 255:
+        raise ValueError(f"mseg_score: ignore_index = {ignore_index}; a label value 0..255, or None")
+    table = [[int(c) for c in row] for row in class_of]
+    if len(table) != n or any(len(row) != K for row in table):
+        raise ValueError(f"mseg_score: class_of holds one row of K = {K} class ids per item ({n} items)")
+    if any(not 0 <= c < nclass for row in table for c in row):
+        raise ValueError(f"mseg_score: every class_of entry must be in 0..{nclass - 1} (nclass = {nclass})")
+    sc = None
+    if scale is not None:
+        scale = [float(v) for v in scale]
+        if len(scale) != K:
+            raise ValueError(f"mseg_score: scale holds one number per concept (K = {K})")
+        sc = (C.c_float * K)(*scale)
+    flags, bw = 0, None
+    if blur_weights is not None:
+        blur_weights = [float(v) for v in blur_weights]
+        if len(blur_weights) != 9:
+            raise ValueError("mseg_score: blur_weights are the nine weights of the 3x3 blur")
+        if h < 2 or w < 2:
+            raise ValueError(f"mseg_score: blur_weights with maps of {h} x {w} cells; the blur's reflect padding needs "
+                             "h >= 2 and w >= 2")
+        flags |= L.MSEG_BLUR
+        bw = (C.c_float * 9)(*blur_weights)
+    for c0 in range(0, n, L.MSEG_MAX_PROBLEMS):
+        m = min(L.MSEG_MAX_PROBLEMS, n - c0)
+        arr = (L.MsegProblem * m)()
+        cof = (C.c_uint8 * (m * K))(*[c for row in table[c0:c0 + m] for c in row])
+        for k in range(m):
+            p, i = arr[k], c0 + k
+            p.maps, p.label, p.counts = maps[i].data_ptr(), labels[i].data_ptr(), counts[i].data_ptr()
+            p.class_out = None if class_out is None else class_out[i].data_ptr()
+            p.index_out = None if index_out is None else index_out[i].data_ptr()
+        L.check(lib.ca_mseg_score(arr, m, K, h, w, Hl, Wl, nclass, ignore, flags, cof, sc, bw, _stream()), "ca_mseg_score")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # T5 encoder kernels (ca_t5.hip).  Rows are tokens; q / k / v are 2-D views with free row strides.
 
 def t5_attention(q, k, v, bias, out, n_seq: int, num_heads: int) -> None:

@@ -10,7 +10,8 @@ What is mirrored
                                    experiments/imagenet_segmentation/run_experiment.py:166-235
 The heat maps themselves come from ``ConceptAttentionFluxPipeline.encode_image`` (one forward of the 19
 double blocks on the HIP path); everything in this file is small host-side arithmetic on (C, side, side)
-maps -- except ``DeviceSegmentationScores`` and ``ConceptAttentionSegmentationModel.score_images``, which score the maps
+maps -- except ``DeviceSegmentationScores`` and ``ConceptAttentionSegmentationModel.score_images`` (and their multi-class
+counterparts ``DeviceMultiClassScores`` / ``score_multiclass_images`` on ca_mseg_score, csrc/ca_mseg.hip), which score the maps
 where they are: one ca_seg_score workgroup per image (csrc/ca_seg.hip) computes the mask, the counts and the exact AP from
 the device accumulators, and only the 40-byte records come back, once.  The image loop of the harness (`run_experiment.py:137`) is the natural multi-GPU shard: every rank
 scores its own images and ``SegmentationScores.all_reduce`` sums the five counters once at the end.
@@ -231,6 +232,161 @@ class DeviceSegmentationScores:
         return self.to_host().result()
 
 
+# ------------------------------------------------------------------------------------------ multi-class scores
+def map_predictions_to_class_indices(index_map, class_of):
+    """The class id of every cell of an argmax map: ``class_of[index_map]``, one table lookup (``class_of[k]`` is the
+    class id of concept k: 0 for the background concepts, ``class_names.index(name)`` for a present class).  The
+    reference's ``map_predictions_to_voc_class_indices`` (run_multi_class_seg_experiment.py:25-37) remaps in place, class
+    after class, so a cell already mapped to class id v is remapped again when a later concept index equals v; this is
+    the one-step table it means.  A tensor gives an int64 tensor, anything else an int64 array."""
+    table = np.asarray([int(c) for c in class_of], dtype=np.int64)
+    if isinstance(index_map, torch.Tensor):
+        return torch.from_numpy(table)[index_map.detach().cpu().long()]
+    return table[np.asarray(index_map).astype(np.int64)]
+
+
+def multiclass_table(background_concepts, target_concepts, class_names) -> list:
+    """class_of for the concept list ``background_concepts + target_concepts``: 0 for every background concept,
+    ``class_names.index(name)`` for every present class (ValueError for a name ``class_names`` does not hold)."""
+    names = list(class_names)
+    missing = [c for c in target_concepts if c not in names]
+    if missing:
+        raise ValueError(f"present classes {missing} are not in class_names")
+    return [0] * len(background_concepts) + [names.index(c) for c in target_concepts]
+
+
+class MultiClassScores:
+    """Running pixAcc / mIoU / per-class IoU of the multi-class harness (run_multi_class_seg_experiment.py:137-140,
+    207-233): exact integer counters ``correct``, ``labelled``, ``inter[nclass]``, ``union[nclass]`` and ``n``."""
+
+    def __init__(self, nclass: int):
+        self.nclass = int(nclass)
+        self.correct = 0
+        self.labelled = 0
+        self.inter = np.zeros(self.nclass, dtype=np.int64)
+        self.union = np.zeros(self.nclass, dtype=np.int64)
+        self.n = 0
+
+    def update(self, class_map, labels, ignore_index=None) -> dict:
+        """class_map, labels: (H, W) class ids at the label resolution.  Over the pixels with ``labels != ignore_index``
+        (None: all of them, as the harness behaves): labelled, correct, and per class c < nclass the pixels with
+        class == label == c and with class == c or label == c.  A label >= nclass that is not ignored is labelled, never
+        correct and in the union of the predicted class only (VOC's 255 border)."""
+        p = np.asarray(_np(class_map)).astype(np.int64)
+        y = np.asarray(_np(labels)).astype(np.int64)
+        if p.shape != y.shape:
+            raise ValueError(f"class map {p.shape} and labels {y.shape} differ in shape")
+        keep = np.ones(y.shape, dtype=bool) if ignore_index is None else y != int(ignore_index)
+        p, y = p[keep], y[keep]
+        hit = p == y
+        inter = np.bincount(p[hit & (p < self.nclass)], minlength=self.nclass)[:self.nclass]
+        union = np.bincount(p[p < self.nclass], minlength=self.nclass)[:self.nclass] + \
+            np.bincount(y[y < self.nclass], minlength=self.nclass)[:self.nclass] - inter
+        cor, lab = int(hit.sum()), int(y.size)
+        self.correct += cor
+        self.labelled += lab
+        self.inter = self.inter + inter
+        self.union = self.union + union
+        self.n += 1
+        return {"correct": cor, "labelled": lab, "inter": inter, "union": union}
+
+    def add_counts(self, counts) -> "MultiClassScores":
+        """One item's int32 [2 + 2 nclass] row of ca_mseg_score: correct, labelled, inter[nclass], union[nclass]."""
+        c = np.asarray(counts).astype(np.int64).reshape(-1)
+        if c.size != 2 + 2 * self.nclass:
+            raise ValueError(f"a row of {c.size} counts for nclass = {self.nclass}")
+        self.correct += int(c[0])
+        self.labelled += int(c[1])
+        self.inter = self.inter + c[2:2 + self.nclass]
+        self.union = self.union + c[2 + self.nclass:]
+        self.n += 1
+        return self
+
+    def all_reduce(self) -> "MultiClassScores":
+        """Sum the counters over ranks (no-op without an initialised process group)."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            from .distributed import allreduce_sum_
+            v = torch.tensor([self.correct, self.labelled, self.n, *self.inter, *self.union], dtype=torch.int64)
+            dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else v.device
+            v = allreduce_sum_(v.to(dev)).cpu().numpy()
+            self.correct, self.labelled, self.n = int(v[0]), int(v[1]), int(v[2])
+            self.inter, self.union = v[3:3 + self.nclass].copy(), v[3 + self.nclass:].copy()
+        return self
+
+    def result(self) -> dict:
+        """pixAcc = correct / (spacing(1) + labelled); mIoU = the sum of inter / union over the classes with union > 0,
+        divided by (their number + 1e-6) (run_multi_class_seg_experiment.py:225-233); IoU: the per-class vector, NaN for a
+        class with an empty union."""
+        eps = np.spacing(1, dtype=np.float64)
+        seen = self.union > 0
+        iou = np.full(self.nclass, np.nan)
+        iou[seen] = self.inter[seen].astype(np.float64) / self.union[seen].astype(np.float64)
+        miou = 0.0
+        for c in range(self.nclass):          # (the harness's loop, in its order)
+            if self.union[c] == 0:
+                continue
+            miou += float(self.inter[c]) / float(self.union[c])
+        miou /= (int(seen.sum()) + 1e-6)
+        return {"pixAcc": float(np.float64(1.0) * self.correct / (eps + self.labelled)), "mIoU": float(miou), "IoU": iou,
+                "n": self.n}
+
+
+class DeviceMultiClassScores:
+    """``MultiClassScores`` whose per-image count rows stay on the device until somebody asks: ``reserve`` hands
+    ``ops.mseg_score`` the next int32 [2 + 2 nclass] rows of a buffer that grows by ``chunk`` rows, and ``records`` /
+    ``to_host`` / ``result`` / ``all_reduce`` download the rows written so far ONCE (and not again until new ones were
+    reserved).  ``ids[r]`` is what the caller named row r (``score_multiclass_images``: the image's position in its call,
+    since images of different concept counts are scored in different forwards)."""
+
+    def __init__(self, nclass: int, device="cuda:0", chunk: int = 256):
+        self.nclass = int(nclass)
+        self.width = 2 + 2 * self.nclass
+        self.device = torch.device(device)
+        self.chunk = max(1, int(chunk))
+        self.n = 0
+        self.ids: list = []
+        self._buf = torch.zeros(self.chunk, self.width, dtype=torch.int32, device=self.device)
+        self._host = None            # (n, rows) of the last download
+
+    def reserve(self, n: int, ids=None) -> torch.Tensor:
+        """int32 [n, 2 + 2 nclass]: the rows of the next n items."""
+        need = self.n + n
+        if need > self._buf.shape[0]:
+            cap = -(-need // self.chunk) * self.chunk
+            grown = torch.zeros(cap, self.width, dtype=torch.int32, device=self.device)
+            grown[:self.n] = self._buf[:self.n]      # (stream-ordered behind the launches that wrote them)
+            self._buf = grown
+        out = self._buf[self.n:need]
+        self.ids += list(range(self.n, need)) if ids is None else list(ids)
+        self.n = need
+        return out
+
+    def records(self) -> np.ndarray:
+        """int32 [n, 2 + 2 nclass] in reservation order (``ids``): the one download."""
+        if self._host is None or self._host[0] != self.n:
+            self._host = (self.n, self._buf[:self.n].cpu().numpy())
+        return self._host[1]
+
+    def to_host(self) -> MultiClassScores:
+        out = MultiClassScores(self.nclass)
+        for row in self.records():
+            out.add_counts(row)
+        return out
+
+    def all_reduce(self) -> MultiClassScores:
+        return self.to_host().all_reduce()
+
+    def result(self) -> dict:
+        return self.to_host().result()
+
+
+# what the multi-class methods accept as **encode_kwargs: the same set as the literal inside score_images (which keeps its
+# own copy); an argument added to one belongs in the other
+_ENCODE_KEYS = {"layers", "num_samples", "num_steps", "noise_timestep", "seed", "height", "width", "batch",
+                "joint_attention_kwargs", "noise", "vae_noise", "attention_norm", "softmax"}
+
+
 # ------------------------------------------------------------------------------------------ model wrapper
 class ConceptAttentionSegmentationModel:
     """Callable with the reference's segmentation-model contract (segmentation.py:34-81):
@@ -330,6 +486,129 @@ class ConceptAttentionSegmentationModel:
         planes = planes.numpy()
         back = {i: k for k, i in enumerate(order)}
         return [masks[back[i]] for i in range(n)], [planes[back[i]] for i in range(n)]
+
+    def _multiclass_arguments(self, what, images, captions, background_concepts, target_concepts, target_space, kw):
+        n = len(images)
+        if isinstance(captions, str) or len(captions) < n:
+            raise ValueError(f"{what}: {n} images need {n} captions")
+        if target_concepts is None or len(target_concepts) != n or any(isinstance(t, str) for t in target_concepts):
+            raise ValueError(f"{what}: target_concepts is one list of present classes per image ({n} images)")
+        if target_space not in ("output", "cross_attention"):
+            raise ValueError("target_space: 'output' or 'cross_attention'")
+        unknown = set(kw) - _ENCODE_KEYS
+        if unknown:
+            raise TypeError(f"{what}: unexpected arguments {sorted(unknown)}")
+        return [list(background_concepts) + list(t) for t in target_concepts]
+
+    @torch.no_grad()
+    def segment_multiclass(self, images, captions, background_concepts, target_concepts, apply_blur: bool = False,
+                           target_space: str = "output", **encode_kwargs):
+        """The reference's ``FluxMultiClassSegmentation.__call__`` (multi_class_segmentation.py:58-79) for a list of
+        images, on the host: per image ``(predicted_concepts, concept_heatmaps, None)`` with the fp32 maps
+        (K, side, side) of the concepts ``background_concepts + target_concepts[i]`` (blurred with ``apply_blur``) and
+        their argmax over the concepts, int64 (side, side).  ``target_concepts``: one list of present classes per image;
+        the images go through ``pipeline.encode_images``, those with one concept count ``batch`` at a time.
+        ``encode_kwargs``: what ``score_images`` takes."""
+        images = list(images)
+        kw = dict(encode_kwargs)
+        concepts = self._multiclass_arguments("segment_multiclass", images, captions, background_concepts, target_concepts,
+                                              target_space, kw)
+        outs = self.pipeline.encode_images(images, concepts, list(captions[:len(images)]), width=kw.get("width", 1024),
+                                           height=kw.get("height", 1024), layer_indices=kw.get("layers", list(range(15, 19))),
+                                           num_samples=kw.get("num_samples", 1), num_steps=kw.get("num_steps", 4),
+                                           noise_timestep=kw.get("noise_timestep", 2), seed=kw.get("seed", 0),
+                                           batch=kw.get("batch", 5), noise=kw.get("noise"), vae_noise=kw.get("vae_noise"),
+                                           return_pil_heatmaps=False, attention_norm=kw.get("attention_norm", "sparsemax"),
+                                           softmax=kw.get("softmax", True),
+                                           joint_attention_kwargs=kw.get("joint_attention_kwargs"))
+        results = []
+        for o in outs:
+            maps = torch.as_tensor(np.asarray(o.concept_heatmaps if target_space == "output" else o.cross_attention_maps),
+                                   dtype=torch.float32)
+            if apply_blur:
+                maps = gaussian_blur3(maps)
+            results.append((maps.argmax(dim=0), maps, None))
+        return results
+
+    @torch.no_grad()
+    def score_multiclass_images(self, images, captions, background_concepts, target_concepts, class_names, labels, scores,
+                                ignore_index=None, apply_blur: bool = False, concept_scale_values=None,
+                                target_space: str = "output", return_predictions: bool = False, **encode_kwargs):
+        """The multi-class (Pascal VOC) evaluation loop of the reference (run_multi_class_seg_experiment.py:143-233)
+        without leaving the device: the chunks of ``pipeline.encode_images``, each item's (K, side, side) planes straight
+        from the device accumulator into ``ops.mseg_score`` (argmax, class table, nearest resize to the label, counts),
+        the count rows into ``scores`` (a ``DeviceMultiClassScores`` of ``len(class_names)`` classes; its ``ids`` name
+        the image of every row).  ``target_concepts``: one list of present classes per image, each a name of
+        ``class_names``; the background concepts count as class 0.  ``labels``: per image a uint8 array of class ids, all
+        of one shape (resizing label files stays the caller's job, as in the harness); ``ignore_index``: the label value
+        that is skipped, None for none (the harness skips none).  ``concept_scale_values``: per image None or one factor
+        per concept, multiplied onto the planes before the argmax (the harness's unimplemented argument).  Nothing per
+        image comes back unless ``return_predictions``: then the class maps, uint8 (side, side) per image, in one download
+        at the end.  Maps of more than 16384 cells raise a ValueError."""
+        from . import _lib as L
+        from . import ops
+        images = list(images)
+        n = len(images)
+        kw = dict(encode_kwargs)
+        what = "score_multiclass_images"
+        concepts = self._multiclass_arguments(what, images, captions, background_concepts, target_concepts, target_space, kw)
+        if len(labels) != n:
+            raise ValueError(f"{what}: {n} images need {n} labels")
+        class_names = list(class_names)
+        if not 1 <= len(class_names) <= L.MSEG_MAX_CLASSES or getattr(scores, "nclass", None) != len(class_names):
+            raise ValueError(f"{what}: class_names holds 1..{L.MSEG_MAX_CLASSES} names and scores counts as many classes")
+        tables = [multiclass_table(background_concepts, t, class_names) for t in target_concepts]
+        if any(not 1 <= len(c) <= L.MSEG_MAX_CONCEPTS for c in concepts):
+            raise ValueError(f"{what}: an image takes 1..{L.MSEG_MAX_CONCEPTS} concepts (background and present classes)")
+        side_h, side_w = kw.get("height", 1024) // 16, kw.get("width", 1024) // 16
+        if side_h * side_w > L.MSEG_MAX_CELLS:
+            raise ValueError(f"{what}: maps of {side_h} x {side_w} cells; the device route takes up to {L.MSEG_MAX_CELLS} "
+                             "(segment_multiclass + MultiClassScores.update remain for larger maps)")
+        lab = []
+        for i, y in enumerate(labels):
+            y = np.asarray(_np(y))
+            if y.ndim != 2 or y.dtype != np.uint8 or (lab and y.shape != lab[0].shape):
+                raise ValueError(f"labels[{i}]: expected a uint8 array of class ids (size, size), all labels of one shape, "
+                                 f"got {y.dtype} {y.shape}")
+            lab.append(y)
+        scales = [None] * n
+        if concept_scale_values is not None:
+            if len(concept_scale_values) != n:
+                raise ValueError(f"{what}: concept_scale_values is one entry per image ({n} images)")
+            for i, v in enumerate(concept_scale_values):
+                if v is not None:
+                    scales[i] = tuple(float(x) for x in v)
+                    if len(scales[i]) != len(concepts[i]):
+                        raise ValueError(f"{what}: concept_scale_values[{i}] needs one factor per concept ({len(concepts[i])})")
+        pipe = self.pipeline
+        blur = ops.seg_blur_weights() if apply_blur else None
+        preds, order = [], []
+        with torch.cuda.device(pipe.device):
+            chunks = pipe._encode_chunks(images, concepts, list(captions[:n]), kw.get("width", 1024), kw.get("height", 1024),
+                                         kw.get("layers", list(range(15, 19))), kw.get("num_samples", 1),
+                                         kw.get("num_steps", 4), kw.get("noise_timestep", 2), kw.get("seed", 0),
+                                         kw.get("batch", 5), kw.get("noise"), kw.get("vae_noise"), True,
+                                         kw.get("attention_norm", "sparsemax"), kw.get("softmax", True),
+                                         kw.get("joint_attention_kwargs"))
+            for idx, acc_o, acc_c in chunks:
+                acc = acc_o if target_space == "output" else acc_c
+                y = torch.from_numpy(np.stack([lab[i] for i in idx])).pin_memory().to(pipe.device, non_blocking=True)
+                groups = {}                      # the items of a launch share one scale
+                for k, i in enumerate(idx):
+                    groups.setdefault(scales[i], []).append(k)
+                for sc, ks in groups.items():
+                    c_out = torch.empty(len(ks), *acc.shape[2:], dtype=torch.uint8, device=pipe.device) \
+                        if return_predictions else None
+                    ops.mseg_score([acc[k] for k in ks], [y[k] for k in ks], scores.reserve(len(ks), [idx[k] for k in ks]),
+                                   [tables[idx[k]] for k in ks], len(class_names), ignore_index=ignore_index, scale=sc,
+                                   blur_weights=blur, class_out=c_out)
+                    if return_predictions:
+                        preds.append(c_out), order.extend(idx[k] for k in ks)
+        if not return_predictions:
+            return None
+        preds = torch.cat(preds).cpu().numpy()
+        back = {i: k for k, i in enumerate(order)}
+        return [preds[back[i]] for i in range(n)]
 
     def __call__(self, images, target_concepts, concepts, captions, mean_value_threshold: bool = True,
                  joint_attention_kwargs=None, apply_blur: bool = False, **kwargs):

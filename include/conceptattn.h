@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CA_VERSION 132 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
+#define CA_VERSION 133 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
                           CA_ATTN_Q_PRESCALED; .1: ca_axpy_f32, ca_split_bf16; .2: ca_attn_stats; .3: ca_gemm_problem.qk_f16,
                           ca_attn_fwd_qk16; .4: ca_qpre_finish_rope_f32; .5: ca_heatmap_fused; .6: ca_gemm_plan;
                           .7: the autoencoder kernels (conv3x3_nhwc, groupnorm_nhwc, softmax_rows_f32, affine_rows_f32);
@@ -36,7 +36,8 @@ extern "C" {
                           129: the CLIP text encoder kernels (clip_attn_bf16, layernorm_f32in, quick_gelu_bf16,
                           clip_embed_f32); 130: the pixel I/O kernels (pixels_u8_to_nhwc32_bf16, nhwc_f32_to_pixels_u8);
                           131: the T5 encoder's e4m3 producers (t5_rmsnorm_f32in_fp8, gated_mul_fp8);
-                          132: segmentation scoring on the device (seg_score) */
+                          132: segmentation scoring on the device (seg_score);
+                          133: multi-class segmentation scoring on the device (mseg_score) */
 
 #define CA_OK 0
 #define CA_ERR_ARG (-1)    /* bad shape / null pointer / misalignment */
@@ -583,6 +584,45 @@ typedef struct {
 } ca_seg_record;
 int ca_seg_score(const ca_seg_problem *problems, int32_t n_problems, int32_t h, int32_t w, int32_t Hl, int32_t Wl,
                  int32_t flags, const float *blur_weights, ca_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Multi-class segmentation scoring (experiments/pascal_voc_segmentation/multi_class_segmentation.py:58-79 and
+ * run_multi_class_seg_experiment.py:25-37, 194-233): one workgroup per item takes the argmax over the item's K
+ * accumulated maps, maps the winning concept to its class and counts the class map against a label image of class ids,
+ * without leaving the device.  Per item, every step one fp32 rounding:
+ *   x_k   = plane k, or with CA_MSEG_BLUR its 3x3 blur with reflect padding exactly as seg_score forms it: the nine
+ *           products blur_weights[3 i + j] * plane[y + i - 1, x + j - 1], each rounded, added in row-major order
+ *   s_k   = scale[k] * x_k when scale is given, else x_k        (the harness's unimplemented concept_scale_values)
+ *   index[cell] = torch.argmax over k: plane k replaces the running best iff s_k > best, or s_k is NaN and best is
+ *           not; so the first index of the maximum wins, -0.0 == 0.0, and the first NaN beats every number
+ *   class[cell] = class_of[item][index[cell]]
+ *   label pixel (Y, X) reads cell (near(Y; Hl, h), near(X; Wl, w)), the near of seg_score
+ *   over the label pixels with label != ignore_index (ignore_index = -1: none are skipped):
+ *     labelled = their number;  correct = those with class == label;
+ *     inter[c] = pixels with class == label == c;  union[c] = pixels with class == c or label == c, for c < nclass
+ *   a label value >= nclass that is not ignored counts as labelled, is never correct and enters only the union of the
+ *   predicted class (VOC's 255 border in lines 207-222 of the harness).  All counts are exact integers.
+ * All problems of a call share K, h, w, Hl, Wl, nclass, ignore_index, flags and scale.  class_of: uint8
+ * [n_problems][K], the class id of every concept of every item, required, every entry < nclass; scale: float [K] or
+ * NULL; blur_weights: float [9], required with CA_MSEG_BLUR.  All three are HOST arrays, read during the call; nothing
+ * is uploaded, allocated or retained.  Limits: 1 <= K <= 32, 1 <= h w <= 16384, 1 <= Hl Wl <= 2^24, 1 <= nclass <= 256,
+ * -1 <= ignore_index <= 255, 1 <= n_problems <= 16, CA_MSEG_BLUR needs h, w >= 2, no other flag bit; CA_ERR_ARG
+ * otherwise, before any launch.  Needs 18 KB of LDS. */
+#define CA_MSEG_MAX_PROBLEMS 16
+#define CA_MSEG_MAX_CONCEPTS 32
+#define CA_MSEG_MAX_CLASSES 256
+#define CA_MSEG_MAX_CELLS 16384
+#define CA_MSEG_BLUR 4
+typedef struct {
+  const float *maps;  /* fp32 [K, h, w] contiguous: the item's accumulated maps, concept-major            */
+  const void *label;  /* uint8 [Hl, Wl] contiguous: class ids                                              */
+  void *counts;       /* int32 [2 + 2 nclass], 8-byte aligned: correct, labelled, inter[nclass], union[..] */
+  void *class_out;    /* uint8 [h, w] or NULL: the predicted class per map cell                            */
+  void *index_out;    /* uint8 [h, w] or NULL: the winning concept index per map cell                      */
+} ca_mseg_problem;
+int ca_mseg_score(const ca_mseg_problem *problems, int32_t n_problems, int32_t K, int32_t h, int32_t w,
+                  int32_t Hl, int32_t Wl, int32_t nclass, int32_t ignore_index, int32_t flags,
+                  const void *class_of, const float *scale, const float *blur_weights, ca_stream_t stream);
 
 #ifdef __cplusplus
 }
