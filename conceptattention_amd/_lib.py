@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CA_LIB_PATH: another build of the same library (an A/B against another source tree); still no fallback
 LIB_PATH = os.environ.get("CA_LIB_PATH") or os.path.join(_HERE, "libconceptattn.so")
 
-CA_VERSION = 133
+CA_VERSION = 134
 EPI_BIAS, EPI_GELU_TANH, EPI_GATE_RESIDUAL, EPI_SPLIT_GELU, EPI_QKV_NORM_ROPE = 0, 1, 2, 3, 4
 TILE_AUTO, TILE_256x256, TILE_256x192, TILE_256x128, TILE_256x64 = 0, 1, 2, 3, 4
 TILE_PP_256x256, TILE_PP_256x128, TILE_PP_256x192 = 5, 6, 7
@@ -33,6 +33,8 @@ MSEG_MAX_CLASSES = 256              # ca_mseg_score: nclass
 MSEG_MAX_CELLS = 16384              # ca_mseg_score: h * w of the maps
 MSEG_MAX_LABEL_PIXELS = 1 << 24     # ca_mseg_score: Hl * Wl of the label
 MSEG_BLUR = 4
+SEGTAB_MAX_MAPS = 65536              # ca_segtab_score: maps of one call
+SEGTAB_MEAN_THRESHOLD, SEGTAB_DOWNSCALE, SEGTAB_BLUR, SEGTAB_RAW = 1, 2, 4, 8
 ATTN_Q_PRESCALED = 0.0   # ca_attn_fwd_bf16(scale=...): the q rows already carry softmax_scale * log2(e)
 
 
@@ -178,6 +180,9 @@ SIGNATURES = {
     "ca_mseg_score": (C.c_int, [C.POINTER(MsegProblem), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                 C.c_void_p]),
+    "ca_segtab_score": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float),
+                                  C.c_void_p]),
 }
 
 _lib = None

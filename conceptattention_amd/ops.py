@@ -819,6 +819,74 @@ def seg_score(maps, labels, results, mean_value_threshold: bool = True, downscal
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Sweep scoring (ca_segtab.hip): a table of maps of one geometry against one label image, one workgroup per map.
+
+def segtab_cells(h: int, w: int, device) -> torch.Tensor:
+    """The workspace of segtab_score for h x w maps: uint32 [4, (h w + 3) & ~3] (torch has no uint32 arithmetic the
+    caller needs; int32 holds the same bits).  The entry zeroes it on every call."""
+    return torch.empty(4, (h * w + 3) & ~3, dtype=torch.int32, device=device)
+
+
+def segtab_score(maps, target, label, records, cells=None, mean_value_threshold: bool = True,
+                 downscale_for_eval: bool = False, blur_weights=None, normalize: bool = True) -> None:
+    """Score the M maps of one concept against ONE label image (ca_segtab_score; include/conceptattn.h states the
+    arithmetic).  maps: fp32 [M, C, h, w] contiguous with ``target`` the concept plane that is scored (the other planes
+    are never read), or fp32 [M, h, w] contiguous (``target`` 0 or None); h * w <= 4096.  label: uint8 [Hl, Wl]
+    contiguous, nonzero = positive, Hl * Wl <= 2^24.  records: uint8 [M, 40] contiguous, one ca_seg_record per map
+    (L.SegRecord).  cells: the int32 [4, (h w + 3) & ~3] workspace (segtab_cells), allocated when not given.
+    ``blur_weights``: nine numbers (seg_blur_weights) to blur every map first, None for no blur; ``normalize=False``
+    scores the raw map values instead of their min-max coefficient.  More than L.SEGTAB_MAX_MAPS maps go in several
+    calls."""
+    lib = L.load()
+    _chk(maps, torch.float32, "maps"), _chk(label, torch.uint8, "label"), _chk(records, torch.uint8, "records")
+    if maps.dim() not in (3, 4) or not maps.is_contiguous() or maps.shape[0] < 1:
+        raise ValueError(f"segtab_score: maps{tuple(maps.shape)} must be contiguous fp32 [M, C, h, w] or [M, h, w], M >= 1")
+    M, Cc = int(maps.shape[0]), (int(maps.shape[1]) if maps.dim() == 4 else 1)
+    h, w = int(maps.shape[-2]), int(maps.shape[-1])
+    k = 0 if target is None else int(target)
+    if not 0 <= k < Cc:
+        raise ValueError(f"segtab_score: target = {target} with {Cc} concept planes")
+    if label.dim() != 2 or not label.is_contiguous() or label.device != maps.device:
+        raise ValueError(f"segtab_score: label{tuple(label.shape)} must be contiguous uint8 [Hl, Wl] on the device of maps")
+    Hl, Wl = int(label.shape[0]), int(label.shape[1])
+    if tuple(records.shape) != (M, SEG_RECORD_BYTES) or not records.is_contiguous() or records.device != maps.device:
+        raise ValueError(f"segtab_score: records{tuple(records.shape)} must be contiguous uint8 [{M}, {SEG_RECORD_BYTES}] on "
+                         "the device of maps")
+    if not 1 <= h * w <= L.SEG_MAX_CELLS:
+        raise ValueError(f"segtab_score: maps of {h} x {w} cells; ca_segtab_score takes 1..{L.SEG_MAX_CELLS} (larger maps "
+                         "are scored on the host: segmentation.SweepScores.update)")
+    if not 1 <= Hl * Wl <= L.SEG_MAX_LABEL_PIXELS:
+        raise ValueError(f"segtab_score: a label of {Hl} x {Wl} pixels; ca_segtab_score takes 1..2^24")
+    hw4 = (h * w + 3) & ~3
+    if cells is None:
+        cells = segtab_cells(h, w, maps.device)
+    _chk(cells, torch.int32, "cells")
+    if tuple(cells.shape) != (4, hw4) or not cells.is_contiguous() or cells.device != maps.device or cells.data_ptr() % 16:
+        raise ValueError(f"segtab_score: cells{tuple(cells.shape)} must be contiguous int32 [4, {hw4}], 16-byte aligned, on "
+                         "the device of maps")
+    flags = (L.SEGTAB_MEAN_THRESHOLD if mean_value_threshold else 0) | (L.SEGTAB_DOWNSCALE if downscale_for_eval else 0) | \
+        (0 if normalize else L.SEGTAB_RAW)
+    bw = None
+    if blur_weights is not None:
+        blur_weights = [float(v) for v in blur_weights]
+        if len(blur_weights) != 9:
+            raise ValueError("segtab_score: blur_weights are the nine weights of the 3x3 blur")
+        if h < 2 or w < 2:
+            raise ValueError(f"segtab_score: blur_weights with maps of {h} x {w} cells; the blur's reflect padding needs "
+                             "h >= 2 and w >= 2")
+        flags |= L.SEGTAB_BLUR
+        bw = (C.c_float * 9)(*blur_weights)
+    stride = Cc * h * w                      # elements between two scored maps: an int64_t of the entry
+    base = maps.data_ptr() + 4 * k * h * w
+    for m0 in range(0, M, L.SEGTAB_MAX_MAPS):
+        n = min(L.SEGTAB_MAX_MAPS, M - m0)
+        L.check(lib.ca_segtab_score(C.cast(base + 4 * m0 * stride, C.POINTER(C.c_float)), stride, _i32(n, "n_maps"),
+                                    label.data_ptr(), records[m0:m0 + n].data_ptr(), cells.data_ptr(), _i32(h, "h"),
+                                    _i32(w, "w"), _i32(Hl, "Hl"), _i32(Wl, "Wl"), flags, bw, _stream()),
+                "ca_segtab_score")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Multi-class segmentation scoring (ca_mseg.hip): an item's K maps against a label image of class ids.
 
 def mseg_score(maps, labels, counts, class_of, nclass: int, ignore_index: Optional[int] = None, scale=None,

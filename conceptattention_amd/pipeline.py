@@ -370,6 +370,27 @@ class ConceptAttentionFluxPipeline:
                            return_vectors=False, heatmaps=reqs)
         return out.view(nl, nlay, C, side, side), cross.view(nl, nlay, C, side, side)
 
+    @torch.no_grad()
+    @on_own_device
+    def layer_noise_sweep(self, image, concepts: list, prompt: str, noise_levels, num_steps: int = 50, layer_indices=None,
+                          num_samples: int = 1, seed: int = 0, width: int = 1024, height: int = 1024, batch: int = 5,
+                          vae_noise=None):
+        """``layer_noise_sweep_on_device`` from an image and strings: ``image`` is a latent tensor (1,16,h/8,w/8) or, with
+        an autoencoder in the pipeline, a PIL image (``vae_noise`` (1,16,h/8,w/8): its sampling noise, drawn on the
+        device when not given); ``concepts`` and ``prompt`` go through the text encoders as in ``encode_image``.
+        Returns the two DEVICE tables (out_space, cross_space), fp32 [len(noise_levels), len(layer_indices), C, side,
+        side]; ``batch`` levels share one forward."""
+        assert height == width, "Height and width must be the same for now"
+        if isinstance(image, torch.Tensor):
+            latent = image.to(self.device, torch.bfloat16)
+        else:
+            latent = self._encode_pixels([image], height, width,
+                                         None if vae_noise is None else vae_noise.to(self.device, torch.float32))
+        txt, vec, con, _, _ = self._embed(prompt, concepts)
+        return self.layer_noise_sweep_on_device(latent, txt, vec, con, [int(v) for v in noise_levels], num_steps=num_steps,
+                                                layer_indices=layer_indices, seed=seed, num_samples=num_samples,
+                                                batch=batch)
+
     # ------------------------------------------------------------------ encode_image (:204-357)
     @torch.no_grad()
     @on_own_device

@@ -13,7 +13,9 @@ double blocks on the HIP path); everything in this file is small host-side arith
 maps -- except ``DeviceSegmentationScores`` and ``ConceptAttentionSegmentationModel.score_images`` (and their multi-class
 counterparts ``DeviceMultiClassScores`` / ``score_multiclass_images`` on ca_mseg_score, csrc/ca_mseg.hip), which score the maps
 where they are: one ca_seg_score workgroup per image (csrc/ca_seg.hip) computes the mask, the counts and the exact AP from
-the device accumulators, and only the 40-byte records come back, once.  The image loop of the harness (`run_experiment.py:137`) is the natural multi-GPU shard: every rank
+the device accumulators, and only the 40-byte records come back, once.  ``SweepScores`` / ``DeviceSweepScores`` /
+``score_sweep`` do the same for the per-layer x per-noise-level tables of ``pipeline.layer_noise_sweep`` (ca_segtab_score,
+csrc/ca_segtab.hip: one record per (level, layer) map, two launches per table).  The image loop of the harness (`run_experiment.py:137`) is the natural multi-GPU shard: every rank
 scores its own images and ``SegmentationScores.all_reduce`` sums the five counters once at the end.
 """
 from __future__ import annotations
@@ -230,6 +232,151 @@ class DeviceSegmentationScores:
 
     def result(self) -> dict:
         return self.to_host().result()
+
+
+# ------------------------------------------------------------------------------------------ sweep scores
+SWEEP_SPACES = ("output", "cross_attention")
+
+
+class SweepScores:
+    """The running tables of the per-layer and per-timestep segmentation sweeps
+    (experiments/per_layer_segmentation/test_segmentations_per_layer.py:164-243,
+    experiments/per_timestep_segmentation/test_segmentations_per_time.py:75-174): per space (``output``,
+    ``cross_attention``) arrays [n_levels, n_columns] of ``correct``, ``labelled``, ``ap_sum`` and ``n`` and
+    [n_levels, n_columns, 2] of ``inter`` and ``union``, summed over images.  A column is a layer, or the extra last
+    column of a sweep scored with ``layer_mean`` (the per-timestep script's "all layers at this level" row)."""
+
+    def __init__(self, n_levels: int, n_layers: int):
+        self.n_levels, self.n_columns = int(n_levels), int(n_layers)
+        shape = (self.n_levels, self.n_columns)
+        self.tables = {s: {"correct": np.zeros(shape), "labelled": np.zeros(shape), "inter": np.zeros(shape + (2,)),
+                           "union": np.zeros(shape + (2,)), "ap_sum": np.zeros(shape), "n": np.zeros(shape, dtype=np.int64)}
+                       for s in SWEEP_SPACES}
+
+    def _add(self, space, level, column, cor, lab, inter, union, ap):
+        t = self.tables[space]
+        t["correct"][level, column] += cor
+        t["labelled"][level, column] += lab
+        t["inter"][level, column] += inter
+        t["union"][level, column] += union
+        t["ap_sum"][level, column] += ap
+        t["n"][level, column] += 1
+
+    def update(self, space: str, level: int, column: int, mask, coefficients, labels) -> dict:
+        """The host route for one map: mask, coefficients (h, w) at the label resolution, labels (h, w) bool; what
+        ``SegmentationScores.update`` computes, added to cell (level, column) of ``space``."""
+        out = SegmentationScores().update(mask, coefficients, labels)
+        self._add(space, level, column, out["correct"], out["labelled"], out["inter"], out["union"], out["ap"])
+        return out
+
+    def add_records(self, space: str, records, label_pixels: int, columns=None) -> "SweepScores":
+        """ca_seg_record rows [n_levels, len(columns)] of ONE image (``columns``: all of them by default), with the
+        (1 - m, m) double counting ``DeviceSegmentationScores.to_host`` documents: a pixel where mask and label agree
+        counts once per class plane."""
+        rec = np.asarray(records)
+        columns = list(range(self.n_columns)) if columns is None else [int(c) for c in columns]
+        rec = rec.reshape(self.n_levels, len(columns))
+        t, n_px = self.tables[space], int(label_pixels)
+        agree = rec["n11"].astype(np.int64) + rec["n00"].astype(np.int64)
+        t["correct"][:, columns] += 2 * agree
+        t["labelled"][:, columns] += 2 * n_px
+        t["inter"][:, columns] += agree[..., None]
+        t["union"][:, columns] += (2 * n_px - agree)[..., None]
+        t["ap_sum"][:, columns] += rec["ap"]
+        t["n"][:, columns] += 1
+        return self
+
+    def _vector(self) -> np.ndarray:
+        return np.concatenate([np.asarray(self.tables[s][k], dtype=np.float64).reshape(-1) for s in SWEEP_SPACES
+                               for k in ("correct", "labelled", "inter", "union", "ap_sum", "n")])
+
+    def all_reduce(self) -> "SweepScores":
+        """Sum the tables over ranks (no-op without an initialised process group)."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            from .distributed import allreduce_sum_
+            v = torch.from_numpy(self._vector())
+            dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else v.device
+            v = allreduce_sum_(v.to(dev)).cpu().numpy()
+            o = 0
+            for s in SWEEP_SPACES:
+                for k in ("correct", "labelled", "inter", "union", "ap_sum", "n"):
+                    a = self.tables[s][k]
+                    part = v[o:o + a.size].reshape(a.shape)
+                    self.tables[s][k] = np.rint(part).astype(np.int64) if k == "n" else part.copy()
+                    o += a.size
+        return self
+
+    def result(self, space: str = "output") -> dict:
+        """pixAcc, mIoU, mAP as arrays [n_levels, n_columns] (the formulas of ``SegmentationScores.result``) and n."""
+        t = self.tables[space]
+        eps = np.spacing(1, dtype=np.float64)
+        iou = t["inter"] / (eps + t["union"])
+        return {"pixAcc": t["correct"] / (eps + t["labelled"]), "mIoU": iou.mean(axis=-1),
+                "mAP": t["ap_sum"] / np.maximum(t["n"], 1), "n": t["n"].copy()}
+
+    def rows(self, space: str = "output"):
+        """(level, column, pixAcc, mIoU, mAP) in the scripts' CSV order: level by level, column by column."""
+        r = self.result(space)
+        for lv in range(self.n_levels):
+            for col in range(self.n_columns):
+                yield lv, col, float(r["pixAcc"][lv, col]), float(r["mIoU"][lv, col]), float(r["mAP"][lv, col])
+
+
+class DeviceSweepScores:
+    """``SweepScores`` whose records stay on the device until somebody asks: ``reserve`` hands ``ops.segtab_score`` the
+    [n_levels * len(columns), 40] records of one call, and ``records`` / ``to_host`` / ``result`` / ``all_reduce``
+    download everything written so far ONCE (and not again until new records were reserved)."""
+
+    def __init__(self, n_levels: int, n_layers: int, device="cuda:0", chunk: int = 4096):
+        self.n_levels, self.n_columns = int(n_levels), int(n_layers)
+        self.device = torch.device(device)
+        self.chunk = max(1, int(chunk))
+        self.n = 0
+        self._calls: list = []       # (space, first record, columns, label pixels) per reserve
+        self._buf = torch.zeros(self.chunk, SEG_RECORD.itemsize, dtype=torch.uint8, device=self.device)
+        self._host = None            # (n, records) of the last download
+
+    def reserve(self, space: str, label_pixels: int, columns=None) -> torch.Tensor:
+        """uint8 [n_levels * len(columns), 40], level-major: the records of one image's maps in ``space``."""
+        if space not in SWEEP_SPACES:
+            raise ValueError(f"space: one of {SWEEP_SPACES}")
+        columns = list(range(self.n_columns)) if columns is None else [int(c) for c in columns]
+        n = self.n_levels * len(columns)
+        need = self.n + n
+        if need > self._buf.shape[0]:
+            cap = -(-need // self.chunk) * self.chunk
+            grown = torch.zeros(cap, SEG_RECORD.itemsize, dtype=torch.uint8, device=self.device)
+            grown[:self.n] = self._buf[:self.n]      # (stream-ordered behind the launches that wrote them)
+            self._buf = grown
+        out = self._buf[self.n:need]
+        self._calls.append((space, self.n, columns, int(label_pixels)))
+        self.n = need
+        return out
+
+    def records(self) -> list:
+        """[(space, columns, records [n_levels, len(columns)] of SEG_RECORD), ...] in reservation order: the one
+        download."""
+        if self._host is None or self._host[0] != self.n:
+            self._host = (self.n, self._buf[:self.n].cpu().numpy().view(SEG_RECORD).reshape(self.n))
+        rec = self._host[1]
+        return [(s, cols, rec[o:o + self.n_levels * len(cols)].reshape(self.n_levels, len(cols)))
+                for s, o, cols, _ in self._calls]
+
+    def to_host(self) -> SweepScores:
+        out = SweepScores(self.n_levels, self.n_columns)
+        for (s, cols, rec), (_, _, _, n_px) in zip(self.records(), self._calls):
+            out.add_records(s, rec, n_px, cols)
+        return out
+
+    def all_reduce(self) -> SweepScores:
+        return self.to_host().all_reduce()
+
+    def result(self, space: str = "output") -> dict:
+        return self.to_host().result(space)
+
+    def rows(self, space: str = "output"):
+        return self.to_host().rows(space)
 
 
 # ------------------------------------------------------------------------------------------ multi-class scores
@@ -486,6 +633,75 @@ class ConceptAttentionSegmentationModel:
         planes = planes.numpy()
         back = {i: k for k, i in enumerate(order)}
         return [masks[back[i]] for i in range(n)], [planes[back[i]] for i in range(n)]
+
+    @torch.no_grad()
+    def score_sweep(self, images, target_concepts, concepts, captions, labels, scores, noise_levels,
+                    mean_value_threshold: bool = True, downscale_for_eval: bool = False, apply_blur: bool = False,
+                    size: int = 224, normalize: bool = True, layer_mean: bool = False, target_space=None, **sweep_kwargs):
+        """The per-layer and per-timestep segmentation sweeps without leaving the device: per image the two tables of
+        ``pipeline.layer_noise_sweep`` ([levels, layers, C, side, side]), then per space ONE ``ops.segtab_score`` call
+        that scores the target concept's levels x layers maps against the image's label; the records go into ``scores``
+        (a ``DeviceSweepScores`` of len(noise_levels) levels and as many columns as layers, plus one with
+        ``layer_mean``).  ``layer_mean=True`` adds a second call per space on ``table.mean(dim=1)``, formed by torch on
+        the device and scored into the extra last column: the per-timestep script's "all layers at this level" row.
+        ``normalize=False`` scores the raw coefficients, as the per-layer script does (its call is ``noise_levels=[t]``,
+        ``normalize=False``).  ``target_space``: "output", "cross_attention", or None for both.  ``labels``: per image a
+        uint8 / bool array (size, size), nonzero = positive.  ``sweep_kwargs``: what ``layer_noise_sweep`` takes
+        (num_steps, layer_indices, num_samples, seed, width, height, batch) and ``vae_noise``, one tensor per image.
+        Nothing per image comes back.  Maps of more than 4096 cells raise a ValueError: ``SweepScores.update`` remains
+        for them, and for the per-timestep script's bilinear resize of the coefficients."""
+        from . import _lib as L
+        from . import ops
+        images = list(images)
+        n = len(images)
+        if target_concepts is None or not (len(target_concepts) == len(labels) == n and len(captions) >= n):
+            raise ValueError(f"score_sweep: {n} images need {n} target concepts, labels and captions")
+        spaces = SWEEP_SPACES if target_space is None else (target_space,)
+        if any(s not in SWEEP_SPACES for s in spaces):
+            raise ValueError("target_space: 'output', 'cross_attention' or None for both")
+        kw = dict(sweep_kwargs)
+        unknown = set(kw) - {"num_steps", "layer_indices", "num_samples", "seed", "width", "height", "batch", "vae_noise"}
+        if unknown:
+            raise TypeError(f"score_sweep: unexpected arguments {sorted(unknown)}")
+        vae_noise = kw.pop("vae_noise", None)
+        if vae_noise is not None and len(vae_noise) != n:
+            raise ValueError(f"score_sweep: vae_noise has {len(vae_noise)} entries for {n} images")
+        pipe = self.pipeline
+        side_h, side_w = kw.get("height", 1024) // 16, kw.get("width", 1024) // 16
+        if side_h * side_w > L.SEG_MAX_CELLS:
+            raise ValueError(f"score_sweep: maps of {side_h} x {side_w} cells; the device route takes up to "
+                             f"{L.SEG_MAX_CELLS} (layer_noise_sweep + SweepScores.update remain for larger maps)")
+        layer_indices = kw.get("layer_indices")
+        n_layers = pipe.params.depth if layer_indices is None else len(layer_indices)
+        levels = [int(v) for v in noise_levels]
+        if (scores.n_levels, scores.n_columns) != (len(levels), n_layers + int(bool(layer_mean))):
+            raise ValueError(f"score_sweep: scores holds {scores.n_levels} x {scores.n_columns} cells; the sweep has "
+                             f"{len(levels)} levels and {n_layers} layers" + (" plus the layer mean" if layer_mean else ""))
+        per_item = list(concepts) if concepts and not isinstance(concepts[0], str) else [list(concepts)] * n
+        target = [per_item[i].index(target_concepts[i]) for i in range(n)]
+        lab = []
+        for i, y in enumerate(labels):
+            y = np.asarray(_np(y))
+            if y.shape != (size, size) or y.dtype not in (np.uint8, np.bool_):
+                raise ValueError(f"labels[{i}]: expected a uint8 / bool array ({size}, {size}), got {y.dtype} {y.shape}")
+            lab.append(y.astype(np.uint8, copy=False))
+        blur = ops.seg_blur_weights() if apply_blur else None
+        flags = dict(mean_value_threshold=mean_value_threshold, downscale_for_eval=downscale_for_eval, blur_weights=blur,
+                     normalize=normalize)
+        with torch.cuda.device(pipe.device):
+            cells = ops.segtab_cells(side_h, side_w, pipe.device)
+            for i in range(n):
+                tabs = pipe.layer_noise_sweep(images[i], per_item[i], captions[i], levels,
+                                              vae_noise=None if vae_noise is None else vae_noise[i], **kw)
+                y = torch.from_numpy(lab[i]).pin_memory().to(pipe.device, non_blocking=True)
+                for space in spaces:
+                    table = tabs[SWEEP_SPACES.index(space)]                     # [levels, layers, C, side, side]
+                    ops.segtab_score(table.reshape(-1, *table.shape[2:]), target[i], y,
+                                     scores.reserve(space, size * size, range(n_layers)), cells, **flags)
+                    if layer_mean:
+                        ops.segtab_score(table.mean(dim=1), target[i], y, scores.reserve(space, size * size, [n_layers]),
+                                         cells, **flags)
+        return None
 
     def _multiclass_arguments(self, what, images, captions, background_concepts, target_concepts, target_space, kw):
         n = len(images)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CA_VERSION 133 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
+#define CA_VERSION 134 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
                           CA_ATTN_Q_PRESCALED; .1: ca_axpy_f32, ca_split_bf16; .2: ca_attn_stats; .3: ca_gemm_problem.qk_f16,
                           ca_attn_fwd_qk16; .4: ca_qpre_finish_rope_f32; .5: ca_heatmap_fused; .6: ca_gemm_plan;
                           .7: the autoencoder kernels (conv3x3_nhwc, groupnorm_nhwc, softmax_rows_f32, affine_rows_f32);
@@ -37,7 +37,8 @@ extern "C" {
                           clip_embed_f32); 130: the pixel I/O kernels (pixels_u8_to_nhwc32_bf16, nhwc_f32_to_pixels_u8);
                           131: the T5 encoder's e4m3 producers (t5_rmsnorm_f32in_fp8, gated_mul_fp8);
                           132: segmentation scoring on the device (seg_score);
-                          133: multi-class segmentation scoring on the device (mseg_score) */
+                          133: multi-class segmentation scoring on the device (mseg_score);
+                          134: sweep tables of maps scored against one label on the device (segtab_score) */
 
 #define CA_OK 0
 #define CA_ERR_ARG (-1)    /* bad shape / null pointer / misalignment */
@@ -623,6 +624,44 @@ typedef struct {
 int ca_mseg_score(const ca_mseg_problem *problems, int32_t n_problems, int32_t K, int32_t h, int32_t w,
                   int32_t Hl, int32_t Wl, int32_t nclass, int32_t ignore_index, int32_t flags,
                   const void *class_of, const float *scale, const float *blur_weights, ca_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Segmentation scoring of a TABLE of maps against one label (the per-layer and per-timestep sweeps:
+ * experiments/per_layer_segmentation/test_segmentations_per_layer.py:164-243 and
+ * experiments/per_timestep_segmentation/test_segmentations_per_time.py:75-174): n_maps heat maps of one geometry, one
+ * ca_seg_record each, from two launches.  A label pass counts once, per map cell, the label pixels that read the cell
+ * and the positive ones among them, for the mask's pixel -> cell mapping and for the coefficient's; a map pass, one
+ * workgroup per map, forms the record from the map and those tables and never reads the label.  Per map, every step
+ * one fp32 rounding unless it says fp64, all of it as seg_score states it:
+ *   x     = map, or with CA_SEGTAB_BLUR its 3x3 blur with reflect padding (nine rounded products, row-major order)
+ *   lo, hi = min x, max x (NaN cells are skipped);  mean = (float)(fp64 sum of x / (h w)), seg_score's fixed tree
+ *   mask  = x > mean  with CA_SEGTAB_MEAN_THRESHOLD, else x > 0
+ *   c     = (x - lo) / (hi - lo), the division correctly rounded; with CA_SEGTAB_RAW c = x (the per-layer script
+ *           scores the raw coefficients, lines 209-215)
+ *   label pixel (Y, X) reads the mask at cell (near(Y; Hl, h), near(X; Wl, w)) and the coefficient at the same cell,
+ *   or with CA_SEGTAB_DOWNSCALE at (near(near(Y; Hl, 14); 14, h), near(near(X; Wl, 14); 14, w)); near as above
+ *   n11, n10, n01, n00 = pixels by (mask, label != 0): sums over the cells of the mask's tables, exact integers
+ *   ap    = the average precision of the 2 Hl Wl stacked scores (float32(1 - c), c) against the one-hot label, both
+ *           scores through np.nan_to_num (NaN -> 0, +-inf -> +-FLT_MAX), -0.0 and 0.0 one threshold: the sum over the
+ *           distinct scores, descending, of (R_k - R_{k-1}) P_k with P_k = tp_k / n_k and R_k = tp_k / (Hl Wl) in
+ *           fp64, tp_k and n_k exact integers; the sum over a fixed tree (the same bits every run)
+ * maps: map m is fp32 [h, w] contiguous at maps + m * map_stride (elements, >= h w; what lies between two maps is
+ * never read: with [levels, layers, C, h w] tables concept k is maps = table + k h w, map_stride = C h w,
+ * n_maps = levels * layers).  label: uint8 [Hl, Wl], nonzero = positive, shared by all maps.  records: n_maps
+ * contiguous ca_seg_record, 8-byte aligned.  cells: device workspace uint32 [4, (h w + 3) & ~3], 16-byte aligned: the
+ * mask's tot / pos and the coefficient's tot / pos per cell; the call zeroes it itself, in a kernel on the stream.
+ * blur_weights: nine floats on the HOST, read during the call, required with CA_SEGTAB_BLUR.  Nothing is allocated,
+ * uploaded or retained.  Limits: 1 <= h w <= 4096, 1 <= Hl Wl <= 2^24, 1 <= n_maps <= CA_SEGTAB_MAX_MAPS,
+ * map_stride >= h w, CA_SEGTAB_BLUR needs h, w >= 2, no other flag bit; CA_ERR_ARG otherwise, before any launch.
+ * Needs up to 112.5 KB of LDS. */
+#define CA_SEGTAB_MAX_MAPS 65536
+#define CA_SEGTAB_MEAN_THRESHOLD 1
+#define CA_SEGTAB_DOWNSCALE 2
+#define CA_SEGTAB_BLUR 4
+#define CA_SEGTAB_RAW 8
+int ca_segtab_score(const float *maps, int64_t map_stride, int32_t n_maps, const void *label, void *records,
+                    void *cells, int32_t h, int32_t w, int32_t Hl, int32_t Wl, int32_t flags,
+                    const float *blur_weights, ca_stream_t stream);
 
 #ifdef __cplusplus
 }
