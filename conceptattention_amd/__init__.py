@@ -32,6 +32,9 @@ def __getattr__(name):  # lazy: keep `import conceptattention_amd` light for hos
                 "map_predictions_to_class_indices", "multiclass_table"):
         from . import segmentation
         return getattr(segmentation, name)
+    if name == "concept_attention_frames":
+        from .video import concept_attention_frames
+        return concept_attention_frames
     if name == "compute_heatmaps_from_vectors":
         from .heatmaps import compute_heatmaps_from_vectors
         return compute_heatmaps_from_vectors

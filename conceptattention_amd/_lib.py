@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CA_LIB_PATH: another build of the same library (an A/B against another source tree); still no fallback
 LIB_PATH = os.environ.get("CA_LIB_PATH") or os.path.join(_HERE, "libconceptattn.so")
 
-CA_VERSION = 134
+CA_VERSION = 135
 EPI_BIAS, EPI_GELU_TANH, EPI_GATE_RESIDUAL, EPI_SPLIT_GELU, EPI_QKV_NORM_ROPE = 0, 1, 2, 3, 4
 TILE_AUTO, TILE_256x256, TILE_256x192, TILE_256x128, TILE_256x64 = 0, 1, 2, 3, 4
 TILE_PP_256x256, TILE_PP_256x128, TILE_PP_256x192 = 5, 6, 7
@@ -35,6 +35,12 @@ MSEG_MAX_LABEL_PIXELS = 1 << 24     # ca_mseg_score: Hl * Wl of the label
 MSEG_BLUR = 4
 SEGTAB_MAX_MAPS = 65536              # ca_segtab_score: maps of one call
 SEGTAB_MEAN_THRESHOLD, SEGTAB_DOWNSCALE, SEGTAB_BLUR, SEGTAB_RAW = 1, 2, 4, 8
+RENDER_MAX_PROBLEMS = 16             # ca_heatmap_render: groups of one launch
+RENDER_MAX_MAPS = 65536              # ca_heatmap_render: planes of one group
+RENDER_MAX_CELLS = 16384             # ca_heatmap_render: h * w of the maps
+RENDER_MAX_SIDE = 4096               # ca_heatmap_render: H and W of the pictures
+RENDER_LUT_ROWS = 259                # 256 colours, then under, over, bad
+RENDER_BILINEAR, RENDER_BLEND = 1, 2
 ATTN_Q_PRESCALED = 0.0   # ca_attn_fwd_bf16(scale=...): the q rows already carry softmax_scale * log2(e)
 
 
@@ -85,6 +91,12 @@ class SegRecord(C.Structure):
 class MsegProblem(C.Structure):
     _fields_ = [("maps", C.c_void_p), ("label", C.c_void_p), ("counts", C.c_void_p), ("class_out", C.c_void_p),
                 ("index_out", C.c_void_p)]
+
+
+class RenderProblem(C.Structure):
+    _fields_ = [("maps", C.c_void_p), ("map_stride", C.c_int64), ("n_maps", C.c_int32), ("range_in", C.c_void_p),
+                ("range_out", C.c_void_p), ("image", C.c_void_p), ("image_stride", C.c_int64), ("out", C.c_void_p),
+                ("out_stride", C.c_int64)]
 
 
 class ModSegment(C.Structure):
@@ -183,6 +195,8 @@ SIGNATURES = {
     "ca_segtab_score": (C.c_int, [C.POINTER(C.c_float), C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float),
                                   C.c_void_p]),
+    "ca_heatmap_render": (C.c_int, [C.POINTER(RenderProblem), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_void_p, C.c_float, C.c_int32, C.c_void_p]),
 }
 
 _lib = None

@@ -9,7 +9,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 LIB = os.path.join(PKG, "libconceptattn.so")
 SOURCES = ["ca_api.hip", "ca_gemm.hip", "ca_attn.hip", "ca_attn4.hip", "ca_rowops.hip", "ca_vae.hip", "ca_t5.hip",
-           "ca_clip.hip", "ca_pixels.hip", "ca_seg.hip", "ca_mseg.hip", "ca_segtab.hip"]
+           "ca_clip.hip", "ca_pixels.hip", "ca_seg.hip", "ca_mseg.hip", "ca_segtab.hip",
+           "ca_render.hip"]
 # ca_attn4.hip owns the AGPR file by hand (literal a[...] registers in its asm statements): hipcc must never park a
 # VGPR there (its default spill target), and the emitted code is audited for it below
 EXTRA_FLAGS = {"ca_attn4.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-save-temps=obj"],
@@ -18,7 +19,8 @@ EXTRA_FLAGS = {"ca_attn4.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-save
                "ca_pixels.hip": ["-save-temps=obj", "-ffp-contract=off"],  # (the same; every operation rounds on its own)
                "ca_seg.hip": ["-save-temps=obj", "-ffp-contract=off"],     # (the same)
                "ca_mseg.hip": ["-save-temps=obj", "-ffp-contract=off"],    # (the same)
-               "ca_segtab.hip": ["-save-temps=obj", "-ffp-contract=off"]}  # (the same)
+               "ca_segtab.hip": ["-save-temps=obj", "-ffp-contract=off"],  # (the same)
+               "ca_render.hip": ["-save-temps=obj", "-ffp-contract=off"]}  # (the same)
 HEADERS = ["ca_common.h", "ca_attn_common.h", "ca_attn4_sched.inc", "ca_attn4_kernel.inc"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function"]
@@ -110,6 +112,13 @@ def audit_segtab(asm_path: str) -> None:
     """ca_segtab_map_kernel is ca_seg_score_kernel with the label loop replaced by sums over tables: the same scalars per
     thread, everything indexed in LDS.  Every kernel of the unit must report no spill and no scratch."""
     _audit_no_spill("ca_segtab", asm_path)
+
+
+def audit_render(asm_path: str) -> None:
+    """ca_render_colour_kernel holds a slot's six pixel colours and its four output words in registers, indexed by unrolled
+    loops only, and the launch struct is indexed by the block's group alone.  Every kernel of the unit must report no spill
+    and no scratch."""
+    _audit_no_spill("ca_render", asm_path)
 
 
 def audit_sgpr_hazards(text: str) -> list:
@@ -367,6 +376,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     audit_seg(os.path.join(HERE, "ca_seg-hip-amdgcn-amd-amdhsa-gfx950.s"))
     audit_mseg(os.path.join(HERE, "ca_mseg-hip-amdgcn-amd-amdhsa-gfx950.s"))
     audit_segtab(os.path.join(HERE, "ca_segtab-hip-amdgcn-amd-amdhsa-gfx950.s"))
+    audit_render(os.path.join(HERE, "ca_render-hip-amdgcn-amd-amdhsa-gfx950.s"))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
     if verbose:
         print(" ".join(cmd), flush=True)

@@ -203,6 +203,13 @@ class FluxGenerator:
             pix = (127.5 * (img + 1.0)).cpu().byte().numpy()
         return [PIL.Image.fromarray(pix[k]) for k in range(pix.shape[0])]
 
+    def decode_pixels(self, x: torch.Tensor, height: int, width: int) -> torch.Tensor:
+        """The bytes ``decode_many`` makes its images from, still on the device: uint8 [B, height, width, 3].  Needs the
+        HIP autoencoder (``AutoEncoder.decode_pixels``)."""
+        if self.ae is None or not hasattr(self.ae, "decode_pixels"):
+            raise ValueError("decode_pixels needs the HIP autoencoder (autoencoder=\"synthetic\" or a .safetensors path)")
+        return self.ae.decode_pixels(sampling.unpack(x.float(), height, width).to(torch.float32))
+
     @torch.no_grad()  # (the reference uses inference_mode; the resident workspace is reused across calls)
     @on_own_device
     def generate_image(self, width, height, num_steps, guidance, seed, prompt, concepts, init_image=None,

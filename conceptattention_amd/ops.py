@@ -20,14 +20,21 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-def _chk(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise ValueError(f"{name}: expected a CUDA(HIP) tensor")
+def _chk_host(t, dtype, name: str) -> torch.Tensor:
+    """_chk without the device: heatmap_render checks everything else first, so that its checks run without one."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name}: expected a tensor")
     if t.dtype != dtype:
         raise ValueError(f"{name}: expected dtype {dtype}, got {t.dtype}")
     if t.dim() >= 1 and t.stride(-1) != 1:
         raise ValueError(f"{name}: innermost dimension must be contiguous")
     return t
+
+
+def _chk(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{name}: expected a CUDA(HIP) tensor")
+    return _chk_host(t, dtype, name)
 
 
 def host_values(values, device, dtype=torch.float32) -> torch.Tensor:
@@ -884,6 +891,140 @@ def segtab_score(maps, target, label, records, cells=None, mean_value_threshold:
                                     label.data_ptr(), records[m0:m0 + n].data_ptr(), cells.data_ptr(), _i32(h, "h"),
                                     _i32(w, "w"), _i32(Hl, "Hl"), _i32(Wl, "Wl"), flags, bw, _stream()),
                 "ca_segtab_score")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Heat-map pictures (ca_render.hip): fp32 map planes to RGB bytes: range, colour map, upscale, blend.
+
+_LUT_CACHE: dict = {}
+
+
+def colormap_lut(cmap, device) -> torch.Tensor:
+    """The look-up table of ca_heatmap_render on ``device``: uint8 [259, 3], rows 0..255
+    ``(cmap(np.arange(256))[:, :3] * 255).astype(uint8)``, then the under, over and bad colours.  ``cmap``: a matplotlib
+    name (cached per name and device; matplotlib is imported on the first use of a name), a matplotlib colour map, or
+    the table itself as a uint8 [259, 3] array or tensor."""
+    import numpy as np
+    device = torch.device(device)
+    if isinstance(cmap, str):
+        key = (cmap, str(device))
+        if key not in _LUT_CACHE:
+            import matplotlib.pyplot as plt
+            _LUT_CACHE[key] = colormap_lut(plt.get_cmap(cmap), device)
+        return _LUT_CACHE[key]
+    if callable(cmap) and hasattr(cmap, "N"):
+        if int(cmap.N) != 256:
+            raise ValueError(f"colormap_lut: a colour map of {cmap.N} entries; ca_heatmap_render's table has 256")
+        rows = [np.asarray(cmap(np.arange(256)))[:, :3]]
+        rows += [np.asarray(cmap(v), dtype=np.float64).reshape(1, 4)[:, :3] for v in (-np.inf, np.inf, np.nan)]
+        cmap = (np.concatenate(rows) * 255).astype(np.uint8)
+    t = torch.as_tensor(cmap)
+    if t.dtype != torch.uint8 or tuple(t.shape) != (L.RENDER_LUT_ROWS, 3):
+        raise ValueError(f"colormap_lut: a table must be uint8 [{L.RENDER_LUT_ROWS}, 3], got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous().to(device)
+
+
+def _plane_step(t: torch.Tensor) -> int:
+    """Bytes from plane 0 to plane 1 of a view [n, ...] (0 for n = 1), taken from the two addresses: the plane steps of
+    ca_render_problem are int64_t fields and may pass 2^31."""
+    return int(t[1].data_ptr() - t[0].data_ptr()) if t.shape[0] > 1 else 0
+
+
+def heatmap_render(groups, lut, size=None, bilinear: bool = False, images=None, alpha: Optional[float] = None,
+                   ranges=None, out=None):
+    """Colour groups of heat maps into RGB bytes (ca_heatmap_render; include/conceptattn.h states the arithmetic).
+    groups: fp32 tensor views [n, h, w], each plane contiguous and the planes equally spaced (a slice ``table[:, k]`` of a
+    contiguous [n, C, h, w] table is one); all groups share h, w, h * w <= 16384; the planes of a group share one range.
+    lut: ``colormap_lut``.  size: None (h, w), an int or (H, W), each 1..4096; bilinear: torch's align_corners=False
+    rule instead of the nearest one.  images: None, or one uint8 [H, W, 3] picture for all groups or one per group (row
+    stride free, a pixel's bytes adjacent) that the colours are blended over with weight ``alpha`` in [0, 1].  ranges:
+    None (every group's own min / max), or fp32 [2] for all groups or [groups, 2] on the device: {lo, hi} as given.
+    out: one uint8 view [n, H, W, 3] per group (planes contiguous, equally spaced, at least 3 H W bytes apart), allocated
+    when not given.  Returns (the list of out, fp32 [groups, 2] with the ranges used).  More than L.RENDER_MAX_PROBLEMS
+    groups go in several launches."""
+    groups = list(groups)
+    G = len(groups)
+    if G < 1:
+        raise ValueError("heatmap_render: no groups")
+    _chk_host(lut, torch.uint8, "lut")
+    dev = lut.device
+    if tuple(lut.shape) != (L.RENDER_LUT_ROWS, 3) or not lut.is_contiguous():
+        raise ValueError(f"heatmap_render: lut{tuple(lut.shape)} must be contiguous uint8 [{L.RENDER_LUT_ROWS}, 3]")
+    h, w = (int(v) for v in groups[0].shape[1:]) if isinstance(groups[0], torch.Tensor) and groups[0].dim() == 3 else (0, 0)
+    for i, g in enumerate(groups):
+        _chk_host(g, torch.float32, f"groups[{i}]")
+        if g.dim() != 3 or tuple(g.shape[1:]) != (h, w) or g.device != dev:
+            raise ValueError(f"heatmap_render: groups[{i}]{tuple(g.shape)} must be fp32 [n, {h}, {w}] on the device of lut")
+        n = int(g.shape[0])
+        if not 1 <= n <= L.RENDER_MAX_MAPS:
+            raise ValueError(f"heatmap_render: groups[{i}] has {n} planes; ca_heatmap_render takes 1..{L.RENDER_MAX_MAPS}")
+        if (h > 1 and g.stride(1) != w) or (n > 1 and g.stride(0) < h * w):
+            raise ValueError(f"heatmap_render: groups[{i}]: every plane contiguous [h, w], the planes equally spaced and "
+                             "at least h * w elements apart")
+    if not 1 <= h * w <= L.RENDER_MAX_CELLS:
+        raise ValueError(f"heatmap_render: maps of {h} x {w} cells; ca_heatmap_render takes 1..{L.RENDER_MAX_CELLS}")
+    if size is None:
+        H, W = h, w
+    elif isinstance(size, int):
+        H, W = size, size
+    else:
+        H, W = (int(v) for v in size)
+    if not (1 <= H <= L.RENDER_MAX_SIDE and 1 <= W <= L.RENDER_MAX_SIDE):
+        raise ValueError(f"heatmap_render: pictures of {H} x {W}; ca_heatmap_render takes sides of 1..{L.RENDER_MAX_SIDE}")
+    flags = L.RENDER_BILINEAR if bilinear else 0
+    if (images is None) != (alpha is None):
+        raise ValueError("heatmap_render: images and alpha come together")
+    if images is not None:
+        alpha = float(alpha)
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f"heatmap_render: alpha = {alpha} outside 0..1")
+        images = [images] * G if isinstance(images, torch.Tensor) else list(images)
+        if len(images) != G:
+            raise ValueError(f"heatmap_render: {len(images)} images for {G} groups")
+        for i, im in enumerate(images):
+            _chk_host(im, torch.uint8, f"images[{i}]")
+            if tuple(im.shape) != (H, W, 3) or (W > 1 and im.stride(1) != 3) or (H > 1 and im.stride(0) < 3 * W) or \
+                    im.device != dev:
+                raise ValueError(f"heatmap_render: images[{i}]{tuple(im.shape)} must be uint8 [{H}, {W}, 3] with adjacent "
+                                 "pixels on the device of lut")
+        flags |= L.RENDER_BLEND
+    if ranges is not None:
+        _chk_host(ranges, torch.float32, "ranges")
+        if tuple(ranges.shape) == (2,):
+            ranges = ranges.expand(G, 2)
+        if tuple(ranges.shape) != (G, 2) or ranges.device != dev:
+            raise ValueError(f"heatmap_render: ranges{tuple(ranges.shape)} must be fp32 [2] or [{G}, 2] on the device of lut")
+    if out is not None:
+        out = list(out)
+        if len(out) != G:
+            raise ValueError(f"heatmap_render: {len(out)} out tensors for {G} groups")
+        for i, o in enumerate(out):
+            _chk_host(o, torch.uint8, f"out[{i}]")
+            n = int(groups[i].shape[0])
+            if tuple(o.shape) != (n, H, W, 3) or o.device != dev or (W > 1 and o.stride(2) != 3) or \
+                    (H > 1 and o.stride(1) != 3 * W) or (n > 1 and o.stride(0) < 3 * H * W):
+                raise ValueError(f"heatmap_render: out[{i}]{tuple(o.shape)} must be uint8 [{n}, {H}, {W}, 3], every plane "
+                                 "contiguous, the planes equally spaced and at least 3 H W bytes apart, on the device of lut")
+    if dev.type != "cuda":
+        raise ValueError("heatmap_render: expected CUDA(HIP) tensors")
+    if out is None:
+        out = [torch.empty(int(g.shape[0]), H, W, 3, dtype=torch.uint8, device=dev) for g in groups]
+    lib = L.load()
+    used = torch.empty(G, 2, dtype=torch.float32, device=dev)
+    for g0 in range(0, G, L.RENDER_MAX_PROBLEMS):
+        m = min(L.RENDER_MAX_PROBLEMS, G - g0)
+        arr = (L.RenderProblem * m)()
+        for k in range(m):
+            p, i = arr[k], g0 + k
+            p.maps, p.map_stride, p.n_maps = groups[i].data_ptr(), _plane_step(groups[i]) // 4, int(groups[i].shape[0])
+            p.range_in = None if ranges is None else ranges[i].data_ptr()
+            p.range_out = used[i].data_ptr()
+            if images is not None:
+                p.image, p.image_stride = images[i].data_ptr(), _plane_step(images[i])
+            p.out, p.out_stride = out[i].data_ptr(), _plane_step(out[i])
+        L.check(lib.ca_heatmap_render(arr, m, _i32(h, "h"), _i32(w, "w"), _i32(H, "H"), _i32(W, "W"), lut.data_ptr(),
+                                      0.0 if alpha is None else alpha, flags, _stream()), "ca_heatmap_render")
+    return out, used
 
 
 # ---------------------------------------------------------------------------------------------------------------------

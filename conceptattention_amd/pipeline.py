@@ -147,8 +147,68 @@ class ConceptAttentionFluxPipeline:
         return ConceptAttentionPipelineOutput(image=image, concept_heatmaps=concept_heatmaps,
                                               cross_attention_maps=cross_attention_maps)
 
+    @staticmethod
+    def _device_renderer(heatmap_renderer, heatmap_size, heatmap_interpolation, overlay_alpha) -> bool:
+        """True for heatmap_renderer="device"; ValueError for an unknown renderer or interpolation, an alpha outside
+        [0, 1], or one of the device-only keywords with the host renderer."""
+        if heatmap_renderer not in ("host", "device"):
+            raise ValueError(f"heatmap_renderer = {heatmap_renderer!r}: \"host\" or \"device\"")
+        if heatmap_interpolation not in ("nearest", "bilinear"):
+            raise ValueError(f"heatmap_interpolation = {heatmap_interpolation!r}: \"nearest\" or \"bilinear\"")
+        if overlay_alpha is not None and not 0.0 <= float(overlay_alpha) <= 1.0:
+            raise ValueError(f"overlay_alpha = {overlay_alpha} outside 0..1")
+        if heatmap_renderer == "host" and (heatmap_size is not None or heatmap_interpolation != "nearest" or
+                                           overlay_alpha is not None):
+            raise ValueError("heatmap_size, heatmap_interpolation and overlay_alpha need heatmap_renderer=\"device\"")
+        return heatmap_renderer == "device"
+
+    def _input_picture(self, image, height: int, width: int) -> torch.Tensor:
+        """The bytes of an encode call's input image on the device, for overlays: uint8 [height, width, 3]."""
+        if isinstance(image, torch.Tensor):
+            raise ValueError("overlay_alpha needs the input as an image; a latent tensor has no picture to lay the maps over")
+        arr = np.asarray(image.convert("RGB"))
+        if arr.shape[:2] != (height, width):
+            raise ValueError(f"overlay_alpha: the input image is {arr.shape[0]} x {arr.shape[1]} (height x width) and the "
+                             f"call asks for {height} x {width}; resize the image first")
+        return torch.from_numpy(np.ascontiguousarray(arr)).to(self.device)
+
+    def _finish_device(self, images, concept_heatmaps, cross_attention_maps, cmap, heatmap_size=None,
+                       heatmap_interpolation="nearest", overlay_alpha=None, pictures=None) -> list:
+        """``_finish`` with PIL heat maps for the B items of a chunk, the pictures made on the device (ops.heatmap_render):
+        one group per item and space (the reference's "global min-max over ALL concepts"), one launch, one download of
+        bytes.  Without the three options the bytes are those of ``colorize_heatmaps``.  ``pictures``: with
+        ``overlay_alpha``, the uint8 [H, W, 3] device tensor of every item that the maps are laid over."""
+        import PIL.Image
+        ho = concept_heatmaps.to(torch.float32).contiguous()
+        hc = cross_attention_maps.to(torch.float32).contiguous()
+        B, C, side = ho.shape[0], ho.shape[1], ho.shape[-1]
+        if overlay_alpha is not None:
+            size = tuple(pictures[0].shape[:2]) if heatmap_size is None else heatmap_size
+        else:
+            size = (side, side) if heatmap_size is None else heatmap_size
+        H, W = (int(size), int(size)) if isinstance(size, int) else (int(v) for v in size)
+        if overlay_alpha is not None and any(tuple(p.shape[:2]) != (H, W) for p in pictures):
+            raise ValueError(f"overlay_alpha: heatmap_size = {H} x {W} is not the picture's size "
+                             f"{tuple(pictures[0].shape[:2])}")
+        buf = torch.empty(2 * B, C, H, W, 3, dtype=torch.uint8, device=self.device)
+        ops.heatmap_render([ho[k] for k in range(B)] + [hc[k] for k in range(B)], ops.colormap_lut(cmap, self.device),
+                           size=(H, W), bilinear=heatmap_interpolation == "bilinear",
+                           images=None if overlay_alpha is None else list(pictures) * 2, alpha=overlay_alpha,
+                           out=list(buf))
+        host = buf.cpu().numpy()                       # the one download of the chunk
+        return [ConceptAttentionPipelineOutput(
+            image=images[k], concept_heatmaps=[PIL.Image.fromarray(host[k, c]) for c in range(C)],
+            cross_attention_maps=[PIL.Image.fromarray(host[B + k, c]) for c in range(C)]) for k in range(B)]
+
     def _decode(self, x: torch.Tensor, height: int, width: int):
         return self.flux_generator.decode(x, height, width)
+
+    def _decode_with_bytes(self, x: torch.Tensor, height: int, width: int):
+        """(PIL images, their uint8 [B, H, W, 3] bytes still on the device) of the B items of ``x``, from one decode."""
+        import PIL.Image
+        pix = self.flux_generator.decode_pixels(x, height, width)
+        host = pix.cpu().numpy()
+        return [PIL.Image.fromarray(host[k]) for k in range(host.shape[0])], pix
 
     def _stream_models(self, n_streams: int):
         """One model (activation set on self.model's weights) and one HIP stream per slot, every replica with
@@ -169,13 +229,19 @@ class ConceptAttentionFluxPipeline:
                        return_pil_heatmaps=True, seed: int = 0, num_inference_steps: int = 4,
                        guidance: float = 0.0, timesteps=None, softmax: bool = True,
                        attention_norm: str = "sparsemax", cmap="plasma", latent: Optional[torch.Tensor] = None,
-                       fused: bool = True) -> ConceptAttentionPipelineOutput:
+                       fused: bool = True, heatmap_renderer: str = "host", heatmap_size=None,
+                       heatmap_interpolation: str = "nearest", overlay_alpha=None) -> ConceptAttentionPipelineOutput:
         """``latent`` (1,16,h/8,w/8) overrides get_noise (device RNG differs between platforms);
-        ``fused=False`` takes the reference's route (stack the per-layer vectors, then reduce)."""
+        ``fused=False`` takes the reference's route (stack the per-layer vectors, then reduce).
+        ``heatmap_renderer="device"`` makes the PIL heat maps on the device (ops.heatmap_render; the same bytes as
+        "host", one download of bytes); only with it: ``heatmap_size`` (an int or (H, W)), ``heatmap_interpolation``
+        ("nearest" or "bilinear") and ``overlay_alpha`` (the maps blended over the decoded picture with that weight,
+        which needs the HIP autoencoder)."""
         assert return_cross_attention is False, "Not supported yet"
         assert all([0 <= li < self.params.depth for li in layer_indices]), "Invalid layer index"
         assert height == width, "Height and width must be the same for now"
         norm = resolve_norm(softmax, attention_norm)  # ValueError on an unknown name, as the reference (:70-71)
+        on_device = self._device_renderer(heatmap_renderer, heatmap_size, heatmap_interpolation, overlay_alpha)
         if timesteps is None:
             timesteps = list(range(num_inference_steps))
         x = latent if latent is not None else sampling.get_noise(1, height, width, self.device, torch.bfloat16, seed)
@@ -183,6 +249,11 @@ class ConceptAttentionFluxPipeline:
         img, concept_heatmaps, cross_attention_maps = self.generate_on_device(
             x, txt, vec, con, layer_indices=layer_indices, num_inference_steps=num_inference_steps,
             guidance=guidance, timesteps=timesteps, fused=fused, norm=norm)
+        if on_device and return_pil_heatmaps:
+            images, pix = self._decode_with_bytes(img, height, width) if overlay_alpha is not None else \
+                ([self._decode(img, height, width)], None)
+            return self._finish_device(images, concept_heatmaps, cross_attention_maps, cmap, heatmap_size,
+                                       heatmap_interpolation, overlay_alpha, pix)[0]
         image = self._decode(img, height, width)
         return self._finish(image, concept_heatmaps, cross_attention_maps, return_pil_heatmaps, cmap)
 
@@ -399,7 +470,9 @@ class ConceptAttentionFluxPipeline:
                      noise_timestep: int = 2, device: str = "cuda:0", return_pil_heatmaps: bool = True,
                      seed: int = 0, cmap="plasma", stop_after_multi_modal_attentions=True,
                      attention_norm: str = "sparsemax", softmax=True,
-                     joint_attention_kwargs=None, noise=None, vae_noise=None) -> ConceptAttentionPipelineOutput:
+                     joint_attention_kwargs=None, noise=None, vae_noise=None, heatmap_renderer: str = "host",
+                     heatmap_size=None, heatmap_interpolation: str = "nearest",
+                     overlay_alpha=None) -> ConceptAttentionPipelineOutput:
         """``image``: a latent tensor (1,16,h/8,w/8), or a PIL image when the pipeline has an autoencoder
         (``autoencoder="synthetic"``, a ``.safetensors`` path, or an injected object).
         One forward of the 19 double blocks per noise sample (stop_after_multimodal_attentions).
@@ -407,10 +480,14 @@ class ConceptAttentionFluxPipeline:
         segmentation harness select the concept cross/self-attention ablations; ``noise`` (a list of num_samples
         tensors shaped like the latent) overrides get_noise, whose device RNG stream differs between platforms;
         ``vae_noise`` (1,16,h/8,w/8) is the autoencoder's sampling noise for a PIL image (drawn on the device when not
-        given), so that a call is reproducible."""
+        given), so that a call is reproducible.  ``heatmap_renderer`` and the three keywords behind it: as in
+        ``generate_image``; the overlays are laid over the INPUT image's bytes, which must already be height x width."""
         assert all([0 <= li < self.params.depth for li in layer_indices]), "Invalid layer index"
         assert height == width, "Height and width must be the same for now"
         norm = resolve_norm(softmax, attention_norm)
+        on_device = self._device_renderer(heatmap_renderer, heatmap_size, heatmap_interpolation, overlay_alpha)
+        picture = self._input_picture(image, height, width) if on_device and overlay_alpha is not None and \
+            return_pil_heatmaps else None
         if isinstance(image, torch.Tensor):
             latent = image.to(self.device, torch.bfloat16)
         else:
@@ -420,6 +497,9 @@ class ConceptAttentionFluxPipeline:
                                                    num_samples, num_steps, noise_timestep, seed,
                                                    stop_after_multi_modal_attentions, joint_attention_kwargs, norm,
                                                    noise=noise)
+        if on_device and return_pil_heatmaps:
+            return self._finish_device([image], out_space, cross_space, cmap, heatmap_size, heatmap_interpolation,
+                                       overlay_alpha, None if picture is None else [picture])[0]
         return self._finish(image, out_space, cross_space, return_pil_heatmaps, cmap)
 
     def _encode_pixels(self, images, height: int, width: int, vae_noise=None) -> torch.Tensor:
@@ -520,7 +600,9 @@ class ConceptAttentionFluxPipeline:
                       layer_indices=list(range(15, 19)), num_samples: int = 1, num_steps: int = 4,
                       noise_timestep: int = 2, seed: int = 0, batch: int = 5, noise=None, vae_noise=None,
                       return_pil_heatmaps: bool = True, cmap="plasma", stop_after_multi_modal_attentions=True,
-                      attention_norm: str = "sparsemax", softmax=True, joint_attention_kwargs=None) -> list:
+                      attention_norm: str = "sparsemax", softmax=True, joint_attention_kwargs=None,
+                      heatmap_renderer: str = "host", heatmap_size=None, heatmap_interpolation: str = "nearest",
+                      overlay_alpha=None) -> list:
         """``encode_image`` for a list of images: a list of ConceptAttentionPipelineOutput in item order, every item with
         the maps of its own ``encode_image`` call.  ``images``: PIL images and / or latents (1,16,h/8,w/8);
         ``concepts``: one list for all items or one list per item; ``prompts``: one string per item (or one for all).
@@ -528,13 +610,24 @@ class ConceptAttentionFluxPipeline:
         call (``FluxGenerator.embed_many``), one autoencoder pass (``AutoEncoder.encode_pixels``) and one forward.
         ``noise``: per item, what ``encode_image`` takes (a list of num_samples tensors); ``vae_noise``: per item, a
         tensor (1,16,h/8,w/8) -- without it the autoencoder draws one batch of noise per forward, so PIL items are then
-        reproducible per call of this method, not against single calls."""
+        reproducible per call of this method, not against single calls.  ``heatmap_renderer="device"``: the pictures of
+        a chunk come from one launch and one download (``_finish_device``)."""
         images = list(images)
         results = [None] * len(images)
+        on_device = self._device_renderer(heatmap_renderer, heatmap_size, heatmap_interpolation, overlay_alpha) and \
+            return_pil_heatmaps
+        pictures = [self._input_picture(im, height, width) for im in images] if on_device and overlay_alpha is not None \
+            else None
         for idx, ho, hc in self._encode_chunks(images, concepts, prompts, width, height, layer_indices, num_samples,
                                                num_steps, noise_timestep, seed, batch, noise, vae_noise,
                                                stop_after_multi_modal_attentions, attention_norm, softmax,
                                                joint_attention_kwargs):
+            if on_device:
+                outs = self._finish_device([images[i] for i in idx], ho, hc, cmap, heatmap_size, heatmap_interpolation,
+                                           overlay_alpha, None if pictures is None else [pictures[i] for i in idx])
+                for k, i in enumerate(idx):
+                    results[i] = outs[k]
+                continue
             for k, i in enumerate(idx):
                 results[i] = self._finish(images[i], ho[k:k + 1], hc[k:k + 1], return_pil_heatmaps, cmap)
         return results
@@ -544,7 +637,9 @@ class ConceptAttentionFluxPipeline:
     def generate_images(self, prompts, concepts, seeds=None, latents=None, width: int = 1024, height: int = 1024,
                         return_cross_attention=False, layer_indices=list(range(15, 19)), return_pil_heatmaps=True,
                         num_inference_steps: int = 4, guidance: float = 0.0, timesteps=None, softmax: bool = True,
-                        attention_norm: str = "sparsemax", cmap="plasma", batch: int = 5) -> list:
+                        attention_norm: str = "sparsemax", cmap="plasma", batch: int = 5,
+                        heatmap_renderer: str = "host", heatmap_size=None, heatmap_interpolation: str = "nearest",
+                        overlay_alpha=None) -> list:
         """``generate_image`` for a list of prompts: a list of ConceptAttentionPipelineOutput in item order, every item
         with the image and maps of its own ``generate_image(prompt, concepts, seed=seeds[i], latent=latents[i])`` call on
         the fused route.  ``concepts``: one list for all items or one list per item; ``seeds``: one per item (default
@@ -554,6 +649,8 @@ class ConceptAttentionFluxPipeline:
         assert all([0 <= li < self.params.depth for li in layer_indices]), "Invalid layer index"
         assert height == width, "Height and width must be the same for now"
         norm = resolve_norm(softmax, attention_norm)
+        on_device = self._device_renderer(heatmap_renderer, heatmap_size, heatmap_interpolation, overlay_alpha) and \
+            return_pil_heatmaps
         prompts = list(prompts)
         n = len(prompts)
         concepts = _per_item(concepts, n, "generate_images: concepts")
@@ -573,6 +670,13 @@ class ConceptAttentionFluxPipeline:
             img, ho, hc = self.generate_on_device(x, txt, vec, con, layer_indices=layer_indices,
                                                   num_inference_steps=num_inference_steps, guidance=guidance,
                                                   timesteps=timesteps, fused=True, norm=norm)
+            if on_device:
+                pictures, pix = self._decode_with_bytes(img, height, width) if overlay_alpha is not None else \
+                    (self.flux_generator.decode_many(img, height, width), None)
+                outs = self._finish_device(pictures, ho, hc, cmap, heatmap_size, heatmap_interpolation, overlay_alpha, pix)
+                for k, i in enumerate(idx):
+                    results[i] = outs[k]
+                continue
             pictures = self.flux_generator.decode_many(img, height, width)
             for k, i in enumerate(idx):
                 results[i] = self._finish(pictures[k], ho[k:k + 1], hc[k:k + 1], return_pil_heatmaps, cmap)

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CA_VERSION 134 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
+#define CA_VERSION 135 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
                           CA_ATTN_Q_PRESCALED; .1: ca_axpy_f32, ca_split_bf16; .2: ca_attn_stats; .3: ca_gemm_problem.qk_f16,
                           ca_attn_fwd_qk16; .4: ca_qpre_finish_rope_f32; .5: ca_heatmap_fused; .6: ca_gemm_plan;
                           .7: the autoencoder kernels (conv3x3_nhwc, groupnorm_nhwc, softmax_rows_f32, affine_rows_f32);
@@ -38,7 +38,8 @@ extern "C" {
                           131: the T5 encoder's e4m3 producers (t5_rmsnorm_f32in_fp8, gated_mul_fp8);
                           132: segmentation scoring on the device (seg_score);
                           133: multi-class segmentation scoring on the device (mseg_score);
-                          134: sweep tables of maps scored against one label on the device (segtab_score) */
+                          134: sweep tables of maps scored against one label on the device (segtab_score);
+                          135: heat-map pictures on the device (heatmap_render) */
 
 #define CA_OK 0
 #define CA_ERR_ARG (-1)    /* bad shape / null pointer / misalignment */
@@ -662,6 +663,61 @@ int ca_mseg_score(const ca_mseg_problem *problems, int32_t n_problems, int32_t K
 int ca_segtab_score(const float *maps, int64_t map_stride, int32_t n_maps, const void *label, void *records,
                     void *cells, int32_t h, int32_t w, int32_t Hl, int32_t Wl, int32_t flags,
                     const float *blur_weights, ca_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Heat-map pictures (the colouring of concept_attention/concept_attention_pipeline.py:174-196, the overlays of
+ * concept_attention/plotting.py::overlay_heatmap_on_image, the frames of concept_attention/video/video_utils.py): fp32
+ * map planes [h, w] become RGB bytes [H, W, 3] without leaving the device.  A problem is a GROUP: the n_maps planes that
+ * share one range ("global min-max over ALL concepts" of an item and space; all frames of a concept).  Every
+ * floating-point operation is fp32 and rounds on its own, except the bilinear source coordinate (below).
+ *   Range.  With range_in == NULL, lo / hi are the minimum / maximum over all n_maps h w cells of the group; if any cell
+ *     is NaN both are NaN, as ndarray.min() gives.  Otherwise range_in = {lo, hi} is used as given, lo >= hi included.
+ *     range_out is always written; range_in may be the range_out of an earlier call or the problem's own, not that of
+ *     another problem of the same call.  The range is taken over the SOURCE cells under bilinear upscaling too (imshow
+ *     autoscales over the upscaled plane: a stated difference).
+ *   Value v at output pixel (y, x).
+ *     nearest (default): v = map[sy, sx], sy = min((int)floorf(y * ((float)h / H)), h - 1), sx likewise: the rule of
+ *       torch.nn.functional.interpolate(mode="nearest") as ca_pixels_u8_to_nhwc32_bf16 uses it;
+ *     CA_RENDER_BILINEAR: torch's align_corners=False rule: fy = fmaf((float)h / H, y + 0.5f, -0.5f), clamped below at 0
+ *       (the one fused operation of the entry: torch's builds contract this expression, and with the product rounded
+ *       first a coordinate near 60 moves by 2^-19, a value by up to 43 x 2^-24 of the largest cell at 64 -> 224),
+ *       y0 = (int)fy, y1 = min(y0 + 1, h - 1), ly = fy - y0, the same for x, and
+ *       v = (1 - ly) * ((1 - lx) * a00 + lx * a01) + ly * ((1 - lx) * a10 + lx * a11) in exactly that order (so
+ *       0 * inf is NaN, as in torch).
+ *   Colour: matplotlib's rule for a float array (Colormap._get_rgba_and_mask): t = (v - lo) / (hi - lo), the division
+ *     correctly rounded; xa = t * 256.0f; LUT row 258 if xa is NaN, else 256 if xa < 0, else 255 if xa == 256, else 257
+ *     if xa >= 256, else (int)xa.  -0.0 is row 0; hi == lo gives NaN everywhere.
+ *     lut: uint8 [259, 3] on the device, made by the caller: rows 0..255 (cmap(arange(256))[:, :3] * 255) as bytes, then
+ *     the under, over and bad colours.
+ *   Blend (CA_RENDER_BLEND): out_c = (uint8)(int)((float)col_c * alpha + (float)img_c * (1.0f - alpha) + 0.5f) with
+ *     1 - alpha formed once; a pixel whose row is 258 keeps the picture's bytes (matplotlib's bad colour is
+ *     transparent).  This is round-half-up on the blended value, not Agg's compositing: a stated difference.
+ * All problems of a call share h, w, H, W, lut, alpha and flags.  Limits: 1 <= n_problems <= CA_RENDER_MAX_PROBLEMS,
+ * 1 <= h w <= CA_RENDER_MAX_CELLS, 1 <= H, W <= CA_RENDER_MAX_SIDE, 1 <= n_maps <= CA_RENDER_MAX_MAPS, map_stride >= h w
+ * and out_stride >= 3 H W when n_maps > 1, no other flag bit; with CA_RENDER_BLEND 0 <= alpha <= 1 and every problem has
+ * an image with image_stride >= 3 W (unused when H = 1); without it alpha and image are ignored.  CA_ERR_ARG otherwise,
+ * before any launch.  Two to four launches on the stream, no host synchronisation, no float atomics (the range is
+ * folded with integer atomics on order keys held in range_out, so the bits do not depend on the arrival order); nothing
+ * depends on what range_out or out held before.  Planes of out may start at any byte. */
+#define CA_RENDER_MAX_PROBLEMS 16
+#define CA_RENDER_MAX_MAPS 65536
+#define CA_RENDER_MAX_CELLS 16384
+#define CA_RENDER_MAX_SIDE 4096
+#define CA_RENDER_BILINEAR 1
+#define CA_RENDER_BLEND 2
+typedef struct {
+  const float *maps;      /* fp32 planes [h, w], each contiguous, map_stride ELEMENTS apart (>= h*w; unused when n_maps = 1) */
+  int64_t map_stride;
+  int32_t n_maps;         /* 1 .. CA_RENDER_MAX_MAPS (65536) */
+  const float *range_in;  /* device fp32 [2] = {lo, hi}, or NULL: the range of all cells of the group's n_maps planes */
+  float *range_out;       /* device fp32 [2]: the {lo, hi} that was used; never NULL */
+  const void *image;      /* uint8 [H, W, 3], rows image_stride BYTES apart, or NULL: no blend */
+  int64_t image_stride;
+  void *out;              /* uint8, n_maps planes [H, W, 3] contiguous, out_stride BYTES apart (>= 3*H*W, any value) */
+  int64_t out_stride;
+} ca_render_problem;
+int ca_heatmap_render(const ca_render_problem *problems, int32_t n_problems, int32_t h, int32_t w, int32_t H, int32_t W,
+                      const void *lut /* uint8 [259, 3], device */, float alpha, int32_t flags, ca_stream_t stream);
 
 #ifdef __cplusplus
 }
