@@ -8,11 +8,12 @@
 // LDS atomics (whose result does not depend on their order).  No floating-point value is ever added up.
 //
 // The arithmetic is stated in include/conceptattn.h and restated in numpy by tests/mseg_cases.py.  The unit is compiled
-// with -ffp-contract=off: the blur's products and sums and the scale product round on their own.  seg_near, seg_reflect
-// and the blur are those of ca_seg.hip, word for word.
+// with -ffp-contract=off: the blur's products and sums and the scale product round on their own.  The nearest rule, the
+// blur and the host's geometry and blur checks are ca_seg_core.h's, shared with ca_seg.hip and ca_segtab.hip; what is
+// here is the argmax and the run-length walk over the label.
 //
 // LDS (static): class bytes [16384] | inter int32 [256] | union int32 [256] | correct, labelled: 18.0 KB.
-#include "ca_common.h"
+#include "ca_seg_core.h"
 
 #define MSEG_THREADS 1024
 #define MSEG_PIXELS_PER_THREAD 4     // consecutive label pixels of one thread per round: mostly one (class, label) run
@@ -22,17 +23,9 @@ struct MsegLaunch {
   uint8_t class_of[CA_MSEG_MAX_PROBLEMS][CA_MSEG_MAX_CONCEPTS];
   float scale[CA_MSEG_MAX_CONCEPTS];
   float blur[9];
-  int32_t K, h, w, Hl, Wl, nclass, ignore_index, flags, has_scale;
-  float sy, sx;            // (float)h / Hl, (float)w / Wl: the nearest rule's scales, formed on the host
+  int32_t K, nclass, ignore_index, flags, has_scale;
+  SegGeom g;               // (the class map is read at the mask's cells: h, w, Hl, Wl, sy, sx)
 };
-
-// torch's interpolate(mode="nearest") source index (the rule of ca_pixels.hip): the product in fp32
-__device__ __forceinline__ int seg_near(int i, float scale, int n_in) {
-  const int s = (int)floorf((float)i * scale);
-  return s < n_in - 1 ? s : n_in - 1;
-}
-
-__device__ __forceinline__ int seg_reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
 __global__ __launch_bounds__(MSEG_THREADS) void ca_mseg_score_kernel(MsegLaunch A) {
   __shared__ uint8_t cls[CA_MSEG_MAX_CELLS];
@@ -42,7 +35,8 @@ __global__ __launch_bounds__(MSEG_THREADS) void ca_mseg_score_kernel(MsegLaunch 
   const int item = blockIdx.x;
   const ca_mseg_problem P = A.p[item];
   const int tid = threadIdx.x, lane = tid & 63;
-  const int K = A.K, h = A.h, w = A.w, hw = h * w, nclass = A.nclass;
+  const SegGeom &G = A.g;
+  const int K = A.K, h = G.h, w = G.w, hw = h * w, nclass = A.nclass;
   const float *maps = P.maps;
 
   if (tid < CA_MSEG_MAX_CLASSES) inter[tid] = 0, uni[tid] = 0;
@@ -57,20 +51,7 @@ __global__ __launch_bounds__(MSEG_THREADS) void ca_mseg_score_kernel(MsegLaunch 
     int index = 0, klass = 0;
     for (int k = 0; k < K; ++k) {
       const float *map = maps + (long)k * hw;
-      float v;
-      if (A.flags & CA_MSEG_BLUR) {
-        v = 0.f;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int j = 0; j < 3; ++j) {
-            const long o = (long)seg_reflect(y + i - 1, h) * w + seg_reflect(xx + j - 1, w);
-            const float prod = A.blur[i * 3 + j] * map[o];
-            v = (i | j) ? v + prod : prod;
-          }
-      } else {
-        v = map[(long)c];
-      }
+      float v = (A.flags & CA_MSEG_BLUR) ? seg_blur_tap(map, y, xx, h, w, A.blur) : map[(long)c];
       if (A.has_scale) v = A.scale[k] * v;
       const int ck = A.class_of[item][k];
       const bool take = k == 0 || v > best || (!(v == v) && best == best);
@@ -86,17 +67,17 @@ __global__ __launch_bounds__(MSEG_THREADS) void ca_mseg_score_kernel(MsegLaunch 
   // and adds a run of equal (class, label) pairs to the tables at once
   {
     const uint8_t *label = (const uint8_t *)P.label;
-    const int N = A.Hl * A.Wl, Wl = A.Wl, ignore = A.ignore_index;
+    const int N = G.Hl * G.Wl, Wl = G.Wl, ignore = A.ignore_index;
     int correct = 0, labelled = 0;
     int run_p = 0, run_l = 0, run_n = 0;
     for (int i0 = tid * MSEG_PIXELS_PER_THREAD; i0 < N; i0 += MSEG_THREADS * MSEG_PIXELS_PER_THREAD) {
       int Y = (int)((unsigned)i0 / (unsigned)Wl), X = i0 - Y * Wl;
-      int my = seg_near(Y, A.sy, h);
+      int my = seg_mask_row(G, Y);
       const int n_here = N - i0 < MSEG_PIXELS_PER_THREAD ? N - i0 : MSEG_PIXELS_PER_THREAD;
       for (int u = 0; u < n_here; ++u) {
         const int l = label[(long)i0 + u];
-        const int p = cls[my * w + seg_near(X, A.sx, w)];
-        if (++X == Wl) X = 0, ++Y, my = seg_near(Y, A.sy, h);
+        const int p = cls[my * w + seg_mask_col(G, X)];
+        if (++X == Wl) X = 0, ++Y, my = seg_mask_row(G, Y);
         if (l == ignore) continue;
         if (run_n && p == run_p && l == run_l) {
           ++run_n;
@@ -141,15 +122,7 @@ extern "C" int ca_mseg_score(const ca_mseg_problem *problems, int32_t n_problems
     ca_set_error("%s: K=%d concepts outside 1..%d", FN, K, CA_MSEG_MAX_CONCEPTS);
     return CA_ERR_ARG;
   }
-  if (h < 1 || w < 1 || (int64_t)h * w > CA_MSEG_MAX_CELLS) {
-    ca_set_error("%s: maps %d x %d: h * w must be in 1..%d (larger maps are scored on the host)", FN, h, w,
-                 CA_MSEG_MAX_CELLS);
-    return CA_ERR_ARG;
-  }
-  if (Hl < 1 || Wl < 1 || (int64_t)Hl * Wl > ((int64_t)1 << 24)) {
-    ca_set_error("%s: label %d x %d: Hl * Wl must be in 1..2^24", FN, Hl, Wl);
-    return CA_ERR_ARG;
-  }
+  if (!seg_check_geometry(FN, "maps", h, w, CA_MSEG_MAX_CELLS, Hl, Wl)) return CA_ERR_ARG;
   if (nclass < 1 || nclass > CA_MSEG_MAX_CLASSES) {
     ca_set_error("%s: nclass=%d outside 1..%d", FN, nclass, CA_MSEG_MAX_CLASSES);
     return CA_ERR_ARG;
@@ -162,10 +135,7 @@ extern "C" int ca_mseg_score(const ca_mseg_problem *problems, int32_t n_problems
     ca_set_error("%s: flags=%d has bits outside CA_MSEG_BLUR", FN, flags);
     return CA_ERR_ARG;
   }
-  if ((flags & CA_MSEG_BLUR) && (h < 2 || w < 2 || !blur_weights)) {
-    ca_set_error("%s: the blur's reflect padding needs h >= 2 and w >= 2 (maps %d x %d) and nine blur_weights", FN, h, w);
-    return CA_ERR_ARG;
-  }
+  if (!seg_check_blur(FN, "maps", flags, h, w, blur_weights)) return CA_ERR_ARG;
   if (!class_of) {
     ca_set_error("%s: class_of is null (uint8 [n_problems][K] on the host, every entry below nclass)", FN);
     return CA_ERR_ARG;
@@ -187,13 +157,12 @@ extern "C" int ca_mseg_score(const ca_mseg_problem *problems, int32_t n_problems
       A.class_of[i][k] = (uint8_t)c;
     }
   }
-  A.K = K, A.h = h, A.w = w, A.Hl = Hl, A.Wl = Wl, A.nclass = nclass, A.ignore_index = ignore_index, A.flags = flags;
+  A.K = K, A.nclass = nclass, A.ignore_index = ignore_index, A.flags = flags;
   A.has_scale = scale != nullptr;
-  A.sy = (float)h / (float)Hl, A.sx = (float)w / (float)Wl;
+  A.g = seg_fill_geom(h, w, Hl, Wl);
   if (scale)
     for (int k = 0; k < K; ++k) A.scale[k] = scale[k];
-  if (flags & CA_MSEG_BLUR)
-    for (int i = 0; i < 9; ++i) A.blur[i] = blur_weights[i];
+  seg_fill_blur(A.blur, flags, blur_weights);
   hipLaunchKernelGGL(ca_mseg_score_kernel, dim3((unsigned)n_problems), dim3(MSEG_THREADS), 0, (hipStream_t)stream, A);
   return ca_check_launch(FN);
 }

@@ -772,6 +772,26 @@ def seg_blur_weights(sigma: float = 1.0) -> list:
     return [float(v) for v in (k[:, None] * k[None, :]).reshape(-1)]
 
 
+def _seg_blur_array(fn: str, blur_weights):
+    """``blur_weights`` of the scoring entry ``fn`` as the nine floats the library takes; None stays None (no blur)."""
+    if blur_weights is None:
+        return None
+    blur_weights = [float(v) for v in blur_weights]
+    if len(blur_weights) != 9:
+        raise ValueError(f"{fn}: blur_weights are the nine weights of the 3x3 blur")
+    return (C.c_float * 9)(*blur_weights)
+
+
+def _seg_check_sizes(fn: str, maps: str, h: int, w: int, max_cells: int, host_route: str, Hl: int, Wl: int,
+                     max_pixels: int) -> None:
+    """The cell and label-pixel ranges of the scoring entry ``fn`` (ca_<fn>); ``maps``: its word for what it scores."""
+    if not 1 <= h * w <= max_cells:
+        raise ValueError(f"{fn}: {maps} of {h} x {w} cells; ca_{fn} takes 1..{max_cells} (larger maps are scored on the "
+                         f"host: segmentation.{host_route})")
+    if not 1 <= Hl * Wl <= max_pixels:
+        raise ValueError(f"{fn}: a label of {Hl} x {Wl} pixels; ca_{fn} takes 1..2^24")
+
+
 def seg_score(maps, labels, results, mean_value_threshold: bool = True, downscale_for_eval: bool = False,
               blur_weights=None, mask_out=None, coeff_out=None) -> None:
     """Score n heat maps against n label images (ca_seg_score; include/conceptattn.h states the arithmetic).
@@ -801,19 +821,11 @@ def seg_score(maps, labels, results, mean_value_threshold: bool = True, downscal
             _chk(t, dt, name)
             if tuple(t.shape) != (n, h, w) or not t.is_contiguous() or t.device != results.device:
                 raise ValueError(f"seg_score: {name}{tuple(t.shape)} must be contiguous [{n}, {h}, {w}] on the same device")
-    if not 1 <= h * w <= L.SEG_MAX_CELLS:
-        raise ValueError(f"seg_score: a map of {h} x {w} cells; ca_seg_score takes 1..{L.SEG_MAX_CELLS} (larger maps are "
-                         "scored on the host: segmentation.SegmentationScores)")
-    if not 1 <= Hl * Wl <= L.SEG_MAX_LABEL_PIXELS:
-        raise ValueError(f"seg_score: a label of {Hl} x {Wl} pixels; ca_seg_score takes 1..2^24")
+    _seg_check_sizes("seg_score", "a map", h, w, L.SEG_MAX_CELLS, "SegmentationScores", Hl, Wl, L.SEG_MAX_LABEL_PIXELS)
     flags = (L.SEG_MEAN_THRESHOLD if mean_value_threshold else 0) | (L.SEG_DOWNSCALE if downscale_for_eval else 0)
-    bw = None
-    if blur_weights is not None:
-        blur_weights = [float(v) for v in blur_weights]
-        if len(blur_weights) != 9:
-            raise ValueError("seg_score: blur_weights are the nine weights of the 3x3 blur")
+    bw = _seg_blur_array("seg_score", blur_weights)      # (the library checks h >= 2 and w >= 2 for this entry)
+    if bw is not None:
         flags |= L.SEG_BLUR
-        bw = (C.c_float * 9)(*blur_weights)
     for c0 in range(0, n, L.SEG_MAX_PROBLEMS):
         m = min(L.SEG_MAX_PROBLEMS, n - c0)
         arr = (L.SegProblem * m)()
@@ -859,11 +871,8 @@ def segtab_score(maps, target, label, records, cells=None, mean_value_threshold:
     if tuple(records.shape) != (M, SEG_RECORD_BYTES) or not records.is_contiguous() or records.device != maps.device:
         raise ValueError(f"segtab_score: records{tuple(records.shape)} must be contiguous uint8 [{M}, {SEG_RECORD_BYTES}] on "
                          "the device of maps")
-    if not 1 <= h * w <= L.SEG_MAX_CELLS:
-        raise ValueError(f"segtab_score: maps of {h} x {w} cells; ca_segtab_score takes 1..{L.SEG_MAX_CELLS} (larger maps "
-                         "are scored on the host: segmentation.SweepScores.update)")
-    if not 1 <= Hl * Wl <= L.SEG_MAX_LABEL_PIXELS:
-        raise ValueError(f"segtab_score: a label of {Hl} x {Wl} pixels; ca_segtab_score takes 1..2^24")
+    _seg_check_sizes("segtab_score", "maps", h, w, L.SEG_MAX_CELLS, "SweepScores.update", Hl, Wl,
+                     L.SEG_MAX_LABEL_PIXELS)
     hw4 = (h * w + 3) & ~3
     if cells is None:
         cells = segtab_cells(h, w, maps.device)
@@ -873,16 +882,12 @@ def segtab_score(maps, target, label, records, cells=None, mean_value_threshold:
                          "the device of maps")
     flags = (L.SEGTAB_MEAN_THRESHOLD if mean_value_threshold else 0) | (L.SEGTAB_DOWNSCALE if downscale_for_eval else 0) | \
         (0 if normalize else L.SEGTAB_RAW)
-    bw = None
-    if blur_weights is not None:
-        blur_weights = [float(v) for v in blur_weights]
-        if len(blur_weights) != 9:
-            raise ValueError("segtab_score: blur_weights are the nine weights of the 3x3 blur")
+    bw = _seg_blur_array("segtab_score", blur_weights)
+    if bw is not None:
         if h < 2 or w < 2:
             raise ValueError(f"segtab_score: blur_weights with maps of {h} x {w} cells; the blur's reflect padding needs "
                              "h >= 2 and w >= 2")
         flags |= L.SEGTAB_BLUR
-        bw = (C.c_float * 9)(*blur_weights)
     stride = Cc * h * w                      # elements between two scored maps: an int64_t of the entry
     base = maps.data_ptr() + 4 * k * h * w
     for m0 in range(0, M, L.SEGTAB_MAX_MAPS):
@@ -1067,11 +1072,7 @@ def mseg_score(maps, labels, counts, class_of, nclass: int, ignore_index: Option
                 raise ValueError(f"mseg_score: {name}{tuple(t.shape)} must be contiguous [{n}, {h}, {w}] on the same device")
     if not 1 <= K <= L.MSEG_MAX_CONCEPTS:
         raise ValueError(f"mseg_score: maps of K = {K} concepts; ca_mseg_score takes 1..{L.MSEG_MAX_CONCEPTS}")
-    if not 1 <= h * w <= L.MSEG_MAX_CELLS:
-        raise ValueError(f"mseg_score: maps of {h} x {w} cells; ca_mseg_score takes 1..{L.MSEG_MAX_CELLS} (larger maps are "
-                         "scored on the host: segmentation.MultiClassScores)")
-    if not 1 <= Hl * Wl <= L.MSEG_MAX_LABEL_PIXELS:
-        raise ValueError(f"mseg_score: a label of {Hl} x {Wl} pixels; ca_mseg_score takes 1..2^24")
+    _seg_check_sizes("mseg_score", "maps", h, w, L.MSEG_MAX_CELLS, "MultiClassScores", Hl, Wl, L.MSEG_MAX_LABEL_PIXELS)
     ignore = -1 if ignore_index is None else int(ignore_index)
     if not -1 <= ignore <= 255:
         raise ValueError(f"mseg_score: ignore_index = {ignore_index}; a label value 0..255, or None")
@@ -1086,16 +1087,12 @@ def mseg_score(maps, labels, counts, class_of, nclass: int, ignore_index: Option
         if len(scale) != K:
             raise ValueError(f"mseg_score: scale holds one number per concept (K = {K})")
         sc = (C.c_float * K)(*scale)
-    flags, bw = 0, None
-    if blur_weights is not None:
-        blur_weights = [float(v) for v in blur_weights]
-        if len(blur_weights) != 9:
-            raise ValueError("mseg_score: blur_weights are the nine weights of the 3x3 blur")
+    flags, bw = 0, _seg_blur_array("mseg_score", blur_weights)
+    if bw is not None:
         if h < 2 or w < 2:
             raise ValueError(f"mseg_score: blur_weights with maps of {h} x {w} cells; the blur's reflect padding needs "
                              "h >= 2 and w >= 2")
         flags |= L.MSEG_BLUR
-        bw = (C.c_float * 9)(*blur_weights)
     for c0 in range(0, n, L.MSEG_MAX_PROBLEMS):
         m = min(L.MSEG_MAX_PROBLEMS, n - c0)
         arr = (L.MsegProblem * m)()

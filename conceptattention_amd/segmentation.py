@@ -127,6 +127,17 @@ def get_ap_scores(predict, target, ignore_index: int = -1):
     return out
 
 
+def _all_reduce_vector(v: torch.Tensor):
+    """The sum of the host vector ``v`` over ranks, on the host in ``v``'s dtype (through the current device under nccl);
+    None without an initialised process group of more than one rank: the caller's counters then stay as they are."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return None
+    from .distributed import allreduce_sum_
+    dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else v.device
+    return allreduce_sum_(v.to(dev)).cpu()
+
+
 @dataclass
 class SegmentationScores:
     """Running pixAcc / mIoU / mAP over images (run_experiment.py:134-232)."""
@@ -156,13 +167,9 @@ class SegmentationScores:
 
     def all_reduce(self) -> "SegmentationScores":
         """Sum the counters over ranks (no-op without an initialised process group)."""
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            from .distributed import allreduce_sum_
-            v = torch.tensor([self.correct, self.labelled, *self.inter, *self.union, self.ap_sum, float(self.n)],
-                             dtype=torch.float64)
-            dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else v.device
-            v = allreduce_sum_(v.to(dev)).cpu()
+        v = _all_reduce_vector(torch.tensor([self.correct, self.labelled, *self.inter, *self.union, self.ap_sum,
+                                             float(self.n)], dtype=torch.float64))
+        if v is not None:
             self.correct, self.labelled = float(v[0]), float(v[1])
             self.inter, self.union = v[2:4].numpy().copy(), v[4:6].numpy().copy()
             self.ap_sum, self.n = float(v[6]), int(round(float(v[7])))
@@ -180,37 +187,52 @@ SEG_RECORD = np.dtype([("n11", "<i4"), ("n10", "<i4"), ("n01", "<i4"), ("n00", "
                        ("lo", "<f4"), ("hi", "<f4"), ("thresholds", "<i4")])   # ca_seg_record (include/conceptattn.h)
 
 
-class DeviceSegmentationScores:
+class _DeviceRows:
+    """The rows of a device tensor [*, width] that grows by ``chunk`` rows, and their download: ``n`` rows are taken,
+    ``_take`` hands out the next ones, ``_rows`` downloads the rows taken so far ONCE (and not again until new ones were
+    taken).  The three ``Device*Scores`` classes keep their records in one."""
+
+    def __init__(self, width: int, dtype, device, chunk: int):
+        self.device = torch.device(device)
+        self.chunk = max(1, int(chunk))
+        self.n = 0
+        self._buf = torch.zeros(self.chunk, width, dtype=dtype, device=self.device)
+        self._host = None            # (n, rows) of the last download
+
+    def _take(self, n: int) -> torch.Tensor:
+        need = self.n + n
+        if need > self._buf.shape[0]:
+            cap = -(-need // self.chunk) * self.chunk
+            grown = torch.zeros(cap, self._buf.shape[1], dtype=self._buf.dtype, device=self.device)
+            grown[:self.n] = self._buf[:self.n]      # (stream-ordered behind the launches that wrote them)
+            self._buf = grown
+        out = self._buf[self.n:need]
+        self.n = need
+        return out
+
+    def _rows(self) -> np.ndarray:
+        if self._host is None or self._host[0] != self.n:
+            self._host = (self.n, self._buf[:self.n].cpu().numpy())
+        return self._host[1]
+
+
+class DeviceSegmentationScores(_DeviceRows):
     """``SegmentationScores`` whose per-image records stay on the device until somebody asks: ``reserve`` hands
     ``ops.seg_score`` the next records of a buffer that grows by ``chunk`` records, and ``to_host`` / ``result`` /
     ``all_reduce`` download the records written so far ONCE (and not again until new ones were reserved)."""
 
     def __init__(self, device="cuda:0", chunk: int = 256):
-        self.device = torch.device(device)
-        self.chunk = max(1, int(chunk))
-        self.n = 0
+        super().__init__(SEG_RECORD.itemsize, torch.uint8, device, chunk)
         self._pixels: list = []      # label pixels per item (host)
-        self._buf = torch.zeros(self.chunk, SEG_RECORD.itemsize, dtype=torch.uint8, device=self.device)
-        self._host = None            # (n, records) of the last download
 
     def reserve(self, n: int, label_pixels: int) -> torch.Tensor:
         """uint8 [n, 40]: the records of the next n items (each scored against ``label_pixels`` label pixels)."""
-        need = self.n + n
-        if need > self._buf.shape[0]:
-            cap = -(-need // self.chunk) * self.chunk
-            grown = torch.zeros(cap, SEG_RECORD.itemsize, dtype=torch.uint8, device=self.device)
-            grown[:self.n] = self._buf[:self.n]      # (stream-ordered behind the launches that wrote them)
-            self._buf = grown
-        out = self._buf[self.n:need]
-        self.n = need
         self._pixels += [int(label_pixels)] * n
-        return out
+        return self._take(n)
 
     def records(self) -> np.ndarray:
         """The n records as a numpy array of SEG_RECORD, in item order: the one download."""
-        if self._host is None or self._host[0] != self.n:
-            self._host = (self.n, self._buf[:self.n].cpu().numpy().view(SEG_RECORD).reshape(self.n))
-        return self._host[1]
+        return self._rows().view(SEG_RECORD).reshape(self.n)
 
     def to_host(self) -> SegmentationScores:
         """The counters the host path would hold after ``update`` on the same items: its (1 - m, m) against (1 - y, y)
@@ -292,13 +314,9 @@ class SweepScores:
 
     def all_reduce(self) -> "SweepScores":
         """Sum the tables over ranks (no-op without an initialised process group)."""
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            from .distributed import allreduce_sum_
-            v = torch.from_numpy(self._vector())
-            dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else v.device
-            v = allreduce_sum_(v.to(dev)).cpu().numpy()
-            o = 0
+        v = _all_reduce_vector(torch.from_numpy(self._vector()))
+        if v is not None:
+            v, o = v.numpy(), 0
             for s in SWEEP_SPACES:
                 for k in ("correct", "labelled", "inter", "union", "ap_sum", "n"):
                     a = self.tables[s][k]
@@ -323,43 +341,28 @@ class SweepScores:
                 yield lv, col, float(r["pixAcc"][lv, col]), float(r["mIoU"][lv, col]), float(r["mAP"][lv, col])
 
 
-class DeviceSweepScores:
+class DeviceSweepScores(_DeviceRows):
     """``SweepScores`` whose records stay on the device until somebody asks: ``reserve`` hands ``ops.segtab_score`` the
     [n_levels * len(columns), 40] records of one call, and ``records`` / ``to_host`` / ``result`` / ``all_reduce``
     download everything written so far ONCE (and not again until new records were reserved)."""
 
     def __init__(self, n_levels: int, n_layers: int, device="cuda:0", chunk: int = 4096):
+        super().__init__(SEG_RECORD.itemsize, torch.uint8, device, chunk)
         self.n_levels, self.n_columns = int(n_levels), int(n_layers)
-        self.device = torch.device(device)
-        self.chunk = max(1, int(chunk))
-        self.n = 0
         self._calls: list = []       # (space, first record, columns, label pixels) per reserve
-        self._buf = torch.zeros(self.chunk, SEG_RECORD.itemsize, dtype=torch.uint8, device=self.device)
-        self._host = None            # (n, records) of the last download
 
     def reserve(self, space: str, label_pixels: int, columns=None) -> torch.Tensor:
         """uint8 [n_levels * len(columns), 40], level-major: the records of one image's maps in ``space``."""
         if space not in SWEEP_SPACES:
             raise ValueError(f"space: one of {SWEEP_SPACES}")
         columns = list(range(self.n_columns)) if columns is None else [int(c) for c in columns]
-        n = self.n_levels * len(columns)
-        need = self.n + n
-        if need > self._buf.shape[0]:
-            cap = -(-need // self.chunk) * self.chunk
-            grown = torch.zeros(cap, SEG_RECORD.itemsize, dtype=torch.uint8, device=self.device)
-            grown[:self.n] = self._buf[:self.n]      # (stream-ordered behind the launches that wrote them)
-            self._buf = grown
-        out = self._buf[self.n:need]
         self._calls.append((space, self.n, columns, int(label_pixels)))
-        self.n = need
-        return out
+        return self._take(self.n_levels * len(columns))
 
     def records(self) -> list:
         """[(space, columns, records [n_levels, len(columns)] of SEG_RECORD), ...] in reservation order: the one
         download."""
-        if self._host is None or self._host[0] != self.n:
-            self._host = (self.n, self._buf[:self.n].cpu().numpy().view(SEG_RECORD).reshape(self.n))
-        rec = self._host[1]
+        rec = self._rows().view(SEG_RECORD).reshape(self.n)
         return [(s, cols, rec[o:o + self.n_levels * len(cols)].reshape(self.n_levels, len(cols)))
                 for s, o, cols, _ in self._calls]
 
@@ -451,12 +454,10 @@ class MultiClassScores:
 
     def all_reduce(self) -> "MultiClassScores":
         """Sum the counters over ranks (no-op without an initialised process group)."""
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            from .distributed import allreduce_sum_
-            v = torch.tensor([self.correct, self.labelled, self.n, *self.inter, *self.union], dtype=torch.int64)
-            dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else v.device
-            v = allreduce_sum_(v.to(dev)).cpu().numpy()
+        v = _all_reduce_vector(torch.tensor([self.correct, self.labelled, self.n, *self.inter, *self.union],
+                                            dtype=torch.int64))
+        if v is not None:
+            v = v.numpy()
             self.correct, self.labelled, self.n = int(v[0]), int(v[1]), int(v[2])
             self.inter, self.union = v[3:3 + self.nclass].copy(), v[3 + self.nclass:].copy()
         return self
@@ -479,7 +480,7 @@ class MultiClassScores:
                 "n": self.n}
 
 
-class DeviceMultiClassScores:
+class DeviceMultiClassScores(_DeviceRows):
     """``MultiClassScores`` whose per-image count rows stay on the device until somebody asks: ``reserve`` hands
     ``ops.mseg_score`` the next int32 [2 + 2 nclass] rows of a buffer that grows by ``chunk`` rows, and ``records`` /
     ``to_host`` / ``result`` / ``all_reduce`` download the rows written so far ONCE (and not again until new ones were
@@ -489,31 +490,17 @@ class DeviceMultiClassScores:
     def __init__(self, nclass: int, device="cuda:0", chunk: int = 256):
         self.nclass = int(nclass)
         self.width = 2 + 2 * self.nclass
-        self.device = torch.device(device)
-        self.chunk = max(1, int(chunk))
-        self.n = 0
+        super().__init__(self.width, torch.int32, device, chunk)
         self.ids: list = []
-        self._buf = torch.zeros(self.chunk, self.width, dtype=torch.int32, device=self.device)
-        self._host = None            # (n, rows) of the last download
 
     def reserve(self, n: int, ids=None) -> torch.Tensor:
         """int32 [n, 2 + 2 nclass]: the rows of the next n items."""
-        need = self.n + n
-        if need > self._buf.shape[0]:
-            cap = -(-need // self.chunk) * self.chunk
-            grown = torch.zeros(cap, self.width, dtype=torch.int32, device=self.device)
-            grown[:self.n] = self._buf[:self.n]      # (stream-ordered behind the launches that wrote them)
-            self._buf = grown
-        out = self._buf[self.n:need]
-        self.ids += list(range(self.n, need)) if ids is None else list(ids)
-        self.n = need
-        return out
+        self.ids += list(range(self.n, self.n + n)) if ids is None else list(ids)
+        return self._take(n)
 
     def records(self) -> np.ndarray:
         """int32 [n, 2 + 2 nclass] in reservation order (``ids``): the one download."""
-        if self._host is None or self._host[0] != self.n:
-            self._host = (self.n, self._buf[:self.n].cpu().numpy())
-        return self._host[1]
+        return self._rows()
 
     def to_host(self) -> MultiClassScores:
         out = MultiClassScores(self.nclass)
@@ -528,10 +515,30 @@ class DeviceMultiClassScores:
         return self.to_host().result()
 
 
-# what the multi-class methods accept as **encode_kwargs: the same set as the literal inside score_images (which keeps its
-# own copy); an argument added to one belongs in the other
+# what score_images and the multi-class methods accept as **encode_kwargs
 _ENCODE_KEYS = {"layers", "num_samples", "num_steps", "noise_timestep", "seed", "height", "width", "batch",
                 "joint_attention_kwargs", "noise", "vae_noise", "attention_norm", "softmax"}
+
+
+def _encode_chunks(pipe, images, concepts, captions, kw: dict):
+    """``pipe._encode_chunks`` with the defaults of ``encode_kwargs`` (keys of _ENCODE_KEYS) and the accumulators kept on
+    the device."""
+    return pipe._encode_chunks(images, concepts, list(captions[:len(images)]), kw.get("width", 1024), kw.get("height", 1024),
+                               kw.get("layers", list(range(15, 19))), kw.get("num_samples", 1), kw.get("num_steps", 4),
+                               kw.get("noise_timestep", 2), kw.get("seed", 0), kw.get("batch", 5), kw.get("noise"),
+                               kw.get("vae_noise"), True, kw.get("attention_norm", "sparsemax"), kw.get("softmax", True),
+                               kw.get("joint_attention_kwargs"))
+
+
+def _binary_labels(labels, size: int) -> list:
+    """score_images' and score_sweep's labels as uint8 arrays (size, size), nonzero = positive."""
+    lab = []
+    for i, y in enumerate(labels):
+        y = np.asarray(_np(y))
+        if y.shape != (size, size) or y.dtype not in (np.uint8, np.bool_):
+            raise ValueError(f"labels[{i}]: expected a uint8 / bool array ({size}, {size}), got {y.dtype} {y.shape}")
+        lab.append(y.astype(np.uint8, copy=False))
+    return lab
 
 
 # ------------------------------------------------------------------------------------------ model wrapper
@@ -596,27 +603,15 @@ class ConceptAttentionSegmentationModel:
         pipe = self.pipeline
         per_item = list(concepts) if concepts and not isinstance(concepts[0], str) else [list(concepts)] * n
         target = [per_item[i].index(target_concepts[i]) for i in range(n)]
-        lab = []
-        for i, y in enumerate(labels):
-            y = np.asarray(_np(y))
-            if y.shape != (size, size) or y.dtype not in (np.uint8, np.bool_):
-                raise ValueError(f"labels[{i}]: expected a uint8 / bool array ({size}, {size}), got {y.dtype} {y.shape}")
-            lab.append(y.astype(np.uint8, copy=False))
+        lab = _binary_labels(labels, size)
         kw = dict(encode_kwargs)
-        unknown = set(kw) - {"layers", "num_samples", "num_steps", "noise_timestep", "seed", "height", "width", "batch",
-                             "joint_attention_kwargs", "noise", "vae_noise", "attention_norm", "softmax"}
+        unknown = set(kw) - _ENCODE_KEYS
         if unknown:
             raise TypeError(f"score_images: unexpected arguments {sorted(unknown)}")
         blur = ops.seg_blur_weights() if apply_blur else None
         masks, planes, order = [], [], []
         with torch.cuda.device(pipe.device):
-            chunks = pipe._encode_chunks(images, concepts, list(captions[:n]), kw.get("width", 1024), kw.get("height", 1024),
-                                         kw.get("layers", list(range(15, 19))), kw.get("num_samples", 1),
-                                         kw.get("num_steps", 4), kw.get("noise_timestep", 2), kw.get("seed", 0),
-                                         kw.get("batch", 5), kw.get("noise"), kw.get("vae_noise"), True,
-                                         kw.get("attention_norm", "sparsemax"), kw.get("softmax", True),
-                                         kw.get("joint_attention_kwargs"))
-            for idx, acc_o, acc_c in chunks:
+            for idx, acc_o, acc_c in _encode_chunks(pipe, images, concepts, captions, kw):
                 acc = acc_o if target_space == "output" else acc_c
                 maps = [acc[k, target[i]] for k, i in enumerate(idx)]
                 y = torch.from_numpy(np.stack([lab[i] for i in idx])).pin_memory().to(pipe.device, non_blocking=True)
@@ -679,12 +674,7 @@ class ConceptAttentionSegmentationModel:
                              f"{len(levels)} levels and {n_layers} layers" + (" plus the layer mean" if layer_mean else ""))
         per_item = list(concepts) if concepts and not isinstance(concepts[0], str) else [list(concepts)] * n
         target = [per_item[i].index(target_concepts[i]) for i in range(n)]
-        lab = []
-        for i, y in enumerate(labels):
-            y = np.asarray(_np(y))
-            if y.shape != (size, size) or y.dtype not in (np.uint8, np.bool_):
-                raise ValueError(f"labels[{i}]: expected a uint8 / bool array ({size}, {size}), got {y.dtype} {y.shape}")
-            lab.append(y.astype(np.uint8, copy=False))
+        lab = _binary_labels(labels, size)
         blur = ops.seg_blur_weights() if apply_blur else None
         flags = dict(mean_value_threshold=mean_value_threshold, downscale_for_eval=downscale_for_eval, blur_weights=blur,
                      normalize=normalize)
@@ -800,13 +790,7 @@ class ConceptAttentionSegmentationModel:
         blur = ops.seg_blur_weights() if apply_blur else None
         preds, order = [], []
         with torch.cuda.device(pipe.device):
-            chunks = pipe._encode_chunks(images, concepts, list(captions[:n]), kw.get("width", 1024), kw.get("height", 1024),
-                                         kw.get("layers", list(range(15, 19))), kw.get("num_samples", 1),
-                                         kw.get("num_steps", 4), kw.get("noise_timestep", 2), kw.get("seed", 0),
-                                         kw.get("batch", 5), kw.get("noise"), kw.get("vae_noise"), True,
-                                         kw.get("attention_norm", "sparsemax"), kw.get("softmax", True),
-                                         kw.get("joint_attention_kwargs"))
-            for idx, acc_o, acc_c in chunks:
+            for idx, acc_o, acc_c in _encode_chunks(pipe, images, concepts, captions, kw):
                 acc = acc_o if target_space == "output" else acc_c
                 y = torch.from_numpy(np.stack([lab[i] for i in idx])).pin_memory().to(pipe.device, non_blocking=True)
                 groups = {}                      # the items of a launch share one scale

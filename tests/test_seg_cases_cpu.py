@@ -89,10 +89,13 @@ def test_large_labels_and_the_lds_limit_boundary_are_cases():
     assert 2 * 3072 < 8192                                     # the rectangular map sorts more slots than it has entries
     ref = T.reference(*by["map2x2-label4096x4096"].inputs())   # the entry point's limit: 2^24 pixels, counts up to 2^24
     assert ref["n11"] + ref["n10"] + ref["n01"] + ref["n00"] == 1 << 24 == T.MAX_LABEL_PIXELS
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "conceptattention_amd", "csrc",
-                            "ca_seg.hip")).read()
-    assert "(size_t)npad * 8 + (size_t)((hw + 3) & ~3) * 12 + SEG_SCRATCH_BYTES" in src and "if (lds > 64 * 1024)" in src
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "conceptattention_amd", "csrc")
+    src = open(os.path.join(csrc, "ca_seg_core.h")).read()     # (where both map kernels' request is formed)
+    size = "(size_t)npad * 8 + (size_t)((hw + 3) & ~3) * 12 + SEG_SCRATCH_BYTES"
+    assert size in src and "if (lds > 64 * 1024)" in src
     assert "48 x 48" not in src
+    units = [open(os.path.join(csrc, f)).read() for f in ("ca_seg.hip", "ca_segtab.hip")]
+    assert sum(t.count(size) for t in units + [src]) == 1, "the LDS size expression exists once"
 
 
 def test_mean_tree_is_the_rounded_fp64_mean():
