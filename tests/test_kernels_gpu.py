@@ -613,8 +613,11 @@ def test_attention_half_precision_q_and_k(nq, nk, n0):
     than the bf16-q/k kernel's (11 vs 8 mantissa bits in the logits)."""
     nh = 2
     H = nh * 128
-    q32 = torch.randn(nq, H, device=DEV) * 1.3
-    k32 = torch.randn(nk, H, device=DEV) * 1.3
+    # (a generator of its own: the process-wide one is seeded afresh in every process, and the last assertion below,
+    # a comparison of two maxima, then held in one run and not in the next)
+    g = torch.Generator(device=DEV).manual_seed(nq + nk + n0)
+    q32 = torch.randn(nq, H, device=DEV, generator=g) * 1.3
+    k32 = torch.randn(nk, H, device=DEV, generator=g) * 1.3
     v = rnd(nk, H, seed=4)
     qh, kh = _as_half_bits(q32 * SL2), _as_half_bits(k32)
     out = torch.zeros(nq, H, device=DEV, dtype=torch.bfloat16)

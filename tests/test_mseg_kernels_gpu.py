@@ -8,6 +8,7 @@ pytestmark = pytest.mark.gpu
 
 import mseg_cases as T  # noqa: E402
 import placement  # noqa: E402
+import stream_gate  # noqa: E402
 from conceptattention_amd import _lib as L  # noqa: E402
 from conceptattention_amd import ops  # noqa: E402
 
@@ -23,7 +24,7 @@ def _guarded(al, shape, dtype, role, src=None, fill=None):
     flat = al.full((n + GUARD,), POISON[dtype] if fill is None else fill, dtype, {role: n // 2})
     t = flat[:n].view(*shape)
     if src is not None:
-        t.copy_(torch.from_numpy(np.ascontiguousarray(src)))
+        t.copy_(src)
     flat[n:].fill_(POISON[dtype])
     return t, flat[n:]
 
@@ -35,13 +36,15 @@ def _launch(case, maps, labels, tables, scale, alloc=None, outputs=None):
     al = alloc or placement.Plain(DEV)
     outputs = case.outputs if outputs is None else outputs
     guards = []
+    # (uploaded before the first allocation: nothing between the allocations and the launch waits for the device)
+    maps_d, labels_d = (torch.from_numpy(np.ascontiguousarray(np.stack(a))).to(DEV) for a in (maps, labels))
 
     def make(shape, dtype, role, src=None, fill=None):
         t, g = _guarded(al, shape, dtype, role, src, fill)
         guards.append((role, g, dtype))
         return t
-    md = make((n, K, h, w), torch.float32, "maps", np.stack(maps))
-    ld = make((n, Hl, Wl), torch.uint8, "label", np.stack(labels))
+    md = make((n, K, h, w), torch.float32, "maps", maps_d)
+    ld = make((n, Hl, Wl), torch.uint8, "label", labels_d)
     counts = make((n, 2 + 2 * case.nclass), torch.int32, "counts")
     c_out = make((n, h, w), torch.uint8, "class_out", fill=0xEE) if outputs in ("both", "class") else None
     i_out = make((n, h, w), torch.uint8, "index_out", fill=0xEE) if outputs in ("both", "index") else None
@@ -86,8 +89,12 @@ def test_a_launch_of_the_cap_equals_the_single_launches_and_a_side_stream_works(
     case = next(c for c in T.CASES if c.items == L.MSEG_MAX_PROBLEMS == T.MAX_PROBLEMS)
     maps, labels, tables, scale = case.inputs()
     stream = torch.cuda.Stream()
+    # (behind a gate, tests/stream_gate.py: a launch on another stream would read poison instead of these inputs)
+    warm = stream_gate.Recording(DEV)
+    _launch(case, maps, labels, tables, scale, alloc=warm, outputs="both")
     with torch.cuda.stream(stream):
-        counts, c_out, i_out = _launch(case, maps, labels, tables, scale, outputs="both")
+        counts, c_out, i_out = _launch(case, maps, labels, tables, scale, outputs="both",
+                                       alloc=stream_gate.Gated(warm, stream_gate.Gate()))
     stream.synchronize()
     for i in (0, 7, 15):
         one, c1, i1 = _launch(case, maps[i:i + 1], labels[i:i + 1], tables[i:i + 1], scale, outputs="both")

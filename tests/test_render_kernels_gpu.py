@@ -10,6 +10,7 @@ pytestmark = pytest.mark.gpu
 
 import placement  # noqa: E402
 import render_cases as R  # noqa: E402
+import stream_gate  # noqa: E402
 from conceptattention_amd import _lib as L  # noqa: E402
 from conceptattention_amd import ops  # noqa: E402
 
@@ -167,8 +168,11 @@ def test_a_matplotlib_table_and_a_side_stream():
     assert ops.colormap_lut("plasma", DEV) is ops.colormap_lut("plasma", DEV)
     inputs = case.inputs()
     stream = torch.cuda.Stream()
+    # (behind a gate, tests/stream_gate.py: a launch on another stream would read poison instead of these inputs)
+    warm = stream_gate.Recording(DEV)
+    launch(case, inputs, lut=lut, alloc=warm)
     with torch.cuda.stream(stream):
-        out, ranges, _ = launch(case, inputs, lut=lut)
+        out, ranges, _ = launch(case, inputs, lut=lut, alloc=stream_gate.Gated(warm, stream_gate.Gate()))
     stream.synchronize()
     check(case, out, ranges, case.references(lut, inputs))
 

@@ -10,6 +10,7 @@ pytestmark = pytest.mark.gpu
 
 import placement  # noqa: E402
 import seg_cases as T  # noqa: E402
+import stream_gate  # noqa: E402
 from conceptattention_amd import _lib as L  # noqa: E402
 from conceptattention_amd import ops  # noqa: E402
 
@@ -93,8 +94,11 @@ def test_any_nonzero_label_byte_is_positive_and_a_non_default_stream_works():
     ref = T.reference(amap, label)
     bytes_ = (label * np.random.default_rng(0).integers(1, 256, size=label.shape)).astype(np.uint8)
     stream = torch.cuda.Stream()
+    # (behind a gate, tests/stream_gate.py: a launch on another stream would read poison instead of these inputs)
+    warm = stream_gate.Recording(DEV)
+    _launch([amap], [bytes_], alloc=warm)
     with torch.cuda.stream(stream):
-        rec, mask, coeff = _launch([amap], [bytes_])
+        rec, mask, coeff = _launch([amap], [bytes_], alloc=stream_gate.Gated(warm, stream_gate.Gate()))
     stream.synchronize()
     _check(rec[0], mask[0], coeff[0], ref, "label bytes 1..255 on a side stream")
 

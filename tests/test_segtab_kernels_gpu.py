@@ -13,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 import placement  # noqa: E402
 import segtab_cases as T  # noqa: E402
+import stream_gate  # noqa: E402
 from conceptattention_amd import _lib as L  # noqa: E402
 from conceptattention_amd import ops  # noqa: E402
 
@@ -132,8 +133,11 @@ def test_any_nonzero_label_byte_is_positive_and_a_non_default_stream_works():
     refs = [T.reference(m, label) for m in maps]
     bytes_ = (label * np.random.default_rng(0).integers(1, 256, size=label.shape)).astype(np.uint8)
     stream = torch.cuda.Stream()
+    # (behind a gate, tests/stream_gate.py: a launch on another stream would read poison instead of these inputs)
+    warm = stream_gate.Recording(DEV)
+    launch(maps, bytes_, C=4, target=1, alloc=warm)
     with torch.cuda.stream(stream):
-        rec, _ = launch(maps, bytes_, C=4, target=1)
+        rec, _ = launch(maps, bytes_, C=4, target=1, alloc=stream_gate.Gated(warm, stream_gate.Gate()))
     stream.synchronize()
     for m in range(6):
         check(rec[m], refs[m], ("label bytes 1..255 on a side stream", m))

@@ -64,14 +64,15 @@ def run_attention(case, alloc=None, guard=GUARD):
     rows behind n_seq * L on q, k and v (a key or value read there poisons the output), a pattern in the output's."""
     q, k, v, bias, ref, bound = _attn_problem(case)
     rows, width = q.shape
+    up = [t.to(DEV, BF) for t in (q, k, v)]       # (uploaded before the first allocation: nothing behind it waits)
     if case.layout == "sliced":
         qkv = _guarded(alloc, rows, 3 * width, NAN, {"q": None, "k": None, "v": None}, guard)
         dq, dk, dv = qkv[:, :width], qkv[:, width:2 * width], qkv[:, 2 * width:]
     else:
         dq, dk, dv = (_guarded(alloc, rows, width + pad, NAN, {n: None}, guard)[:, :width]
                       for n, pad in (("q", 8), ("k", 16), ("v", 24)))
-    for d, t in ((dq, q), (dk, k), (dv, v)):
-        d[:rows] = t.to(DEV, BF)
+    for d, t in zip((dq, dk, dv), up):
+        d[:rows] = t
     full = _guarded(alloc, rows, width + 64, PATTERN, {"out": None}, guard)
     full[:rows] = NAN
     out = full[:, :width]
@@ -135,12 +136,12 @@ def run_gated_mul(case, alloc=None):
     us = al.to(_widened(u, C + 2 * pad).to(BF), {"u": None})
     full = al.full((rows, C + 3 * pad), NAN, BF, {"out": None})
     ops.gated_mul(gs[:, :C], us[:, :C], full[:, :C])
+    got, us1 = full[:, :C].clone(), us.clone()                     # (us after the first launch; both copies in stream order)
+    ops.gated_mul(gs[:, :C], us[:, :C], us[:, :C])                 # in place, as the model runs it
     torch.cuda.synchronize()
     _ratio(f"gated_mul {C}x{rows}", "gated_mul", full[:, :C], ref, bound)
     assert torch.isnan(full[:, C:]).all()
-    assert torch.equal(gs[:, :C].cpu().float(), g) and torch.equal(us[:, :C].cpu().float(), u), "an input changed"
-    got = full[:, :C].clone()
-    ops.gated_mul(gs[:, :C], us[:, :C], us[:, :C])                 # in place, as the model runs it
+    assert torch.equal(gs[:, :C].cpu().float(), g) and torch.equal(us1[:, :C].cpu().float(), u), "an input changed"
     assert torch.equal(us[:, :C], got) and (us[:, C:] == 0).all()
     return {"out": got}
 
