@@ -38,7 +38,7 @@ import torch
 from . import _lib as L
 from . import ops
 from .params import ClipTextParams, clip_params, tiny_clip_params
-from .weights import _gen
+from .weights import _gen, fill_tensors, load_text_weights
 
 __all__ = ["ClipTextEncoder", "ClipTextParams", "HipClipEmbedder", "ToyClipTokenizer", "load_clip",
            "synthetic_clip_state_dict", "clip_state_dict_spec", "pooled_positions", "synthetic_clip_embedder"]
@@ -152,15 +152,7 @@ class ClipTextEncoder:
             k = k[len(PREFIX):] if k.startswith(PREFIX) else k
             if k not in IGNORED_KEYS:
                 own[k] = v
-        missing = [k for k in self.spec if k not in own]
-        unexpected = [k for k in own if k not in self.spec]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"load_state_dict: missing {missing[:4]}.. unexpected {unexpected[:4]}..")
-        for k, shape in self.spec.items():
-            if k in own:
-                if tuple(own[k].shape) != tuple(shape):
-                    raise RuntimeError(f"load_state_dict: {k} has shape {tuple(own[k].shape)}, expected {tuple(shape)}")
-                self.tensors[k] = own[k].detach().to("cpu", torch.float32)
+        missing, unexpected = fill_tensors(self.spec, own, strict, self.tensors)
         if not missing:
             self._pack()
         return missing, unexpected
@@ -280,20 +272,9 @@ def load_clip(params="clip-vit-large-patch14", device="cuda", weights="synthetic
     other keys of a full CLIP checkpoint are ignored, a missing text-model key is an error).  The ``CLIP`` environment
     variable names the checkpoint when the caller gives none ("synthetic"), as ``T5`` does for the T5 encoder; nothing
     is ever downloaded."""
-    from .t5 import _read_safetensors
     p = clip_params[params] if isinstance(params, str) else params
-    enc = ClipTextEncoder(p, device)
-    if isinstance(weights, str) and weights == "synthetic" and os.environ.get("CLIP"):
-        weights = os.environ["CLIP"]
-    if isinstance(weights, dict):
-        enc.load_state_dict(weights, strict=True)
-    elif weights == "synthetic":
-        enc.load_state_dict(synthetic_clip_state_dict(p, seed), strict=True)
-    else:
-        missing, _ = enc.load_state_dict(_read_safetensors(str(weights)), strict=False)
-        if missing:
-            raise RuntimeError(f"load_clip: {weights} lacks {len(missing)} text-model tensors: {missing[:4]}..")
-    return enc
+    return load_text_weights(ClipTextEncoder(p, device), "load_clip", "CLIP", weights,
+                             lambda: synthetic_clip_state_dict(p, seed), "text-model")
 
 
 # ---------------------------------------------------------------------------------------------------------- text in

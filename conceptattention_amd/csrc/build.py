@@ -21,7 +21,8 @@ EXTRA_FLAGS = {"ca_attn4.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-save
                "ca_mseg.hip": ["-save-temps=obj", "-ffp-contract=off"],    # (the same)
                "ca_segtab.hip": ["-save-temps=obj", "-ffp-contract=off"],  # (the same)
                "ca_render.hip": ["-save-temps=obj", "-ffp-contract=off"]}  # (the same)
-HEADERS = ["ca_common.h", "ca_attn_common.h", "ca_attn4_sched.inc", "ca_attn4_kernel.inc", "ca_seg_core.h"]
+HEADERS = ["ca_common.h", "ca_attn_common.h", "ca_attn4_sched.inc", "ca_attn4_kernel.inc", "ca_seg_core.h",
+           "ca_text_core.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function"]
 

@@ -2,34 +2,25 @@
 // sequences that fill no tile, the LayerNorm of the fp32 residual stream (with a row gather for the pooled read-out),
 // quick_gelu and the token + position embedding.  The projections run on the grouped GEMM of ca_gemm.hip.  Every element
 // offset is formed in 64 bits.
-#include "ca_common.h"
+#include "ca_text_core.h"
 
 // ------------------------------------------------------------------------------------------------------------------
-// out = softmax(scale q k^T + causal mask) v per (sequence, head); head dim 64; L any value in 1..128.
+// out = softmax(scale q k^T + causal mask) v per (sequence, head); head dim 64; L any value in 1..128.  The tile and its
+// steps are ca_text_core.h's.
 //
-// The layout is ca_t5_attn_kernel's: a workgroup of 4 waves owns 64 query positions of one (sequence, head), a wave 16
-// of them; K sits in LDS row-major ([key][64], rows of 72 bf16), V transposed ([d][key], rows of LP + 16 bf16); scores
-// are computed transposed (S^T = K Q^T), so a lane holds ONE query (lane & 15) and keys 16 t + 4 (lane >> 4) + 0..3 of
-// every 16-key tile t, all of them in registers, and the softmax is the exact two-pass one.  P, rounded once to bf16
-// (unnormalised, in [0, 1]), is the B operand of O^T = V^T P^T; the sum runs over the fp32 values.
-//
-// What is new here.  LP = 32 NU >= L is the padded key count (P V contracts 32 keys per MFMA).  Positions >= L of the
-// last tile belong to the next sequence, or past the last sequence to nobody: they are never loaded -- K rows, V columns
-// and query fragments of such positions are ZEROS (a masked probability of 0 times a NaN in V would be NaN) -- and such
-// query rows are never stored.  A query at position i sees keys 0..i: the other scores become -inf before the maximum
-// (key 0 is visible to everyone, so the maximum is finite and exp2(-inf) = 0).  For a query < L every key <= i is < L, so
-// the zero rows are always masked.  A workgroup stages only the keys its 64 queries can see, a wave skips the key tiles
-// that lie wholly above its 16 queries, and a wave whose queries are all >= L leaves after the barrier.
-#define CLIP_D 64
-#define CLIP_LDK 72
-
+// What is this kernel's own.  LP = 32 NU >= L is the padded key count (P V contracts 32 keys per MFMA).  Positions >= L of
+// the last tile belong to the next sequence, or past the last sequence to nobody: they are never loaded -- K rows, V
+// columns and query fragments of such positions are ZEROS -- and such query rows are never stored.  A query at position i
+// sees keys 0..i: the other scores become -inf before the maximum (key 0 is visible to everyone, so the maximum is finite
+// and exp2(-inf) = 0).  For a query < L every key <= i is < L, so the zero rows are always masked.  A workgroup stages only
+// the keys its 64 queries can see, a wave skips the key tiles that lie wholly above its 16 queries, and a wave whose
+// queries are all >= L leaves after the barrier.
 template <int NU>   // NU = LP / 32 key steps of P V, 2 NU key tiles of 16
 __global__ __launch_bounds__(256) void ca_clip_attn_kernel(const bf16 *q, const bf16 *k, const bf16 *v, bf16 *out, long ldq,
                                                             long ldk, long ldv, long ldo, int heads, int L, float scale) {
   constexpr int NT = 2 * NU, LP = 32 * NU, LDV = LP + 16;
-  extern __shared__ __attribute__((aligned(16))) unsigned char clip_smem[];
-  bf16 *sK = (bf16 *)clip_smem;                      // [LP][CLIP_LDK]
-  bf16 *sV = sK + LP * CLIP_LDK;                     // [64][LDV], transposed
+  bf16 *sK, *sV;
+  tx_carve(LP, sK, sV);
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -40,43 +31,17 @@ __global__ __launch_bounds__(256) void ca_clip_attn_kernel(const bf16 *q, const 
   const int h = (int)(sh % heads);
   const long seq = sh / heads;
   const long row0 = seq * L;                         // first token row of the sequence
-  const long col = (long)h * CLIP_D;
+  const long col = (long)h * TX_D;
   const int nkeys = LP < qt * 64 + 64 ? LP : qt * 64 + 64;   // keys the workgroup's queries can see (a multiple of 32)
 
-  // ---- K and V^T into LDS; positions >= L are zeros and touch no memory
-  {
-    const int c = tid & 7;
-    for (int r = tid >> 3; r < nkeys; r += 32) {
-      uint4 x = {0u, 0u, 0u, 0u};
-      if (r < L) x = *(const uint4 *)(k + (row0 + r) * ldk + col + c * 8);
-      *(uint4 *)(sK + r * CLIP_LDK + c * 8) = x;
-    }
-    const int kp0 = tid & 31, cv = tid >> 5;         // key pair, 8-column chunk
-    for (int kp = kp0; kp < nkeys / 2; kp += 32) {
-      bf16x8 a, b;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) a[i] = b[i] = (bf16)0.f;
-      if (2 * kp < L) a = *(const bf16x8 *)(v + (row0 + 2 * kp) * ldv + col + cv * 8);
-      if (2 * kp + 1 < L) b = *(const bf16x8 *)(v + (row0 + 2 * kp + 1) * ldv + col + cv * 8);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        bf16x2 pr = {a[i], b[i]};
-        *(bf16x2 *)(sV + (cv * 8 + i) * LDV + 2 * kp) = pr;
-      }
-    }
-  }
-
-  // ---- this lane's query row as the B operand of S^T = K Q^T
+  tx_stage_kv<LDV>(k, v, row0, col, ldk, ldv, sK, sV, nkeys, L);
   const int j = lane & 15, g = lane >> 4;
   const int qbase = qt * 64 + wave * 16;             // wave-uniform
   const int qpos = qbase + j;
   bf16x8 qf[2];
 #pragma unroll
-  for (int kk = 0; kk < 2; ++kk) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) qf[kk][i] = (bf16)0.f;
-    if (qpos < L) qf[kk] = *(const bf16x8 *)(q + (row0 + qpos) * ldq + col + kk * 32 + g * 8);
-  }
+  for (int i = 0; i < 8; ++i) qf[0][i] = qf[1][i] = (bf16)0.f;
+  if (qpos < L) tx_load_q(q, row0, qpos, ldq, col, g, qf);
   __syncthreads();
   if (qbase >= L) return;                            // no query of this wave exists (no barrier follows)
 
@@ -86,12 +51,7 @@ __global__ __launch_bounds__(256) void ca_clip_attn_kernel(const bf16 *q, const 
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     if (t * 16 <= qbase + 15) {                      // wave-uniform: some query of the wave sees some key of the tile
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const bf16x8 kf = *(const bf16x8 *)(sK + (t * 16 + j) * CLIP_LDK + kk * 32 + g * 8);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], acc, 0, 0, 0);
-      }
+      const f32x4 acc = tx_score_tile(sK, t, j, g, qf);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         s[t][r] = t * 16 + g * 4 + r <= qpos ? acc[r] * scale : -INFINITY;
@@ -101,60 +61,17 @@ __global__ __launch_bounds__(256) void ca_clip_attn_kernel(const bf16 *q, const 
       s[t] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     }
   }
-  mx = fmaxf(mx, __shfl_xor(mx, 16));
-  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  const float sum = tx_softmax(s, mx);
 
-  float sum = 0.f;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      s[t][r] = __builtin_amdgcn_exp2f((s[t][r] - mx) * 1.4426950409f);
-      sum += s[t][r];
-    }
-  }
-  sum += __shfl_xor(sum, 16);
-  sum += __shfl_xor(sum, 32);
-
-  // ---- O^T = V^T P^T: lane holds columns 16 dt + 4 g + 0..3 of query j
   f32x4 o[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int u = 0; u < NU; ++u) {
-    if (u * 32 <= qbase + 15) {                      // wave-uniform: beyond it every probability is 0
-      bf16x8 pf;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        pf[r] = (bf16)s[2 * u][r];
-        pf[4 + r] = (bf16)s[2 * u + 1][r];
-      }
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const bf16 *vr = sV + (dt * 16 + j) * LDV + u * 32 + g * 4;
-        const bf16x4 lo = *(const bf16x4 *)vr, hi = *(const bf16x4 *)(vr + 16);
-        const bf16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[dt], 0, 0, 0);
-      }
-    }
-  }
-
-  if (qpos < L) {
-    const float inv = 1.0f / sum;
-    bf16 *orow = out + (row0 + qpos) * ldo + col + g * 4;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      const uint2 w = {ca_pack2(o[dt][0] * inv, o[dt][1] * inv), ca_pack2(o[dt][2] * inv, o[dt][3] * inv)};
-      *(uint2 *)(orow + dt * 16) = w;
-    }
-  }
+  tx_pv<LDV>(sV, s, j, g, qbase + 15, o);
+  if (qpos < L) tx_store_o(out, row0, qpos, ldo, col, g, o, sum);
 }
 
 template <int NU>
 static int clip_attn_launch(const bf16 *q, const bf16 *k, const bf16 *v, bf16 *out, long ldq, long ldk, long ldv, long ldo,
                             int heads, int L, float scale, long blocks, hipStream_t st, const char *FN) {
-  constexpr int LP = 32 * NU;
-  const int lds = LP * CLIP_LDK * 2 + CLIP_D * (LP + 16) * 2;   // at most 36864 bytes: below the default limit
+  const int lds = tx_attn_lds_bytes(32 * NU, 0);   // at most 36864 bytes: below the default limit
   hipLaunchKernelGGL(ca_clip_attn_kernel<NU>, dim3((unsigned)blocks), dim3(256), lds, st, q, k, v, out, ldq, ldk, ldv, ldo,
                      heads, L, scale);
   return ca_check_launch(FN);
@@ -168,7 +85,7 @@ extern "C" int ca_clip_attn_bf16(const void *q, const void *k, const void *v, vo
     ca_set_error("%s: null pointer", FN);
     return CA_ERR_ARG;
   }
-  const long width = (long)heads * CLIP_D;
+  const long width = (long)heads * TX_D;
   if (n_seq < 1 || heads < 1 || L < 1 || L > 128 || ldq < width || ldk < width || ldv < width || ldo < width || ldq % 8 ||
       ldk % 8 || ldv % 8 || ldo % 8 || !(scale > 0.f) || !(scale < INFINITY)) {
     ca_set_error("%s: bad sizes (n_seq=%d heads=%d L=%d [1..128] ldq=%d ldk=%d ldv=%d ldo=%d [>= heads*64, %% 8] scale=%g "
@@ -202,15 +119,6 @@ extern "C" int ca_clip_attn_bf16(const void *q, const void *k, const void *v, vo
 // src = row_idx ? row_idx[r] : r and var the biased variance ABOUT the mean (a second pass over the row: the one-pass
 // form sum x^2 / H - mean^2 cancels when the mean is large against the spread).  A workgroup per output row, three
 // passes over the source row (the later ones hit the cache).
-__device__ __forceinline__ float clip_block_sum(float v, float *red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 __global__ __launch_bounds__(256) void ca_layernorm_kernel(const float *x, long ldx, const int32_t *row_idx, const float *w,
                                                             const float *b, bf16 *out, long ldo, long rows, int H, float eps) {
   __shared__ float red[4];
@@ -223,14 +131,14 @@ __global__ __launch_bounds__(256) void ca_layernorm_kernel(const float *x, long 
       const f32x4 a = *(const f32x4 *)(xr + i);
       sm += (a[0] + a[1]) + (a[2] + a[3]);
     }
-    const float mean = clip_block_sum(sm, red) / (float)H;
+    const float mean = tx_block_sum(sm, red) / (float)H;
     float ss = 0.f;
     for (int i = threadIdx.x * 4; i < H; i += 1024) {
       const f32x4 a = *(const f32x4 *)(xr + i);
       const float d0 = a[0] - mean, d1 = a[1] - mean, d2 = a[2] - mean, d3 = a[3] - mean;
       ss += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
     }
-    ss = clip_block_sum(ss, red);
+    ss = tx_block_sum(ss, red);
     const float rs = 1.0f / sqrtf(ss / (float)H + eps);
     for (int i = threadIdx.x * 4; i < H; i += 1024) {
       const f32x4 a = *(const f32x4 *)(xr + i), g = *(const f32x4 *)(w + i), c = *(const f32x4 *)(b + i);
@@ -253,8 +161,7 @@ extern "C" int ca_layernorm_f32in(const float *x, int32_t ldx, const int32_t *ro
     ca_set_error("%s: x, w and b must be 16-byte aligned, out 8-byte, row_idx 4-byte", FN);
     return CA_ERR_ARG;
   }
-  const long blocks = rows < 65536 ? rows : 65536;
-  hipLaunchKernelGGL(ca_layernorm_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, row_idx,
+  hipLaunchKernelGGL(ca_layernorm_kernel, dim3(tx_row_blocks(rows)), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, row_idx,
                      w, b, (bf16 *)out, (long)ldo, (long)rows, H, eps);
   return ca_check_launch(FN);
 }
@@ -270,11 +177,7 @@ __device__ __forceinline__ float clip_quick_gelu(float x) {
 }
 
 __global__ __launch_bounds__(256) void ca_quick_gelu_kernel(const bf16 *x, long ldx, bf16 *out, long ldo, long rows, int C) {
-  const int cq = C / 8;
-  const long total = rows * cq;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const long r = i / cq;
-    const int c = (int)(i - r * cq) * 8;
+  tx_walk8(rows, C, [&](long r, int c) {
     const bf16x8 a = *(const bf16x8 *)(x + r * ldx + c);
     uint4 o;
     o.x = ca_pack2(clip_quick_gelu((float)a[0]), clip_quick_gelu((float)a[1]));
@@ -282,7 +185,7 @@ __global__ __launch_bounds__(256) void ca_quick_gelu_kernel(const bf16 *x, long 
     o.z = ca_pack2(clip_quick_gelu((float)a[4]), clip_quick_gelu((float)a[5]));
     o.w = ca_pack2(clip_quick_gelu((float)a[6]), clip_quick_gelu((float)a[7]));
     *(uint4 *)(out + r * ldo + c) = o;
-  }
+  });
 }
 
 extern "C" int ca_quick_gelu_bf16(const void *x, int32_t ldx, void *out, int32_t ldo, int64_t rows, int32_t C,
@@ -294,9 +197,7 @@ extern "C" int ca_quick_gelu_bf16(const void *x, int32_t ldx, void *out, int32_t
                  FN, (long long)rows, C, ldx, ldo);
     return CA_ERR_ARG;
   }
-  long blocks = (rows * (C / 8) + 255) / 256;
-  if (blocks > 65536) blocks = 65536;
-  hipLaunchKernelGGL(ca_quick_gelu_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16 *)x,
+  hipLaunchKernelGGL(ca_quick_gelu_kernel, dim3(tx_walk8_blocks(rows, C)), dim3(256), 0, (hipStream_t)stream, (const bf16 *)x,
                      (long)ldx, (bf16 *)out, (long)ldo, (long)rows, C);
   return ca_check_launch(FN);
 }
@@ -307,11 +208,7 @@ extern "C" int ca_quick_gelu_bf16(const void *x, int32_t ldx, void *out, int32_t
 __global__ __launch_bounds__(256) void ca_clip_embed_kernel(const bf16 *tok, long ldt, const bf16 *pos, long ldp,
                                                              const int32_t *ids, float *out, long ldo, long rows, int L,
                                                              int H) {
-  const int cq = H / 8;
-  const long total = rows * cq;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const long r = i / cq;
-    const int c = (int)(i - r * cq) * 8;
+  tx_walk8(rows, H, [&](long r, int c) {
     const bf16x8 a = *(const bf16x8 *)(tok + (long)ids[r] * ldt + c);
     const bf16x8 p = *(const bf16x8 *)(pos + (r % L) * ldp + c);
     float *o = out + r * ldo + c;
@@ -319,7 +216,7 @@ __global__ __launch_bounds__(256) void ca_clip_embed_kernel(const bf16 *tok, lon
                         (float)a[3] + (float)p[3]};
     *(f32x4 *)(o + 4) = f32x4{(float)a[4] + (float)p[4], (float)a[5] + (float)p[5], (float)a[6] + (float)p[6],
                               (float)a[7] + (float)p[7]};
-  }
+  });
 }
 
 extern "C" int ca_clip_embed_f32(const void *tok, int32_t ldt, const void *pos, int32_t ldp, const int32_t *ids, float *out,
@@ -331,9 +228,7 @@ extern "C" int ca_clip_embed_f32(const void *tok, int32_t ldt, const void *pos, 
                  "pos and out 16-byte aligned, ids 4-byte, all non-null)", FN, (long long)rows, L, H, ldt, ldp, ldo);
     return CA_ERR_ARG;
   }
-  long blocks = (rows * (H / 8) + 255) / 256;
-  if (blocks > 65536) blocks = 65536;
-  hipLaunchKernelGGL(ca_clip_embed_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16 *)tok,
+  hipLaunchKernelGGL(ca_clip_embed_kernel, dim3(tx_walk8_blocks(rows, H)), dim3(256), 0, (hipStream_t)stream, (const bf16 *)tok,
                      (long)ldt, (const bf16 *)pos, (long)ldp, ids, out, (long)ldo, (long)rows, L, H);
   return ca_check_launch(FN);
 }

@@ -2,36 +2,19 @@
 // v_mfma_f32_16x16x32_bf16, the RMS layer norm of the fp32 residual stream, the gated-GELU product (each also as a
 // producer of e4m3 rows with one scale per row, for the fp8 mode) and the embedding gather.  The projections run on
 // the grouped GEMM of ca_gemm.hip.  Every element offset is formed in 64 bits.
-#include "ca_common.h"
+#include "ca_text_core.h"
 
 // ------------------------------------------------------------------------------------------------------------------
-// out = softmax(q k^T + bias) v per (sequence, head); head dim 64, no 1/sqrt(d) scale, no mask.
-//
-// A workgroup of 4 waves owns 64 query rows of one (sequence, head); a wave owns 16 of them.  K of the head sits in LDS
-// row-major ([key][64], rows of 72 bf16 so that the 16 rows of a ds_read_b128 fragment read fall on 16 distinct 16-byte
-// slots), V transposed ([d][key], rows of L + 16 bf16) because P V contracts over the keys and an MFMA operand wants its
-// 8 contraction elements contiguous in a lane; the head's bias row (2L - 1 floats) sits beside them.
-//
-// Scores are computed transposed, S^T = K Q^T: with K as the MFMA's A operand and Q as B, a lane ends up with ONE query
-// (lane & 15) and keys 16 t + 4 (lane >> 4) + 0..3 of every 16-key tile t.  All L scores of the wave's 16 queries are
-// held in registers (L / 4 floats per lane), so the softmax is the exact two-pass one: row maximum, then exp and sum,
-// each finished by two cross-lane exchanges over the 4 lanes of a query.  The same registers, rounded to bf16, are the
-// B operand of O^T = V^T P^T: the contraction slot (g, e) of 32-key step u stands for key 32 u + 4 g + e (e < 4) or
-// 32 u + 16 + 4 g + e - 4 (e >= 4), and the V^T fragment is read from LDS under the same permutation.  The lane's
-// query is the same in both products, so 1 / sum is a per-lane scalar.  P is rounded to bf16 unnormalised (in (0, 1]);
-// the sum is taken over the fp32 values.
-#define T5_D 64
-#define T5_LDK 72
-
+// out = softmax(q k^T + bias) v per (sequence, head); head dim 64, no 1/sqrt(d) scale, no mask.  The tile and its steps
+// are ca_text_core.h's; here L = 16 NT is a compile-time constant, every position exists, and the head's bias row
+// (2L - 1 floats) sits in LDS behind K and V^T.
 template <int NT>   // NT = L / 16 key tiles
 __global__ __launch_bounds__(256) void ca_t5_attn_kernel(const bf16 *q, const bf16 *k, const bf16 *v, const float *bias,
                                                           bf16 *out, long ldq, long ldk, long ldv, long ldo, int heads) {
   constexpr int L = NT * 16;
   constexpr int LDV = L + 16;
-  extern __shared__ __attribute__((aligned(16))) unsigned char t5_smem[];
-  bf16 *sK = (bf16 *)t5_smem;                        // [L][T5_LDK]
-  bf16 *sV = sK + L * T5_LDK;                        // [64][LDV], transposed
-  float *sB = (float *)(sV + T5_D * LDV);            // [2 L] (2 L - 1 used)
+  bf16 *sK, *sV;
+  float *sB = (float *)tx_carve(L, sK, sV);          // [2 L] (2 L - 1 used)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   constexpr int QT = L / 64;
@@ -41,50 +24,21 @@ __global__ __launch_bounds__(256) void ca_t5_attn_kernel(const bf16 *q, const bf
   const int h = (int)(sh % heads);
   const long seq = sh / heads;
   const long row0 = seq * L;                         // first token row of the sequence
-  const long col = (long)h * T5_D;
+  const long col = (long)h * TX_D;
 
-  // ---- K, V^T and the bias row into LDS
-  {
-    const int c = tid & 7;
-#pragma unroll 4
-    for (int r = tid >> 3; r < L; r += 32) {
-      const uint4 x = *(const uint4 *)(k + (row0 + r) * ldk + col + c * 8);
-      *(uint4 *)(sK + r * T5_LDK + c * 8) = x;
-    }
-    const int kp0 = tid & 31, cv = tid >> 5;         // key pair within a 64-key slab, 8-column chunk
-#pragma unroll 2
-    for (int kp = kp0; kp < L / 2; kp += 32) {
-      const bf16x8 a = *(const bf16x8 *)(v + (row0 + 2 * kp) * ldv + col + cv * 8);
-      const bf16x8 b = *(const bf16x8 *)(v + (row0 + 2 * kp + 1) * ldv + col + cv * 8);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        bf16x2 pr = {a[i], b[i]};
-        *(bf16x2 *)(sV + (cv * 8 + i) * LDV + 2 * kp) = pr;
-      }
-    }
-    const float *bh = bias + (long)h * (2 * L - 1);
-    for (int i = tid; i < 2 * L - 1; i += 256) sB[i] = bh[i];
-  }
+  tx_stage_kv<LDV>(k, v, row0, col, ldk, ldv, sK, sV, L, L);
+  const float *bh = bias + (long)h * (2 * L - 1);
+  for (int i = tid; i < 2 * L - 1; i += 256) sB[i] = bh[i];
 
-  // ---- this lane's query row as the B operand of S^T = K Q^T
   const int j = lane & 15, g = lane >> 4;
   const int qpos = qt * 64 + wave * 16 + j;
   bf16x8 qf[2];
-#pragma unroll
-  for (int kk = 0; kk < 2; ++kk) qf[kk] = *(const bf16x8 *)(q + (row0 + qpos) * ldq + col + kk * 32 + g * 8);
+  tx_load_q(q, row0, qpos, ldq, col, g, qf);
   __syncthreads();
 
   f32x4 s[NT];
 #pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const bf16x8 kf = *(const bf16x8 *)(sK + (t * 16 + j) * T5_LDK + kk * 32 + g * 8);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], acc, 0, 0, 0);
-    }
-    s[t] = acc;
-  }
+  for (int t = 0; t < NT; ++t) s[t] = tx_score_tile(sK, t, j, g, qf);
 
   // ---- + bias[key - query + L - 1], row maximum
   float mx = -INFINITY;
@@ -97,58 +51,18 @@ __global__ __launch_bounds__(256) void ca_t5_attn_kernel(const bf16 *q, const bf
       mx = fmaxf(mx, s[t][r]);
     }
   }
-  mx = fmaxf(mx, __shfl_xor(mx, 16));
-  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  const float sum = tx_softmax(s, mx);
 
-  float sum = 0.f;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      s[t][r] = __builtin_amdgcn_exp2f((s[t][r] - mx) * 1.4426950409f);
-      sum += s[t][r];
-    }
-  }
-  sum += __shfl_xor(sum, 16);
-  sum += __shfl_xor(sum, 32);
-
-  // ---- O^T = V^T P^T: lane holds columns 16 dt + 4 g + 0..3 of query j
   f32x4 o[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int u = 0; u < NT / 2; ++u) {
-    bf16x8 pf;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      pf[r] = (bf16)s[2 * u][r];
-      pf[4 + r] = (bf16)s[2 * u + 1][r];
-    }
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      const bf16 *vr = sV + (dt * 16 + j) * LDV + u * 32 + g * 4;
-      const bf16x4 lo = *(const bf16x4 *)vr, hi = *(const bf16x4 *)(vr + 16);
-      const bf16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[dt], 0, 0, 0);
-    }
-  }
-
-  const float inv = 1.0f / sum;
-  bf16 *orow = out + (row0 + qpos) * ldo + col + g * 4;
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) {
-    const uint2 w = {ca_pack2(o[dt][0] * inv, o[dt][1] * inv), ca_pack2(o[dt][2] * inv, o[dt][3] * inv)};
-    *(uint2 *)(orow + dt * 16) = w;
-  }
+  tx_pv<LDV>(sV, s, j, g, L - 1, o);
+  tx_store_o(out, row0, qpos, ldo, col, g, o, sum);
 }
-
-static int t5_attn_lds_bytes(int L) { return L * T5_LDK * 2 + T5_D * (L + 16) * 2 + 2 * L * 4; }
 
 template <int NT>
 static int t5_attn_launch(const bf16 *q, const bf16 *k, const bf16 *v, const float *bias, bf16 *out, long ldq, long ldk,
                           long ldv, long ldo, int heads, long blocks, hipStream_t st, const char *FN) {
   static std::atomic<unsigned long long> raised{0};
-  const int lds = t5_attn_lds_bytes(NT * 16);
+  const int lds = tx_attn_lds_bytes(NT * 16, 2 * NT * 16);
   const int rc = ca_raise_lds_limit({(const void *)ca_t5_attn_kernel<NT>}, lds, raised, FN);
   if (rc != CA_OK) return rc;
   hipLaunchKernelGGL(ca_t5_attn_kernel<NT>, dim3((unsigned)blocks), dim3(256), lds, st, q, k, v, bias, out, ldq, ldk, ldv,
@@ -164,7 +78,7 @@ extern "C" int ca_t5_attn_bf16(const void *q, const void *k, const void *v, cons
     ca_set_error("%s: null pointer", FN);
     return CA_ERR_ARG;
   }
-  const long width = (long)heads * T5_D;
+  const long width = (long)heads * TX_D;
   if (n_seq < 1 || heads < 1 || L < 64 || L > 512 || L % 64 || ldq < width || ldk < width || ldv < width || ldo < width ||
       ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8) {
     ca_set_error("%s: bad sizes (n_seq=%d heads=%d L=%d [64..512, %% 64] ldq=%d ldk=%d ldv=%d ldo=%d [>= heads*64, %% 8])",
@@ -196,15 +110,6 @@ extern "C" int ca_t5_attn_bf16(const void *q, const void *k, const void *v, cons
 // ------------------------------------------------------------------------------------------------------------------
 // T5LayerNorm: out[r, :] = bf16(x[r, :] * rsqrt(mean(x[r, :]^2) + eps) * w[:]); no mean subtraction, no bias.  A
 // workgroup per row (rows walked with the grid's stride), two passes over the row (the second hits the cache).
-__device__ __forceinline__ float t5_block_sum(float v, float *red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 __global__ __launch_bounds__(256) void ca_t5_rmsnorm_kernel(const float *x, long ldx, const float *w, bf16 *out, long ldo,
                                                              long rows, int H, float eps) {
   __shared__ float red[4];
@@ -216,7 +121,7 @@ __global__ __launch_bounds__(256) void ca_t5_rmsnorm_kernel(const float *x, long
       const f32x4 a = *(const f32x4 *)(xr + i);
       ss += (a[0] * a[0] + a[1] * a[1]) + (a[2] * a[2] + a[3] * a[3]);
     }
-    ss = t5_block_sum(ss, red);
+    ss = tx_block_sum(ss, red);
     const float rs = 1.0f / sqrtf(ss / (float)H + eps);
     for (int i = threadIdx.x * 4; i < H; i += 1024) {
       const f32x4 a = *(const f32x4 *)(xr + i), g = *(const f32x4 *)(w + i);
@@ -238,8 +143,7 @@ extern "C" int ca_t5_rmsnorm_f32in(const float *x, int32_t ldx, const float *w, 
     ca_set_error("%s: x and w must be 16-byte aligned, out 8-byte", FN);
     return CA_ERR_ARG;
   }
-  const long blocks = rows < 65536 ? rows : 65536;
-  hipLaunchKernelGGL(ca_t5_rmsnorm_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, w,
+  hipLaunchKernelGGL(ca_t5_rmsnorm_kernel, dim3(tx_row_blocks(rows)), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, w,
                      (bf16 *)out, (long)ldo, (long)rows, H, eps);
   return ca_check_launch(FN);
 }
@@ -248,15 +152,6 @@ extern "C" int ca_t5_rmsnorm_f32in(const float *x, int32_t ldx, const float *w, 
 // The e4m3 producers of the fp8 mode: a row leaves as e4m3 bytes plus one fp32 scale (amax / 448, or 1 for a zero row;
 // the rule of ca_quantize_rows_fp8_kernel), the A operand of ca_gemm_fp8.  A workgroup owns a whole row, so the row
 // maximum is known before the store and the row never exists in bf16.
-__device__ __forceinline__ float t5_block_max(float v, float *red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
 // y[0..8) = x[i..i+8) * rs * w[i..i+8): products only, so the pass that takes the maximum and the pass that stores
 // form the same bits
 __device__ __forceinline__ void t5_norm8(const float *xr, const float *w, int i, float rs, float *y) {
@@ -283,7 +178,7 @@ __global__ __launch_bounds__(256) void ca_t5_rmsnorm_fp8_kernel(const float *x, 
       ss += ((a[0] * a[0] + a[1] * a[1]) + (a[2] * a[2] + a[3] * a[3])) +
             ((b[0] * b[0] + b[1] * b[1]) + (b[2] * b[2] + b[3] * b[3]));
     }
-    ss = t5_block_sum(ss, red);
+    ss = tx_block_sum(ss, red);
     const float rs = 1.0f / sqrtf(ss / (float)H + eps);
     float amax = 0.f;
     for (int i = threadIdx.x * 8; i < H; i += 2048) {
@@ -292,10 +187,7 @@ __global__ __launch_bounds__(256) void ca_t5_rmsnorm_fp8_kernel(const float *x, 
 #pragma unroll
       for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(y[j]));
     }
-    amax = t5_block_max(amax, red);
-    const float sc = amax > 0.f ? amax * (1.0f / E4M3_MAX) : 1.0f;
-    const float inv = 1.0f / sc;
-    if (threadIdx.x == 0) out_scale[r] = sc;
+    const float inv = tx_fp8_row_scale(amax, red, out_scale + r);
     for (int i = threadIdx.x * 8; i < H; i += 2048) {
       float y[8];
       t5_norm8(xr, w, i, rs, y);
@@ -319,8 +211,7 @@ extern "C" int ca_t5_rmsnorm_f32in_fp8(const float *x, int32_t ldx, const float 
     ca_set_error("%s: x and w must be 16-byte aligned, out8 8-byte, out_scale 4-byte", FN);
     return CA_ERR_ARG;
   }
-  const long blocks = rows < 65536 ? rows : 65536;
-  hipLaunchKernelGGL(ca_t5_rmsnorm_fp8_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, w,
+  hipLaunchKernelGGL(ca_t5_rmsnorm_fp8_kernel, dim3(tx_row_blocks(rows)), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, w,
                      (uint8_t *)out8, (long)ldo, out_scale, (long)rows, H, eps);
   return ca_check_launch(FN);
 }
@@ -329,11 +220,7 @@ extern "C" int ca_t5_rmsnorm_f32in_fp8(const float *x, int32_t ldx, const float 
 // out = bf16(float(g) * float(u)): the gelu(wi_0 x) * (wi_1 x) product of T5DenseGatedActDense, 8 elements per thread.
 __global__ __launch_bounds__(256) void ca_gated_mul_kernel(const bf16 *g, long ldg, const bf16 *u, long ldu, bf16 *out,
                                                             long ldo, long rows, int C) {
-  const int cq = C / 8;
-  const long total = rows * cq;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const long r = i / cq;
-    const int c = (int)(i - r * cq) * 8;
+  tx_walk8(rows, C, [&](long r, int c) {
     const bf16x8 a = *(const bf16x8 *)(g + r * ldg + c), b = *(const bf16x8 *)(u + r * ldu + c);
     uint4 o;
     o.x = ca_pack2((float)a[0] * (float)b[0], (float)a[1] * (float)b[1]);
@@ -341,7 +228,7 @@ __global__ __launch_bounds__(256) void ca_gated_mul_kernel(const bf16 *g, long l
     o.z = ca_pack2((float)a[4] * (float)b[4], (float)a[5] * (float)b[5]);
     o.w = ca_pack2((float)a[6] * (float)b[6], (float)a[7] * (float)b[7]);
     *(uint4 *)(out + r * ldo + c) = o;
-  }
+  });
 }
 
 extern "C" int ca_gated_mul_bf16(const void *g, int32_t ldg, const void *u, int32_t ldu, void *out, int32_t ldo,
@@ -353,9 +240,7 @@ extern "C" int ca_gated_mul_bf16(const void *g, int32_t ldg, const void *u, int3
                  FN, (long long)rows, C, ldg, ldu, ldo);
     return CA_ERR_ARG;
   }
-  long blocks = (rows * (C / 8) + 255) / 256;
-  if (blocks > 65536) blocks = 65536;
-  hipLaunchKernelGGL(ca_gated_mul_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16 *)g,
+  hipLaunchKernelGGL(ca_gated_mul_kernel, dim3(tx_walk8_blocks(rows, C)), dim3(256), 0, (hipStream_t)stream, (const bf16 *)g,
                      (long)ldg, (const bf16 *)u, (long)ldu, (bf16 *)out, (long)ldo, (long)rows, C);
   return ca_check_launch(FN);
 }
@@ -375,10 +260,7 @@ __global__ __launch_bounds__(256) void ca_gated_mul_fp8_kernel(const bf16 *g, lo
 #pragma unroll
       for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf((float)a[j] * (float)b[j]));
     }
-    amax = t5_block_max(amax, red);
-    const float sc = amax > 0.f ? amax * (1.0f / E4M3_MAX) : 1.0f;
-    const float inv = 1.0f / sc;
-    if (threadIdx.x == 0) out_scale[r] = sc;
+    const float inv = tx_fp8_row_scale(amax, red, out_scale + r);
     for (int i = threadIdx.x * 8; i < C; i += 2048) {
       const bf16x8 a = *(const bf16x8 *)(gr + i), b = *(const bf16x8 *)(ur + i);
       float y[8];
@@ -402,8 +284,7 @@ extern "C" int ca_gated_mul_fp8(const void *g, int32_t ldg, const void *u, int32
     ca_set_error("%s: g and u must be 16-byte aligned, out8 8-byte, out_scale 4-byte", FN);
     return CA_ERR_ARG;
   }
-  const long blocks = rows < 65536 ? rows : 65536;
-  hipLaunchKernelGGL(ca_gated_mul_fp8_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16 *)g,
+  hipLaunchKernelGGL(ca_gated_mul_fp8_kernel, dim3(tx_row_blocks(rows)), dim3(256), 0, (hipStream_t)stream, (const bf16 *)g,
                      (long)ldg, (const bf16 *)u, (long)ldu, (uint8_t *)out8, (long)ldo, out_scale, (long)rows, C);
   return ca_check_launch(FN);
 }
@@ -413,16 +294,12 @@ extern "C" int ca_gated_mul_fp8(const void *g, int32_t ldg, const void *u, int32
 // responsibility (the Python wrapper rejects any outside [0, vocab) before the launch).
 __global__ __launch_bounds__(256) void ca_embed_rows_kernel(const bf16 *table, long ldt, const int32_t *ids, float *out,
                                                              long ldo, long rows, int H) {
-  const int cq = H / 8;
-  const long total = rows * cq;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const long r = i / cq;
-    const int c = (int)(i - r * cq) * 8;
+  tx_walk8(rows, H, [&](long r, int c) {
     const bf16x8 a = *(const bf16x8 *)(table + (long)ids[r] * ldt + c);
     float *o = out + r * ldo + c;
     *(f32x4 *)o = f32x4{(float)a[0], (float)a[1], (float)a[2], (float)a[3]};
     *(f32x4 *)(o + 4) = f32x4{(float)a[4], (float)a[5], (float)a[6], (float)a[7]};
-  }
+  });
 }
 
 extern "C" int ca_embed_rows_f32(const void *table, int32_t ldt, const int32_t *ids, float *out, int32_t ldo, int64_t rows,
@@ -434,9 +311,7 @@ extern "C" int ca_embed_rows_f32(const void *table, int32_t ldt, const int32_t *
                  "aligned, ids 4-byte)", FN, (long long)rows, H, ldt, ldo);
     return CA_ERR_ARG;
   }
-  long blocks = (rows * (H / 8) + 255) / 256;
-  if (blocks > 65536) blocks = 65536;
-  hipLaunchKernelGGL(ca_embed_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16 *)table,
+  hipLaunchKernelGGL(ca_embed_rows_kernel, dim3(tx_walk8_blocks(rows, H)), dim3(256), 0, (hipStream_t)stream, (const bf16 *)table,
                      (long)ldt, ids, out, (long)ldo, (long)rows, H);
   return ca_check_launch(FN);
 }

@@ -1106,21 +1106,39 @@ def mseg_score(maps, labels, counts, class_of, nclass: int, ignore_index: Option
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# T5 encoder kernels (ca_t5.hip).  Rows are tokens; q / k / v are 2-D views with free row strides.
+# T5 encoder kernels (ca_t5.hip).  Rows are tokens; q / k / v are 2-D views with free row strides.  The two checks in
+# front serve the CLIP wrappers below as well.
+
+def _attn_views(fn: str, q, k, v, out, n_seq: int, num_heads: int) -> int:
+    """The four bf16 [n_seq * L, num_heads * 64] views of a text-encoder attention call (row strides free); returns L."""
+    for n, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        _chk(t, torch.bfloat16, n)
+        if t.dim() != 2 or t.shape[1] != num_heads * 64 or t.shape[0] != q.shape[0]:
+            raise ValueError(f"{fn}: {n} must be 2-D [n_seq * L, num_heads*64 = {num_heads * 64}], got {tuple(t.shape)}")
+    if n_seq < 1 or q.shape[0] % n_seq:
+        raise ValueError(f"{fn}: {q.shape[0]} rows are not n_seq = {n_seq} sequences of one length")
+    return q.shape[0] // n_seq
+
+
+def _vocab_ids(fn: str, ids, table, shapes: str, shapes_ok) -> torch.Tensor:
+    """The int32 [rows] token ids (host or device) of a gather from ``table`` [vocab, H], on the table's device: their form,
+    the caller's shapes, then every id in [0, vocab) -- the kernel cannot check it -- before anything is launched."""
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous():
+        raise ValueError(f"{fn}: ids must be a contiguous 1-D int32 tensor")
+    if not shapes_ok():
+        raise ValueError(f"{fn}: {shapes}")
+    lo, hi = int(ids.min()), int(ids.max())
+    if lo < 0 or hi >= table.shape[0]:
+        raise ValueError(f"{fn}: ids span [{lo}, {hi}], outside the vocabulary [0, {table.shape[0]})")
+    return ids.to(table.device)
+
 
 def t5_attention(q, k, v, bias, out, n_seq: int, num_heads: int) -> None:
     """out = softmax(q k^T + bias) v per (sequence, head); head dim 64, no 1/sqrt(d) scale, no mask.  q, k, v, out bf16
     [n_seq * L, num_heads * 64] views (row stride free, e.g. column slices of one projection output); bias fp32
     [num_heads, 2 L - 1] contiguous, indexed by key_pos - query_pos + L - 1."""
-    for n, t in (("q", q), ("k", k), ("v", v), ("out", out)):
-        _chk(t, torch.bfloat16, n)
-        if t.dim() != 2 or t.shape[1] != num_heads * 64 or t.shape[0] != q.shape[0]:
-            raise ValueError(f"t5_attention: {n} must be 2-D [n_seq * L, num_heads*64 = {num_heads * 64}], got {tuple(t.shape)}")
-    _chk(bias, torch.float32, "bias")
-    if n_seq < 1 or q.shape[0] % n_seq:
-        raise ValueError(f"t5_attention: {q.shape[0]} rows are not n_seq = {n_seq} sequences of one length")
-    Lq = q.shape[0] // n_seq
-    if tuple(bias.shape) != (num_heads, 2 * Lq - 1) or not bias.is_contiguous():
+    Lq = _attn_views("t5_attention", q, k, v, out, n_seq, num_heads)
+    if tuple(_chk(bias, torch.float32, "bias").shape) != (num_heads, 2 * Lq - 1) or not bias.is_contiguous():
         raise ValueError(f"t5_attention: bias must be contiguous fp32 [num_heads, 2 L - 1] = [{num_heads}, {2 * Lq - 1}], "
                          f"got {tuple(bias.shape)}")
     L.check(L.load().ca_t5_attn_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), bias.data_ptr(), out.data_ptr(),
@@ -1188,14 +1206,8 @@ def embed_rows(table, ids, out) -> None:
     """out[r, :] = float(table[ids[r], :]): table bf16 [vocab, H], ids int32 [rows] (host or device), out fp32 [rows, H].
     An id outside [0, vocab) is a ValueError here, before anything is launched (the kernel cannot check it)."""
     _chk(table, torch.bfloat16, "table"), _chk(out, torch.float32, "out")
-    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous():
-        raise ValueError("embed_rows: ids must be a contiguous 1-D int32 tensor")
-    if table.dim() != 2 or out.dim() != 2 or out.shape[0] != ids.shape[0] or out.shape[1] != table.shape[1] or ids.numel() < 1:
-        raise ValueError("embed_rows: table [vocab, H], ids [rows >= 1], out [rows, H]")
-    lo, hi = int(ids.min()), int(ids.max())
-    if lo < 0 or hi >= table.shape[0]:
-        raise ValueError(f"embed_rows: ids span [{lo}, {hi}], outside the vocabulary [0, {table.shape[0]})")
-    ids = ids.to(table.device)
+    ids = _vocab_ids("embed_rows", ids, table, "table [vocab, H], ids [rows >= 1], out [rows, H]", lambda: table.dim() == 2 and
+                     out.dim() == 2 and ids.numel() >= 1 and out.shape[0] == ids.shape[0] and out.shape[1] == table.shape[1])
     L.check(L.load().ca_embed_rows_f32(table.data_ptr(), _i32(table.stride(0), "ldt"), ids.data_ptr(), out.data_ptr(),
                                        _i32(out.stride(0), "ldo"), ids.shape[0], _i32(table.shape[1], "H"), _stream()),
             "ca_embed_rows_f32")
@@ -1208,15 +1220,10 @@ def clip_attention(q, k, v, out, n_seq: int, num_heads: int, scale: float = 0.12
     """out = softmax(scale q k^T + causal mask) v per (sequence, head); head dim 64.  q, k, v, out bf16
     [n_seq * L, num_heads * 64] views (row stride free), L = rows / n_seq any value in 1..128; a query at position i
     sees keys 0..i of its own sequence."""
-    for n, t in (("q", q), ("k", k), ("v", v), ("out", out)):
-        _chk(t, torch.bfloat16, n)
-        if t.dim() != 2 or t.shape[1] != num_heads * 64 or t.shape[0] != q.shape[0]:
-            raise ValueError(f"clip_attention: {n} must be 2-D [n_seq * L, num_heads*64 = {num_heads * 64}], got {tuple(t.shape)}")
-    if n_seq < 1 or q.shape[0] % n_seq:
-        raise ValueError(f"clip_attention: {q.shape[0]} rows are not n_seq = {n_seq} sequences of one length")
+    Lq = _attn_views("clip_attention", q, k, v, out, n_seq, num_heads)
     L.check(L.load().ca_clip_attn_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _i32(q.stride(0), "ldq"),
                                        _i32(k.stride(0), "ldk"), _i32(v.stride(0), "ldv"), _i32(out.stride(0), "ldo"),
-                                       _i32(n_seq, "n_seq"), _i32(num_heads, "num_heads"), _i32(q.shape[0] // n_seq, "L"),
+                                       _i32(n_seq, "n_seq"), _i32(num_heads, "num_heads"), _i32(Lq, "L"),
                                        float(scale), _stream()), "ca_clip_attn_bf16")
 
 
@@ -1260,15 +1267,9 @@ def clip_embed(tok, pos, ids, out, length: int) -> None:
     int32 [rows] (host or device), out fp32 [rows, H].  An id outside [0, vocab) is a ValueError here, before anything is
     launched (the kernel cannot check it)."""
     _chk(tok, torch.bfloat16, "tok"), _chk(pos, torch.bfloat16, "pos"), _chk(out, torch.float32, "out")
-    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous():
-        raise ValueError("clip_embed: ids must be a contiguous 1-D int32 tensor")
-    if tok.dim() != 2 or pos.dim() != 2 or out.dim() != 2 or out.shape[0] != ids.shape[0] or ids.numel() < 1 or \
-            out.shape[1] != tok.shape[1] or pos.shape[1] != tok.shape[1] or not 1 <= length <= pos.shape[0]:
-        raise ValueError("clip_embed: tok [vocab, H], pos [>= length, H], ids [rows >= 1], out [rows, H]")
-    lo, hi = int(ids.min()), int(ids.max())
-    if lo < 0 or hi >= tok.shape[0]:
-        raise ValueError(f"clip_embed: ids span [{lo}, {hi}], outside the vocabulary [0, {tok.shape[0]})")
-    ids = ids.to(tok.device)
+    ids = _vocab_ids("clip_embed", ids, tok, "tok [vocab, H], pos [>= length, H], ids [rows >= 1], out [rows, H]",
+                     lambda: tok.dim() == 2 and pos.dim() == 2 and out.dim() == 2 and ids.numel() >= 1 and out.shape[0] == ids.shape[0]
+                     and out.shape[1] == tok.shape[1] and pos.shape[1] == tok.shape[1] and 1 <= length <= pos.shape[0])
     L.check(L.load().ca_clip_embed_f32(tok.data_ptr(), _i32(tok.stride(0), "ldt"), pos.data_ptr(),
                                        _i32(pos.stride(0), "ldp"), ids.data_ptr(), out.data_ptr(),
                                        _i32(out.stride(0), "ldo"), ids.shape[0],

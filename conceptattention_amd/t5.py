@@ -46,7 +46,7 @@ import torch
 from . import _lib as L
 from . import ops
 from .params import T5Params, t5_params, tiny_t5_params
-from .weights import _gen
+from .weights import _gen, _read_safetensors, fill_tensors, load_text_weights  # noqa: F401
 
 __all__ = ["T5Encoder", "T5Params", "HipTextEncoder", "ToyByteTokenizer", "load_t5", "synthetic_t5_state_dict",
            "t5_state_dict_spec", "relative_position_bucket", "relative_bias_table", "FP8_PROJECTIONS"]
@@ -196,19 +196,9 @@ class T5Encoder:
         if TIED_EMBEDDING in sd:
             twin = sd.pop(TIED_EMBEDDING)
             sd.setdefault("shared.weight", twin)
-        missing = [k for k in self.spec if k not in sd]
-        unexpected = [k for k in sd if k not in self.spec]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"load_state_dict: missing {missing[:4]}.. unexpected {unexpected[:4]}..")
-        for k, shape in self.spec.items():
-            if k in sd:
-                if tuple(sd[k].shape) != tuple(shape):
-                    raise RuntimeError(f"load_state_dict: {k} has shape {tuple(sd[k].shape)}, expected {tuple(shape)}")
-                self.tensors[k] = sd[k].detach().to("cpu", torch.float32)
-                if sd[k].dtype == torch.float8_e4m3fn:
-                    self.e4m3.add(k)
-                else:
-                    self.e4m3.discard(k)
+        missing, unexpected = fill_tensors(self.spec, sd, strict, self.tensors)
+        found = {k for k in self.spec if k in sd}
+        self.e4m3 = (self.e4m3 - found) | {k for k in found if sd[k].dtype == torch.float8_e4m3fn}
         if not missing:
             self._pack()
         return missing, unexpected
@@ -376,20 +366,6 @@ class T5Encoder:
         return self
 
 
-def _read_safetensors(path: str) -> dict:
-    from safetensors.torch import load_file
-    if os.path.isdir(path):
-        files = sorted(os.path.join(path, f) for f in os.listdir(path) if f.endswith(".safetensors"))
-        if not files:
-            raise FileNotFoundError(f"load_t5: no .safetensors file in {path}")
-    else:
-        files = [path]
-    sd: dict = {}
-    for f in files:
-        sd.update(load_file(f, device="cpu"))
-    return sd
-
-
 def load_t5(params="t5-v1_1-xxl", device="cuda", weights="synthetic", seed: int = 0, precision: str = "bf16",
             fp8_projections: Sequence[str] = FP8_PROJECTIONS) -> T5Encoder:
     """``params``: a T5Params or a name of ``params.t5_params``.  ``weights``: "synthetic", a state dict, or a local
@@ -400,17 +376,7 @@ def load_t5(params="t5-v1_1-xxl", device="cuda", weights="synthetic", seed: int 
     become the fp8 operands unchanged; in bf16 mode they are widened exactly)."""
     p = t5_params[params] if isinstance(params, str) else params
     enc = T5Encoder(p, device, precision=precision, fp8_projections=fp8_projections)
-    if isinstance(weights, str) and weights == "synthetic" and os.environ.get("T5"):
-        weights = os.environ["T5"]
-    if isinstance(weights, dict):
-        enc.load_state_dict(weights, strict=True)
-    elif weights == "synthetic":
-        enc.load_state_dict(synthetic_t5_state_dict(p, seed), strict=True)
-    else:
-        missing, _ = enc.load_state_dict(_read_safetensors(str(weights)), strict=False)
-        if missing:
-            raise RuntimeError(f"load_t5: {weights} lacks {len(missing)} encoder tensors: {missing[:4]}..")
-    return enc
+    return load_text_weights(enc, "load_t5", "T5", weights, lambda: synthetic_t5_state_dict(p, seed), "encoder")
 
 
 # ---------------------------------------------------------------------------------------------------------- text in

@@ -11,6 +11,7 @@ construction order and is identical on every rank.
 from __future__ import annotations
 
 import math
+import os
 import zlib
 from typing import Iterator
 
@@ -130,3 +131,53 @@ def synthetic_inputs(p: FluxParams, height: int, width: int, n_txt: int, n_conce
         "concept_ids": torch.zeros(1, n_concepts, 3, device=device),
         "concept_vec": torch.zeros(1, p.vec_in_dim, device=device, dtype=dtype),
     }
+
+
+# ---------------------------------------------------------------------------------------------------------- text encoders
+# What t5.py and clip.py share of loading: the checkpoint reader, the fill loop of load_state_dict and the resolution of
+# the ``weights`` argument of load_t5 / load_clip.
+def _read_safetensors(path: str) -> dict:
+    from safetensors.torch import load_file
+    if os.path.isdir(path):
+        files = sorted(os.path.join(path, f) for f in os.listdir(path) if f.endswith(".safetensors"))
+        if not files:
+            raise FileNotFoundError(f"load_t5: no .safetensors file in {path}")
+    else:
+        files = [path]
+    sd: dict = {}
+    for f in files:
+        sd.update(load_file(f, device="cpu"))
+    return sd
+
+
+def fill_tensors(spec: dict, sd: dict, strict: bool, tensors: dict) -> tuple:
+    """``sd`` (under the encoder's own key names) against ``spec`` (name -> shape) with nn.Module.load_state_dict's
+    (missing, unexpected) semantics; a shape mismatch always raises.  Every tensor found lands in ``tensors`` as an fp32
+    host copy."""
+    missing = [k for k in spec if k not in sd]
+    unexpected = [k for k in sd if k not in spec]
+    if strict and (missing or unexpected):
+        raise RuntimeError(f"load_state_dict: missing {missing[:4]}.. unexpected {unexpected[:4]}..")
+    for k, shape in spec.items():
+        if k in sd:
+            if tuple(sd[k].shape) != tuple(shape):
+                raise RuntimeError(f"load_state_dict: {k} has shape {tuple(sd[k].shape)}, expected {tuple(shape)}")
+            tensors[k] = sd[k].detach().to("cpu", torch.float32)
+    return missing, unexpected
+
+
+def load_text_weights(enc, who: str, env: str, weights, synthetic, what: str):
+    """``weights`` of ``who`` (load_t5, load_clip) into ``enc``: the checkpoint the environment variable ``env`` names when
+    the caller gives none ("synthetic"), a state dict, ``synthetic()``, or a local path that must hold every ``what``
+    tensor.  Nothing is ever downloaded."""
+    if isinstance(weights, str) and weights == "synthetic" and os.environ.get(env):
+        weights = os.environ[env]
+    if isinstance(weights, dict):
+        enc.load_state_dict(weights, strict=True)
+    elif weights == "synthetic":
+        enc.load_state_dict(synthetic(), strict=True)
+    else:
+        missing, _ = enc.load_state_dict(_read_safetensors(str(weights)), strict=False)
+        if missing:
+            raise RuntimeError(f"{who}: {weights} lacks {len(missing)} {what} tensors: {missing[:4]}..")
+    return enc

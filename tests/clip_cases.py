@@ -202,8 +202,8 @@ def ln_gather(rows: int) -> tuple:
 
 
 # ---- grid wrap: the capped grids of ca_clip.hip, restated
-ROW_GRID_CAP = 65536                 # workgroups, one row each: `rows < 65536 ? rows : 65536` (ca_clip.hip:256)
-ELEM_GRID_CAP = 65536 * 256          # threads, 8 elements each: `if (blocks > 65536) blocks = 65536` (ca_clip.hip:298, 335)
+ROW_GRID_CAP = 65536                 # workgroups, one row each: `rows < 65536 ? rows : 65536` (tx_row_blocks)
+ELEM_GRID_CAP = 65536 * 256          # threads, 8 elements each: `if (blocks > 65536) blocks = 65536` (tx_walk8_blocks)
 WRAP_ROWS, WRAP_H = ROW_GRID_CAP + 5, 264
 # op -> (units of work: rows or threads, the cap in the same units, units per workgroup, the case itself)
 WRAP_CASES = {

@@ -199,8 +199,8 @@ GATE_CASES = [(C, rows, strided) for C in (512, 10240) for rows in ROW_ROWS for 
              [(C, rows, strided) for C in (2056, 8) for rows in WIDTH_ROWS for strided in (False, True)]
 # ---- grid wrap: the capped grids of ca_t5.hip, restated.  A case that exceeds its cap sends workgroups through a second
 # iteration of the kernel's stride loop (in the row kernels with the 4-float `red` array reused across iterations).
-ROW_GRID_CAP = 65536                 # workgroups, one row each: `rows < 65536 ? rows : 65536` (ca_t5.hip:241, 322, 405)
-ELEM_GRID_CAP = 65536 * 256          # threads, 8 elements each: `if (blocks > 65536) blocks = 65536` (ca_t5.hip:357, 438)
+ROW_GRID_CAP = 65536                 # workgroups, one row each: `rows < 65536 ? rows : 65536` (tx_row_blocks)
+ELEM_GRID_CAP = 65536 * 256          # threads, 8 elements each: `if (blocks > 65536) blocks = 65536` (tx_walk8_blocks)
 WRAP_ROWS, WRAP_H = ROW_GRID_CAP + 5, 264
 # op -> (units of work: rows or threads, the cap in the same units, units per workgroup, the case itself)
 WRAP_CASES = {

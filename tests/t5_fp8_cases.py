@@ -69,8 +69,8 @@ GATE_CASES = [(C, rows) for C in (512, 10240) for rows in (1, 3, 130)]
 # the entry points' minimum width (one thread works, 255 bring 0 to the reductions)
 RMS_CASES += [(H, rows, strided) for H in (2056, 8) for rows in (1, 7) for strided in (False, True)]
 GATE_CASES += [(C, rows) for C in (2056, 8) for rows in (1, 7)]
-# grid wrap: both producers launch one workgroup per row up to 65536 (`rows < 65536 ? rows : 65536`, ca_t5.hip:322, 405) and
-# walk the rest with the grid's stride, with the 4-float `red` array of t5_block_sum / t5_block_max reused
+# grid wrap: both producers launch one workgroup per row up to 65536 (`rows < 65536 ? rows : 65536`, tx_row_blocks) and
+# walk the rest with the grid's stride, with the 4-float `red` array of tx_block_sum / tx_block_max reused
 ROW_GRID_CAP = 65536
 WRAP_ROWS, WRAP_WIDTH = ROW_GRID_CAP + 5, 264
 WRAP_CASES = {"t5_rmsnorm_fp8": (WRAP_ROWS, ROW_GRID_CAP, 1, dict(H=WRAP_WIDTH, rows=WRAP_ROWS)),

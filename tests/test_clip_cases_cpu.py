@@ -81,8 +81,10 @@ def test_the_ragged_and_minimum_widths_are_cases_and_the_wrap_cases_exceed_their
             assert {(1032, rows, s), (4, rows, s)} <= set(T.LN_CASES) and {(2056, rows, s), (8, rows, s)} <= set(T.QG_CASES)
     assert 8 in T.EMBED_H and [T.ln_id(c) for c in T.LN_CASES][:2] == ["64-False", "64-True"]
     assert all(max(T.ln_gather(r)) == r - 1 and len(T.ln_gather(r)) == 6 for r in (1, 7, 9)) and T.ln_gather(9) == T.LN_GATHER
-    src = open(os.path.join(ROOT, "conceptattention_amd", "csrc", "ca_clip.hip")).read()      # the caps, as the source has them
-    assert src.count("rows < 65536 ? rows : 65536") == 1 and src.count("if (blocks > 65536) blocks = 65536;") == 2
+    src = open(os.path.join(ROOT, "conceptattention_amd", "csrc", "ca_clip.hip")).read()      # the caps, as the source has them:
+    core = open(os.path.join(ROOT, "conceptattention_amd", "csrc", "ca_text_core.h")).read()  # stated once, used by every launch
+    assert core.count("rows < 65536 ? rows : 65536") == 1 and core.count("if (blocks > 65536) blocks = 65536;") == 1
+    assert src.count("dim3(tx_row_blocks(rows))") == 1 and src.count("dim3(tx_walk8_blocks(rows, ") == 2 and "65536" not in src
     assert T.ROW_GRID_CAP == 65536 and T.ELEM_GRID_CAP == 65536 * 256
     assert set(T.WRAP_CASES) == {"layernorm", "quick_gelu", "clip_embed"}
     for op, (units, cap, per_wg, case) in T.WRAP_CASES.items():

@@ -79,11 +79,14 @@ def test_every_attention_instantiation_and_the_ragged_and_minimum_widths_are_cas
 
 
 def test_wrap_cases_exceed_their_caps_by_a_workgroup_and_by_less_than_a_quarter():
-    """The caps are restated from ca_t5.hip; the source must still hold them."""
+    """The caps are restated from ca_text_core.h, where ca_t5.hip's launches take them from; the source must still hold
+    them."""
     import os
-    src = open(os.path.join(os.path.dirname(os.path.abspath(entry.__file__)), "conceptattention_amd", "csrc", "ca_t5.hip")).read()
-    assert src.count("rows < 65536 ? rows : 65536") == 3 and src.count("if (blocks > 65536) blocks = 65536;") == 2
-    assert src.count("dim3(256)") == 6
+    csrc = os.path.join(os.path.dirname(os.path.abspath(entry.__file__)), "conceptattention_amd", "csrc")
+    src, core = open(os.path.join(csrc, "ca_t5.hip")).read(), open(os.path.join(csrc, "ca_text_core.h")).read()
+    assert core.count("rows < 65536 ? rows : 65536") == 1 and core.count("if (blocks > 65536) blocks = 65536;") == 1
+    assert src.count("dim3(tx_row_blocks(rows))") == 3 and src.count("dim3(tx_walk8_blocks(rows, ") == 2
+    assert src.count("dim3(256)") == 6 and "65536" not in src
     assert T.ROW_GRID_CAP == 65536 and T.ELEM_GRID_CAP == 65536 * 256
     assert set(T.WRAP_CASES) == {"t5_rmsnorm", "gated_mul", "embed_rows"}
     for op, (units, cap, per_wg, case) in T.WRAP_CASES.items():
