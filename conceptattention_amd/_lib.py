@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CA_LIB_PATH: another build of the same library (an A/B against another source tree); still no fallback
 LIB_PATH = os.environ.get("CA_LIB_PATH") or os.path.join(_HERE, "libconceptattn.so")
 
-CA_VERSION = 135
+CA_VERSION = 136
 EPI_BIAS, EPI_GELU_TANH, EPI_GATE_RESIDUAL, EPI_SPLIT_GELU, EPI_QKV_NORM_ROPE = 0, 1, 2, 3, 4
 TILE_AUTO, TILE_256x256, TILE_256x192, TILE_256x128, TILE_256x64 = 0, 1, 2, 3, 4
 TILE_PP_256x256, TILE_PP_256x128, TILE_PP_256x192 = 5, 6, 7
@@ -23,6 +23,8 @@ MAX_SEGMENTS = 16
 GEMM_MAX_PROBLEMS = 2
 ATTN_MAX_PROBLEMS = 16
 HEATMAP_MAX_PROBLEMS = 16
+HEATMAP_MAX_CONCEPTS = 32            # ca_heatmap_many, and the sparse norms of ca_heatmap_norm_accumulate
+HEATMAP_SPARSE_MAX_3LAUNCH = 16      # what ops.heatmap_softmax_accumulate takes with a sparse norm (ops.heatmap_norm_accumulate: 32)
 SEG_MAX_PROBLEMS = 16
 SEG_MAX_CELLS = 4096                # ca_seg_score: h * w of the map
 SEG_MAX_LABEL_PIXELS = 1 << 24      # ca_seg_score: Hl * Wl of the label
@@ -199,6 +201,12 @@ SIGNATURES = {
                                     C.c_void_p, C.c_float, C.c_int32, C.c_void_p]),
 }
 
+# exported by the library and bound here, not declared in include/conceptattn.h yet (csrc/ca_heatmap_core.h declares it)
+INTERNAL_SIGNATURES = {
+    "ca_heatmap_many": (C.c_int, [C.POINTER(HeatmapProblem), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -220,7 +228,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no fallback path.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **INTERNAL_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -33,6 +33,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .heatmaps import check_concept_count
 from .params import FluxParams
 from .weights import iter_synthetic_state_dict, state_dict_spec
 
@@ -491,6 +492,8 @@ class HipFluxDiT:
         if p.guidance_embed and guidance is None:
             raise ValueError("Didn't get guidance strength for guidance distilled model.")
         Li, T, C = img.shape[1], txt.shape[1], concepts.shape[1]
+        for h in () if heatmaps is None else heatmaps if isinstance(heatmaps, (list, tuple)) else [heatmaps]:
+            check_concept_count(h.norm, C)   # (before the first launch of the forward)
         self._workspace(Li, T, C, B)
         self._rope_table(img_ids, txt_ids, concept_ids, C, T)
         g = _Geom(B, C, T, Li)
@@ -861,7 +864,15 @@ class HipFluxDiT:
         ``route``: this layer's LayerRoute, which says where the attention left the output-space logits' inputs."""
         ATT, QPRE = self.ATT, self.QPRE
         B, C, Li, oT, oI = g.B, g.C, g.L, g.oT, g.oI
-        fused = self.fused_heatmaps and ops.heatmap_fused_fits(C, self.hidden_size)
+        # one launch per layer: ca_heatmap_fused up to 8 concepts, ca_heatmap_many for 9 .. 32 (the concept vectors through
+        # LDS in chunks; its image vectors are the fp32 rows ATTI32, as use_part needs C <= 8); the three-launch form
+        # otherwise (fused_heatmaps = False, the parity reference, or more than 32 concepts with the softmax)
+        launch = None
+        if self.fused_heatmaps and ops.heatmap_fused_fits(C, self.hidden_size):
+            launch = ops.heatmap_fused
+        elif self.fused_heatmaps and ops.heatmap_many_fits(C, self.hidden_size):
+            launch = ops.heatmap_many
+        fused = launch is not None
         launches = {}   # norm -> problems of this layer: ONE launch for all work items and both spaces
         for j in range(B if heatmaps is not None else 0):
             hm = heatmaps[j]
@@ -883,12 +894,12 @@ class HipFluxDiT:
                         None if table is None else table[li], hm.per_layer_weight,
                         part=self.PART[j] if img_vec is None else None))
                     continue
-                # the three-launch form (more than 8 concepts, or fused_heatmaps = False: the parity reference)
+                # the three-launch form (more than 32 concepts, or fused_heatmaps = False: the parity reference)
                 ops.heatmap_logits(img_vec, con_vec, self.LOGITS[:C])
                 if acc is not None:
-                    ops.heatmap_softmax_accumulate(self.LOGITS[:C], acc, hm.weight, hm.norm)
+                    ops.heatmap_norm_accumulate(self.LOGITS[:C], acc, hm.weight, hm.norm)
                 if table is not None:
-                    ops.heatmap_softmax_accumulate(self.LOGITS[:C], table[li], hm.per_layer_weight, hm.norm)
+                    ops.heatmap_norm_accumulate(self.LOGITS[:C], table[li], hm.per_layer_weight, hm.norm)
         for norm, probs in launches.items():
             # one launch per norm; problems that name an accumulator already in the launch (two requests sharing a
             # tensor) start a new one: within a launch the updates are unordered read-modify-writes
@@ -897,7 +908,7 @@ class HipFluxDiT:
                 ptrs = set() if pr is None else {t.data_ptr() for t in (pr.acc, pr.acc2) if t is not None}
                 if pr is None or len(batch) == L.HEATMAP_MAX_PROBLEMS or (ptrs & seen):
                     if batch:
-                        ops.heatmap_fused(batch, norm)
+                        launch(batch, norm)
                     batch, seen = [], set()
                 if pr is not None:
                     batch.append(pr)

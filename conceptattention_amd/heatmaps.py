@@ -28,6 +28,15 @@ def resolve_norm(softmax: bool, attention_norm: str) -> int:
     raise ValueError(f"Unknown attention_norm={attention_norm}")
 
 
+def check_concept_count(norm: int, n_concepts: int) -> None:
+    """Refuse what no route can serve BEFORE anything is launched: the sparse norms sort a patch's logits in registers,
+    at most L.HEATMAP_MAX_CONCEPTS of them (the softmax has no bound: beyond the limit it takes the three-launch form)."""
+    if norm != L.NORM_SOFTMAX and n_concepts > L.HEATMAP_MAX_CONCEPTS:
+        name = {v: k for k, v in L.NORMS.items()}[norm]
+        raise ValueError(f"{n_concepts} concepts with attention_norm={name!r}: the sparse norms take at most "
+                         f"{L.HEATMAP_MAX_CONCEPTS} concepts (softmax has no limit)")
+
+
 def linear_normalization(x: torch.Tensor, dim: int) -> torch.Tensor:
     """concept_attention/utils.py:35-44 (host-side, tiny: C x dim)."""
     x_min = torch.min(x, dim=dim, keepdim=True)[0]
@@ -59,6 +68,7 @@ def compute_heatmaps_from_vectors(image_vectors, concept_vectors, layer_indices,
     ts = [int(t) for t in timesteps]
     ls = [int(l) for l in layer_indices]
     n_patches, C = image_vectors.shape[3], concept_vectors.shape[3]
+    check_concept_count(norm, C)
     dev = image_vectors.device
     acc = torch.zeros(C, n_patches, device=dev, dtype=torch.float32)
     logits = torch.empty(C, n_patches, device=dev, dtype=torch.float32)
@@ -68,7 +78,7 @@ def compute_heatmaps_from_vectors(image_vectors, concept_vectors, layer_indices,
             iv = image_vectors[t, l, 0].to(torch.bfloat16).contiguous()
             cv = concept_vectors[t, l, 0].to(torch.bfloat16).contiguous()
             ops.heatmap_logits(iv, cv, logits)
-            ops.heatmap_softmax_accumulate(logits, acc, w, norm)
+            ops.heatmap_norm_accumulate(logits, acc, w, norm)
     side = int(round(math.sqrt(n_patches)))
     if side * side != n_patches:
         raise ValueError(f"{n_patches} patches do not form a square grid")

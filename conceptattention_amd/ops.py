@@ -517,7 +517,18 @@ def heatmap_logits(img_vec, con_vec, logits) -> None:
 
 
 def heatmap_softmax_accumulate(logits, acc, weight: float, norm: int = L.NORM_SOFTMAX) -> None:
-    """acc += weight * norm_over_concepts(logits); norm: L.NORM_SOFTMAX | NORM_SPARSEMAX | NORM_ENTMAX15."""
+    """acc += weight * norm_over_concepts(logits); norm: L.NORM_SOFTMAX | NORM_SPARSEMAX | NORM_ENTMAX15.  The sparse norms
+    with at most 16 concepts, as ever (a ValueError beyond); ``heatmap_norm_accumulate`` takes them up to 32."""
+    if norm != L.NORM_SOFTMAX and isinstance(logits, torch.Tensor) and logits.dim() == 2 and \
+            logits.shape[0] > L.HEATMAP_SPARSE_MAX_3LAUNCH:
+        raise ValueError(f"heatmap_softmax_accumulate: C = {logits.shape[0]}; the sparse norms need C <= "
+                         f"{L.HEATMAP_SPARSE_MAX_3LAUNCH} here (heatmap_norm_accumulate: C <= {L.HEATMAP_MAX_CONCEPTS})")
+    heatmap_norm_accumulate(logits, acc, weight, norm)
+
+
+def heatmap_norm_accumulate(logits, acc, weight: float, norm: int = L.NORM_SOFTMAX) -> None:
+    """acc += weight * norm_over_concepts(logits), the weighting launch of the three-launch form: the softmax for any number
+    of concepts, the sparse norms for up to L.HEATMAP_MAX_CONCEPTS = 32 (ca_heatmap_norm_accumulate)."""
     lib = L.load()
     _chk(logits, torch.float32, "logits"), _chk(acc, torch.float32, "acc")
     if logits.shape != acc.shape or not logits.is_contiguous() or not acc.is_contiguous():
@@ -554,32 +565,33 @@ def heatmap_fused_fits(C: int, dim: int) -> bool:
     return 1 <= C <= 8 and dim % 8 == 0 and 8 <= dim <= 4096
 
 
-def heatmap_fused(problems: Sequence[Heatmap], norm: int = L.NORM_SOFTMAX) -> None:
-    """All heat-map updates of one layer in ONE launch (ca_heatmap_fused): bit-identical to heatmap_logits followed by
-    heatmap_softmax_accumulate per problem and accumulator."""
+def _heatmap_launch(FN: str, problems: Sequence[Heatmap], norm: int, parts: bool) -> None:
+    """The argument checks and the launch of heatmap_fused / heatmap_many (``parts``: Heatmap.part is accepted)."""
     lib = L.load()
     if not 1 <= len(problems) <= L.HEATMAP_MAX_PROBLEMS:
-        raise ValueError(f"heatmap_fused: 1..{L.HEATMAP_MAX_PROBLEMS} problems per launch")
+        raise ValueError(f"{FN}: 1..{L.HEATMAP_MAX_PROBLEMS} problems per launch")
     arr = (L.HeatmapProblem * len(problems))()
     some = next((t for h in problems for t in (h.acc, h.acc2, h.logits) if t is not None), None)
     if some is None:
-        raise ValueError("heatmap_fused: every problem needs acc, acc2 or logits")
+        raise ValueError(f"{FN}: every problem needs acc, acc2 or logits")
     Cc, Lp = some.shape
     vec = next((h for h in problems if h.part is None), None)
     dim = 8 if vec is None else vec.img_vec.shape[1]
     for i, h in enumerate(problems):
         p = arr[i]
         if h.part is not None:
+            if not parts:
+                raise ValueError(f"{FN}[{i}]: per-head partial logits (part) have 8 slots: heatmap_fused takes them")
             _chk(h.part, torch.float32, "part")
             if h.part.dim() != 3 or tuple(h.part.shape[1:]) != (Lp, 8) or not h.part.is_contiguous():
-                raise ValueError(f"heatmap_fused[{i}]: part must be contiguous fp32 [heads, L, 8]")
+                raise ValueError(f"{FN}[{i}]: part must be contiguous fp32 [heads, L, 8]")
             p.img_vec, p.ldi, p.img_f32 = h.part.data_ptr(), _i32(h.part.shape[0], "heads"), 2
         else:
             if h.img_vec.dtype not in (torch.bfloat16, torch.float32) or h.con_vec.dtype not in (torch.bfloat16, torch.float32):
-                raise ValueError(f"heatmap_fused[{i}]: img_vec and con_vec must be bf16 or fp32")
+                raise ValueError(f"{FN}[{i}]: img_vec and con_vec must be bf16 or fp32")
             _chk(h.img_vec, h.img_vec.dtype, "img_vec"), _chk(h.con_vec, h.con_vec.dtype, "con_vec")
             if tuple(h.img_vec.shape) != (Lp, dim) or tuple(h.con_vec.shape) != (Cc, dim):
-                raise ValueError(f"heatmap_fused[{i}]: all problems of a launch share L, C and dim")
+                raise ValueError(f"{FN}[{i}]: all problems of a launch share L, C and dim")
             p.img_vec, p.con_vec = h.img_vec.data_ptr(), h.con_vec.data_ptr()
             p.ldi, p.ldc = _i32(h.img_vec.stride(0), "ldi"), _i32(h.con_vec.stride(0), "ldc")
             p.img_f32, p.con_f32 = int(h.img_vec.dtype == torch.float32), int(h.con_vec.dtype == torch.float32)
@@ -588,11 +600,29 @@ def heatmap_fused(problems: Sequence[Heatmap], norm: int = L.NORM_SOFTMAX) -> No
             if t is not None:
                 _chk(t, torch.float32, name)
                 if tuple(t.shape) != (Cc, Lp) or not t.is_contiguous():
-                    raise ValueError(f"heatmap_fused[{i}]: {name} must be contiguous fp32 [C,L]")
+                    raise ValueError(f"{FN}[{i}]: {name} must be contiguous fp32 [C,L]")
                 setattr(p, name, t.data_ptr())
         p.weight, p.weight2 = float(h.weight), float(h.weight2)
-    L.check(lib.ca_heatmap_fused(arr, len(problems), _i32(Lp, "L"), _i32(Cc, "C"), _i32(dim, "dim"), int(norm), _stream()),
-            "ca_heatmap_fused")
+    entry = getattr(lib, "ca_" + FN)
+    L.check(entry(arr, len(problems), _i32(Lp, "L"), _i32(Cc, "C"), _i32(dim, "dim"), int(norm), _stream()), "ca_" + FN)
+
+
+def heatmap_fused(problems: Sequence[Heatmap], norm: int = L.NORM_SOFTMAX) -> None:
+    """All heat-map updates of one layer in ONE launch (ca_heatmap_fused): bit-identical to heatmap_logits followed by
+    heatmap_softmax_accumulate per problem and accumulator."""
+    _heatmap_launch("heatmap_fused", problems, norm, parts=True)
+
+
+def heatmap_many_fits(C: int, dim: int) -> bool:
+    """Does ca_heatmap_many take this geometry (the concept vectors through LDS in chunks of at most 8 rows)?"""
+    return 1 <= C <= L.HEATMAP_MAX_CONCEPTS and dim % 8 == 0 and 8 <= dim <= 4096
+
+
+def heatmap_many(problems: Sequence[Heatmap], norm: int = L.NORM_SOFTMAX) -> None:
+    """heatmap_fused for up to L.HEATMAP_MAX_CONCEPTS concepts, still ONE launch per layer (ca_heatmap_many): bit-identical
+    to heatmap_logits followed by heatmap_norm_accumulate per problem and accumulator, and to heatmap_fused at C <= 8.
+    Vector problems only (no Heatmap.part)."""
+    _heatmap_launch("heatmap_many", problems, norm, parts=False)
 
 
 def axpy(x, y, a: float) -> None:

@@ -24,7 +24,7 @@ import torch
 
 from . import _lib, ops, sampling
 from .flux_dit import HeatmapRequest, HipFluxDiT, on_own_device
-from .heatmaps import compute_heatmaps_from_vectors, resolve_norm
+from .heatmaps import check_concept_count, compute_heatmaps_from_vectors, resolve_norm
 from .params import configs
 
 
@@ -241,6 +241,7 @@ class ConceptAttentionFluxPipeline:
         assert all([0 <= li < self.params.depth for li in layer_indices]), "Invalid layer index"
         assert height == width, "Height and width must be the same for now"
         norm = resolve_norm(softmax, attention_norm)  # ValueError on an unknown name, as the reference (:70-71)
+        check_concept_count(norm, len(concepts))
         on_device = self._device_renderer(heatmap_renderer, heatmap_size, heatmap_interpolation, overlay_alpha)
         if timesteps is None:
             timesteps = list(range(num_inference_steps))
@@ -485,6 +486,7 @@ class ConceptAttentionFluxPipeline:
         assert all([0 <= li < self.params.depth for li in layer_indices]), "Invalid layer index"
         assert height == width, "Height and width must be the same for now"
         norm = resolve_norm(softmax, attention_norm)
+        check_concept_count(norm, len(concepts))
         on_device = self._device_renderer(heatmap_renderer, heatmap_size, heatmap_interpolation, overlay_alpha)
         picture = self._input_picture(image, height, width) if on_device and overlay_alpha is not None and \
             return_pil_heatmaps else None
@@ -570,6 +572,7 @@ class ConceptAttentionFluxPipeline:
         n = len(images)
         prompts = [prompts] * n if isinstance(prompts, str) else list(prompts)
         concepts = _per_item(concepts, n, "encode_images: concepts")
+        check_concept_count(norm, max((len(c) for c in concepts), default=0))
         for name, v in (("prompts", prompts), ("noise", noise), ("vae_noise", vae_noise)):
             if v is not None and len(v) != n:
                 raise ValueError(f"encode_images: {name} has {len(v)} entries for {n} images")
@@ -654,6 +657,7 @@ class ConceptAttentionFluxPipeline:
         prompts = list(prompts)
         n = len(prompts)
         concepts = _per_item(concepts, n, "generate_images: concepts")
+        check_concept_count(norm, max((len(c) for c in concepts), default=0))
         seeds = list(range(n)) if seeds is None else list(seeds)
         for name, v in (("seeds", seeds), ("latents", latents)):
             if v is not None and len(v) != n:

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CA_VERSION 135 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
+#define CA_VERSION 136 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
                           CA_ATTN_Q_PRESCALED; .1: ca_axpy_f32, ca_split_bf16; .2: ca_attn_stats; .3: ca_gemm_problem.qk_f16,
                           ca_attn_fwd_qk16; .4: ca_qpre_finish_rope_f32; .5: ca_heatmap_fused; .6: ca_gemm_plan;
                           .7: the autoencoder kernels (conv3x3_nhwc, groupnorm_nhwc, softmax_rows_f32, affine_rows_f32);
@@ -39,7 +39,8 @@ extern "C" {
                           132: segmentation scoring on the device (seg_score);
                           133: multi-class segmentation scoring on the device (mseg_score);
                           134: sweep tables of maps scored against one label on the device (segtab_score);
-                          135: heat-map pictures on the device (heatmap_render) */
+                          135: heat-map pictures on the device (heatmap_render);
+                          136: sparse norms of heatmap_norm_accumulate up to C = 32 (CA_HEATMAP_MAX_CONCEPTS) */
 
 #define CA_OK 0
 #define CA_ERR_ARG (-1)    /* bad shape / null pointer / misalignment */
@@ -341,7 +342,7 @@ int ca_heatmap_softmax_accumulate(const float *logits, int32_t C, int32_t L, flo
  * CA_NORM_SPARSEMAX or CA_NORM_ENTMAX15.  The reference takes the latter two from the third-party `entmax`
  * package, which it neither pins nor vendors: they are implemented here from the published algorithms
  * (Martins & Astudillo 2016; Peters, Niculae & Martins 2019) and their parity with that package is UNPINNED.
- * The sparse norms need C <= 16. */
+ * The sparse norms need C <= CA_HEATMAP_MAX_CONCEPTS. */
 #define CA_NORM_SOFTMAX 0
 #define CA_NORM_SPARSEMAX 1
 #define CA_NORM_ENTMAX15 2
@@ -374,6 +375,11 @@ typedef struct {
 } ca_heatmap_problem;
 int ca_heatmap_fused(const ca_heatmap_problem *problems, int32_t n_problems, int32_t L, int32_t C, int32_t dim,
                      int32_t norm, ca_stream_t stream);
+
+/* Most concepts of one patch the heat-map kernels weight: the sparse norms of ca_heatmap_norm_accumulate, and the
+ * library's one-launch-per-layer form for more than 8 concepts (exported and bound by conceptattention_amd/_lib.py, declared
+ * in conceptattention_amd/csrc/ca_heatmap_core.h; not part of this header yet). */
+#define CA_HEATMAP_MAX_CONCEPTS 32
 
 /* Sinusoidal timestep embedding (timestep_embedding, flux/modules/layers.py:28-49):
  * out[v, 0:dim/2] = cos(time_factor*t[v]*f_i), out[v, dim/2:] = sin(...), f_i = max_period^(-i/(dim/2)). */
