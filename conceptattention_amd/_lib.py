@@ -43,6 +43,9 @@ RENDER_MAX_CELLS = 16384             # ca_heatmap_render: h * w of the maps
 RENDER_MAX_SIDE = 4096               # ca_heatmap_render: H and W of the pictures
 RENDER_LUT_ROWS = 259                # 256 colours, then under, over, bad
 RENDER_BILINEAR, RENDER_BLEND = 1, 2
+TOKMAP_MAX_PROBLEMS = 16             # ca_token_maps: problems of one launch (ops.token_maps splits longer lists)
+TOKMAP_MAX_TEXT = 512                # ca_token_maps: n0, the text key rows of a problem
+TOKMAP_QK_F16 = 1                    # ca_token_maps flags: IEEE half bits in the bf16-typed q / k rows
 ATTN_Q_PRESCALED = 0.0   # ca_attn_fwd_bf16(scale=...): the q rows already carry softmax_scale * log2(e)
 
 
@@ -78,6 +81,12 @@ class HeatmapProblem(C.Structure):
     _fields_ = [("img_vec", C.c_void_p), ("con_vec", C.c_void_p), ("acc", C.c_void_p), ("acc2", C.c_void_p),
                 ("logits", C.c_void_p), ("ldi", C.c_int32), ("ldc", C.c_int32), ("img_f32", C.c_int32),
                 ("con_f32", C.c_int32), ("weight", C.c_float), ("weight2", C.c_float)]
+
+
+class TokmapProblem(C.Structure):    # ca_tokmap_problem (csrc/ca_tokmap.h), field for field
+    _fields_ = [("q", C.c_void_p), ("k0", C.c_void_p), ("k1", C.c_void_p), ("acc", C.c_void_p), ("acc2", C.c_void_p),
+                ("lse", C.c_void_p), ("nq", C.c_int32), ("ldq", C.c_int32), ("n0", C.c_int32), ("n1", C.c_int32),
+                ("ldk", C.c_int32), ("n_tok", C.c_int32), ("weight", C.c_float), ("weight2", C.c_float)]
 
 
 class SegProblem(C.Structure):
@@ -201,10 +210,14 @@ SIGNATURES = {
                                     C.c_void_p, C.c_float, C.c_int32, C.c_void_p]),
 }
 
-# exported by the library and bound here, not declared in include/conceptattn.h yet (csrc/ca_heatmap_core.h declares it)
+# exported by the library and bound here, not declared in include/conceptattn.h yet (csrc/ca_heatmap_core.h and
+# csrc/ca_tokmap.h declare them)
 INTERNAL_SIGNATURES = {
     "ca_heatmap_many": (C.c_int, [C.POINTER(HeatmapProblem), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_void_p]),
+    "ca_token_maps": (C.c_int, [C.POINTER(TokmapProblem), C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p,
+                                C.c_int64, C.c_void_p]),
+    "ca_token_maps_workspace_bytes": (C.c_int64, [C.POINTER(TokmapProblem), C.c_int32, C.c_int32]),
 }
 
 _lib = None

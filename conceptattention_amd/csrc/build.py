@@ -10,7 +10,7 @@ PKG = os.path.dirname(HERE)
 LIB = os.path.join(PKG, "libconceptattn.so")
 SOURCES = ["ca_api.hip", "ca_gemm.hip", "ca_attn.hip", "ca_attn4.hip", "ca_rowops.hip", "ca_vae.hip", "ca_t5.hip",
            "ca_clip.hip", "ca_pixels.hip", "ca_seg.hip", "ca_mseg.hip", "ca_segtab.hip",
-           "ca_render.hip", "ca_heatmap_many.hip"]
+           "ca_render.hip", "ca_heatmap_many.hip", "ca_tokmap.hip"]
 # ca_attn4.hip owns the AGPR file by hand (literal a[...] registers in its asm statements): hipcc must never park a
 # VGPR there (its default spill target), and the emitted code is audited for it below
 EXTRA_FLAGS = {"ca_attn4.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-save-temps=obj"],
@@ -23,9 +23,10 @@ EXTRA_FLAGS = {"ca_attn4.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-save
                "ca_render.hip": ["-save-temps=obj", "-ffp-contract=off"],  # (the same)
                # (read for spills as well; contraction stays on: the unit shares ca_heatmap_core.h's arithmetic with
                # ca_rowops.hip and must round as that unit does)
-               "ca_heatmap_many.hip": ["-save-temps=obj"]}
+               "ca_heatmap_many.hip": ["-save-temps=obj"],
+               "ca_tokmap.hip": ["-save-temps=obj"]}   # (read for spills below)
 HEADERS = ["ca_common.h", "ca_attn_common.h", "ca_attn4_sched.inc", "ca_attn4_kernel.inc", "ca_seg_core.h",
-           "ca_text_core.h", "ca_heatmap_core.h"]
+           "ca_text_core.h", "ca_heatmap_core.h", "ca_tokmap.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function"]
 
@@ -130,6 +131,13 @@ def audit_heatmap_many(asm_path: str) -> None:
     chunks, and ca_heatmap_sparse_kernel<32, .> sorts 32 logits in registers: both only while every index is resolved at
     compile time.  Every kernel of the unit must report no spill and no scratch."""
     _audit_no_spill("ca_heatmap_many", asm_path)
+
+
+def audit_tokmap(asm_path: str) -> None:
+    """ca_tokmap_kernel keeps a wave's q fragments (16 registers), the next head's, a tile's staged pieces (16) and a
+    tile's 16 scores per lane in registers, all indexed by unrolled loops.  Every kernel of the unit must report no spill
+    and no scratch."""
+    _audit_no_spill("ca_tokmap", asm_path)
 
 
 def audit_sgpr_hazards(text: str) -> list:
@@ -389,6 +397,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     audit_segtab(os.path.join(HERE, "ca_segtab-hip-amdgcn-amd-amdhsa-gfx950.s"))
     audit_render(os.path.join(HERE, "ca_render-hip-amdgcn-amd-amdhsa-gfx950.s"))
     audit_heatmap_many(os.path.join(HERE, "ca_heatmap_many-hip-amdgcn-amd-amdhsa-gfx950.s"))
+    audit_tokmap(os.path.join(HERE, "ca_tokmap-hip-amdgcn-amd-amdhsa-gfx950.s"))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
     if verbose:
         print(" ".join(cmd), flush=True)

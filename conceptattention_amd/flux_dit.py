@@ -160,6 +160,12 @@ class HeatmapRequest:
     per_layer_cross: Optional[torch.Tensor] = None
     per_layer_weight: float = 1.0
     norm: int = L.NORM_SOFTMAX    # weighting across concepts: softmax | sparsemax | entmax15 (_lib.NORM_*)
+    # prompt-token maps (ops.token_maps): the probability the image rows' joint [text | image] softmax gives to the first
+    # n_tok text keys of the item, averaged over the heads, accumulated over the captured layers with ``weight`` /
+    # ``per_layer_weight`` as the concept maps are.  fp32 [n_tok, L] and / or [len(layer_indices), n_tok, L]; n_tok is
+    # their first / second dimension (at most the text length); None: no launch
+    token_space: Optional[torch.Tensor] = None
+    per_layer_token: Optional[torch.Tensor] = None
 
 
 class LayerRoute(NamedTuple):
@@ -859,6 +865,46 @@ class HipFluxDiT:
 
     forward = __call__
 
+    def _capture_token_maps(self, layer, g, NH, heatmaps, route):
+        """The prompt-token maps of a captured layer: ONE ops.token_maps launch for all items that ask for them, over the
+        q and k rows this layer's joint attention problems have just read (QKV still holds them): the attention the image
+        is made with, capture_independent_image included.  No launch when no item asks."""
+        H, T, Li, oT, oI = self.hidden_size, g.T, g.L, g.oT, g.oI
+        qs, ks = self.QKV[:, :H], self.QKV[:, H:2 * H]
+        probs = []
+        for j in range(g.B if heatmaps is not None else 0):
+            hm = heatmaps[j]
+            if layer not in hm.layer_indices or (hm.token_space is None and hm.per_layer_token is None):
+                continue
+            li = hm.layer_indices.index(layer)
+            table = None if hm.per_layer_token is None else hm.per_layer_token[li]
+            n_tok = (hm.token_space if hm.token_space is not None else table).shape[0]
+            tj, ij = slice(oT + j * T, oT + (j + 1) * T), slice(oI + j * Li, oI + (j + 1) * Li)
+            probs.append(ops.TokenMaps(qs[ij], ks[tj], ks[ij], n_tok, acc=hm.token_space, weight=hm.weight, acc2=table,
+                                       weight2=hm.per_layer_weight))
+        # (two requests that share an accumulator start a new launch, as the concept maps' do)
+        batch, seen = [], set()
+        for pr in probs + [None]:
+            ptrs = set() if pr is None else {t.data_ptr() for t in (pr.acc, pr.acc2) if t is not None}
+            if pr is None or (ptrs & seen):
+                if batch:
+                    ops.token_maps(batch, NH, 1.0, qk_f16=route.qk16, workspace=self._token_maps_workspace(batch, NH))
+                batch, seen = [], set()
+            if pr is not None:
+                batch.append(pr)
+                seen |= ptrs
+
+    def _token_maps_workspace(self, probs, NH):
+        """ops.token_maps' scratch memory: a model buffer allocated on first use and grown on demand (None while the
+        kernel needs none)."""
+        need = ops.token_maps_workspace_bytes(probs, NH)
+        if need == 0:
+            return None
+        ws = getattr(self, "_tokmap_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._tokmap_ws = torch.empty(need, device=self.device, dtype=torch.uint8)
+        return ws
+
     def _capture(self, out, layer, g, NH, return_vectors, heatmaps, route):
         """Dict capture (modified_double_stream_block.py:185-191) and/or fused heat-map update, per work item;
         ``route``: this layer's LayerRoute, which says where the attention left the output-space logits' inputs."""
@@ -913,6 +959,7 @@ class HipFluxDiT:
                 if pr is not None:
                     batch.append(pr)
                     seen |= ptrs
+        self._capture_token_maps(layer, g, NH, heatmaps, route)
         if return_vectors:
             H = self.hidden_size
             cf = torch.contiguous_format

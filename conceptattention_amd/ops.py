@@ -625,6 +625,111 @@ def heatmap_many(problems: Sequence[Heatmap], norm: int = L.NORM_SOFTMAX) -> Non
     _heatmap_launch("heatmap_many", problems, norm, parts=False)
 
 
+@dataclass
+class TokenMaps:
+    """One problem of a prompt-token map launch (ca_token_maps): the probability that the joint softmax over the keys
+    [k0 | k1] of every query row of ``q`` gives to the first ``n_tok`` rows of ``k0``, averaged over the heads:
+    acc += weight * map and / or acc2 += weight2 * map.  q / k0 / k1 bf16 2-D views [rows, num_heads*128] (row stride free,
+    k0 and k1 share theirs), acc / acc2 fp32 [n_tok, nq] contiguous, ``lse`` (optional output) fp32 [num_heads, nq]
+    contiguous: the natural-log sum of exponentials of every head's row."""
+    q: torch.Tensor
+    k0: torch.Tensor
+    k1: Optional[torch.Tensor] = None
+    n_tok: Optional[int] = None             # None: all rows of k0
+    acc: Optional[torch.Tensor] = None
+    weight: float = 0.0
+    acc2: Optional[torch.Tensor] = None
+    weight2: float = 0.0
+    lse: Optional[torch.Tensor] = None
+
+
+def _token_maps_array(problems: Sequence[TokenMaps], num_heads: int):
+    """ops.token_maps' argument checks (no device needed for the shape rules) and the problem array."""
+    FN = "token_maps"
+    width = num_heads * 128
+    arr = (L.TokmapProblem * len(problems))()
+    seen = {}
+    for i, t in enumerate(problems):
+        _chk(t.q, torch.bfloat16, "q"), _chk(t.k0, torch.bfloat16, "k0")
+        k1 = t.k1 if t.k1 is not None and t.k1.shape[0] > 0 else None
+        if k1 is not None:
+            _chk(k1, torch.bfloat16, "k1")
+        for n, x in (("q", t.q), ("k0", t.k0), ("k1", k1)):
+            if x is not None and (x.dim() != 2 or x.shape[1] != width):
+                raise ValueError(f"{FN}[{i}]: {n} must be 2-D with num_heads*128 = {width} columns, got {tuple(x.shape)}")
+        if k1 is not None and k1.stride(0) != t.k0.stride(0):
+            raise ValueError(f"{FN}[{i}]: both key segments must share one row stride")
+        nq, n0 = t.q.shape[0], t.k0.shape[0]
+        n_tok = n0 if t.n_tok is None else int(t.n_tok)
+        if nq < 1 or not 1 <= n_tok <= n0 <= L.TOKMAP_MAX_TEXT:
+            raise ValueError(f"{FN}[{i}]: need nq >= 1 and 1 <= n_tok <= n0 <= {L.TOKMAP_MAX_TEXT}, got nq = {nq}, "
+                             f"n_tok = {n_tok}, n0 = {n0}")
+        if t.acc is None and t.acc2 is None:
+            raise ValueError(f"{FN}[{i}]: every problem needs acc or acc2")
+        p = arr[i]
+        for name, shape in (("acc", (n_tok, nq)), ("acc2", (n_tok, nq)), ("lse", (num_heads, nq))):
+            x = getattr(t, name)
+            if x is None:
+                continue
+            _chk(x, torch.float32, name)
+            if tuple(x.shape) != shape or not x.is_contiguous():
+                raise ValueError(f"{FN}[{i}]: {name} must be contiguous fp32 {list(shape)}, got {tuple(x.shape)}")
+            if name != "lse":
+                if x.data_ptr() in seen:
+                    raise ValueError(f"{FN}[{i}]: {name} is also an accumulator of problem {seen[x.data_ptr()]} of this "
+                                     "call (their updates would race)")
+                seen[x.data_ptr()] = i
+            setattr(p, name, x.data_ptr())
+        p.q, p.k0, p.k1 = t.q.data_ptr(), t.k0.data_ptr(), _ptr(k1)
+        p.nq, p.n0, p.n1, p.n_tok = _i32(nq, "nq"), n0, _i32(0 if k1 is None else k1.shape[0], "n1"), n_tok
+        p.ldq, p.ldk = _i32(t.q.stride(0), "ldq"), _i32(t.k0.stride(0), "ldk")
+        p.weight, p.weight2 = float(t.weight), float(t.weight2)
+    return arr
+
+
+def token_maps_workspace_bytes(problems: Sequence[TokenMaps], num_heads: int) -> int:
+    """The scratch memory one ops.token_maps call over these problems needs (the largest of its launches)."""
+    lib = L.load()
+    arr = _token_maps_array(problems, num_heads)
+    need = 0
+    for s in range(0, len(problems), L.TOKMAP_MAX_PROBLEMS):
+        n = min(L.TOKMAP_MAX_PROBLEMS, len(problems) - s)
+        sub = (L.TokmapProblem * n).from_buffer(arr, s * C.sizeof(L.TokmapProblem))
+        rc = lib.ca_token_maps_workspace_bytes(sub, n, _i32(num_heads, "num_heads"))
+        if rc < 0:
+            L.check(int(rc), "ca_token_maps_workspace_bytes")
+        need = max(need, int(rc))
+    return need
+
+
+def token_maps(problems: Sequence[TokenMaps], num_heads: int, scale_log2: float = 1.0, qk_f16: bool = False,
+               workspace: Optional[torch.Tensor] = None) -> None:
+    """Prompt-token attention maps (ca_token_maps), up to L.TOKMAP_MAX_PROBLEMS problems per launch (longer lists are
+    split, in order).  ``scale_log2``: 1.0 for q rows that already carry softmax_scale * log2(e) (the model's), otherwise
+    softmax_scale * log2(e).  ``qk_f16``: the q and k rows hold IEEE half bits in their bf16-typed tensors (Gemm.qk_f16).
+    ``workspace``: a uint8 device tensor of at least token_maps_workspace_bytes() bytes (None when that is 0)."""
+    lib = L.load()
+    if len(problems) < 1:
+        raise ValueError("token_maps: at least one problem")
+    if not num_heads >= 1:
+        raise ValueError("token_maps: num_heads must be >= 1")
+    if not math.isfinite(scale_log2):
+        raise ValueError("token_maps: scale_log2 must be finite")
+    arr = _token_maps_array(problems, num_heads)
+    ws_ptr, ws_bytes = None, 0
+    if workspace is not None:
+        _chk(workspace, torch.uint8, "workspace")
+        if not workspace.is_contiguous():
+            raise ValueError("token_maps: workspace must be contiguous")
+        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel()
+    flags = L.TOKMAP_QK_F16 if qk_f16 else 0
+    for s in range(0, len(problems), L.TOKMAP_MAX_PROBLEMS):
+        n = min(L.TOKMAP_MAX_PROBLEMS, len(problems) - s)
+        sub = (L.TokmapProblem * n).from_buffer(arr, s * C.sizeof(L.TokmapProblem))
+        L.check(lib.ca_token_maps(sub, n, _i32(num_heads, "num_heads"), float(scale_log2), flags, ws_ptr, ws_bytes,
+                                  _stream()), "ca_token_maps")
+
+
 def axpy(x, y, a: float) -> None:
     """x += a*y (bf16, fp32 math)."""
     lib = L.load()

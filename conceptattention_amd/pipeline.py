@@ -34,6 +34,11 @@ class ConceptAttentionPipelineOutput:
     image: object  # PIL.Image.Image | np.ndarray
     concept_heatmaps: list
     cross_attention_maps: list
+    # prompt-token maps (token_maps=True or an int): one map per prompt token, the attention the image tokens give that
+    # token's key in the captured double blocks (mean over heads, layers and steps; DAAM), and the tokenizer's strings
+    # (None when the maps were asked for by count)
+    token_heatmaps: Optional[list] = None
+    tokens: Optional[list] = None
 
 
 class SyntheticTextEncoder:
@@ -138,14 +143,58 @@ class ConceptAttentionFluxPipeline:
     def _embed(self, prompt: str, concepts: Sequence[str]):
         return self.flux_generator.embed(prompt, concepts)
 
-    def _finish(self, image, concept_heatmaps, cross_attention_maps, return_pil_heatmaps, cmap):
+    def _finish(self, image, concept_heatmaps, cross_attention_maps, return_pil_heatmaps, cmap, token_maps=None,
+                tokens=None):
+        """``token_maps``: the item's prompt-token maps fp32 [n_tok, side, side] on the device, or None."""
         concept_heatmaps = concept_heatmaps.to(torch.float32).detach().cpu().numpy()[0]
         cross_attention_maps = cross_attention_maps.to(torch.float32).detach().cpu().numpy()[0]
+        if token_maps is not None:
+            token_maps = token_maps.to(torch.float32).detach().cpu().numpy()
         if return_pil_heatmaps:
             concept_heatmaps = colorize_heatmaps(concept_heatmaps, cmap)
             cross_attention_maps = colorize_heatmaps(cross_attention_maps, cmap)
+            if token_maps is not None:                   # (global min-max over the prompt's tokens)
+                token_maps = colorize_heatmaps(token_maps, cmap)
         return ConceptAttentionPipelineOutput(image=image, concept_heatmaps=concept_heatmaps,
-                                              cross_attention_maps=cross_attention_maps)
+                                              cross_attention_maps=cross_attention_maps, token_heatmaps=token_maps,
+                                              tokens=tokens)
+
+    # ------------------------------------------------------------------ prompt-token maps
+    def _token_request(self, prompt: str, token_maps):
+        """(n_tok, tokens) of a call's ``token_maps`` argument: None / False -> (0, None); True -> the tokenizer's tokens of
+        the prompt without the end-of-string token (DAAM keeps maps[:len(tokens)]), truncated to the text length; an int n
+        -> the first n text rows, tokens None (the route for a text encoder without a tokenizer)."""
+        if token_maps is None or token_maps is False:
+            return 0, None
+        T = self._text_length()
+        if token_maps is True:
+            tokenizer = getattr(self.text_encoder, "tokenizer", None)
+            if tokenizer is None or not hasattr(tokenizer, "tokenize"):
+                raise ValueError("token_maps=True needs a text encoder whose tokenizer has .tokenize (text_encoder="
+                                 "\"synthetic-t5\", \"synthetic-t5-clip\" or a HipTextEncoder); pass an int n for the first n "
+                                 "text rows")
+            tokens = list(tokenizer.tokenize(prompt))[:T]
+            if not tokens:
+                raise ValueError("token_maps=True: the prompt has no tokens")
+            return len(tokens), tokens
+        n = int(token_maps)
+        if not 1 <= n <= min(T, _lib.TOKMAP_MAX_TEXT):
+            raise ValueError(f"token_maps = {n}: 1 .. {min(T, _lib.TOKMAP_MAX_TEXT)} (the text length) rows")
+        return n, None
+
+    def _token_accumulators(self, n_toks, n_patches: int) -> Optional[list]:
+        """One fp32 [n_tok, n_patches] accumulator per item (None for an item that asks for none); None if no item asks."""
+        if not any(n_toks):
+            return None
+        return [torch.zeros(n, n_patches, device=self.device) if n else None for n in n_toks]
+
+    @staticmethod
+    def _token_views(token_acc, k: int):
+        """Item k's accumulator as [n_tok, side, side], or None."""
+        if token_acc is None or token_acc[k] is None:
+            return None
+        side = int(round(token_acc[k].shape[1] ** 0.5))
+        return token_acc[k].view(-1, side, side)
 
     @staticmethod
     def _device_renderer(heatmap_renderer, heatmap_size, heatmap_interpolation, overlay_alpha) -> bool:
@@ -173,11 +222,14 @@ class ConceptAttentionFluxPipeline:
         return torch.from_numpy(np.ascontiguousarray(arr)).to(self.device)
 
     def _finish_device(self, images, concept_heatmaps, cross_attention_maps, cmap, heatmap_size=None,
-                       heatmap_interpolation="nearest", overlay_alpha=None, pictures=None) -> list:
+                       heatmap_interpolation="nearest", overlay_alpha=None, pictures=None, token_maps=None,
+                       tokens=None) -> list:
         """``_finish`` with PIL heat maps for the B items of a chunk, the pictures made on the device (ops.heatmap_render):
         one group per item and space (the reference's "global min-max over ALL concepts"), one launch, one download of
         bytes.  Without the three options the bytes are those of ``colorize_heatmaps``.  ``pictures``: with
-        ``overlay_alpha``, the uint8 [H, W, 3] device tensor of every item that the maps are laid over."""
+        ``overlay_alpha``, the uint8 [H, W, 3] device tensor of every item that the maps are laid over.  ``token_maps``:
+        per item, the prompt-token maps [n_tok, side, side] or None -- one more group per item in the same launch;
+        ``tokens``: per item, the token strings."""
         import PIL.Image
         ho = concept_heatmaps.to(torch.float32).contiguous()
         hc = cross_attention_maps.to(torch.float32).contiguous()
@@ -190,15 +242,30 @@ class ConceptAttentionFluxPipeline:
         if overlay_alpha is not None and any(tuple(p.shape[:2]) != (H, W) for p in pictures):
             raise ValueError(f"overlay_alpha: heatmap_size = {H} x {W} is not the picture's size "
                              f"{tuple(pictures[0].shape[:2])}")
-        buf = torch.empty(2 * B, C, H, W, 3, dtype=torch.uint8, device=self.device)
-        ops.heatmap_render([ho[k] for k in range(B)] + [hc[k] for k in range(B)], ops.colormap_lut(cmap, self.device),
+        with_tok = [k for k in range(B) if token_maps is not None and token_maps[k] is not None]
+        n_tok = [token_maps[k].shape[0] for k in with_tok]
+        # one allocation: the 2 B groups of C planes, then the token groups (n_tok planes each)
+        flat = torch.empty((2 * B * C + sum(n_tok)) * H * W * 3, dtype=torch.uint8, device=self.device)
+        buf = flat[:2 * B * C * H * W * 3].view(2 * B, C, H, W, 3)
+        tok_out, o = [], 2 * B * C
+        for n in n_tok:
+            tok_out.append(flat[o * H * W * 3:(o + n) * H * W * 3].view(n, H, W, 3))
+            o += n
+        ops.heatmap_render([ho[k] for k in range(B)] + [hc[k] for k in range(B)] +
+                           [token_maps[k].to(torch.float32).contiguous() for k in with_tok],
+                           ops.colormap_lut(cmap, self.device),
                            size=(H, W), bilinear=heatmap_interpolation == "bilinear",
-                           images=None if overlay_alpha is None else list(pictures) * 2, alpha=overlay_alpha,
-                           out=list(buf))
-        host = buf.cpu().numpy()                       # the one download of the chunk
+                           images=None if overlay_alpha is None else list(pictures) * 2 + [pictures[k] for k in with_tok],
+                           alpha=overlay_alpha, out=list(buf) + tok_out)
+        host = flat.cpu().numpy()                      # the one download of the chunk
+        planes = host.reshape(-1, H, W, 3)
+        first = {k: 2 * B * C + sum(n_tok[:i]) for i, k in enumerate(with_tok)}
         return [ConceptAttentionPipelineOutput(
-            image=images[k], concept_heatmaps=[PIL.Image.fromarray(host[k, c]) for c in range(C)],
-            cross_attention_maps=[PIL.Image.fromarray(host[B + k, c]) for c in range(C)]) for k in range(B)]
+            image=images[k], concept_heatmaps=[PIL.Image.fromarray(planes[k * C + c]) for c in range(C)],
+            cross_attention_maps=[PIL.Image.fromarray(planes[(B + k) * C + c]) for c in range(C)],
+            token_heatmaps=[PIL.Image.fromarray(planes[first[k] + t]) for t in range(token_maps[k].shape[0])]
+            if k in first else None,
+            tokens=None if tokens is None else tokens[k]) for k in range(B)]
 
     def _decode(self, x: torch.Tensor, height: int, width: int):
         return self.flux_generator.decode(x, height, width)
@@ -230,33 +297,43 @@ class ConceptAttentionFluxPipeline:
                        guidance: float = 0.0, timesteps=None, softmax: bool = True,
                        attention_norm: str = "sparsemax", cmap="plasma", latent: Optional[torch.Tensor] = None,
                        fused: bool = True, heatmap_renderer: str = "host", heatmap_size=None,
-                       heatmap_interpolation: str = "nearest", overlay_alpha=None) -> ConceptAttentionPipelineOutput:
+                       heatmap_interpolation: str = "nearest", overlay_alpha=None,
+                       token_maps=None) -> ConceptAttentionPipelineOutput:
         """``latent`` (1,16,h/8,w/8) overrides get_noise (device RNG differs between platforms);
         ``fused=False`` takes the reference's route (stack the per-layer vectors, then reduce).
         ``heatmap_renderer="device"`` makes the PIL heat maps on the device (ops.heatmap_render; the same bytes as
         "host", one download of bytes); only with it: ``heatmap_size`` (an int or (H, W)), ``heatmap_interpolation``
         ("nearest" or "bilinear") and ``overlay_alpha`` (the maps blended over the decoded picture with that weight,
-        which needs the HIP autoencoder)."""
+        which needs the HIP autoencoder).
+        ``token_maps``: True -> ``token_heatmaps`` holds one map per token of the prompt (``tokens``: the tokenizer's
+        strings, the end-of-string token excluded): the attention the image tokens give that token's key in the double
+        blocks ``layer_indices``, mean over heads, layers and ``timesteps`` (DAAM; ops.token_maps); an int n -> the first
+        n text rows, ``tokens`` None.  Needs the fused route."""
         assert return_cross_attention is False, "Not supported yet"
         assert all([0 <= li < self.params.depth for li in layer_indices]), "Invalid layer index"
         assert height == width, "Height and width must be the same for now"
         norm = resolve_norm(softmax, attention_norm)  # ValueError on an unknown name, as the reference (:70-71)
         check_concept_count(norm, len(concepts))
         on_device = self._device_renderer(heatmap_renderer, heatmap_size, heatmap_interpolation, overlay_alpha)
+        n_tok, tokens = self._token_request(prompt, token_maps)
+        if n_tok and not fused:
+            raise ValueError("token_maps needs the fused route (fused=True)")
         if timesteps is None:
             timesteps = list(range(num_inference_steps))
         x = latent if latent is not None else sampling.get_noise(1, height, width, self.device, torch.bfloat16, seed)
         txt, vec, con, con_ids, con_vec = self._embed(prompt, concepts)
+        token_acc = self._token_accumulators([n_tok], (x.shape[-1] // 2) * (x.shape[-2] // 2))
         img, concept_heatmaps, cross_attention_maps = self.generate_on_device(
             x, txt, vec, con, layer_indices=layer_indices, num_inference_steps=num_inference_steps,
-            guidance=guidance, timesteps=timesteps, fused=fused, norm=norm)
+            guidance=guidance, timesteps=timesteps, fused=fused, norm=norm, token_acc=token_acc)
+        tok = self._token_views(token_acc, 0)
         if on_device and return_pil_heatmaps:
             images, pix = self._decode_with_bytes(img, height, width) if overlay_alpha is not None else \
                 ([self._decode(img, height, width)], None)
             return self._finish_device(images, concept_heatmaps, cross_attention_maps, cmap, heatmap_size,
-                                       heatmap_interpolation, overlay_alpha, pix)[0]
+                                       heatmap_interpolation, overlay_alpha, pix, [tok], [tokens])[0]
         image = self._decode(img, height, width)
-        return self._finish(image, concept_heatmaps, cross_attention_maps, return_pil_heatmaps, cmap)
+        return self._finish(image, concept_heatmaps, cross_attention_maps, return_pil_heatmaps, cmap, tok, tokens)
 
     @torch.no_grad()
     @on_own_device
@@ -314,9 +391,11 @@ class ConceptAttentionFluxPipeline:
     @on_own_device
     def generate_on_device(self, latent, txt, vec, concept_embeddings, layer_indices=list(range(15, 19)),
                            num_inference_steps: int = 4, guidance: float = 0.0, timesteps=None, fused: bool = True,
-                           norm: int = 0):
+                           norm: int = 0, token_acc=None):
+        """``token_acc``: per item, an fp32 [n_tok, patches] accumulator of the caller's for the prompt-token maps (zeroed
+        by the caller; None, or None for an item: no token maps).  The return tuple is the same with and without."""
         gen = self._generate_steps(self.model, latent, txt, vec, concept_embeddings, layer_indices,
-                                   num_inference_steps, guidance, timesteps, fused, norm)
+                                   num_inference_steps, guidance, timesteps, fused, norm, token_acc)
         while True:
             try:
                 next(gen)
@@ -325,7 +404,7 @@ class ConceptAttentionFluxPipeline:
 
     def _generate_steps(self, model, latent, txt, vec, concept_embeddings, layer_indices=list(range(15, 19)),
                         num_inference_steps: int = 4, guidance: float = 0.0, timesteps=None, fused: bool = True,
-                        norm: int = 0):
+                        norm: int = 0, token_acc=None):
         """The device-resident core of generate_image for B work items at once (B = 1 from the public API):
         latent (B,16,h/8,w/8), txt (B,T,4096), vec (B,768), concept_embeddings (B,C,4096) already in HBM ->
         (final latent tokens, concept heat maps fp32 [B,C,side,side], cross-attention maps fp32
@@ -355,22 +434,28 @@ class ConceptAttentionFluxPipeline:
         try:
             return (yield from self._generate_steps_inner(model, x, inp, con, con_ids, con_vec, schedule, ts, ls,
                                                           C, n_patches, guidance, layer_indices, timesteps, fused,
-                                                          norm))
+                                                          norm, token_acc))
         finally:
             model.keep_bf16_layers = keep_before  # this call's choice does not leak into later sweeps / encodes
 
     def _generate_steps_inner(self, model, x, inp, con, con_ids, con_vec, schedule, ts, ls, C, n_patches, guidance,
-                              layer_indices, timesteps, fused, norm=0):
+                              layer_indices, timesteps, fused, norm=0, token_acc=None):
         names = {v: k for k, v in _lib.NORMS.items()}
         # repeated indices weigh a (step, layer) pair repeatedly in the reference's fancy indexing
         # (concept_attention_pipeline.py:76-77); the fused accumulation covers distinct pairs only
         if fused and (len(set(ts)) != len(ts) or len(set(ls)) != len(ls)):
             fused = False
         B = x.shape[0]
+        if token_acc is not None and any(t is not None for t in token_acc):
+            if not fused:
+                raise ValueError("token_maps needs the fused route (fused=True, distinct timesteps and layer indices)")
+            if len(token_acc) != B:
+                raise ValueError("token_acc: one accumulator (or None) per work item")
         if fused:
             acc_o = torch.zeros(B, C, n_patches, device=self.device)
             acc_c = torch.zeros(B, C, n_patches, device=self.device)
-            reqs = [HeatmapRequest(tuple(ls), 1.0 / (len(ts) * len(ls)), acc_o[j], acc_c[j], norm=norm)
+            reqs = [HeatmapRequest(tuple(ls), 1.0 / (len(ts) * len(ls)), acc_o[j], acc_c[j], norm=norm,
+                                   token_space=None if token_acc is None else token_acc[j])
                     for j in range(B)]
             img, _, _ = yield from sampling.denoise_steps(
                 model, **inp, timesteps=schedule, guidance=guidance, concepts=con, concept_ids=con_ids,
@@ -473,7 +558,7 @@ class ConceptAttentionFluxPipeline:
                      attention_norm: str = "sparsemax", softmax=True,
                      joint_attention_kwargs=None, noise=None, vae_noise=None, heatmap_renderer: str = "host",
                      heatmap_size=None, heatmap_interpolation: str = "nearest",
-                     overlay_alpha=None) -> ConceptAttentionPipelineOutput:
+                     overlay_alpha=None, token_maps=None) -> ConceptAttentionPipelineOutput:
         """``image``: a latent tensor (1,16,h/8,w/8), or a PIL image when the pipeline has an autoencoder
         (``autoencoder="synthetic"``, a ``.safetensors`` path, or an injected object).
         One forward of the 19 double blocks per noise sample (stop_after_multimodal_attentions).
@@ -482,12 +567,14 @@ class ConceptAttentionFluxPipeline:
         tensors shaped like the latent) overrides get_noise, whose device RNG stream differs between platforms;
         ``vae_noise`` (1,16,h/8,w/8) is the autoencoder's sampling noise for a PIL image (drawn on the device when not
         given), so that a call is reproducible.  ``heatmap_renderer`` and the three keywords behind it: as in
-        ``generate_image``; the overlays are laid over the INPUT image's bytes, which must already be height x width."""
+        ``generate_image``; the overlays are laid over the INPUT image's bytes, which must already be height x width.
+        ``token_maps``: as in ``generate_image`` (the mean runs over heads, layers and noise samples)."""
         assert all([0 <= li < self.params.depth for li in layer_indices]), "Invalid layer index"
         assert height == width, "Height and width must be the same for now"
         norm = resolve_norm(softmax, attention_norm)
         check_concept_count(norm, len(concepts))
         on_device = self._device_renderer(heatmap_renderer, heatmap_size, heatmap_interpolation, overlay_alpha)
+        n_tok, tokens = self._token_request(prompt, token_maps)
         picture = self._input_picture(image, height, width) if on_device and overlay_alpha is not None and \
             return_pil_heatmaps else None
         if isinstance(image, torch.Tensor):
@@ -495,14 +582,16 @@ class ConceptAttentionFluxPipeline:
         else:
             latent = self._encode_pixels([image], height, width, vae_noise)
         txt, vec, con, con_ids, con_vec = self._embed(prompt, concepts)
+        token_acc = self._token_accumulators([n_tok], (latent.shape[-1] // 2) * (latent.shape[-2] // 2))
         out_space, cross_space = self._encode_maps(self.model, latent, txt, vec, con, con_ids, con_vec, layer_indices,
                                                    num_samples, num_steps, noise_timestep, seed,
                                                    stop_after_multi_modal_attentions, joint_attention_kwargs, norm,
-                                                   noise=noise)
+                                                   noise=noise, token_acc=token_acc)
+        tok = self._token_views(token_acc, 0)
         if on_device and return_pil_heatmaps:
             return self._finish_device([image], out_space, cross_space, cmap, heatmap_size, heatmap_interpolation,
-                                       overlay_alpha, None if picture is None else [picture])[0]
-        return self._finish(image, out_space, cross_space, return_pil_heatmaps, cmap)
+                                       overlay_alpha, None if picture is None else [picture], [tok], [tokens])[0]
+        return self._finish(image, out_space, cross_space, return_pil_heatmaps, cmap, tok, tokens)
 
     def _encode_pixels(self, images, height: int, width: int, vae_noise=None) -> torch.Tensor:
         """PIL images -> bf16 latents (B,16,h/8,w/8).  The HIP autoencoder takes the bytes (``encode_pixels``: resize,
@@ -523,13 +612,16 @@ class ConceptAttentionFluxPipeline:
 
     def _encode_maps(self, model, latent, txt, vec, con, con_ids, con_vec, layer_indices, num_samples, num_steps,
                      noise_timestep, seed, stop_after_multi_modal_attentions=True, joint_attention_kwargs=None,
-                     norm: int = 0, noise=None):
+                     norm: int = 0, noise=None, token_acc=None):
         """Device core of encode_image for B images at once (latent (B,16,h,w), txt (B,T,4096), ...): one forward
         per noise sample on ``model``; returns the two fp32 maps [B, C, side, side].  ``noise``: optional list of
-        num_samples tensors (1 or B,16,h,w) used instead of get_noise(seed + i)."""
+        num_samples tensors (1 or B,16,h,w) used instead of get_noise(seed + i).  ``token_acc``: per item, the caller's
+        zeroed fp32 [n_tok, patches] accumulator of the prompt-token maps (or None); the return tuple stays."""
         if noise is not None and len(noise) != num_samples:
             raise ValueError("noise: one tensor per noise sample")
         B, C = con.shape[0], con.shape[1]
+        if token_acc is not None and len(token_acc) != B:
+            raise ValueError("token_acc: one accumulator (or None) per work item")
         n_patches = (latent.shape[-1] // 2) * (latent.shape[-2] // 2)
         height, width = latent.shape[-2] * 8, latent.shape[-1] * 8
         # the reference indexes the stacked samples with the float schedule values
@@ -538,7 +630,8 @@ class ConceptAttentionFluxPipeline:
         acc_o = torch.zeros(B, C, n_patches, device=self.device)
         acc_c = torch.zeros(B, C, n_patches, device=self.device)
         req = [HeatmapRequest(tuple(int(l) for l in layer_indices), 1.0 / (num_samples * len(layer_indices)),
-                              acc_o[j], acc_c[j], norm=norm) for j in range(B)]
+                              acc_o[j], acc_c[j], norm=norm, token_space=None if token_acc is None else token_acc[j])
+               for j in range(B)]
         schedule = sampling.get_schedule(num_steps, n_patches, shift=(not self.is_schnell))
         for i in range(num_samples):
             # add_noise_to_image (concept_attention/segmentation.py:85-113)
@@ -563,9 +656,10 @@ class ConceptAttentionFluxPipeline:
 
     def _encode_chunks(self, images, concepts, prompts, width, height, layer_indices, num_samples, num_steps,
                        noise_timestep, seed, batch, noise, vae_noise, stop_after_multi_modal_attentions, attention_norm,
-                       softmax, joint_attention_kwargs):
+                       softmax, joint_attention_kwargs, token_acc=None):
         """The forwards of ``encode_images``, one at a time: yields (item indices, acc_o, acc_c) with the two fp32 maps
-        [len(indices), C, side, side] of the chunk still on the device (``_encode_maps``).  ``images`` is a list."""
+        [len(indices), C, side, side] of the chunk still on the device (``_encode_maps``).  ``images`` is a list.
+        ``token_acc``: per item of the call, the caller's accumulator of the prompt-token maps (or None)."""
         assert all([0 <= li < self.params.depth for li in layer_indices]), "Invalid layer index"
         assert height == width, "Height and width must be the same for now"
         norm = resolve_norm(softmax, attention_norm)
@@ -594,7 +688,8 @@ class ConceptAttentionFluxPipeline:
                                              for s_ in range(num_samples)]
             ho, hc = self._encode_maps(self.model, latent, txt, vec, con, con_ids, con_vec, layer_indices, num_samples,
                                        num_steps, noise_timestep, seed, stop_after_multi_modal_attentions,
-                                       joint_attention_kwargs, norm, noise=nz)
+                                       joint_attention_kwargs, norm, noise=nz,
+                                       token_acc=None if token_acc is None else [token_acc[i] for i in idx])
             yield idx, ho, hc
 
     @torch.no_grad()
@@ -605,7 +700,7 @@ class ConceptAttentionFluxPipeline:
                       return_pil_heatmaps: bool = True, cmap="plasma", stop_after_multi_modal_attentions=True,
                       attention_norm: str = "sparsemax", softmax=True, joint_attention_kwargs=None,
                       heatmap_renderer: str = "host", heatmap_size=None, heatmap_interpolation: str = "nearest",
-                      overlay_alpha=None) -> list:
+                      overlay_alpha=None, token_maps=None) -> list:
         """``encode_image`` for a list of images: a list of ConceptAttentionPipelineOutput in item order, every item with
         the maps of its own ``encode_image`` call.  ``images``: PIL images and / or latents (1,16,h/8,w/8);
         ``concepts``: one list for all items or one list per item; ``prompts``: one string per item (or one for all).
@@ -614,9 +709,18 @@ class ConceptAttentionFluxPipeline:
         ``noise``: per item, what ``encode_image`` takes (a list of num_samples tensors); ``vae_noise``: per item, a
         tensor (1,16,h/8,w/8) -- without it the autoencoder draws one batch of noise per forward, so PIL items are then
         reproducible per call of this method, not against single calls.  ``heatmap_renderer="device"``: the pictures of
-        a chunk come from one launch and one download (``_finish_device``)."""
+        a chunk come from one launch and one download (``_finish_device``).  ``token_maps``: as in ``encode_image``, for
+        every item's own prompt (the items of a chunk may have different numbers of tokens)."""
         images = list(images)
         results = [None] * len(images)
+        plist = [prompts] * len(images) if isinstance(prompts, str) else list(prompts)
+        treq = [self._token_request(p, token_maps) for p in plist] if token_maps is not None and token_maps is not False else []
+        token_acc = None
+        if treq:
+            token_acc = [self._token_accumulators(
+                [n], (im.shape[-1] // 2) * (im.shape[-2] // 2) if isinstance(im, torch.Tensor)
+                else (height // 16) * (width // 16))[0] for (n, _), im in zip(treq, images)]
+        tokens = [t for _, t in treq] if treq else None
         on_device = self._device_renderer(heatmap_renderer, heatmap_size, heatmap_interpolation, overlay_alpha) and \
             return_pil_heatmaps
         pictures = [self._input_picture(im, height, width) for im in images] if on_device and overlay_alpha is not None \
@@ -624,15 +728,18 @@ class ConceptAttentionFluxPipeline:
         for idx, ho, hc in self._encode_chunks(images, concepts, prompts, width, height, layer_indices, num_samples,
                                                num_steps, noise_timestep, seed, batch, noise, vae_noise,
                                                stop_after_multi_modal_attentions, attention_norm, softmax,
-                                               joint_attention_kwargs):
+                                               joint_attention_kwargs, **({"token_acc": token_acc} if treq else {})):
             if on_device:
                 outs = self._finish_device([images[i] for i in idx], ho, hc, cmap, heatmap_size, heatmap_interpolation,
-                                           overlay_alpha, None if pictures is None else [pictures[i] for i in idx])
+                                           overlay_alpha, None if pictures is None else [pictures[i] for i in idx],
+                                           [self._token_views(token_acc, i) for i in idx],
+                                           None if tokens is None else [tokens[i] for i in idx])
                 for k, i in enumerate(idx):
                     results[i] = outs[k]
                 continue
             for k, i in enumerate(idx):
-                results[i] = self._finish(images[i], ho[k:k + 1], hc[k:k + 1], return_pil_heatmaps, cmap)
+                results[i] = self._finish(images[i], ho[k:k + 1], hc[k:k + 1], return_pil_heatmaps, cmap,
+                                          self._token_views(token_acc, i), None if tokens is None else tokens[i])
         return results
 
     @torch.no_grad()
@@ -642,12 +749,13 @@ class ConceptAttentionFluxPipeline:
                         num_inference_steps: int = 4, guidance: float = 0.0, timesteps=None, softmax: bool = True,
                         attention_norm: str = "sparsemax", cmap="plasma", batch: int = 5,
                         heatmap_renderer: str = "host", heatmap_size=None, heatmap_interpolation: str = "nearest",
-                        overlay_alpha=None) -> list:
+                        overlay_alpha=None, token_maps=None) -> list:
         """``generate_image`` for a list of prompts: a list of ConceptAttentionPipelineOutput in item order, every item
         with the image and maps of its own ``generate_image(prompt, concepts, seed=seeds[i], latent=latents[i])`` call on
         the fused route.  ``concepts``: one list for all items or one list per item; ``seeds``: one per item (default
         0, 1, 2, ...).  Items with one concept count go ``batch`` (at most 5) at a time through one text-encoder call,
-        one denoising loop and one autoencoder pass whose bytes are made on the device."""
+        one denoising loop and one autoencoder pass whose bytes are made on the device.  ``token_maps``: as in
+        ``generate_image``, for every item's own prompt (the items of a chunk may have different numbers of tokens)."""
         assert return_cross_attention is False, "Not supported yet"
         assert all([0 <= li < self.params.depth for li in layer_indices]), "Invalid layer index"
         assert height == width, "Height and width must be the same for now"
@@ -666,6 +774,10 @@ class ConceptAttentionFluxPipeline:
             timesteps = list(range(num_inference_steps))
         shapes = [(16, height // 8, width // 8) if latents is None else tuple(latents[i].shape[1:]) for i in range(n)]
         results = [None] * n
+        treq = [self._token_request(p, token_maps) for p in prompts] if token_maps is not None and token_maps is not False else []
+        token_acc = [self._token_accumulators([nt], (shapes[i][1] // 2) * (shapes[i][2] // 2))[0]
+                     for i, (nt, _) in enumerate(treq)] if treq else None
+        tokens = [t for _, t in treq] if treq else None
         for idx in plan_batches([(shapes[i], len(concepts[i]), self._text_length()) for i in range(n)], batch):
             emb = self.flux_generator.embed_many([prompts[i] for i in idx], [concepts[i] for i in idx])
             txt, vec, con = (torch.cat([e[k] for e in emb], 0) if len(idx) > 1 else emb[0][k] for k in range(3))
@@ -673,17 +785,21 @@ class ConceptAttentionFluxPipeline:
                            sampling.get_noise(1, height, width, self.device, torch.bfloat16, seeds[i]) for i in idx], 0)
             img, ho, hc = self.generate_on_device(x, txt, vec, con, layer_indices=layer_indices,
                                                   num_inference_steps=num_inference_steps, guidance=guidance,
-                                                  timesteps=timesteps, fused=True, norm=norm)
+                                                  timesteps=timesteps, fused=True, norm=norm,
+                                                  token_acc=None if token_acc is None else [token_acc[i] for i in idx])
             if on_device:
                 pictures, pix = self._decode_with_bytes(img, height, width) if overlay_alpha is not None else \
                     (self.flux_generator.decode_many(img, height, width), None)
-                outs = self._finish_device(pictures, ho, hc, cmap, heatmap_size, heatmap_interpolation, overlay_alpha, pix)
+                outs = self._finish_device(pictures, ho, hc, cmap, heatmap_size, heatmap_interpolation, overlay_alpha, pix,
+                                           [self._token_views(token_acc, i) for i in idx],
+                                           None if tokens is None else [tokens[i] for i in idx])
                 for k, i in enumerate(idx):
                     results[i] = outs[k]
                 continue
             pictures = self.flux_generator.decode_many(img, height, width)
             for k, i in enumerate(idx):
-                results[i] = self._finish(pictures[k], ho[k:k + 1], hc[k:k + 1], return_pil_heatmaps, cmap)
+                results[i] = self._finish(pictures[k], ho[k:k + 1], hc[k:k + 1], return_pil_heatmaps, cmap,
+                                          self._token_views(token_acc, i), None if tokens is None else tokens[i])
         return results
 
     @torch.no_grad()

@@ -395,6 +395,11 @@ class ToyByteTokenizer:
             ids[r, : len(tok)] = torch.tensor(tok, dtype=torch.long)
         return {"input_ids": ids}
 
+    def tokenize(self, text: str) -> list:
+        """One string per byte of the text, in order (no end-of-string token), as a HuggingFace tokenizer's ``tokenize``
+        returns its pieces: what the prompt-token maps are named by."""
+        return [bytes([b]).decode("latin-1") for b in text.encode("utf-8")]
+
 
 class HipTextEncoder:
     """The ``HFEmbedder`` contract (conditioner.py:6-38) with T5 on the HIP encoder: ``t5(text) -> [1, L, d_model]`` bf16,
