@@ -83,13 +83,22 @@ __device__ __forceinline__ uint32_t ca_pack2_f16(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, v);
 }
 
-// 8 floats (already divided by the row scale) -> 8 OCP e4m3 bytes (v_cvt_pk_fp8_f32, RNE; inputs clamped to
-// the largest finite e4m3 value so nothing overflows to NaN)
+// 8 floats (already divided by the row scale) -> 8 OCP e4m3 bytes (v_cvt_pk_fp8_f32, RNE).  Finite inputs are clamped to
+// the largest finite e4m3 value, so no rounding overflows to NaN; a NaN input stays a NaN (the conversion stores 0xFF
+// or 0x7F).  The clamp is v_med3_f32, which returns a bound for a NaN (as fminf(fmaxf()) does), so the NaN is put back by
+// one fused multiply-add: y * 0 + clamp is the clamp, bit for bit, for every finite y (y * 0 is a zero of y's sign, and
+// so is a zero clamp) and NaN for a NaN or an infinite y.  The producers reach it with y * (1 / scale), which is never
+// infinite: an infinite y has an infinite row scale, and inf * 0 is already NaN.
 constexpr float E4M3_MAX = 448.0f;
+// the e4m3 row scale of a row whose |y| maximum (taken with fmaxf: over the non-NaN elements) is amax: amax / 448,
+// floored at the smallest normal float so that 1 / scale stays finite for a vanishing row; 1 for a zero or all-NaN row
+__device__ __forceinline__ float ca_fp8_row_scale(float amax) {
+  return amax > 0.f ? fmaxf(amax * (1.0f / E4M3_MAX), __FLT_MIN__) : 1.0f;
+}
 __device__ __forceinline__ uint2 ca_pack_fp8x8(const float *y) {
   float c[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) c[j] = fminf(fmaxf(y[j], -E4M3_MAX), E4M3_MAX);
+  for (int j = 0; j < 8; ++j) c[j] = __builtin_fmaf(y[j], 0.0f, __builtin_amdgcn_fmed3f(y[j], -E4M3_MAX, E4M3_MAX));
   int lo = 0, hi = 0;
   lo = __builtin_amdgcn_cvt_pk_fp8_f32(c[0], c[1], lo, false);
   lo = __builtin_amdgcn_cvt_pk_fp8_f32(c[2], c[3], lo, true);

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void ca_ln_modulate_kernel(const XT *__restric
   }
   if constexpr (FP8) {
     amax = wave_max(amax);
-    const float sc = amax > 0.f ? amax * (1.0f / E4M3_MAX) : 1.0f;
+    const float sc = ca_fp8_row_scale(amax);
     const float inv = 1.0f / sc;
     if (lane == 0) out_scale[row] = sc;
     uint8_t *orow = (uint8_t *)out_ + (size_t)row * ldo;
@@ -234,10 +234,15 @@ __global__ __launch_bounds__(256) void ca_quantize_rows_fp8_kernel(const bf16 *_
   for (int k = lane * 8; k < K; k += 512) {
     const bf16x8 t = *(const bf16x8 *)(xr + k);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf((float)t[j]));
+    for (int j = 0; j < 8; ++j) {
+      // canonicalised first: the elements come straight from memory, and a SIGNALLING NaN makes v_max_f32 return a
+      // NaN (IEEE mode), which the next maximum drops together with what the lane had found so far.  (The other
+      // producers take the maximum of arithmetic results, which are quiet.)
+      amax = fmaxf(amax, __builtin_canonicalizef(fabsf((float)t[j])));
+    }
   }
   amax = wave_max(amax);
-  const float sc = amax > 0.f ? amax * (1.0f / E4M3_MAX) : 1.0f;
+  const float sc = ca_fp8_row_scale(amax);
   const float inv = 1.0f / sc;
   if (lane == 0) out_scale[row] = sc;
   uint8_t *orow = out + (size_t)row * ldo;

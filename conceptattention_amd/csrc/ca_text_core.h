@@ -165,7 +165,7 @@ __device__ __forceinline__ float tx_block_max(float v, float *red) {
 // ca_quantize_rows_fp8_kernel); thread 0 writes it; returns its inverse, the factor of the store pass
 __device__ __forceinline__ float tx_fp8_row_scale(float amax, float *red, float *out_scale) {
   amax = tx_block_max(amax, red);
-  const float sc = amax > 0.f ? amax * (1.0f / E4M3_MAX) : 1.0f;
+  const float sc = ca_fp8_row_scale(amax);
   const float inv = 1.0f / sc;
   if (threadIdx.x == 0) *out_scale = sc;
   return inv;

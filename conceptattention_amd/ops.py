@@ -92,6 +92,9 @@ class Gemm:
     qk_f16: bool = False                       # QKV_NORM_ROPE: rotated q / k stored as fp16 bits (attention(qk_f16=True))
     a_scale: Optional[torch.Tensor] = None  # fp8 mode: a, w are uint8 (e4m3 bytes) with fp32 row scales
     w_scale: Optional[torch.Tensor] = None  # ([M] and [N]); the launch then goes to ca_gemm_fp8
+    # (there a NaN byte, 0x7F / 0xFF, in a makes its output row NaN, one in w its column -- its head under QKV_NORM_ROPE;
+    # an infinite a_scale[m] leaves row m without a finite element; a result beyond bf16 is stored as +-inf.
+    # acc * a_scale is formed before * w_scale and may overflow on its own: include/conceptattn.h, G1 .. G4)
     # batched forward: rows < gate_rows are items of gate_item_rows rows, the others items of gate2_item_rows rows;
     # item i of a range uses gate (gate2) + i * gate_stride floats.  gate_stride = 0: one vector per range.
     gate_stride: int = 0
@@ -326,7 +329,9 @@ def set_attn_hook(hook) -> None:
 
 def ln_modulate(x, out, segments, eps: float = 1e-6, out_scale=None, out_lo=None) -> None:
     """segments: [(row_end, shift fp32[H], scale fp32[H]), ...] covering all rows of x.
-    With ``out`` uint8 and ``out_scale`` fp32 [M] the result is quantised to e4m3 per row (ca_ln_modulate_fp8).
+    With ``out`` uint8 and ``out_scale`` fp32 [M] the result is quantised to e4m3 per row (ca_ln_modulate_fp8), under
+    the value-range rules of ``quantize_rows_fp8``: a NaN or inf in x gives a row of NaN bytes with scale 1, a NaN in a
+    column of a segment's shift or scale a NaN byte in that column of the segment's rows.
     ``out_lo`` (bf16, fp32 input only): second plane bf16(y - float(bf16(y))) (ca_ln_modulate_f32in_split)."""
     lib = L.load()
     fp8 = out.dtype == torch.uint8
@@ -387,7 +392,11 @@ def qpre_finish(x, d, norm_scale, num_heads: int, rope=None, q_out=None, q_out_s
 
 
 def quantize_rows_fp8(x, out=None, out_scale=None):
-    """Row-wise absmax quantisation bf16 [M,K] -> (uint8 e4m3 [M,K], fp32 scale [M])."""
+    """Row-wise absmax quantisation bf16 [M,K] -> (uint8 e4m3 [M,K], fp32 scale [M]).  scale = max|x| / 448 over the
+    row's non-NaN elements, never below 2^-126, and 1 for a zero or all-NaN row.  A NaN element (quiet or signalling)
+    becomes a NaN byte (0x7F / 0xFF) and changes nothing else in its row; a row with +-inf has scale inf, NaN bytes at
+    the infinities and +-0 elsewhere; a finite non-zero row, however small, has finite bytes and a finite normal scale
+    (include/conceptattn.h, "e4m3 value range", P1 .. P5; the other e4m3 producers follow the same rules)."""
     lib = L.load()
     _chk(x, torch.bfloat16, "x")
     if x.dim() != 2:
@@ -1313,7 +1322,9 @@ def _chk_fp8_out(what: str, out, out_scale, shape) -> None:
 def t5_rmsnorm_fp8(x, weight, out, out_scale, eps: float = 1e-6) -> None:
     """t5_rmsnorm written as an fp8 GEMM operand: with y = x * rsqrt(mean(x^2) + eps) * weight in fp32 (never rounded to
     bf16), out_scale[r] = max|y[r]| / 448 (1 for a zero row) and out[r] = e4m3(y[r] / out_scale[r]).  x fp32 [rows, H],
-    weight fp32 [H], out uint8 [rows, H] (row stride free), out_scale fp32 [rows] contiguous."""
+    weight fp32 [H], out uint8 [rows, H] (row stride free), out_scale fp32 [rows] contiguous.  Value range as for
+    ``quantize_rows_fp8``: a NaN in x gives a row of NaN bytes with scale 1, an inf in x one NaN byte (inf * 0) in a
+    row of zeros; the scale of a vanishing row stops at 2^-126."""
     _chk(x, torch.float32, "x"), _chk(weight, torch.float32, "weight")
     if x.dim() != 2 or weight.numel() != x.shape[1] or not weight.is_contiguous():
         raise ValueError("t5_rmsnorm_fp8: x must be 2-D, weight contiguous [H]")
@@ -1327,7 +1338,9 @@ def t5_rmsnorm_fp8(x, weight, out, out_scale, eps: float = 1e-6) -> None:
 def gated_mul_fp8(g, u, out, out_scale) -> None:
     """gated_mul written as an fp8 GEMM operand: y = float(g) * float(u) (exact), out_scale[r] = max|y[r]| / 448 (1 for
     a zero row), out[r] = e4m3(y[r] / out_scale[r]).  g, u bf16 [rows, C] row views, out uint8 [rows, C] (row stride
-    free), out_scale fp32 [rows] contiguous."""
+    free), out_scale fp32 [rows] contiguous.  Value range as for ``quantize_rows_fp8``: a NaN product is a NaN byte, an
+    infinite product (an infinite factor, or an overflow of fp32) an infinite scale, a product that underflows to 0 a
+    zero."""
     _chk(g, torch.bfloat16, "g"), _chk(u, torch.bfloat16, "u")
     if g.dim() != 2 or u.shape != g.shape:
         raise ValueError("gated_mul_fp8: g and u must be 2-D of one shape")

@@ -148,6 +148,18 @@ int ca_gemm_auto_tile(const ca_gemm_problem *problems, int32_t n_problems);
  * A8/W8 are e4m3 bytes produced by ca_quantize_rows_fp8 (absmax per row), lda/ldw in elements (= bytes),
  * K % 128 == 0, lda/ldw % 16 == 0; the accumulation is fp32 (v_mfma_scale_f32_16x16x128_f8f6f4 with unit
  * block scales), out/resid/bias/gates stay bf16/fp32 as above.  256x256 ping-pong tile only (N % 256 == 0).
+ * e4m3 value range (the consumer's side; the producers' side is at ca_quantize_rows_fp8).  Bytes 0x7F and 0xFF are NaN.
+ *   G1  a NaN byte at A8[m, k]: row m is NaN in every column the launch writes (out2 and q_prerope included); every
+ *       other row has the bits of the launch with that byte 0.
+ *   G2  a NaN byte at W8[n, k]: column n, and the columns the epilogue couples with it (QKV_NORM_ROPE: the 128 columns
+ *       of n's head in q or k, and in a normalised q_prerope), are NaN in every row; every other column has those bits.
+ *   G3  a_scale[m] = +inf: row m holds no finite element, and NaN where its accumulator is 0; the other rows keep
+ *       their bits.
+ *   G4  an epilogue result beyond the bf16 range is stored as +-inf (round to nearest even, as torch's fp32 -> bf16
+ *       cast), never as NaN or as the largest finite bf16.
+ * Limit: the epilogue multiplies the accumulator by a_scale[m] first and by w_scale[n] second, each product rounded to
+ * fp32: acc * a_scale[m] can overflow to +-inf where acc * a_scale[m] * w_scale[n] would be finite (a large row scale
+ * against a small column scale).  The result is then +-inf, not the finite value.
  */
 int ca_gemm_fp8(const ca_gemm_problem *problems, int32_t n_problems, ca_stream_t stream);
 
@@ -263,6 +275,8 @@ int ca_ln_modulate_bf16(const void *x, int32_t ldx, void *out, int32_t ldo, int3
  * (its per-block bf16 rounding is what makes the heat-map error grow with depth). */
 int ca_ln_modulate_f32in(const float *x, int32_t ldx, void *out, int32_t ldo, int32_t M, int32_t H,
                          const ca_mod_segment *segs, int32_t n_segs, float eps, ca_stream_t stream);
+/* ca_ln_modulate_fp8 (below) with the fp32 input: the same e4m3 output, scale rule and value range (P1 .. P5 at
+ * ca_quantize_rows_fp8), y being the modulated row in fp32. */
 int ca_ln_modulate_f32in_fp8(const float *x, int32_t ldx, void *out8, int32_t ldo, float *out_scale, int32_t M,
                              int32_t H, const ca_mod_segment *segs, int32_t n_segs, float eps, ca_stream_t stream);
 /* ca_ln_modulate_f32in with a second bf16 plane out_lo = bf16(y - float(bf16(y))) (row stride ldlo): what the bf16
@@ -271,11 +285,28 @@ int ca_ln_modulate_f32in_split(const float *x, int32_t ldx, void *out, int32_t l
                                int32_t M, int32_t H, const ca_mod_segment *segs, int32_t n_segs, float eps,
                                ca_stream_t stream);
 /* Same, with the result quantised for ca_gemm_fp8: out8 = e4m3 bytes (row stride ldo bytes, % 16),
- * out_scale[row] = absmax(row) / 448 (fp32 [M]). */
+ * out_scale[row] = absmax(row) / 448 (fp32 [M]).  Value range: P1 .. P5 at ca_quantize_rows_fp8, with y the modulated
+ * row (1 + scale) * LayerNorm(x) + shift in fp32.  A NaN or an infinity in x makes the whole row NaN (bytes NaN, scale
+ * 1); a NaN in one column of a segment's shift or scale is a NaN byte in that column of that segment's rows only. */
 int ca_ln_modulate_fp8(const void *x, int32_t ldx, void *out8, int32_t ldo, float *out_scale, int32_t M,
                        int32_t H, const ca_mod_segment *segs, int32_t n_segs, float eps, ca_stream_t stream);
 /* Row-wise absmax quantisation bf16 [M,K] -> e4m3 [M,K] + fp32 scale per row (weights once per model;
- * activations between two fp8 GEMMs). */
+ * activations between two fp8 GEMMs).
+ * e4m3 value range, for this entry and the four other e4m3 producers (ca_ln_modulate_fp8, ca_ln_modulate_f32in_fp8,
+ * ca_t5_rmsnorm_f32in_fp8, ca_gated_mul_fp8).  y is the fp32 row the producer quantises (here: x), amax the largest |y|
+ * over the row's non-NaN elements, out_scale = max(amax * fl(1 / 448), 2^-126), or 1 where amax is 0, and
+ * out8[c] = e4m3(clamp(y[c] * (1 / out_scale), +-448)), round to nearest even.
+ *   P1  a finite row with amax * fl(1 / 448) >= 2^-126: as stated, the bytes and scales the entries have always written.
+ *   P2  y[c] NaN (either sign, any payload, quiet or signalling): out8[c] is an e4m3 NaN (0x7F or 0xFF), never a
+ *       finite byte.
+ *   P3  the scale ignores NaN elements: out_scale and every other byte of the row are those of the same row with its NaN
+ *       elements set to 0, bit for bit; a row that is all NaN has scale 1.
+ *   P4  a row with +-inf in y: out_scale = +inf, NaN bytes at the infinite positions (inf * (1 / inf)), +-0 with the
+ *       element's sign at the finite ones.  This covers a gated product that overflows fp32.
+ *   P5  a finite non-zero row: out_scale is finite, positive and normal and every byte is finite, however small the
+ *       row; below amax / 448 = 2^-126 the scale is 2^-126 (1 / out_scale stays finite; without the floor it was inf,
+ *       every non-zero element +-448 and every zero 0 * inf).
+ * A special row changes no other row. */
 int ca_quantize_rows_fp8(const void *x, int32_t ldx, void *out8, int32_t ldo, float *out_scale, int32_t M,
                          int32_t K, ca_stream_t stream);
 
@@ -487,7 +518,11 @@ int ca_gated_mul_bf16(const void *g, int32_t ldg, const void *u, int32_t ldu, vo
 /* The two above as producers of ca_gemm_fp8's A operand (the T5 encoder's fp8 mode): the fp32 row y (the norm's
  * x * rsqrt(mean(x^2) + eps) * w, not rounded to bf16; the exact product float(g) * float(u)) leaves as OCP e4m3 bytes
  * and one fp32 scale per row: out_scale[r] = max|y| / 448, or 1 for an all-zero row (which stores zero bytes);
- * out8[r, :] = e4m3(y / out_scale[r]), round-to-nearest-even, saturating at +-448 -- the rule of ca_quantize_rows_fp8.
+ * out8[r, :] = e4m3(y / out_scale[r]), round-to-nearest-even, saturating at +-448 -- the rule of ca_quantize_rows_fp8,
+ * with its value range (P1 .. P5 there).  ca_t5_rmsnorm_f32in_fp8: a NaN in x makes the whole row NaN (bytes NaN, scale
+ * 1); an inf in x makes rsqrt(...) 0, so y is inf * 0 = NaN in that column and x * 0 elsewhere (scale 1); a NaN or inf
+ * in w[c] is a NaN or inf y[c] in every row.  ca_gated_mul_fp8: a NaN factor is a NaN y[c]; an infinite factor, or
+ * finite factors whose product overflows fp32, an infinite y[c] (P4); a product that underflows to 0 counts as 0.
  * out8 uint8 [rows, ldo] with ldo in bytes, >= the row length and % 8 (ca_gemm_fp8 itself wants lda % 16), 8-byte
  * aligned; out_scale fp32 [rows] contiguous.  H % 8 == 0 / C % 8 == 0; inputs as for the bf16 forms (x, w, g, u
  * 16-byte aligned, ldx % 4, ldg / ldu % 8).  One workgroup owns a row. */

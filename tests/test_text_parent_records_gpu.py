@@ -22,7 +22,15 @@ everything else compares by bits.
   ``models``      the tiny T5 in bf16 and in fp8 (all four projections) on 3 sequences of L = 64 and of L = 256; the tiny
                   CLIP's encode_ids and hidden_states at L = 77 for 3 and for 17 sequences (two passes).
 
-The inputs come from the case modules, generated on the CPU from their seeds."""
+The inputs come from the case modules, generated on the CPU from their seeds.
+
+267 bytes of two outputs have moved since the recording, on purpose (``MOVED``).  The recorded kernels clamped the scaled
+row with fminf(fmaxf(z, -448), 448), which returns -448 for a NaN: a NaN element of the fp32 row an e4m3 producer
+quantises was stored as the finite byte 0xFE.  The e4m3 value-range contract of include/conceptattn.h stores a NaN byte
+there (tests/fp8_edge_cases.py, P2).  In ``t5_rmsnorm_fp8 specials`` these are row 1 column 3 (inf * 0) and all of row 2
+(a NaN in x), in ``gated_mul_fp8 specials`` row 1 column 3 (inf under an infinite scale) and row 2 column 132 (the NaN
+product).  Those two byte planes are compared with the parent's everywhere else and with 0x7F there; their scales, and
+every other output, compare bit for bit as before."""
 import functools
 import hashlib
 import os
@@ -48,6 +56,10 @@ NF_VALUES = (NAN, float("inf"), -float("inf"), -0.0, BF16_MAX)
 WIDTHS = (264, 1032, 2056)                    # behind each kernel's minimum width
 ROWS = (1, 5)
 FAMILIES = ("t5_attn", "clip_attn", "nf_attn", "rows", "wrap_t5", "wrap_fp8", "wrap_clip", "models")
+# output -> the (row, column) cells of its 5 x 264 e4m3 plane where the fp32 row is not finite: the parent holds 0xFE
+# there, the contract a NaN byte (0x7F after canonical_bytes)
+MOVED = {"t5_rmsnorm_fp8 specials [0]": [(1, 3)] + [(2, c) for c in range(264)],
+         "gated_mul_fp8 specials [0]": [(1, 3), (2, 132)]}
 
 
 def canonical_bytes(t: torch.Tensor) -> bytes:
@@ -311,8 +323,18 @@ def test_the_outputs_are_the_parents_bit_for_bit(parent, family):
     print(family, len(names), "outputs,", int((lens > 0).sum()), "stored whole")
     assert sha.shape == parent[family + ".sha"].shape and np.array_equal(lens, parent[family + ".len"]), family
     ends = np.cumsum(lens)
+    moved = 0
     for i, name in enumerate(names):
+        if name in MOVED:   # the parent's bytes with a NaN byte where it held the laundered -448
+            a, b = kept[ends[i] - lens[i]:ends[i]], parent[family + ".bytes"][ends[i] - lens[i]:ends[i]].copy()
+            cells = np.array([r * 264 + c for r, c in MOVED[name]])
+            assert lens[i] == 5 * 264 and (b[cells] == 0xFE).all(), name
+            b[cells] = 0x7F
+            moved += len(cells)
+            assert np.array_equal(a, b), (name, np.nonzero(a != b)[0][:8], a[a != b][:8], b[a != b][:8])
+            continue
         if lens[i]:         # readable: the first bytes that differ
             a, b = kept[ends[i] - lens[i]:ends[i]], parent[family + ".bytes"][ends[i] - lens[i]:ends[i]]
             assert np.array_equal(a, b), (name, np.nonzero(a != b)[0][:8], a[a != b][:8], b[a != b][:8])
         assert np.array_equal(sha[i], parent[family + ".sha"][i]), name
+    assert moved == (267 if family == "rows" else 0)
