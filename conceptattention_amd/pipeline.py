@@ -16,7 +16,7 @@ vocabularies.
 from __future__ import annotations
 
 import zlib
-from dataclasses import dataclass
+from dataclasses import InitVar, dataclass, field, fields
 from typing import Optional, Sequence
 
 import numpy as np
@@ -78,12 +78,54 @@ def colorize_heatmaps(heatmaps: np.ndarray, cmap: str = "plasma") -> list:
 MAX_ITEMS_PER_FORWARD = min(_lib.ATTN_MAX_PROBLEMS // 2, _lib.MAX_SEGMENTS // 3)   # launch limits: 5 items
 
 
+def items_per_forward(batch: int) -> int:
+    """What a ``batch`` argument means: 1 .. MAX_ITEMS_PER_FORWARD work items in one forward."""
+    return max(1, min(int(batch), MAX_ITEMS_PER_FORWARD))
+
+
+@dataclass(frozen=True)
+class EncodeSettings:
+    """What an encode call is asked to do, apart from its images, strings and noise.  The defaults are written here, once
+    (tests/test_frontend_cpu.py holds the public signatures to them); the constructor makes the checks of such a call."""
+    layer_indices: Sequence = field(default_factory=lambda: list(range(15, 19)))
+    num_samples: int = 1
+    num_steps: int = 4
+    noise_timestep: int = 2
+    seed: int = 0
+    width: int = 1024
+    height: int = 1024
+    batch: int = 5
+    stop_after_multi_modal_attentions: bool = True
+    joint_attention_kwargs: Optional[dict] = None
+    attention_norm: str = "sparsemax"
+    softmax: bool = True
+    norm: int = field(init=False, default=_lib.NORM_SOFTMAX)   # the resolved (softmax, attention_norm)
+    depth: InitVar[Optional[int]] = None     # the model's double blocks, when the layer indices are to be checked
+    n_concepts: InitVar[int] = 0             # the largest concept count of the call
+
+    def __post_init__(self, depth, n_concepts):
+        assert depth is None or all([0 <= li < depth for li in self.layer_indices]), "Invalid layer index"
+        assert self.height == self.width, "Height and width must be the same for now"
+        object.__setattr__(self, "norm", resolve_norm(self.softmax, self.attention_norm))   # ValueError on an unknown name
+        check_concept_count(self.norm, n_concepts)
+
+    def keywords(self) -> dict:
+        """The settings under the parameter names of ``encode_images``."""
+        return {f.name: getattr(self, f.name) for f in fields(self) if f.init}
+
+
+def _cat(tensors) -> torch.Tensor:
+    """The items of a forward along the item axis; one item is passed on as it is (no copy)."""
+    tensors = list(tensors)
+    return tensors[0] if len(tensors) == 1 else torch.cat(tensors, 0)
+
+
 def plan_batches(keys: Sequence, batch: int) -> list:
     """The forwards of a batched call, as lists of item indices.  ``keys[i]`` is whatever item i must share with the
     others of its forward -- (latent shape, concept count, text length).  Items of one key form a group, the groups in the
     order of their first item; a group is cut into chunks of at most min(batch, MAX_ITEMS_PER_FORWARD) items in their
     original order.  Pure: no device, no tensors."""
-    size = max(1, min(int(batch), MAX_ITEMS_PER_FORWARD))
+    size = items_per_forward(batch)
     groups: dict = {}
     for i, k in enumerate(keys):
         groups.setdefault(k, []).append(i)
@@ -182,24 +224,20 @@ class ConceptAttentionFluxPipeline:
             raise ValueError(f"token_maps = {n}: 1 .. {min(T, _lib.TOKMAP_MAX_TEXT)} (the text length) rows")
         return n, None
 
-    def _token_accumulators(self, n_toks, n_patches: int) -> Optional[list]:
-        """One fp32 [n_tok, n_patches] accumulator per item (None for an item that asks for none); None if no item asks."""
-        if not any(n_toks):
-            return None
-        return [torch.zeros(n, n_patches, device=self.device) if n else None for n in n_toks]
+    def _token_plan(self, prompts, token_maps, n_patches) -> tuple:
+        """(token_acc, tokens) of a call's ``token_maps`` argument: per item a zeroed fp32 [n_tok, n_patches[i]]
+        accumulator and the token strings of its prompt (``_token_request``); (None, None) when no maps are asked for."""
+        if token_maps is None or token_maps is False:
+            return None, None
+        treq = [self._token_request(p, token_maps) for p in prompts]
+        return [torch.zeros(n, p, device=self.device) for (n, _), p in zip(treq, n_patches)], [t for _, t in treq]
 
     @staticmethod
-    def _token_views(token_acc, k: int):
-        """Item k's accumulator as [n_tok, side, side], or None."""
-        if token_acc is None or token_acc[k] is None:
-            return None
-        side = int(round(token_acc[k].shape[1] ** 0.5))
-        return token_acc[k].view(-1, side, side)
-
-    @staticmethod
-    def _device_renderer(heatmap_renderer, heatmap_size, heatmap_interpolation, overlay_alpha) -> bool:
-        """True for heatmap_renderer="device"; ValueError for an unknown renderer or interpolation, an alpha outside
-        [0, 1], or one of the device-only keywords with the host renderer."""
+    def _device_renderer(return_pil_heatmaps, cmap, heatmap_renderer, heatmap_size, heatmap_interpolation,
+                         overlay_alpha) -> tuple:
+        """A call's presentation keywords, checked once, as ``_chunk_outputs`` takes them; the first entry is True when
+        the pictures are made on the device (heatmap_renderer="device" and PIL heat maps asked for).  ValueError for an
+        unknown renderer or interpolation, an alpha outside [0, 1], or a device-only keyword with the host renderer."""
         if heatmap_renderer not in ("host", "device"):
             raise ValueError(f"heatmap_renderer = {heatmap_renderer!r}: \"host\" or \"device\"")
         if heatmap_interpolation not in ("nearest", "bilinear"):
@@ -209,7 +247,23 @@ class ConceptAttentionFluxPipeline:
         if heatmap_renderer == "host" and (heatmap_size is not None or heatmap_interpolation != "nearest" or
                                            overlay_alpha is not None):
             raise ValueError("heatmap_size, heatmap_interpolation and overlay_alpha need heatmap_renderer=\"device\"")
-        return heatmap_renderer == "device"
+        return (heatmap_renderer == "device" and bool(return_pil_heatmaps), return_pil_heatmaps, cmap, heatmap_size,
+                heatmap_interpolation, overlay_alpha)
+
+    def _chunk_outputs(self, idx, images, concept_heatmaps, cross_attention_maps, show, token_acc=None, tokens=None,
+                       pictures=None) -> list:
+        """The one way out of every call: the ConceptAttentionPipelineOutput of the items ``idx`` of a call after their
+        forward.  ``images``: what ``image`` becomes; the two maps [len(idx), C, side, side] on the device; ``show``:
+        ``_device_renderer``'s tuple; ``token_acc`` / ``tokens``: the call's (``_token_plan``); ``pictures``: with an
+        overlay, the chunk's uint8 [H, W, 3] device tensors the maps are laid over."""
+        on_device, return_pil_heatmaps, cmap, heatmap_size, heatmap_interpolation, overlay_alpha = show
+        tok = [None if token_acc is None else token_acc[i].view(-1, *concept_heatmaps.shape[-2:]) for i in idx]
+        tokens = [None if tokens is None else tokens[i] for i in idx]
+        if on_device:
+            return self._finish_device(images, concept_heatmaps, cross_attention_maps, cmap, heatmap_size,
+                                       heatmap_interpolation, overlay_alpha, pictures, tok, tokens)
+        return [self._finish(images[k], concept_heatmaps[k:k + 1], cross_attention_maps[k:k + 1], return_pil_heatmaps, cmap,
+                             tok[k], tokens[k]) for k in range(len(idx))]
 
     def _input_picture(self, image, height: int, width: int) -> torch.Tensor:
         """The bytes of an encode call's input image on the device, for overlays: uint8 [height, width, 3]."""
@@ -267,11 +321,11 @@ class ConceptAttentionFluxPipeline:
             if k in first else None,
             tokens=None if tokens is None else tokens[k]) for k in range(B)]
 
-    def _decode(self, x: torch.Tensor, height: int, width: int):
-        return self.flux_generator.decode(x, height, width)
-
-    def _decode_with_bytes(self, x: torch.Tensor, height: int, width: int):
-        """(PIL images, their uint8 [B, H, W, 3] bytes still on the device) of the B items of ``x``, from one decode."""
+    def _decode(self, x: torch.Tensor, height: int, width: int, with_bytes: bool):
+        """(the images of the B items of ``x``, None), or with ``with_bytes`` (PIL images, their uint8 [B, H, W, 3] bytes
+        still on the device) for an overlay: one decode either way."""
+        if not with_bytes:
+            return self.flux_generator.decode_many(x, height, width), None
         import PIL.Image
         pix = self.flux_generator.decode_pixels(x, height, width)
         host = pix.cpu().numpy()
@@ -309,31 +363,33 @@ class ConceptAttentionFluxPipeline:
         strings, the end-of-string token excluded): the attention the image tokens give that token's key in the double
         blocks ``layer_indices``, mean over heads, layers and ``timesteps`` (DAAM; ops.token_maps); an int n -> the first
         n text rows, ``tokens`` None.  Needs the fused route."""
+        if fused:   # (repeated timestep or layer indices still end on the stacked route: _generate_steps_inner)
+            return self.generate_images(
+                [prompt], [concepts], seeds=[seed], latents=None if latent is None else [latent], width=width, height=height,
+                return_cross_attention=return_cross_attention, layer_indices=layer_indices, cmap=cmap, timesteps=timesteps,
+                return_pil_heatmaps=return_pil_heatmaps, num_inference_steps=num_inference_steps, guidance=guidance,
+                softmax=softmax, attention_norm=attention_norm, heatmap_renderer=heatmap_renderer, heatmap_size=heatmap_size,
+                heatmap_interpolation=heatmap_interpolation, overlay_alpha=overlay_alpha, token_maps=token_maps)[0]
+        norm = self._generate_norm(return_cross_attention, layer_indices, height, width, softmax, attention_norm)
+        check_concept_count(norm, len(concepts))
+        show = self._device_renderer(return_pil_heatmaps, cmap, heatmap_renderer, heatmap_size, heatmap_interpolation,
+                                     overlay_alpha)
+        if self._token_request(prompt, token_maps)[0]:
+            raise ValueError("token_maps needs the fused route (fused=True)")
+        x = latent if latent is not None else sampling.get_noise(1, height, width, self.device, torch.bfloat16, seed)
+        txt, vec, con, con_ids, con_vec = self._embed(prompt, concepts)
+        img, concept_heatmaps, cross_attention_maps = self.generate_on_device(
+            x, txt, vec, con, layer_indices=layer_indices, num_inference_steps=num_inference_steps,
+            guidance=guidance, timesteps=timesteps, fused=False, norm=norm)
+        images, pix = self._decode(img, height, width, show[0] and overlay_alpha is not None)
+        return self._chunk_outputs([0], images, concept_heatmaps, cross_attention_maps, show, pictures=pix)[0]
+
+    def _generate_norm(self, return_cross_attention, layer_indices, height, width, softmax, attention_norm) -> int:
+        """The opening checks of a generate call; the resolved norm."""
         assert return_cross_attention is False, "Not supported yet"
         assert all([0 <= li < self.params.depth for li in layer_indices]), "Invalid layer index"
         assert height == width, "Height and width must be the same for now"
-        norm = resolve_norm(softmax, attention_norm)  # ValueError on an unknown name, as the reference (:70-71)
-        check_concept_count(norm, len(concepts))
-        on_device = self._device_renderer(heatmap_renderer, heatmap_size, heatmap_interpolation, overlay_alpha)
-        n_tok, tokens = self._token_request(prompt, token_maps)
-        if n_tok and not fused:
-            raise ValueError("token_maps needs the fused route (fused=True)")
-        if timesteps is None:
-            timesteps = list(range(num_inference_steps))
-        x = latent if latent is not None else sampling.get_noise(1, height, width, self.device, torch.bfloat16, seed)
-        txt, vec, con, con_ids, con_vec = self._embed(prompt, concepts)
-        token_acc = self._token_accumulators([n_tok], (x.shape[-1] // 2) * (x.shape[-2] // 2))
-        img, concept_heatmaps, cross_attention_maps = self.generate_on_device(
-            x, txt, vec, con, layer_indices=layer_indices, num_inference_steps=num_inference_steps,
-            guidance=guidance, timesteps=timesteps, fused=fused, norm=norm, token_acc=token_acc)
-        tok = self._token_views(token_acc, 0)
-        if on_device and return_pil_heatmaps:
-            images, pix = self._decode_with_bytes(img, height, width) if overlay_alpha is not None else \
-                ([self._decode(img, height, width)], None)
-            return self._finish_device(images, concept_heatmaps, cross_attention_maps, cmap, heatmap_size,
-                                       heatmap_interpolation, overlay_alpha, pix, [tok], [tokens])[0]
-        image = self._decode(img, height, width)
-        return self._finish(image, concept_heatmaps, cross_attention_maps, return_pil_heatmaps, cmap, tok, tokens)
+        return resolve_norm(softmax, attention_norm)  # ValueError on an unknown name, as the reference (:70-71)
 
     @torch.no_grad()
     @on_own_device
@@ -347,16 +403,8 @@ class ConceptAttentionFluxPipeline:
         ``n_streams`` groups are kept in flight on separate HIP streams, each with its own activation set and the
         shared weights.  Every item's result is bit-identical to ``generate_on_device`` on that item alone.
         Returns [(img, heat, cross), ...] in item order."""
-        batch = max(1, min(batch, _lib.ATTN_MAX_PROBLEMS // 2, _lib.MAX_SEGMENTS // 3))  # launch limits: 5 items
-        groups = [list(range(g0, min(g0 + batch, len(items)))) for g0 in range(0, len(items), batch)]
-        n_streams = max(1, min(n_streams, len(groups)))
-        self._stream_models(n_streams)
-        cur = torch.cuda.current_stream(self.device)
-        self.model.materialize()  # shared fp8 weight images: built on `cur`, which every side stream waits on
+        groups, n_streams, cur, cat = self._fan_out(items, n_streams, batch)
         results = [None] * len(items)
-
-        def cat(idx, key):
-            return torch.cat([items[i][key] for i in idx], 0) if len(idx) > 1 else items[idx[0]][key]
         for w0 in range(0, len(groups), n_streams):
             wave = groups[w0:w0 + n_streams]
             gens = {}
@@ -380,12 +428,30 @@ class ConceptAttentionFluxPipeline:
             for slot, idx in enumerate(wave):
                 img, hm, cm = done[slot]
                 if n_streams > 1:
-                    cur.wait_stream(self._streams[slot])
-                    for t in (img, hm, cm):  # allocated on the side stream, consumed on the caller's stream
-                        t.record_stream(cur)
+                    self._hand_back(cur, [self._streams[slot]], (img, hm, cm))
                 for k, i in enumerate(idx):
                     results[i] = (img[k:k + 1], hm[k:k + 1], cm[k:k + 1])
         return results
+
+    def _fan_out(self, items, n_streams: int, batch: int):
+        """The prologue of the two throughput calls: (groups, n_streams, cur, cat) -- the item indices of every forward
+        (``batch`` items, at most MAX_ITEMS_PER_FORWARD), the number of streams in use with their models ready
+        (``_stream_models``), the caller's stream, and cat(idx, key): the items' ``key`` tensors along the item axis."""
+        batch = items_per_forward(batch)
+        groups = [list(range(g0, min(g0 + batch, len(items)))) for g0 in range(0, len(items), batch)]
+        n_streams = max(1, min(n_streams, len(groups)))
+        self._stream_models(n_streams)
+        cur = torch.cuda.current_stream(self.device)
+        self.model.materialize()  # shared fp8 weight images: built on `cur`, which every side stream waits on
+        return groups, n_streams, cur, lambda idx, key: _cat(items[i][key] for i in idx)
+
+    @staticmethod
+    def _hand_back(cur, streams, tensors):
+        """``cur`` waits for the side ``streams``; the result tensors were allocated there and are consumed on ``cur``."""
+        for st in streams:
+            cur.wait_stream(st)
+        for t in tensors:
+            t.record_stream(cur)
 
     @torch.no_grad()
     @on_own_device
@@ -504,7 +570,7 @@ class ConceptAttentionFluxPipeline:
         out = torch.zeros(nl, nlay, C, n_patches, device=self.device)
         cross = torch.zeros(nl, nlay, C, n_patches, device=self.device)
         height, width = latent.shape[-2] * 8, latent.shape[-1] * 8
-        batch = max(1, min(batch, _lib.ATTN_MAX_PROBLEMS // 2, _lib.MAX_SEGMENTS // 3))
+        batch = items_per_forward(batch)
         mine = list(range(rank, nl, world))
         for g0 in range(0, len(mine), batch):
             grp = mine[g0:g0 + batch]
@@ -538,11 +604,8 @@ class ConceptAttentionFluxPipeline:
         Returns the two DEVICE tables (out_space, cross_space), fp32 [len(noise_levels), len(layer_indices), C, side,
         side]; ``batch`` levels share one forward."""
         assert height == width, "Height and width must be the same for now"
-        if isinstance(image, torch.Tensor):
-            latent = image.to(self.device, torch.bfloat16)
-        else:
-            latent = self._encode_pixels([image], height, width,
-                                         None if vae_noise is None else vae_noise.to(self.device, torch.float32))
+        latent = image.to(self.device, torch.bfloat16) if isinstance(image, torch.Tensor) else \
+            self._encode_pixels([image], height, width, vae_noise)
         txt, vec, con, _, _ = self._embed(prompt, concepts)
         return self.layer_noise_sweep_on_device(latent, txt, vec, con, [int(v) for v in noise_levels], num_steps=num_steps,
                                                 layer_indices=layer_indices, seed=seed, num_samples=num_samples,
@@ -569,37 +632,24 @@ class ConceptAttentionFluxPipeline:
         given), so that a call is reproducible.  ``heatmap_renderer`` and the three keywords behind it: as in
         ``generate_image``; the overlays are laid over the INPUT image's bytes, which must already be height x width.
         ``token_maps``: as in ``generate_image`` (the mean runs over heads, layers and noise samples)."""
-        assert all([0 <= li < self.params.depth for li in layer_indices]), "Invalid layer index"
-        assert height == width, "Height and width must be the same for now"
-        norm = resolve_norm(softmax, attention_norm)
-        check_concept_count(norm, len(concepts))
-        on_device = self._device_renderer(heatmap_renderer, heatmap_size, heatmap_interpolation, overlay_alpha)
-        n_tok, tokens = self._token_request(prompt, token_maps)
-        picture = self._input_picture(image, height, width) if on_device and overlay_alpha is not None and \
-            return_pil_heatmaps else None
-        if isinstance(image, torch.Tensor):
-            latent = image.to(self.device, torch.bfloat16)
-        else:
-            latent = self._encode_pixels([image], height, width, vae_noise)
-        txt, vec, con, con_ids, con_vec = self._embed(prompt, concepts)
-        token_acc = self._token_accumulators([n_tok], (latent.shape[-1] // 2) * (latent.shape[-2] // 2))
-        out_space, cross_space = self._encode_maps(self.model, latent, txt, vec, con, con_ids, con_vec, layer_indices,
-                                                   num_samples, num_steps, noise_timestep, seed,
-                                                   stop_after_multi_modal_attentions, joint_attention_kwargs, norm,
-                                                   noise=noise, token_acc=token_acc)
-        tok = self._token_views(token_acc, 0)
-        if on_device and return_pil_heatmaps:
-            return self._finish_device([image], out_space, cross_space, cmap, heatmap_size, heatmap_interpolation,
-                                       overlay_alpha, None if picture is None else [picture], [tok], [tokens])[0]
-        return self._finish(image, out_space, cross_space, return_pil_heatmaps, cmap, tok, tokens)
+        return self.encode_images(
+            [image], [concepts], [prompt], width=width, height=height, layer_indices=layer_indices, num_samples=num_samples,
+            num_steps=num_steps, noise_timestep=noise_timestep, seed=seed, noise=None if noise is None else [noise],
+            vae_noise=None if vae_noise is None else [vae_noise], return_pil_heatmaps=return_pil_heatmaps, cmap=cmap,
+            stop_after_multi_modal_attentions=stop_after_multi_modal_attentions, attention_norm=attention_norm,
+            softmax=softmax, joint_attention_kwargs=joint_attention_kwargs, heatmap_renderer=heatmap_renderer,
+            heatmap_size=heatmap_size, heatmap_interpolation=heatmap_interpolation, overlay_alpha=overlay_alpha,
+            token_maps=token_maps)[0]
 
     def _encode_pixels(self, images, height: int, width: int, vae_noise=None) -> torch.Tensor:
         """PIL images -> bf16 latents (B,16,h/8,w/8).  The HIP autoencoder takes the bytes (``encode_pixels``: resize,
         scaling and cast in one kernel per image); an injected object with ``encode`` alone gets the reference's fp32
-        image tensor."""
+        image tensor.  ``vae_noise`` (B,16,h/8,w/8) comes to the device as fp32 here, for every caller."""
         if self.autoencoder is None:
             raise ValueError("encode_image needs a latent tensor, or a pipeline built with autoencoder=\"synthetic\", a "
                              ".safetensors path or an object with encode / decode")
+        if vae_noise is not None:
+            vae_noise = vae_noise.to(self.device, torch.float32)
         arrays = [np.asarray(im.convert("RGB")) for im in images]
         if hasattr(self.autoencoder, "encode_pixels"):
             return self.autoencoder.encode_pixels(arrays, height, width, noise=vae_noise).to(torch.bfloat16)
@@ -610,13 +660,13 @@ class ConceptAttentionFluxPipeline:
         kw = {} if vae_noise is None else {"noise": vae_noise}
         return self.autoencoder.encode(torch.cat(xs), **kw).to(torch.bfloat16)
 
-    def _encode_maps(self, model, latent, txt, vec, con, con_ids, con_vec, layer_indices, num_samples, num_steps,
-                     noise_timestep, seed, stop_after_multi_modal_attentions=True, joint_attention_kwargs=None,
-                     norm: int = 0, noise=None, token_acc=None):
+    def _encode_maps(self, model, latent, txt, vec, con, con_ids, con_vec, settings: EncodeSettings, *, noise=None,
+                     token_acc=None):
         """Device core of encode_image for B images at once (latent (B,16,h,w), txt (B,T,4096), ...): one forward
         per noise sample on ``model``; returns the two fp32 maps [B, C, side, side].  ``noise``: optional list of
         num_samples tensors (1 or B,16,h,w) used instead of get_noise(seed + i).  ``token_acc``: per item, the caller's
         zeroed fp32 [n_tok, patches] accumulator of the prompt-token maps (or None); the return tuple stays."""
+        layer_indices, num_samples, noise_timestep = settings.layer_indices, settings.num_samples, settings.noise_timestep
         if noise is not None and len(noise) != num_samples:
             raise ValueError("noise: one tensor per noise sample")
         B, C = con.shape[0], con.shape[1]
@@ -630,13 +680,13 @@ class ConceptAttentionFluxPipeline:
         acc_o = torch.zeros(B, C, n_patches, device=self.device)
         acc_c = torch.zeros(B, C, n_patches, device=self.device)
         req = [HeatmapRequest(tuple(int(l) for l in layer_indices), 1.0 / (num_samples * len(layer_indices)),
-                              acc_o[j], acc_c[j], norm=norm, token_space=None if token_acc is None else token_acc[j])
+                              acc_o[j], acc_c[j], norm=settings.norm, token_space=None if token_acc is None else token_acc[j])
                for j in range(B)]
-        schedule = sampling.get_schedule(num_steps, n_patches, shift=(not self.is_schnell))
+        schedule = sampling.get_schedule(settings.num_steps, n_patches, shift=(not self.is_schnell))
         for i in range(num_samples):
             # add_noise_to_image (concept_attention/segmentation.py:85-113)
             nz = (noise[i].to(self.device, torch.bfloat16) if noise is not None
-                  else sampling.get_noise(1, height, width, self.device, torch.bfloat16, seed + i))
+                  else sampling.get_noise(1, height, width, self.device, torch.bfloat16, settings.seed + i))
             t = schedule[noise_timestep]
             x = (t * nz.float() + (1.0 - t) * latent.float()).to(torch.bfloat16)
             inp = sampling.prepare_from_embeddings(x, txt, vec)
@@ -644,8 +694,8 @@ class ConceptAttentionFluxPipeline:
             model(img=inp["img"], img_ids=inp["img_ids"], txt=inp["txt"], txt_ids=inp["txt_ids"],
                   concepts=con, concept_ids=con_ids, concept_vec=con_vec, y=con_vec, timesteps=t_vec,
                   guidance=torch.zeros(B, device=self.device),
-                  stop_after_multimodal_attentions=stop_after_multi_modal_attentions,
-                  joint_attention_kwargs=joint_attention_kwargs, return_vectors=False, heatmaps=req)
+                  stop_after_multimodal_attentions=settings.stop_after_multi_modal_attentions,
+                  joint_attention_kwargs=settings.joint_attention_kwargs, return_vectors=False, heatmaps=req)
         side = int(round(n_patches ** 0.5))
         return acc_o.view(B, C, side, side), acc_c.view(B, C, side, side)
 
@@ -654,41 +704,38 @@ class ConceptAttentionFluxPipeline:
         enc = self.text_encoder
         return int(getattr(enc, "max_length", getattr(enc, "n_tokens", 0)))
 
-    def _encode_chunks(self, images, concepts, prompts, width, height, layer_indices, num_samples, num_steps,
-                       noise_timestep, seed, batch, noise, vae_noise, stop_after_multi_modal_attentions, attention_norm,
-                       softmax, joint_attention_kwargs, token_acc=None):
+    def _embed_chunk(self, prompts, concepts, idx, n_out: int = 5) -> tuple:
+        """The first ``n_out`` of (txt, vec, con, con_ids, con_vec) for the items ``idx`` of a call, along the item axis:
+        one text-encoder call (``FluxGenerator.embed_many``)."""
+        emb = self.flux_generator.embed_many([prompts[i] for i in idx], [concepts[i] for i in idx])
+        return tuple(_cat(e[k] for e in emb) for k in range(n_out))
+
+    def _encode_chunks(self, images, concepts, prompts, settings: EncodeSettings, *, noise=None, vae_noise=None,
+                       token_acc=None):
         """The forwards of ``encode_images``, one at a time: yields (item indices, acc_o, acc_c) with the two fp32 maps
-        [len(indices), C, side, side] of the chunk still on the device (``_encode_maps``).  ``images`` is a list.
+        [len(indices), C, side, side] of the chunk still on the device (``_encode_maps``).  ``images`` and ``prompts`` are lists;
+        ``settings`` was built with the call's largest concept count; ``noise`` / ``vae_noise``: as ``encode_images`` takes them;
         ``token_acc``: per item of the call, the caller's accumulator of the prompt-token maps (or None)."""
-        assert all([0 <= li < self.params.depth for li in layer_indices]), "Invalid layer index"
-        assert height == width, "Height and width must be the same for now"
-        norm = resolve_norm(softmax, attention_norm)
-        n = len(images)
-        prompts = [prompts] * n if isinstance(prompts, str) else list(prompts)
+        n, height, width = len(images), settings.height, settings.width
         concepts = _per_item(concepts, n, "encode_images: concepts")
-        check_concept_count(norm, max((len(c) for c in concepts), default=0))
         for name, v in (("prompts", prompts), ("noise", noise), ("vae_noise", vae_noise)):
             if v is not None and len(v) != n:
                 raise ValueError(f"encode_images: {name} has {len(v)} entries for {n} images")
         shapes = [tuple(im.shape[1:]) if isinstance(im, torch.Tensor) else (16, height // 8, width // 8) for im in images]
-        for idx in plan_batches([(shapes[i], len(concepts[i]), self._text_length()) for i in range(n)], batch):
-            emb = self.flux_generator.embed_many([prompts[i] for i in idx], [concepts[i] for i in idx])
-            txt, vec, con, con_ids, con_vec = (torch.cat([e[k] for e in emb], 0) if len(idx) > 1 else emb[0][k]
-                                               for k in range(5))
+        for idx in plan_batches([(shapes[i], len(concepts[i]), self._text_length()) for i in range(n)], settings.batch):
+            txt, vec, con, con_ids, con_vec = self._embed_chunk(prompts, concepts, idx)
             pil = [i for i in idx if not isinstance(images[i], torch.Tensor)]
             lat = {}
             if pil:
-                vn = None if vae_noise is None else torch.cat([vae_noise[i].to(self.device, torch.float32) for i in pil], 0)
-                enc = self._encode_pixels([images[i] for i in pil], height, width, vn)
+                enc = self._encode_pixels([images[i] for i in pil], height, width,
+                                          None if vae_noise is None else _cat(vae_noise[i] for i in pil))
                 lat = {i: enc[k:k + 1] for k, i in enumerate(pil)}
-            latent = torch.cat([lat[i] if i in lat else images[i].to(self.device, torch.bfloat16) for i in idx], 0)
-            if noise is not None and any(len(noise[i]) != num_samples for i in idx):
+            latent = _cat(lat[i] if i in lat else images[i].to(self.device, torch.bfloat16) for i in idx)
+            if noise is not None and any(len(noise[i]) != settings.num_samples for i in idx):
                 raise ValueError("noise: one tensor per noise sample")
-            nz = None if noise is None else [torch.cat([noise[i][s_].to(self.device, torch.bfloat16) for i in idx], 0)
-                                             for s_ in range(num_samples)]
-            ho, hc = self._encode_maps(self.model, latent, txt, vec, con, con_ids, con_vec, layer_indices, num_samples,
-                                       num_steps, noise_timestep, seed, stop_after_multi_modal_attentions,
-                                       joint_attention_kwargs, norm, noise=nz,
+            nz = None if noise is None else [_cat(noise[i][s_].to(self.device, torch.bfloat16) for i in idx)
+                                             for s_ in range(settings.num_samples)]
+            ho, hc = self._encode_maps(self.model, latent, txt, vec, con, con_ids, con_vec, settings, noise=nz,
                                        token_acc=None if token_acc is None else [token_acc[i] for i in idx])
             yield idx, ho, hc
 
@@ -712,35 +759,25 @@ class ConceptAttentionFluxPipeline:
         a chunk come from one launch and one download (``_finish_device``).  ``token_maps``: as in ``encode_image``, for
         every item's own prompt (the items of a chunk may have different numbers of tokens)."""
         images = list(images)
-        results = [None] * len(images)
-        plist = [prompts] * len(images) if isinstance(prompts, str) else list(prompts)
-        treq = [self._token_request(p, token_maps) for p in plist] if token_maps is not None and token_maps is not False else []
-        token_acc = None
-        if treq:
-            token_acc = [self._token_accumulators(
-                [n], (im.shape[-1] // 2) * (im.shape[-2] // 2) if isinstance(im, torch.Tensor)
-                else (height // 16) * (width // 16))[0] for (n, _), im in zip(treq, images)]
-        tokens = [t for _, t in treq] if treq else None
-        on_device = self._device_renderer(heatmap_renderer, heatmap_size, heatmap_interpolation, overlay_alpha) and \
-            return_pil_heatmaps
-        pictures = [self._input_picture(im, height, width) for im in images] if on_device and overlay_alpha is not None \
+        n = len(images)
+        prompts = [prompts] * n if isinstance(prompts, str) else list(prompts)
+        concepts = _per_item(concepts, n, "encode_images: concepts")
+        settings = EncodeSettings(layer_indices, num_samples, num_steps, noise_timestep, seed, width, height, batch,
+                                  stop_after_multi_modal_attentions, joint_attention_kwargs, attention_norm, softmax,
+                                  depth=self.params.depth, n_concepts=max((len(c) for c in concepts), default=0))
+        show = self._device_renderer(return_pil_heatmaps, cmap, heatmap_renderer, heatmap_size, heatmap_interpolation,
+                                     overlay_alpha)
+        token_acc, tokens = self._token_plan(prompts, token_maps, [
+            (im.shape[-1] // 2) * (im.shape[-2] // 2) if isinstance(im, torch.Tensor) else (height // 16) * (width // 16)
+            for im in images])
+        pictures = [self._input_picture(im, height, width) for im in images] if show[0] and overlay_alpha is not None \
             else None
-        for idx, ho, hc in self._encode_chunks(images, concepts, prompts, width, height, layer_indices, num_samples,
-                                               num_steps, noise_timestep, seed, batch, noise, vae_noise,
-                                               stop_after_multi_modal_attentions, attention_norm, softmax,
-                                               joint_attention_kwargs, **({"token_acc": token_acc} if treq else {})):
-            if on_device:
-                outs = self._finish_device([images[i] for i in idx], ho, hc, cmap, heatmap_size, heatmap_interpolation,
-                                           overlay_alpha, None if pictures is None else [pictures[i] for i in idx],
-                                           [self._token_views(token_acc, i) for i in idx],
-                                           None if tokens is None else [tokens[i] for i in idx])
-                for k, i in enumerate(idx):
-                    results[i] = outs[k]
-                continue
-            for k, i in enumerate(idx):
-                results[i] = self._finish(images[i], ho[k:k + 1], hc[k:k + 1], return_pil_heatmaps, cmap,
-                                          self._token_views(token_acc, i), None if tokens is None else tokens[i])
-        return results
+        results = {}
+        for idx, ho, hc in self._encode_chunks(images, concepts, prompts, settings, noise=noise, vae_noise=vae_noise,
+                                               token_acc=token_acc):
+            results.update(zip(idx, self._chunk_outputs(idx, [images[i] for i in idx], ho, hc, show, token_acc, tokens,
+                                                        None if pictures is None else [pictures[i] for i in idx])))
+        return [results[i] for i in range(n)]
 
     @torch.no_grad()
     @on_own_device
@@ -756,12 +793,9 @@ class ConceptAttentionFluxPipeline:
         0, 1, 2, ...).  Items with one concept count go ``batch`` (at most 5) at a time through one text-encoder call,
         one denoising loop and one autoencoder pass whose bytes are made on the device.  ``token_maps``: as in
         ``generate_image``, for every item's own prompt (the items of a chunk may have different numbers of tokens)."""
-        assert return_cross_attention is False, "Not supported yet"
-        assert all([0 <= li < self.params.depth for li in layer_indices]), "Invalid layer index"
-        assert height == width, "Height and width must be the same for now"
-        norm = resolve_norm(softmax, attention_norm)
-        on_device = self._device_renderer(heatmap_renderer, heatmap_size, heatmap_interpolation, overlay_alpha) and \
-            return_pil_heatmaps
+        norm = self._generate_norm(return_cross_attention, layer_indices, height, width, softmax, attention_norm)
+        show = self._device_renderer(return_pil_heatmaps, cmap, heatmap_renderer, heatmap_size, heatmap_interpolation,
+                                     overlay_alpha)
         prompts = list(prompts)
         n = len(prompts)
         concepts = _per_item(concepts, n, "generate_images: concepts")
@@ -770,37 +804,20 @@ class ConceptAttentionFluxPipeline:
         for name, v in (("seeds", seeds), ("latents", latents)):
             if v is not None and len(v) != n:
                 raise ValueError(f"generate_images: {name} has {len(v)} entries for {n} prompts")
-        if timesteps is None:
-            timesteps = list(range(num_inference_steps))
         shapes = [(16, height // 8, width // 8) if latents is None else tuple(latents[i].shape[1:]) for i in range(n)]
-        results = [None] * n
-        treq = [self._token_request(p, token_maps) for p in prompts] if token_maps is not None and token_maps is not False else []
-        token_acc = [self._token_accumulators([nt], (shapes[i][1] // 2) * (shapes[i][2] // 2))[0]
-                     for i, (nt, _) in enumerate(treq)] if treq else None
-        tokens = [t for _, t in treq] if treq else None
+        token_acc, tokens = self._token_plan(prompts, token_maps, [(s[1] // 2) * (s[2] // 2) for s in shapes])
+        results = {}
         for idx in plan_batches([(shapes[i], len(concepts[i]), self._text_length()) for i in range(n)], batch):
-            emb = self.flux_generator.embed_many([prompts[i] for i in idx], [concepts[i] for i in idx])
-            txt, vec, con = (torch.cat([e[k] for e in emb], 0) if len(idx) > 1 else emb[0][k] for k in range(3))
-            x = torch.cat([latents[i].to(self.device, torch.bfloat16) if latents is not None else
-                           sampling.get_noise(1, height, width, self.device, torch.bfloat16, seeds[i]) for i in idx], 0)
+            txt, vec, con = self._embed_chunk(prompts, concepts, idx, 3)
+            x = _cat(latents[i].to(self.device, torch.bfloat16) if latents is not None else
+                     sampling.get_noise(1, height, width, self.device, torch.bfloat16, seeds[i]) for i in idx)
             img, ho, hc = self.generate_on_device(x, txt, vec, con, layer_indices=layer_indices,
                                                   num_inference_steps=num_inference_steps, guidance=guidance,
                                                   timesteps=timesteps, fused=True, norm=norm,
                                                   token_acc=None if token_acc is None else [token_acc[i] for i in idx])
-            if on_device:
-                pictures, pix = self._decode_with_bytes(img, height, width) if overlay_alpha is not None else \
-                    (self.flux_generator.decode_many(img, height, width), None)
-                outs = self._finish_device(pictures, ho, hc, cmap, heatmap_size, heatmap_interpolation, overlay_alpha, pix,
-                                           [self._token_views(token_acc, i) for i in idx],
-                                           None if tokens is None else [tokens[i] for i in idx])
-                for k, i in enumerate(idx):
-                    results[i] = outs[k]
-                continue
-            pictures = self.flux_generator.decode_many(img, height, width)
-            for k, i in enumerate(idx):
-                results[i] = self._finish(pictures[k], ho[k:k + 1], hc[k:k + 1], return_pil_heatmaps, cmap,
-                                          self._token_views(token_acc, i), None if tokens is None else tokens[i])
-        return results
+            pictures, pix = self._decode(img, height, width, show[0] and overlay_alpha is not None)
+            results.update(zip(idx, self._chunk_outputs(idx, pictures, ho, hc, show, token_acc, tokens, pix)))
+        return [results[i] for i in range(n)]
 
     @torch.no_grad()
     @on_own_device
@@ -813,29 +830,19 @@ class ConceptAttentionFluxPipeline:
         dealt round-robin to ``n_streams`` HIP streams, each with its own activation set (the same throughput
         mode as generate_many_on_device).  Returns [(heat [1,C,s,s], cross [1,C,s,s]), ...], identical to
         encoding the items one by one."""
-        batch = max(1, min(batch, _lib.ATTN_MAX_PROBLEMS // 2, _lib.MAX_SEGMENTS // 3))
-        groups = [list(range(g0, min(g0 + batch, len(items)))) for g0 in range(0, len(items), batch)]
-        n_streams = max(1, min(n_streams, len(groups)))
-        self._stream_models(n_streams)
-        cur = torch.cuda.current_stream(self.device)
-        self.model.materialize()  # shared fp8 weight images: built on `cur`, which every side stream waits on
+        settings = EncodeSettings(layer_indices, num_samples, num_steps, noise_timestep, seed)
+        groups, n_streams, cur, cat = self._fan_out(items, n_streams, batch)
         for st in self._streams[:n_streams]:
             st.wait_stream(cur)
         results = [None] * len(items)
         for gi, idx in enumerate(groups):   # ``batch`` images share every launch of a forward (see generate_many)
             slot = gi % n_streams
             with torch.cuda.stream(self._streams[slot]):
-                def cat(key):
-                    return torch.cat([items[i][key] for i in idx], 0) if len(idx) > 1 else items[idx[0]][key]
-                latent = cat("latent").to(self.device, torch.bfloat16)
-                con, con_ids, con_vec = sampling.concept_inputs(cat("concepts"), cat("vec"))
-                ho, hc = self._encode_maps(self._replicas[slot], latent, cat("txt"), cat("vec"), con, con_ids, con_vec,
-                                           layer_indices, num_samples, num_steps, noise_timestep, seed, noise=noise)
+                latent = cat(idx, "latent").to(self.device, torch.bfloat16)
+                con, con_ids, con_vec = sampling.concept_inputs(cat(idx, "concepts"), cat(idx, "vec"))
+                ho, hc = self._encode_maps(self._replicas[slot], latent, cat(idx, "txt"), cat(idx, "vec"), con, con_ids,
+                                           con_vec, settings, noise=noise)
                 for k, i in enumerate(idx):
                     results[i] = (ho[k:k + 1], hc[k:k + 1])
-        for st in self._streams[:n_streams]:
-            cur.wait_stream(st)
-        for pair in results:
-            for t in pair:
-                t.record_stream(cur)
+        self._hand_back(cur, self._streams[:n_streams], [t for pair in results for t in pair])
         return results

@@ -20,12 +20,14 @@ scores its own images and ``SegmentationScores.all_reduce`` sums the five counte
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, fields
 
 import numpy as np
 import torch
 
-from . import sampling
+from . import _lib as L
+from . import ops, sampling
+from .pipeline import EncodeSettings
 
 
 # ------------------------------------------------------------------------------------------ noise
@@ -515,30 +517,44 @@ class DeviceMultiClassScores(_DeviceRows):
         return self.to_host().result()
 
 
-# what score_images and the multi-class methods accept as **encode_kwargs
-_ENCODE_KEYS = {"layers", "num_samples", "num_steps", "noise_timestep", "seed", "height", "width", "batch",
-                "joint_attention_kwargs", "noise", "vae_noise", "attention_norm", "softmax"}
+# what score_images and the multi-class methods accept as **encode_kwargs: the settings a caller chooses under the harness's
+# names (``layers`` for layer_indices), and the per-call ``noise`` / ``vae_noise``
+_ENCODE_KEYS = {"layers", "noise", "vae_noise"} | {f.name for f in fields(EncodeSettings) if f.init} - {
+    "layer_indices", "stop_after_multi_modal_attentions"}
 
 
-def _encode_chunks(pipe, images, concepts, captions, kw: dict):
-    """``pipe._encode_chunks`` with the defaults of ``encode_kwargs`` (keys of _ENCODE_KEYS) and the accumulators kept on
-    the device."""
-    return pipe._encode_chunks(images, concepts, list(captions[:len(images)]), kw.get("width", 1024), kw.get("height", 1024),
-                               kw.get("layers", list(range(15, 19))), kw.get("num_samples", 1), kw.get("num_steps", 4),
-                               kw.get("noise_timestep", 2), kw.get("seed", 0), kw.get("batch", 5), kw.get("noise"),
-                               kw.get("vae_noise"), True, kw.get("attention_norm", "sparsemax"), kw.get("softmax", True),
-                               kw.get("joint_attention_kwargs"))
+def encode_settings(kw: dict, what: str = "encode_settings", pipeline=None, concepts=()) -> EncodeSettings:
+    """The settings record of a harness call's keywords ``kw`` (keys of _ENCODE_KEYS; ``noise`` / ``vae_noise`` are not
+    settings and stay in ``kw``), with EncodeSettings' defaults and checks: against ``pipeline``'s depth and the per-item
+    ``concepts`` lists where they are given.  TypeError, under the name ``what``, for any other key."""
+    unknown = set(kw) - _ENCODE_KEYS
+    if unknown:
+        raise TypeError(f"{what}: unexpected arguments {sorted(unknown)}")
+    given = {"layer_indices" if k == "layers" else k: v for k, v in kw.items() if k not in ("noise", "vae_noise")}
+    return EncodeSettings(**given, depth=None if pipeline is None else pipeline.params.depth,
+                          n_concepts=max((len(c) for c in concepts), default=0))
 
 
-def _binary_labels(labels, size: int) -> list:
-    """score_images' and score_sweep's labels as uint8 arrays (size, size), nonzero = positive."""
+def _encode_chunks(pipe, images, concepts, captions, settings: EncodeSettings, kw: dict):
+    """``pipe._encode_chunks`` for a harness call (``kw``: its encode_kwargs): the accumulators stay on the device."""
+    return pipe._encode_chunks(images, concepts, list(captions[:len(images)]), settings, noise=kw.get("noise"),
+                               vae_noise=kw.get("vae_noise"))
+
+
+def _scoring_inputs(concepts, target_concepts, labels, size: int, apply_blur: bool) -> tuple:
+    """(per_item, target, lab, blur) of score_images and score_sweep: every item's concept list (``concepts``: one list for
+    all items or one per item), the index of its target concept in it (ValueError when missing), its label as a uint8 array
+    (size, size), nonzero = positive (ValueError naming ``labels[i]`` otherwise), and the device's blur weights or None."""
+    n = len(target_concepts)
+    per_item = list(concepts) if concepts and not isinstance(concepts[0], str) else [list(concepts)] * n
+    target = [per_item[i].index(target_concepts[i]) for i in range(n)]
     lab = []
     for i, y in enumerate(labels):
         y = np.asarray(_np(y))
         if y.shape != (size, size) or y.dtype not in (np.uint8, np.bool_):
             raise ValueError(f"labels[{i}]: expected a uint8 / bool array ({size}, {size}), got {y.dtype} {y.shape}")
         lab.append(y.astype(np.uint8, copy=False))
-    return lab
+    return per_item, target, lab, ops.seg_blur_weights() if apply_blur else None
 
 
 # ------------------------------------------------------------------------------------------ model wrapper
@@ -556,12 +572,8 @@ class ConceptAttentionSegmentationModel:
                                  num_steps: int = 4, noise_timestep: int = 2, seed: int = 0, height: int = 1024,
                                  width: int = 1024, target_space: str = "output", joint_attention_kwargs=None,
                                  **_unused):
-        out = self.pipeline.encode_image(image, concepts, prompt=caption, width=width, height=height,
-                                         layer_indices=layers, num_samples=num_samples, num_steps=num_steps,
-                                         noise_timestep=noise_timestep, seed=seed, return_pil_heatmaps=False,
-                                         joint_attention_kwargs=joint_attention_kwargs)
-        maps = out.concept_heatmaps if target_space == "output" else out.cross_attention_maps
-        return torch.as_tensor(np.asarray(maps), dtype=torch.float32), None
+        return self.segment_images([image], [concepts], [caption], layers, num_samples, num_steps, noise_timestep, seed, height,
+                                   width, target_space, joint_attention_kwargs)[0]   # (encode_image is encode_images of one)
 
     @torch.no_grad()
     def segment_images(self, images, concepts, captions, layers=list(range(15, 19)), num_samples: int = 1,
@@ -570,12 +582,17 @@ class ConceptAttentionSegmentationModel:
                        **_unused):
         """``segment_individual_image`` for a list of images through ``pipeline.encode_images``: up to ``batch`` images
         per forward, every image with the coefficients of its own call."""
-        outs = self.pipeline.encode_images(images, concepts, list(captions[:len(images)]), width=width, height=height,
-                                           layer_indices=layers, num_samples=num_samples, num_steps=num_steps,
-                                           noise_timestep=noise_timestep, seed=seed, batch=batch,
-                                           return_pil_heatmaps=False, joint_attention_kwargs=joint_attention_kwargs)
-        return [(torch.as_tensor(np.asarray(o.concept_heatmaps if target_space == "output" else o.cross_attention_maps),
-                                 dtype=torch.float32), None) for o in outs]
+        kw = dict(layers=layers, num_samples=num_samples, num_steps=num_steps, noise_timestep=noise_timestep, seed=seed,
+                  height=height, width=width, joint_attention_kwargs=joint_attention_kwargs, batch=batch)
+        return [(maps, None) for maps in self._encoded_maps(images, concepts, captions, encode_settings(kw), kw, target_space)]
+
+    def _encoded_maps(self, images, concepts, captions, settings: EncodeSettings, kw: dict, target_space: str) -> list:
+        """Per image the fp32 maps (C, side, side) of ``target_space`` on the host, from ``pipeline.encode_images`` under
+        ``settings`` and the ``noise`` / ``vae_noise`` of the encode_kwargs ``kw``."""
+        outs = self.pipeline.encode_images(images, concepts, list(captions[:len(images)]), noise=kw.get("noise"),
+                                           vae_noise=kw.get("vae_noise"), return_pil_heatmaps=False, **settings.keywords())
+        return [torch.as_tensor(np.asarray(o.concept_heatmaps if target_space == "output" else o.cross_attention_maps),
+                                dtype=torch.float32) for o in outs]
 
     @torch.no_grad()
     def score_images(self, images, target_concepts, concepts, captions, labels, scores, size: int = 224,
@@ -591,7 +608,6 @@ class ConceptAttentionSegmentationModel:
         then ``(all_masks, all_coefficients)`` as ``__call__`` returns them, at map resolution (one download at the end).
         Maps of more than 4096 cells raise a ValueError: ``__call__`` + ``prepare_for_scoring`` +
         ``SegmentationScores.update`` remain for them, and for ``target_concepts=None``."""
-        from . import ops
         if target_concepts is None:
             raise ValueError("score_images scores one target concept per image; multi-class masks go through __call__")
         images = list(images)
@@ -601,17 +617,11 @@ class ConceptAttentionSegmentationModel:
         if target_space not in ("output", "cross_attention"):
             raise ValueError("target_space: 'output' or 'cross_attention'")
         pipe = self.pipeline
-        per_item = list(concepts) if concepts and not isinstance(concepts[0], str) else [list(concepts)] * n
-        target = [per_item[i].index(target_concepts[i]) for i in range(n)]
-        lab = _binary_labels(labels, size)
-        kw = dict(encode_kwargs)
-        unknown = set(kw) - _ENCODE_KEYS
-        if unknown:
-            raise TypeError(f"score_images: unexpected arguments {sorted(unknown)}")
-        blur = ops.seg_blur_weights() if apply_blur else None
+        per_item, target, lab, blur = _scoring_inputs(concepts, target_concepts, labels, size, apply_blur)
+        settings = encode_settings(encode_kwargs, "score_images", pipe, per_item)
         masks, planes, order = [], [], []
         with torch.cuda.device(pipe.device):
-            for idx, acc_o, acc_c in _encode_chunks(pipe, images, concepts, captions, kw):
+            for idx, acc_o, acc_c in _encode_chunks(pipe, images, concepts, captions, settings, encode_kwargs):
                 acc = acc_o if target_space == "output" else acc_c
                 maps = [acc[k, target[i]] for k, i in enumerate(idx)]
                 y = torch.from_numpy(np.stack([lab[i] for i in idx])).pin_memory().to(pipe.device, non_blocking=True)
@@ -645,8 +655,6 @@ class ConceptAttentionSegmentationModel:
         (num_steps, layer_indices, num_samples, seed, width, height, batch) and ``vae_noise``, one tensor per image.
         Nothing per image comes back.  Maps of more than 4096 cells raise a ValueError: ``SweepScores.update`` remains
         for them, and for the per-timestep script's bilinear resize of the coefficients."""
-        from . import _lib as L
-        from . import ops
         images = list(images)
         n = len(images)
         if target_concepts is None or not (len(target_concepts) == len(labels) == n and len(captions) >= n):
@@ -672,10 +680,7 @@ class ConceptAttentionSegmentationModel:
         if (scores.n_levels, scores.n_columns) != (len(levels), n_layers + int(bool(layer_mean))):
             raise ValueError(f"score_sweep: scores holds {scores.n_levels} x {scores.n_columns} cells; the sweep has "
                              f"{len(levels)} levels and {n_layers} layers" + (" plus the layer mean" if layer_mean else ""))
-        per_item = list(concepts) if concepts and not isinstance(concepts[0], str) else [list(concepts)] * n
-        target = [per_item[i].index(target_concepts[i]) for i in range(n)]
-        lab = _binary_labels(labels, size)
-        blur = ops.seg_blur_weights() if apply_blur else None
+        per_item, target, lab, blur = _scoring_inputs(concepts, target_concepts, labels, size, apply_blur)
         flags = dict(mean_value_threshold=mean_value_threshold, downscale_for_eval=downscale_for_eval, blur_weights=blur,
                      normalize=normalize)
         with torch.cuda.device(pipe.device):
@@ -701,10 +706,8 @@ class ConceptAttentionSegmentationModel:
             raise ValueError(f"{what}: target_concepts is one list of present classes per image ({n} images)")
         if target_space not in ("output", "cross_attention"):
             raise ValueError("target_space: 'output' or 'cross_attention'")
-        unknown = set(kw) - _ENCODE_KEYS
-        if unknown:
-            raise TypeError(f"{what}: unexpected arguments {sorted(unknown)}")
-        return [list(background_concepts) + list(t) for t in target_concepts]
+        concepts = [list(background_concepts) + list(t) for t in target_concepts]
+        return concepts, encode_settings(kw, what, self.pipeline, concepts)
 
     @torch.no_grad()
     def segment_multiclass(self, images, captions, background_concepts, target_concepts, apply_blur: bool = False,
@@ -716,21 +719,10 @@ class ConceptAttentionSegmentationModel:
         the images go through ``pipeline.encode_images``, those with one concept count ``batch`` at a time.
         ``encode_kwargs``: what ``score_images`` takes."""
         images = list(images)
-        kw = dict(encode_kwargs)
-        concepts = self._multiclass_arguments("segment_multiclass", images, captions, background_concepts, target_concepts,
-                                              target_space, kw)
-        outs = self.pipeline.encode_images(images, concepts, list(captions[:len(images)]), width=kw.get("width", 1024),
-                                           height=kw.get("height", 1024), layer_indices=kw.get("layers", list(range(15, 19))),
-                                           num_samples=kw.get("num_samples", 1), num_steps=kw.get("num_steps", 4),
-                                           noise_timestep=kw.get("noise_timestep", 2), seed=kw.get("seed", 0),
-                                           batch=kw.get("batch", 5), noise=kw.get("noise"), vae_noise=kw.get("vae_noise"),
-                                           return_pil_heatmaps=False, attention_norm=kw.get("attention_norm", "sparsemax"),
-                                           softmax=kw.get("softmax", True),
-                                           joint_attention_kwargs=kw.get("joint_attention_kwargs"))
+        concepts, settings = self._multiclass_arguments("segment_multiclass", images, captions, background_concepts,
+                                                        target_concepts, target_space, encode_kwargs)
         results = []
-        for o in outs:
-            maps = torch.as_tensor(np.asarray(o.concept_heatmaps if target_space == "output" else o.cross_attention_maps),
-                                   dtype=torch.float32)
+        for maps in self._encoded_maps(images, concepts, captions, settings, encode_kwargs, target_space):
             if apply_blur:
                 maps = gaussian_blur3(maps)
             results.append((maps.argmax(dim=0), maps, None))
@@ -751,13 +743,11 @@ class ConceptAttentionSegmentationModel:
         per concept, multiplied onto the planes before the argmax (the harness's unimplemented argument).  Nothing per
         image comes back unless ``return_predictions``: then the class maps, uint8 (side, side) per image, in one download
         at the end.  Maps of more than 16384 cells raise a ValueError."""
-        from . import _lib as L
-        from . import ops
         images = list(images)
         n = len(images)
-        kw = dict(encode_kwargs)
         what = "score_multiclass_images"
-        concepts = self._multiclass_arguments(what, images, captions, background_concepts, target_concepts, target_space, kw)
+        concepts, settings = self._multiclass_arguments(what, images, captions, background_concepts, target_concepts,
+                                                        target_space, encode_kwargs)
         if len(labels) != n:
             raise ValueError(f"{what}: {n} images need {n} labels")
         class_names = list(class_names)
@@ -766,7 +756,7 @@ class ConceptAttentionSegmentationModel:
         tables = [multiclass_table(background_concepts, t, class_names) for t in target_concepts]
         if any(not 1 <= len(c) <= L.MSEG_MAX_CONCEPTS for c in concepts):
             raise ValueError(f"{what}: an image takes 1..{L.MSEG_MAX_CONCEPTS} concepts (background and present classes)")
-        side_h, side_w = kw.get("height", 1024) // 16, kw.get("width", 1024) // 16
+        side_h, side_w = settings.height // 16, settings.width // 16
         if side_h * side_w > L.MSEG_MAX_CELLS:
             raise ValueError(f"{what}: maps of {side_h} x {side_w} cells; the device route takes up to {L.MSEG_MAX_CELLS} "
                              "(segment_multiclass + MultiClassScores.update remain for larger maps)")
@@ -790,7 +780,7 @@ class ConceptAttentionSegmentationModel:
         blur = ops.seg_blur_weights() if apply_blur else None
         preds, order = [], []
         with torch.cuda.device(pipe.device):
-            for idx, acc_o, acc_c in _encode_chunks(pipe, images, concepts, captions, kw):
+            for idx, acc_o, acc_c in _encode_chunks(pipe, images, concepts, captions, settings, encode_kwargs):
                 acc = acc_o if target_space == "output" else acc_c
                 y = torch.from_numpy(np.stack([lab[i] for i in idx])).pin_memory().to(pipe.device, non_blocking=True)
                 groups = {}                      # the items of a launch share one scale

@@ -1,10 +1,16 @@
 """CPU checks of the batched front end's host logic: the grouping plan of ``encode_images`` / ``generate_images`` and the
 concept cache of ``FluxGenerator.embed_many`` (with a fake text encoder: no GPU, no kernels)."""
+import inspect
+from dataclasses import fields
+
+import numpy as np
 import pytest
 import torch
 
+from conceptattention_amd import segmentation as S
 from conceptattention_amd.image_generator import ConceptCache, FluxGenerator
-from conceptattention_amd.pipeline import MAX_ITEMS_PER_FORWARD, _per_item, plan_batches
+from conceptattention_amd.pipeline import (MAX_ITEMS_PER_FORWARD, ConceptAttentionFluxPipeline, EncodeSettings, _per_item,
+                                           plan_batches)
 
 
 # ---------------------------------------------------------------------------------------------------------- the plan
@@ -34,6 +40,76 @@ def test_one_concept_list_for_all_items_or_one_per_item():
     assert _per_item([["cat"], ["sky", "sea"]], 2, "x") == [["cat"], ["sky", "sea"]]
     with pytest.raises(ValueError):
         _per_item([["cat"], ["sky"]], 3, "x")
+
+
+# ---------------------------------------------------------------------------------------------------------- the settings
+@pytest.mark.parametrize("method", [ConceptAttentionFluxPipeline.encode_image, ConceptAttentionFluxPipeline.encode_images,
+                                    ConceptAttentionFluxPipeline.encode_many_on_device,
+                                    S.ConceptAttentionSegmentationModel.segment_images,
+                                    S.ConceptAttentionSegmentationModel.segment_individual_image],
+                         ids=lambda m: m.__name__)
+def test_the_public_defaults_are_the_settings_records(method):
+    """Every parameter of a public encode call that is a field of the record (``layers``: the harness's name of
+    layer_indices) has the record's default.  The one exception is ``batch`` of ``encode_many_on_device``: the throughput
+    call's own argument, public with the default 1 (one item per forward unless the caller asks) since before the record."""
+    record, params, seen = EncodeSettings(), inspect.signature(method).parameters, set()
+    for f in fields(EncodeSettings):
+        name = "layers" if f.name == "layer_indices" and "layers" in params else f.name
+        if name not in params or (method.__name__, name) == ("encode_many_on_device", "batch"):
+            continue
+        assert params[name].default == getattr(record, f.name), (method.__name__, name)
+        seen.add(f.name)
+    assert {"layer_indices", "num_samples", "num_steps", "noise_timestep", "seed"} <= seen
+
+
+def test_harness_keywords_become_the_settings_record():
+    assert S.encode_settings({}) == EncodeSettings()
+    with pytest.raises(TypeError, match=r"^score_images: unexpected arguments \['layer'\]$"):
+        S.encode_settings({"layer": 1, "seed": 0}, "score_images")
+    values = {"layers": [0, 1], "num_samples": 2, "num_steps": 3, "noise_timestep": 1, "seed": 7, "height": 256, "width": 256,
+              "batch": 2, "joint_attention_kwargs": {"concept_self_attention": False}, "noise": [None], "vae_noise": [None],
+              "attention_norm": "entmax15", "softmax": False}
+    assert set(values) == S._ENCODE_KEYS
+    for key, value in values.items():
+        got = S.encode_settings({key: value, **({"width": 256} if key == "height" else {"height": 256} if key == "width" else {})})
+        if key not in ("noise", "vae_noise"):                          # (per-call data: no field of the record)
+            assert getattr(got, "layer_indices" if key == "layers" else key) == value
+    full = S.encode_settings(values)
+    assert (full.layer_indices, full.batch, full.norm, full.stop_after_multi_modal_attentions) == ([0, 1], 2, 2, True)
+    assert full.keywords()["layer_indices"] == [0, 1] and "norm" not in full.keywords()
+
+
+def test_the_settings_record_makes_the_checks_of_an_encode_call():
+    assert EncodeSettings(layer_indices=[0, 18], depth=19).norm == 0      # softmax=True wins over the name
+    for bad in ([19], [-1], [0, 2]):
+        with pytest.raises(AssertionError, match="Invalid layer index"):
+            EncodeSettings(layer_indices=bad, depth=2 if bad == [0, 2] else 19)
+    with pytest.raises(AssertionError, match="Height and width"):
+        EncodeSettings(height=512)
+    with pytest.raises(ValueError, match="Unknown attention_norm=softmin"):
+        EncodeSettings(attention_norm="softmin", softmax=False)
+    assert EncodeSettings(attention_norm="softmin").norm == 0             # (as the reference: never looked at with softmax)
+    with pytest.raises(ValueError, match=r"33 concepts.*at most 32"):
+        EncodeSettings(softmax=False, n_concepts=33)
+    assert EncodeSettings(n_concepts=33).norm == 0                        # the softmax has no limit
+    with pytest.raises(Exception):                                        # frozen
+        EncodeSettings().seed = 1
+
+
+# ---------------------------------------------------------------------------------------------------------- scoring inputs
+def test_scoring_inputs_from_one_concept_list_or_one_per_item():
+    labels = [np.zeros((8, 8), dtype=np.uint8), np.ones((8, 8), dtype=bool)]
+    per_item, target, lab, blur = S._scoring_inputs(["cat", "sky"], ["sky", "cat"], labels, 8, False)
+    assert per_item == [["cat", "sky"]] * 2 and target == [1, 0] and blur is None
+    assert [y.dtype for y in lab] == [np.uint8, np.uint8] and lab[1].all() and not lab[0].any()
+    per_item, target, _, _ = S._scoring_inputs([["cat", "sky"], ["sea", "sky", "cat"]], ["sky", "cat"], labels, 8, False)
+    assert per_item == [["cat", "sky"], ["sea", "sky", "cat"]] and target == [1, 2]
+    with pytest.raises(ValueError, match="unicorn"):
+        S._scoring_inputs(["cat", "sky"], ["sky", "unicorn"], labels, 8, False)
+    with pytest.raises(ValueError, match=r"^labels\[1\]: expected a uint8 / bool array \(8, 8\), got uint8 \(8, 4\)$"):
+        S._scoring_inputs(["cat", "sky"], ["sky", "cat"], [labels[0], np.zeros((8, 4), dtype=np.uint8)], 8, False)
+    with pytest.raises(ValueError, match=r"^labels\[0\]: .*got int64 \(8, 8\)$"):
+        S._scoring_inputs(["cat", "sky"], ["sky", "cat"], [np.zeros((8, 8), dtype=np.int64), labels[1]], 8, False)
 
 
 # ---------------------------------------------------------------------------------------------------------- the cache
