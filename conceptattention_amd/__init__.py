@@ -9,10 +9,10 @@ from .params import (AutoEncoderParams, ClipTextParams, FluxParams, T5Params, ae
 
 
 def __getattr__(name):  # lazy: keep `import conceptattention_amd` light for host-only tools
-    if name in ("ConceptAttentionFluxPipeline", "ConceptAttentionPipelineOutput"):
+    if name in ("ConceptAttentionFluxPipeline", "ConceptAttentionPipelineOutput", "ImageTrace"):
         from . import pipeline
         return getattr(pipeline, name)
-    if name in ("HipFluxDiT", "FluxWeights", "HeatmapRequest"):
+    if name in ("HipFluxDiT", "FluxWeights", "HeatmapRequest", "StepTrace"):
         from . import flux_dit
         return getattr(flux_dit, name)
     if name in ("FluxGenerator", "load_flow_model"):

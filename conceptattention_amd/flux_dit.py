@@ -168,6 +168,83 @@ class HeatmapRequest:
     per_layer_token: Optional[torch.Tensor] = None
 
 
+def modulation_rows(params: FluxParams) -> int:
+    """Rows of the stacked adaLN matrix (FluxWeights.mod_rows): 2 x 6H per double block, 3H per single block, 2H for the
+    final layer.  One fp32 vector of that length is every block's shift / scale / gate for one conditioning vector."""
+    H = params.hidden_size
+    return (12 * params.depth + 3 * params.depth_single_blocks + 2) * H
+
+
+def step_trace_nbytes(params: FluxParams, C: int, T: int, L_img: int, blocks: int, n_layers: int) -> int:
+    """Bytes one traced step keeps per work item (INTEGRATION.md "Concept re-query"): the bf16 [C+T+L, 3H] qkv slab of
+    each of the first ``blocks`` double blocks, per captured layer the fp32 [T+L, H] attention rows and the fp32
+    [C+T+L, H] pre-RoPE q rows, and one fp32 modulation vector.  Pure arithmetic."""
+    H, n = params.hidden_size, C + T + L_img
+    return blocks * n * 3 * H * 2 + n_layers * ((T + L_img) * H * 4 + n * H * 4) + modulation_rows(params) * 4
+
+
+class StepTrace:
+    """What one forward leaves of its image side for ``HipFluxDiT.requery``, in storage of its own.
+
+    The no-copy form: while a traced double block runs, the model's QKV (and, in a captured layer, ATTI32 and QPRE) ARE
+    the tensors kept here, so the rotated image k and v are exactly what the attention launch read and nothing is copied.
+    The slabs keep the forward's [C+T+L, 3H] rows -- the concept and text rows and the q third ride along unused (13 % at
+    1024 x 1024 against a compact [L, 2H] layout, which would cost a 50 MB row copy per block and item) -- and with them the
+    3H row stride, so a re-query's own [C', 3H] concept rows and the kept image rows are two key / value segments of one
+    row stride.  Pass an empty ``StepTrace()`` as ``trace=``; the forward fills it.  A forward of B items leaves one
+    storage; ``items()`` are the per-item views ``requery`` takes."""
+
+    def __init__(self):
+        self.model = None            # the HipFluxDiT whose forward filled the trace
+        self.item = None             # index into the forward's items (a view made by items()); None: the storage itself
+        self.B = self.C = self.T = self.L = 0
+        self.layers = ()             # the captured double blocks (sorted)
+        self.qkv = []                # per double block 0 .. max(layers): bf16 [B (C+T+L), 3H]
+        self.att_img = {}            # captured layer -> fp32 [B, T+L, H] attention rows of [text | image]
+        self.qpre = {}               # captured layer -> fp32 [B (C+T+L), H] post-QKNorm pre-RoPE q
+        self.split = []              # per block: q from the unrounded LayerNorm output (LayerRoute.split)
+        self.qk16 = []               # per block: rotated q / k stored as IEEE half (LayerRoute.qk16)
+        self.mod = None              # fp32 [B, mod_rows]: every block's modulation of the concept rows
+        self.released = False
+
+    @property
+    def filled(self) -> bool:
+        return self.model is not None
+
+    def items(self) -> list:
+        """One view per work item of the traced forward, sharing this storage."""
+        out = []
+        for j in range(self.B):
+            v = StepTrace()
+            v.__dict__.update(self.__dict__)
+            v.item = j
+            out.append(v)
+        return out
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes kept per work item (``step_trace_nbytes``); B times that for the storage of a batched forward."""
+        if not self.filled or self.released:
+            return 0
+        per_item = step_trace_nbytes(self.model.params, self.C, self.T, self.L, len(self.qkv), len(self.layers))
+        return per_item * (self.B if self.item is None else 1)
+
+    def release(self) -> None:
+        """Drop this object's hold on the storage (it is freed once every view of a batched forward has let go)."""
+        self.qkv, self.att_img, self.qpre, self.mod, self.released = [], {}, {}, None, True
+
+    def image_kv(self, block: int):
+        """The rotated image k and v rows [L, H] (row stride 3H) block ``block``'s attention read for this item."""
+        H, j = self.qkv[block].shape[1] // 3, self.item or 0
+        r = slice(self.B * (self.C + self.T) + j * self.L, self.B * (self.C + self.T) + (j + 1) * self.L)
+        return self.qkv[block][r, H:2 * H], self.qkv[block][r, 2 * H:]
+
+    def image_vectors(self, layer: int):
+        """(fp32 attention rows, fp32 pre-RoPE q rows) [L, H] of this item's image tokens in a captured layer."""
+        j, o = self.item or 0, self.B * (self.C + self.T)
+        return self.att_img[layer][j, self.T:], self.qpre[layer][o + j * self.L:o + (j + 1) * self.L]
+
+
 class LayerRoute(NamedTuple):
     """What HipFluxDiT._layer_route decides for one double block."""
     capture: bool    # the layer's vectors are returned or turned into heat maps
@@ -210,6 +287,7 @@ class HipFluxDiT:
         self._rope_key = None
         self._mod_cur = None
         self._mod_steps = None
+        self._traced = {}    # lazy buffers a traced block has pointed at a StepTrace's storage (_traced_block)
         # The residual streams X are kept in fp32 by default: every block adds two gated projections to them, and
         # rounding the running sum to bf16 after each add (as a bf16 activation tensor does, the reference's own
         # bf16 run included) is what makes the heat-map error grow with depth -- 38 roundings by layer 18.
@@ -365,6 +443,8 @@ class HipFluxDiT:
     }
 
     def _lazy_buffer(self, name: str) -> torch.Tensor:
+        if name in self._traced:     # a traced block: the buffer is the trace's storage (_traced_block)
+            return self._traced[name]
         ws = self._ws_cache[self._ws_key]
         t = ws.get(name)
         if t is None:
@@ -449,17 +529,21 @@ class HipFluxDiT:
             key = None
         if key is not None and self._rope_key == key:
             return
-        ids = torch.cat((concept_ids.reshape(-1, 3), txt_ids.reshape(-1, 3), img_ids.reshape(-1, 3)), 0) \
-            .to(self.device, torch.float64)
+        self._rope_fill(torch.cat((concept_ids.reshape(-1, 3), txt_ids.reshape(-1, 3), img_ids.reshape(-1, 3)), 0),
+                        self.ROPE)
+        self._rope_key = key
+
+    def _rope_fill(self, ids, rope) -> None:
+        """rope[r] = (cos, sin) of row r's position ids [rows, 3]."""
+        ids = ids.to(self.device, torch.float64)
         col = 0
         for a, d in enumerate(self.params.axes_dim):
             scale = torch.arange(0, d, 2, dtype=torch.float64, device=self.device) / d
             omega = 1.0 / (self.params.theta ** scale)
             ang = ids[:, a:a + 1] * omega[None]
-            self.ROPE[:, col:col + d // 2, 0] = torch.cos(ang).float()
-            self.ROPE[:, col:col + d // 2, 1] = torch.sin(ang).float()
+            rope[:, col:col + d // 2, 0] = torch.cos(ang).float()
+            rope[:, col:col + d // 2, 1] = torch.sin(ang).float()
             col += d // 2
-        self._rope_key = key
 
     def _mod(self, name: str, row: int, chunk: int, item: int = 0) -> torch.Tensor:
         """fp32 view of one modulation chunk of work item ``item``: name = '<block>.lin' base, row 0 = vec,
@@ -475,7 +559,7 @@ class HipFluxDiT:
     def __call__(self, img, img_ids, txt, txt_ids, concepts, concept_ids, concept_vec, timesteps, y,
                  guidance=None, stop_after_multimodal_attentions: bool = False, edit_metadata=None,
                  iteration=None, joint_attention_kwargs=None, return_vectors: bool = True,
-                 heatmaps=None, cond_slot: Optional[int] = None, **kwargs):
+                 heatmaps=None, cond_slot: Optional[int] = None, trace: Optional[StepTrace] = None, **kwargs):
         """Same keyword contract as ModifiedFluxDiT.forward (modified_flux_dit.py:75-92), for a batch of B
         independent work items (the reference's callers use B = 1): img (B,L,64), txt (B,T,4096), concepts
         (B,C,4096), y / concept_vec (B,768), timesteps / guidance (B,), ids (B,n,3).
@@ -484,8 +568,61 @@ class HipFluxDiT:
         per-layer vector stacks (the dict is then empty); ``heatmaps`` (one HeatmapRequest, or a list of B)
         accumulates softmax-over-concepts maps for the requested layers inside the forward; ``cond_slot=i``
         uses step i of a preceding ``precompute_conditioning`` call instead of recomputing the
-        conditioning vectors from ``timesteps`` / ``y`` / ``guidance``."""
+        conditioning vectors from ``timesteps`` / ``y`` / ``guidance``; ``trace`` (an empty StepTrace, with
+        ``heatmaps``) keeps the image side of the requested layers for ``requery``: the captured layers then take the fp32
+        image rows' route (epilogue_logits = False) and the prediction stays bit for bit what it is without."""
         assert concept_vec is not None, "Concept vectors must be provided for this implementation."
+        if trace is not None:
+            if trace.filled:
+                raise ValueError("trace: an empty StepTrace per forward (this one is already filled)")
+            if heatmaps is None or return_vectors:
+                raise ValueError("trace: a tracing forward takes heatmaps= and return_vectors=False (the stacked route keeps "
+                                 "no fp32 image rows)")
+            self._check_traceable("trace", joint_attention_kwargs)
+            before = self.epilogue_logits
+            self.epilogue_logits = False     # the fp32 image rows must exist: the use_part route never writes them
+            try:
+                return self._forward(img, img_ids, txt, txt_ids, concepts, concept_ids, concept_vec, timesteps, y, guidance,
+                                     stop_after_multimodal_attentions, joint_attention_kwargs, return_vectors, heatmaps,
+                                     cond_slot, trace)
+            finally:
+                self.epilogue_logits = before
+                self._end_traced_block()
+        return self._forward(img, img_ids, txt, txt_ids, concepts, concept_ids, concept_vec, timesteps, y, guidance,
+                             stop_after_multimodal_attentions, joint_attention_kwargs, return_vectors, heatmaps, cond_slot)
+
+    def _check_traceable(self, what: str, joint_attention_kwargs=None) -> None:
+        """The settings a trace and a re-query do not cover, each named; raised before anything is launched."""
+        if self.precision != "bf16":
+            raise ValueError(f"{what}: precision=\"fp8\" is not covered by the concept re-query (precision=\"bf16\" only)")
+        if self.capture_independent_image:
+            raise ValueError(f"{what}: capture_independent_image=True is not covered by the concept re-query")
+        jak = joint_attention_kwargs or {}
+        if not (jak.get("concept_cross_attention", True) and jak.get("concept_self_attention", True)):
+            raise ValueError(f"{what}: the ablation joint_attention_kwargs (concept_cross_attention / "
+                             "concept_self_attention = False) are not covered by the concept re-query")
+
+    def _begin_traced_block(self, trace: StepTrace, i: int, captured: bool, n: int, B: int, T: int, Li: int) -> None:
+        """Point QKV (and in a captured layer ATTI32 and QPRE) at fresh storage the trace owns, for block ``i``."""
+        H, dev = self.hidden_size, self.device
+        trace.qkv.append(torch.empty(n, 3 * H, device=dev, dtype=torch.bfloat16))
+        self.__dict__["QKV"] = trace.qkv[i]
+        self._traced = {}
+        if captured:
+            trace.att_img[i] = torch.empty(B, T + Li, H, device=dev, dtype=torch.float32)
+            trace.qpre[i] = torch.empty(n, H, device=dev, dtype=torch.float32)
+            self._traced = {"ATTI32": trace.att_img[i], "QPRE": trace.qpre[i]}
+
+    def _end_traced_block(self) -> None:
+        """The model's own reusable buffers again."""
+        self._traced = {}
+        if self._ws_key is not None:
+            self.__dict__["QKV"] = self._ws_cache[self._ws_key]["QKV"]
+
+    def _forward(self, img, img_ids, txt, txt_ids, concepts, concept_ids, concept_vec, timesteps, y, guidance,
+                 stop_after_multimodal_attentions, joint_attention_kwargs, return_vectors, heatmaps, cond_slot,
+                 trace=None):
+        """The forward behind ``__call__`` (its arguments, checked); ``trace``: the StepTrace to fill, or None."""
         if img.ndim != 3 or txt.ndim != 3:
             raise ValueError("Input img and txt tensors must have 3 dimensions.")
         B = img.shape[0]
@@ -540,8 +677,20 @@ class HipFluxDiT:
             self._conditioning(timesteps, y, concept_vec, guidance, B)
 
         out = {k: [] for k in DICT_KEYS} if return_vectors else {}
+        if trace is not None:
+            trace.layers = tuple(sorted({int(l) for h in heatmaps for l in h.layer_indices}))
+            trace.B, trace.C, trace.T, trace.L = B, C, T, Li
+            trace.mod = self._mod_cur[:, 1].clone()      # (a copy: MOD is reused, the steps' table is replaced)
+            trace.model = self
         for i in range(p.depth):
+            if trace is not None and trace.layers and i <= trace.layers[-1]:
+                route = self._layer_route(i, C, return_vectors, heatmaps)
+                trace.split.append(bool(route.split))
+                trace.qk16.append(bool(route.qk16))
+                self._begin_traced_block(trace, i, i in trace.layers, g.n, B, T, Li)
             self._double_block(i, g, joint_attention_kwargs, out, return_vectors, heatmaps)
+            if trace is not None:
+                self._end_traced_block()
         if return_vectors:
             out = {k: torch.stack(v, 0) for k, v in out.items()}
         if stop_after_multimodal_attentions:
@@ -684,6 +833,33 @@ class HipFluxDiT:
                     and ops.heatmap_fused_fits(C, self.hidden_size))
         return LayerRoute(capture, fp8, fp8_qkv, split, indep, qk16, use_part, f32img=capture and maps and not use_part)
 
+    # ---- the projection problems of a double block over one row range.  ``stream`` / the weight name select the image
+    # or the text weights; the concept rows use the text weights, inside the [concept | text] range of a forward or on
+    # their own in a re-query.  (a8 / a8s: the e4m3 image of the operand and its row scales, fp8 mode only)
+    def _qkv_problem(self, b, stream, xm, qkv, rope, qpre, split, qk16, fp8_qkv=False, a8=None, a8s=None):
+        """qkv with QK-RMSNorm and RoPE in the epilogue; ``qpre``: where the pre-RoPE q goes (None: nowhere)."""
+        W, a = self.weights, f"{b}{stream}_attn."
+        return self._gemm(fp8_qkv, xm, a8, a8s, a + "qkv.weight", W.tensors.get(a + "qkv.bias"), qkv,
+                          L.EPI_QKV_NORM_ROPE, n_split=3 * self.hidden_size, norm_q=W[a + "norm.query_norm.scale"],
+                          norm_k=W[a + "norm.key_norm.scale"], rope=rope, q_prerope=qpre, q_out_scale=Q_OUT_SCALE,
+                          qpre_raw=split, qk_f16=qk16)
+
+    def _q_low_plane_problem(self, b, stream, xml, q_out, rope, qpre, qk16):
+        """The q weights applied to the low plane of the LayerNorm output (``split``): added to the raw projection in
+        ``qpre``, normalised there, and the rotated, scaled q written to ``q_out``."""
+        W, a, H = self.weights, f"{b}{stream}_attn.", self.hidden_size
+        return ops.Gemm(xml, W[a + "qkv.weight"][:H], None, q_out, epilogue=L.EPI_QKV_NORM_ROPE, n_split=3 * H,
+                        norm_q=W[a + "norm.query_norm.scale"], norm_k=W[a + "norm.key_norm.scale"], rope=rope,
+                        q_prerope=qpre, q_out_scale=Q_OUT_SCALE, qpre_add=True, qk_f16=qk16)
+
+    def _gated_problem(self, lin, a, x, fp8=False, a8=None, a8s=None, **gates):
+        """x += gate * (a @ W.T + bias): proj and the second MLP matrix."""
+        return self._gemm(fp8, a, a8, a8s, lin + ".weight", self.weights[lin + ".bias"], x, L.EPI_GATE_RESIDUAL,
+                          resid=x, **gates)
+
+    def _mlp_in_problem(self, lin, xm, hid, fp8=False, a8=None, a8s=None):
+        return self._gemm(fp8, xm, a8, a8s, lin + ".weight", self.weights[lin + ".bias"], hid, L.EPI_GELU_TANH)
+
     def _double_block(self, i, g, joint_attention_kwargs=None, out=None, return_vectors=False, heatmaps=None):
         """ModifiedDoubleStreamBlock.forward (modified_double_stream_block.py:69-204) on the resident X rows
         [concepts | text | image] of all work items; 7 launches."""
@@ -719,25 +895,16 @@ class HipFluxDiT:
                     [(oI + (j + 1) * Li, self._mod(im, 0, sh, j), self._mod(im, 0, sc, j)) for j in range(B)])
 
         gs = 0 if B == 1 else self._mod_cur.stride(0)   # floats between consecutive items' gate vectors
-        G = self._gemm
         # K4: LayerNorm + (1+scale)*x+shift, per row range and item (:88-89,94-95,100-101)
         ops.ln_modulate(X, segments=[sg for sg in segs(0, 1) if sg[0] > 0], **xm_out_qkv,
                         **({"out_lo": self.XML} if split else {}))
         # K5+K6+K7: qkv projections (image stream + [concept|text] stream in one grouped launch) with
         # QK-RMSNorm and RoPE fused into the epilogue; pre-RoPE q kept for the cross-attention maps
         qpre = self.QPRE if capture else None
-        ops.gemm([G(fp8_qkv, XM[oI:], rows(XM8, oI, n), rows(XMS, oI, n), b + "img_attn.qkv.weight",
-                    W.tensors.get(b + "img_attn.qkv.bias"), QKV[oI:],
-                    L.EPI_QKV_NORM_ROPE, n_split=3 * H, norm_q=W[b + "img_attn.norm.query_norm.scale"],
-                    norm_k=W[b + "img_attn.norm.key_norm.scale"], rope=self.ROPE[oI:],
-                    q_prerope=None if qpre is None else qpre[oI:], q_out_scale=Q_OUT_SCALE,
-                    qpre_raw=split, qk_f16=qk16),
-                  G(fp8_qkv, XM[:oI], rows(XM8, 0, oI), rows(XMS, 0, oI), b + "txt_attn.qkv.weight",
-                    W.tensors.get(b + "txt_attn.qkv.bias"), QKV[:oI],
-                    L.EPI_QKV_NORM_ROPE, n_split=3 * H, norm_q=W[b + "txt_attn.norm.query_norm.scale"],
-                    norm_k=W[b + "txt_attn.norm.key_norm.scale"], rope=self.ROPE[:oI],
-                    q_prerope=None if qpre is None else qpre[:oI], q_out_scale=Q_OUT_SCALE,
-                    qpre_raw=split, qk_f16=qk16)])
+        ops.gemm([self._qkv_problem(b, "img", XM[oI:], QKV[oI:], self.ROPE[oI:], rows(qpre, oI, n), split, qk16,
+                                    fp8_qkv, rows(XM8, oI, n), rows(XMS, oI, n)),
+                  self._qkv_problem(b, "txt", XM[:oI], QKV[:oI], self.ROPE[:oI], rows(qpre, 0, oI), split, qk16,
+                                    fp8_qkv, rows(XM8, 0, oI), rows(XMS, 0, oI))])
         if split:
             # the q weights applied to the low plane of y -- image rows and concept rows; text rows are not captured --
             # with the correction, the RMS norm, the rotation and the store of the ATTENTION's q fused into that launch's
@@ -748,13 +915,9 @@ class HipFluxDiT:
             # (256 x 256 tiles named: the automatic choice prices the concept rows' problem and lands on 256 x 128,
             # 376 vs 332 us per 5-item launch)
             q_acc = self.QACC if indep else qs
-            lo = dict(epilogue=L.EPI_QKV_NORM_ROPE, n_split=3 * H, q_out_scale=Q_OUT_SCALE, qpre_add=True, qk_f16=qk16)
-            ops.gemm([ops.Gemm(self.XML[oI:], W[b + "img_attn.qkv.weight"][:H], None, q_acc[oI:],
-                               norm_q=W[b + "img_attn.norm.query_norm.scale"], norm_k=W[b + "img_attn.norm.key_norm.scale"],
-                               rope=self.ROPE[oI:], q_prerope=qpre[oI:], **lo),
-                      ops.Gemm(self.XML[:oT], W[b + "txt_attn.qkv.weight"][:H], None, q_acc[:oT],
-                               norm_q=W[b + "txt_attn.norm.query_norm.scale"], norm_k=W[b + "txt_attn.norm.key_norm.scale"],
-                               rope=self.ROPE[:oT], q_prerope=qpre[:oT], **lo)], L.TILE_PP_256x256)
+            ops.gemm([self._q_low_plane_problem(b, "img", self.XML[oI:], q_acc[oI:], self.ROPE[oI:], qpre[oI:], qk16),
+                      self._q_low_plane_problem(b, "txt", self.XML[:oT], q_acc[:oT], self.ROPE[:oT], qpre[:oT], qk16)],
+                     L.TILE_PP_256x256)
 
         # K8+K9: per item, joint text+image attention and the concept rows; one launch (concept problems first)
         def concept_problem(j, q_rows, out_rows, out32):
@@ -800,30 +963,25 @@ class HipFluxDiT:
         if fp8:
             ops.quantize_rows_fp8(ATT, ATT8, ATTS)
         # K12: proj + gated residual (:194,198,201); concept rows use txt weights + concept gate
-        ops.gemm([G(fp8, ATT[oI:], rows(ATT8, oI, n), rows(ATTS, oI, n), b + "img_attn.proj.weight",
-                             W[b + "img_attn.proj.bias"], X[oI:],
-                             L.EPI_GATE_RESIDUAL, resid=X[oI:], gate=self._mod(im, 0, 2), gate_stride=gs,
-                             gate_item_rows=Li),
-                           G(fp8, ATT[:oI], rows(ATT8, 0, oI), rows(ATTS, 0, oI), b + "txt_attn.proj.weight",
-                             W[b + "txt_attn.proj.bias"], X[:oI],
-                             L.EPI_GATE_RESIDUAL, resid=X[:oI], gate=self._mod(tm, 1, 2), gate2=self._mod(tm, 0, 2),
-                             gate_rows=oT, gate_stride=gs, gate_item_rows=max(C, 1), gate2_item_rows=T)])
+        img_gate = dict(gate_stride=gs, gate_item_rows=Li)
+
+        def txt_gate(chunk):
+            return dict(gate=self._mod(tm, 1, chunk), gate2=self._mod(tm, 0, chunk), gate_rows=oT, gate_stride=gs,
+                        gate_item_rows=max(C, 1), gate2_item_rows=T)
+        ops.gemm([self._gated_problem(b + "img_attn.proj", ATT[oI:], X[oI:], fp8, rows(ATT8, oI, n), rows(ATTS, oI, n),
+                                      gate=self._mod(im, 0, 2), **img_gate),
+                  self._gated_problem(b + "txt_attn.proj", ATT[:oI], X[:oI], fp8, rows(ATT8, 0, oI), rows(ATTS, 0, oI),
+                                      **txt_gate(2))])
         # K13: LN + modulate + MLP + gated residual (:196,199,202)
         ops.ln_modulate(X, segments=[sg for sg in segs(3, 4) if sg[0] > 0], **xm_out)
-        ops.gemm([G(fp8, XM[oI:], rows(XM8, oI, n), rows(XMS, oI, n), b + "img_mlp.0.weight",
-                             W[b + "img_mlp.0.bias"], HID[oI:], L.EPI_GELU_TANH),
-                           G(fp8, XM[:oI], rows(XM8, 0, oI), rows(XMS, 0, oI), b + "txt_mlp.0.weight",
-                             W[b + "txt_mlp.0.bias"], HID[:oI], L.EPI_GELU_TANH)])
+        ops.gemm([self._mlp_in_problem(b + "img_mlp.0", XM[oI:], HID[oI:], fp8, rows(XM8, oI, n), rows(XMS, oI, n)),
+                  self._mlp_in_problem(b + "txt_mlp.0", XM[:oI], HID[:oI], fp8, rows(XM8, 0, oI), rows(XMS, 0, oI))])
         if fp8:
             ops.quantize_rows_fp8(HID, HID8, HIDS)
-        ops.gemm([G(fp8, HID[oI:], rows(HID8, oI, n), rows(HIDS, oI, n), b + "img_mlp.2.weight",
-                             W[b + "img_mlp.2.bias"], X[oI:],
-                             L.EPI_GATE_RESIDUAL, resid=X[oI:], gate=self._mod(im, 0, 5), gate_stride=gs,
-                             gate_item_rows=Li),
-                           G(fp8, HID[:oI], rows(HID8, 0, oI), rows(HIDS, 0, oI), b + "txt_mlp.2.weight",
-                             W[b + "txt_mlp.2.bias"], X[:oI],
-                             L.EPI_GATE_RESIDUAL, resid=X[:oI], gate=self._mod(tm, 1, 5), gate2=self._mod(tm, 0, 5),
-                             gate_rows=oT, gate_stride=gs, gate_item_rows=max(C, 1), gate2_item_rows=T)])
+        ops.gemm([self._gated_problem(b + "img_mlp.2", HID[oI:], X[oI:], fp8, rows(HID8, oI, n), rows(HIDS, oI, n),
+                                      gate=self._mod(im, 0, 5), **img_gate),
+                  self._gated_problem(b + "txt_mlp.2", HID[:oI], X[:oI], fp8, rows(HID8, 0, oI), rows(HIDS, 0, oI),
+                                      **txt_gate(5))])
 
     def _single_block(self, i, g):
         """ModifiedSingleStreamBlock.forward (modified_single_stream_block.py:43-56) on the [text | image] rows of
@@ -910,55 +1068,15 @@ class HipFluxDiT:
         ``route``: this layer's LayerRoute, which says where the attention left the output-space logits' inputs."""
         ATT, QPRE = self.ATT, self.QPRE
         B, C, Li, oT, oI = g.B, g.C, g.L, g.oT, g.oI
-        # one launch per layer: ca_heatmap_fused up to 8 concepts, ca_heatmap_many for 9 .. 32 (the concept vectors through
-        # LDS in chunks; its image vectors are the fp32 rows ATTI32, as use_part needs C <= 8); the three-launch form
-        # otherwise (fused_heatmaps = False, the parity reference, or more than 32 concepts with the softmax)
-        launch = None
-        if self.fused_heatmaps and ops.heatmap_fused_fits(C, self.hidden_size):
-            launch = ops.heatmap_fused
-        elif self.fused_heatmaps and ops.heatmap_many_fits(C, self.hidden_size):
-            launch = ops.heatmap_many
-        fused = launch is not None
-        launches = {}   # norm -> problems of this layer: ONE launch for all work items and both spaces
-        for j in range(B if heatmaps is not None else 0):
-            hm = heatmaps[j]
-            if layer not in hm.layer_indices:
-                continue
+
+        def operands(j):
             # output space: the C concept rows come from the fp32 copy the attention kernel wrote
             # (their bf16 rounding, multiplied by the large component all attention outputs share,
             # is the dominant heat-map error otherwise -- DESIGN.md "tolerance")
-            li = hm.layer_indices.index(layer)
             cj, ij = slice(j * C, (j + 1) * C), slice(oI + j * Li, oI + (j + 1) * Li)
             img_out = None if route.use_part else self.ATTI32[j, g.T:]   # (a layer with maps has use_part or f32img)
-            for img_vec, con_vec, acc, table in ((img_out, self.ATT32[cj], hm.out_space, hm.per_layer_out),
-                                                 (QPRE[ij], QPRE[cj], hm.cross_space, hm.per_layer_cross)):
-                if acc is None and table is None:
-                    continue
-                if fused:
-                    launches.setdefault(hm.norm, []).append(ops.Heatmap(
-                        img_vec, None if img_vec is None else con_vec, acc, hm.weight,
-                        None if table is None else table[li], hm.per_layer_weight,
-                        part=self.PART[j] if img_vec is None else None))
-                    continue
-                # the three-launch form (more than 32 concepts, or fused_heatmaps = False: the parity reference)
-                ops.heatmap_logits(img_vec, con_vec, self.LOGITS[:C])
-                if acc is not None:
-                    ops.heatmap_norm_accumulate(self.LOGITS[:C], acc, hm.weight, hm.norm)
-                if table is not None:
-                    ops.heatmap_norm_accumulate(self.LOGITS[:C], table[li], hm.per_layer_weight, hm.norm)
-        for norm, probs in launches.items():
-            # one launch per norm; problems that name an accumulator already in the launch (two requests sharing a
-            # tensor) start a new one: within a launch the updates are unordered read-modify-writes
-            batch, seen = [], set()
-            for pr in probs + [None]:
-                ptrs = set() if pr is None else {t.data_ptr() for t in (pr.acc, pr.acc2) if t is not None}
-                if pr is None or len(batch) == L.HEATMAP_MAX_PROBLEMS or (ptrs & seen):
-                    if batch:
-                        launch(batch, norm)
-                    batch, seen = [], set()
-                if pr is not None:
-                    batch.append(pr)
-                    seen |= ptrs
+            return ((img_out, self.ATT32[cj], self.PART[j] if route.use_part else None), (QPRE[ij], QPRE[cj], None))
+        self._heatmap_updates(layer, C, heatmaps, operands, self.LOGITS)
         self._capture_token_maps(layer, g, NH, heatmaps, route)
         if return_vectors:
             H = self.hidden_size
@@ -974,3 +1092,160 @@ class HipFluxDiT:
                 QPRE[:oT].view(B, C, NH, 128).permute(0, 2, 1, 3).to(torch.bfloat16, memory_format=cf, copy=True))
             out["cross_attention_image_vectors"].append(
                 QPRE[oI:].view(B, Li, NH, 128).permute(0, 2, 1, 3).to(torch.bfloat16, memory_format=cf, copy=True))
+
+    def _heatmap_updates(self, layer, C, heatmaps, operands, logits):
+        """The heat-map updates of one captured layer for every work item whose request names it.  ``operands(j)``: item
+        j's (image vectors, concept vectors, per-head partial logits or None) of the output space and of the
+        cross-attention space -- the forward's own buffers, or in a re-query the image side a trace kept; ``logits``: fp32
+        [>= C, L] scratch of the three-launch form."""
+        # one launch per layer: ca_heatmap_fused up to 8 concepts, ca_heatmap_many for 9 .. 32 (the concept vectors through
+        # LDS in chunks; its image vectors are the fp32 rows ATTI32, as use_part needs C <= 8); the three-launch form
+        # otherwise (fused_heatmaps = False, the parity reference, or more than 32 concepts with the softmax)
+        launch = None
+        if self.fused_heatmaps and ops.heatmap_fused_fits(C, self.hidden_size):
+            launch = ops.heatmap_fused
+        elif self.fused_heatmaps and ops.heatmap_many_fits(C, self.hidden_size):
+            launch = ops.heatmap_many
+        fused = launch is not None
+        launches = {}   # norm -> problems of this layer: ONE launch for all work items and both spaces
+        for j, hm in enumerate(heatmaps if heatmaps is not None else ()):
+            if layer not in hm.layer_indices:
+                continue
+            li = hm.layer_indices.index(layer)
+            (img_out, con_out, part), (img_q, con_q, _) = operands(j)
+            for img_vec, con_vec, acc, table in ((img_out, con_out, hm.out_space, hm.per_layer_out),
+                                                 (img_q, con_q, hm.cross_space, hm.per_layer_cross)):
+                if acc is None and table is None:
+                    continue
+                if fused:
+                    launches.setdefault(hm.norm, []).append(ops.Heatmap(
+                        img_vec, None if img_vec is None else con_vec, acc, hm.weight,
+                        None if table is None else table[li], hm.per_layer_weight,
+                        part=part if img_vec is None else None))
+                    continue
+                # the three-launch form (more than 32 concepts, or fused_heatmaps = False: the parity reference)
+                ops.heatmap_logits(img_vec, con_vec, logits[:C])
+                if acc is not None:
+                    ops.heatmap_norm_accumulate(logits[:C], acc, hm.weight, hm.norm)
+                if table is not None:
+                    ops.heatmap_norm_accumulate(logits[:C], table[li], hm.per_layer_weight, hm.norm)
+        for norm, probs in launches.items():
+            # one launch per norm; problems that name an accumulator already in the launch (two requests sharing a
+            # tensor) start a new one: within a launch the updates are unordered read-modify-writes
+            batch, seen = [], set()
+            for pr in probs + [None]:
+                ptrs = set() if pr is None else {t.data_ptr() for t in (pr.acc, pr.acc2) if t is not None}
+                if pr is None or len(batch) == L.HEATMAP_MAX_PROBLEMS or (ptrs & seen):
+                    if batch:
+                        launch(batch, norm)
+                    batch, seen = [], set()
+                if pr is not None:
+                    batch.append(pr)
+                    seen |= ptrs
+
+    # ------------------------------------------------------------------ concept re-query
+    @torch.no_grad()
+    @on_own_device
+    def requery(self, step_traces, concepts, concept_ids, heatmaps) -> None:
+        """New concept rows against the kept image side of B <= 5 traced items of one geometry: the concept stream of
+        the double blocks alone (txt_in, then per block LayerNorm, qkv, the concept attention over [own keys | kept image
+        keys], the heat-map capture, proj and the MLP with the text weights and the kept concept modulation).  No image
+        or text row is computed and no single block runs.
+
+        ``step_traces``: B per-item StepTraces (``StepTrace.items()``; the trace of a one-item forward is its own
+        item); ``concepts`` (B, C', 4096), C' >= 1, any C' whatever the traced forward's was; ``concept_ids`` (B, C', 3);
+        ``heatmaps``: one HeatmapRequest per item, its layers a subset of the traced ones.  The concept rows take every
+        block's route of the tracing forward (a layer it captured keeps the accurate q whether or not this call asks for
+        its maps), so a layer's maps do not depend on which other layers are asked for."""
+        traces = [t for t in step_traces]
+        B = len(traces)
+        if not 1 <= B <= min(L.ATTN_MAX_PROBLEMS, L.MAX_SEGMENTS, 5):
+            raise ValueError(f"requery: 1 .. 5 traced items per call, got {B}")
+        if concepts.ndim != 3 or concepts.shape[0] != B or concepts.shape[1] < 1:
+            raise ValueError("requery: concepts must be (B, C' >= 1, context_in_dim), one row set per traced item")
+        C = concepts.shape[1]
+        if concept_ids.reshape(-1, 3).shape[0] != B * C:
+            raise ValueError("requery: concept_ids must be (B, C', 3)")
+        heatmaps = list(heatmaps) if isinstance(heatmaps, (list, tuple)) else [heatmaps]
+        if len(heatmaps) != B:
+            raise ValueError("requery: one HeatmapRequest per traced item")
+        self._check_traceable("requery")
+        t0 = traces[0]
+        for t in traces:
+            if t.released:
+                raise ValueError("requery: the trace has been released")
+            if not t.filled or t.model is not self:
+                raise ValueError("requery: the trace comes from another model object (or from no forward at all)")
+            if t.item is None and t.B != 1:
+                raise ValueError("requery: a batched forward's trace is passed by item (StepTrace.items())")
+            if (t.L, t.layers, t.split, t.qk16) != (t0.L, t0.layers, t0.split, t0.qk16):
+                raise ValueError("requery: the traced items of one call must share their geometry (image tokens) and "
+                                 "layer routes")
+        for t, h in zip(traces, heatmaps):
+            check_concept_count(h.norm, C)
+            if h.token_space is not None or h.per_layer_token is not None:
+                raise ValueError("requery: token maps are not part of a re-query (the text side has not changed)")
+            missing = [l for l in h.layer_indices if l not in t.layers]
+            if missing:
+                raise ValueError(f"requery: layer_indices {missing} lie outside the trace (traced layers {list(t.layers)})")
+        blocks = 1 + max((l for h in heatmaps for l in h.layer_indices), default=-1)
+        p, W, H, dev = self.params, self.weights, self.hidden_size, self.device
+        N = B * C
+        bf = dict(device=dev, dtype=torch.bfloat16)
+        f32 = dict(device=dev, dtype=torch.float32)
+        # the concept rows' own activation set (a few hundred KB): allocated per call, on the caller's stream
+        R = dict(X=torch.empty(N, H, device=dev, dtype=self.residual_dtype), XM=torch.empty(N, H, **bf),
+                 XML=torch.empty(N, H, **bf), QKV=torch.empty(N, 3 * H, **bf), ATT=torch.empty(N, H, **bf),
+                 ATT32=torch.empty(N, H, **f32), QPRE=torch.empty(N, H, **f32), HID=torch.empty(N, p.mlp_hidden, **bf),
+                 ROPE=torch.empty(N, 64, 2, **f32), LOGITS=torch.empty(C, t0.L, **f32),
+                 MOD=torch.empty(B, W.mod_rows, **f32))
+        txt_in = torch.empty(N, p.context_in_dim, **bf)
+        txt_in.copy_(concepts.reshape(N, -1))
+        for j, t in enumerate(traces):
+            R["MOD"][j].copy_(t.mod[t.item or 0])
+        self._rope_fill(concept_ids.reshape(-1, 3), R["ROPE"])
+        ops.gemm([ops.Gemm(txt_in, W["txt_in.weight"], W["txt_in.bias"], R["X"])])
+        for i in range(blocks):
+            self._requery_block(i, B, C, R, traces, heatmaps, last=i == blocks - 1)
+
+    def _requery_block(self, i, B, C, R, traces, heatmaps, last=False) -> None:
+        """The concept rows' part of ``_double_block`` for block ``i``: the same problems over the rows R, their second
+        key / value segment and the heat maps' image operands from the traces; 7 launches, 9 in a captured layer.
+        ``last``: nothing reads the residual stream after this block's maps, so it ends there."""
+        H, NH = self.hidden_size, self.params.num_heads
+        X, XM, QKV, ATT, ATT32, HID, MOD = R["X"], R["XM"], R["QKV"], R["ATT"], R["ATT32"], R["HID"], R["MOD"]
+        qs, ks, vs = QKV[:, :H], QKV[:, H:2 * H], QKV[:, 2 * H:]
+        b = f"double_blocks.{i}."
+        o = self.weights.mod_offset[b + "txt_mod.lin"]
+        captured, split, qk16 = i in traces[0].layers, traces[0].split[i], traces[0].qk16[i]
+
+        def mod(chunk, j=0):
+            return MOD[j, o + chunk * H:o + (chunk + 1) * H]
+
+        def segs(sh, sc):
+            return [((j + 1) * C, mod(sh, j), mod(sc, j)) for j in range(B)]
+
+        def gate(chunk):
+            return dict(gate=mod(chunk), gate_stride=0 if B == 1 else MOD.stride(0), gate_item_rows=C)
+        ops.ln_modulate(X, out=XM, segments=segs(0, 1), **({"out_lo": R["XML"]} if split else {}))
+        qpre = R["QPRE"] if captured else None
+        ops.gemm([self._qkv_problem(b, "txt", XM, QKV, R["ROPE"], qpre, split, qk16)])
+        if split:
+            ops.gemm([self._q_low_plane_problem(b, "txt", R["XML"], qs, R["ROPE"], qpre, qk16)], L.TILE_PP_256x256)
+        probs = []
+        for j, t in enumerate(traces):
+            cj = slice(j * C, (j + 1) * C)
+            probs.append(ops.Attn(qs[cj], ATT[cj], ks[cj], vs[cj], *t.image_kv(i), out_f32=ATT32[cj]))
+        ops.attention(probs, NH, q_prescaled=True, qk_f16=qk16)
+        if captured:
+            def operands(j):
+                cj = slice(j * C, (j + 1) * C)
+                img_out, img_q = traces[j].image_vectors(i)
+                return (img_out, ATT32[cj], None), (img_q, R["QPRE"][cj], None)
+            self._heatmap_updates(i, C, heatmaps, operands, R["LOGITS"])
+        if last:
+            return
+        ops.gemm([self._gated_problem(b + "txt_attn.proj", ATT, X, **gate(2))])
+        ops.ln_modulate(X, out=XM, segments=segs(3, 4))
+        ops.gemm([self._mlp_in_problem(b + "txt_mlp.0", XM, HID)])
+        ops.gemm([self._gated_problem(b + "txt_mlp.2", HID, X, **gate(5))])

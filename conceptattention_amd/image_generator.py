@@ -158,19 +158,9 @@ class FluxGenerator:
         many = getattr(self.text_encoder, "t5_many", None)
         if many is None:
             return [self.embed(p, c) for p, c in zip(prompts, concepts_per_item)]
-        cache = self.concept_cache
-        cache.bind(self.text_encoder)
         uniq_prompts = list(dict.fromkeys(prompts))
-        concepts = list(dict.fromkeys(c for cs in concepts_per_item for c in cs))
-        # read every cached vector BEFORE anything is inserted: an insertion may evict an entry this call still needs
-        con_vecs = {c: cache.get(c) for c in concepts}
-        new = [c for c in concepts if con_vecs[c] is None]
-        both = many(uniq_prompts + new)
-        self.t5_sequences_encoded += len(uniq_prompts) + len(new)
+        both, con_vecs = self._t5_with_concepts(uniq_prompts, concepts_per_item)
         txts = {p: both[i:i + 1] for i, p in enumerate(uniq_prompts)}
-        for j, c in enumerate(new):
-            con_vecs[c] = both[len(uniq_prompts) + j, 0, :].clone()     # (a copy: the entry must not pin the whole batch)
-            cache.put(c, con_vecs[c])
         clip_many = getattr(getattr(self.text_encoder, "clip_embedder", None), "clip_many", None)
         if clip_many is not None:
             pooled = clip_many(uniq_prompts)
@@ -182,6 +172,34 @@ class FluxGenerator:
             con = torch.stack([con_vecs[c] for c in cs]).unsqueeze(0)
             out.append((txts[p], vecs[p], *sampling.concept_inputs(con, vecs[p])))
         return out
+
+    def _t5_with_concepts(self, sequences, concepts_per_item):
+        """ONE ``t5_many`` call over ``sequences`` and the concepts ``concept_cache`` does not hold yet: (the encoder's
+        output, whose first rows are the sequences'; concept string -> its first-token vector).  No call when there is
+        nothing to encode."""
+        cache = self.concept_cache
+        cache.bind(self.text_encoder)
+        concepts = list(dict.fromkeys(c for cs in concepts_per_item for c in cs))
+        # read every cached vector BEFORE anything is inserted: an insertion may evict an entry this call still needs
+        con_vecs = {c: cache.get(c) for c in concepts}
+        new = [c for c in concepts if con_vecs[c] is None]
+        both = self.text_encoder.t5_many(list(sequences) + new) if (sequences or new) else None
+        self.t5_sequences_encoded += len(sequences) + len(new)
+        for j, c in enumerate(new):
+            con_vecs[c] = both[len(sequences) + j, 0, :].clone()     # (a copy: the entry must not pin the whole batch)
+            cache.put(c, con_vecs[c])
+        return both, con_vecs
+
+    def embed_concepts_many(self, concepts_per_item) -> list:
+        """The concept side of ``embed_many`` alone, for a re-query: per item (con (1,C,4096), con_ids (1,C,3)), the
+        same bits ``embed`` / ``embed_many`` give those concept strings; the prompt is not encoded."""
+        concepts_per_item = [list(c) for c in concepts_per_item]
+        if getattr(self.text_encoder, "t5_many", None) is None:
+            cons = [torch.stack([self.t5(c)[0, 0, :] for c in cs]).unsqueeze(0) for cs in concepts_per_item]
+        else:
+            _, con_vecs = self._t5_with_concepts([], concepts_per_item)
+            cons = [torch.stack([con_vecs[c] for c in cs]).unsqueeze(0) for cs in concepts_per_item]
+        return [(con, sampling.zero_ids(con.shape[1], con.device, 1)) for con in cons]
 
     def decode(self, x: torch.Tensor, height: int, width: int):
         """unpack + VAE decode + PIL (image_generator.py:189-204); without an autoencoder the unpacked

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops, sampling
-from .flux_dit import HeatmapRequest, HipFluxDiT, on_own_device
+from .flux_dit import HeatmapRequest, HipFluxDiT, StepTrace, on_own_device
 from .heatmaps import check_concept_count, compute_heatmaps_from_vectors, resolve_norm
 from .params import configs
 
@@ -39,6 +39,44 @@ class ConceptAttentionPipelineOutput:
     # (None when the maps were asked for by count)
     token_heatmaps: Optional[list] = None
     tokens: Optional[list] = None
+    # keep_trace=True: the image side of the call's traced steps, for ``ConceptAttentionFluxPipeline.requery``
+    trace: Optional["ImageTrace"] = None
+
+
+@dataclass
+class ImageTrace:
+    """What a ``keep_trace=True`` call keeps of ONE item: per traced step (a ``timesteps`` index of a generate call, a
+    noise-sample index of an encode call) the item's ``flux_dit.StepTrace``, the settings of the call and the finished
+    image.  ``nbytes`` is the device memory it holds (INTEGRATION.md "Concept re-query"); ``release()`` lets go of it."""
+    steps: dict                   # step key -> StepTrace (the item's view of its forward's storage)
+    settings: dict                # the keywords of the call that made it ("call": "generate_image" | "encode_image")
+    image: object                 # what the call returned as ``image``
+    released: bool = False
+
+    @property
+    def layer_indices(self) -> list:
+        return list(next(iter(self.steps.values())).layers) if self.steps else []
+
+    @property
+    def timesteps(self) -> list:
+        return list(self.steps)
+
+    @property
+    def nbytes(self) -> int:
+        return sum(s.nbytes for s in self.steps.values())
+
+    def release(self) -> None:
+        for s in self.steps.values():
+            s.release()
+        self.released = True
+
+
+def trace_nbytes(params, n_concepts: int, n_text: int, n_image: int, layer_indices, n_steps: int) -> int:
+    """``ImageTrace.nbytes`` of an item from the call's settings alone: ``n_steps`` traced steps, each the double blocks
+    0 .. max(layer_indices) and the captured layers' fp32 rows (``flux_dit.step_trace_nbytes``).  Pure arithmetic."""
+    from .flux_dit import step_trace_nbytes
+    layers = sorted({int(l) for l in layer_indices})
+    return n_steps * step_trace_nbytes(params, n_concepts, n_text, n_image, layers[-1] + 1 if layers else 0, len(layers))
 
 
 class SyntheticTextEncoder:
@@ -130,6 +168,15 @@ def plan_batches(keys: Sequence, batch: int) -> list:
     for i, k in enumerate(keys):
         groups.setdefault(k, []).append(i)
     return [idx[c0:c0 + size] for idx in groups.values() for c0 in range(0, len(idx), size)]
+
+
+def plan_requery(geometries: Sequence, concept_counts: Sequence) -> list:
+    """The forwards of a ``requery`` call, as lists of item indices: items that share ``geometries[i]`` (whatever a
+    trace needs the others of its forward to share) and a concept count go through one concept-row pass, at most
+    MAX_ITEMS_PER_FORWARD at a time, in item order (``plan_batches``).  Pure: no device, no tensors."""
+    if len(geometries) != len(concept_counts):
+        raise ValueError("plan_requery: one geometry and one concept count per item")
+    return plan_batches(list(zip(geometries, concept_counts)), MAX_ITEMS_PER_FORWARD)
 
 
 def _per_item(value, n: int, what: str) -> list:
@@ -352,7 +399,7 @@ class ConceptAttentionFluxPipeline:
                        attention_norm: str = "sparsemax", cmap="plasma", latent: Optional[torch.Tensor] = None,
                        fused: bool = True, heatmap_renderer: str = "host", heatmap_size=None,
                        heatmap_interpolation: str = "nearest", overlay_alpha=None,
-                       token_maps=None) -> ConceptAttentionPipelineOutput:
+                       token_maps=None, keep_trace: bool = False) -> ConceptAttentionPipelineOutput:
         """``latent`` (1,16,h/8,w/8) overrides get_noise (device RNG differs between platforms);
         ``fused=False`` takes the reference's route (stack the per-layer vectors, then reduce).
         ``heatmap_renderer="device"`` makes the PIL heat maps on the device (ops.heatmap_render; the same bytes as
@@ -362,14 +409,19 @@ class ConceptAttentionFluxPipeline:
         ``token_maps``: True -> ``token_heatmaps`` holds one map per token of the prompt (``tokens``: the tokenizer's
         strings, the end-of-string token excluded): the attention the image tokens give that token's key in the double
         blocks ``layer_indices``, mean over heads, layers and ``timesteps`` (DAAM; ops.token_maps); an int n -> the first
-        n text rows, ``tokens`` None.  Needs the fused route."""
+        n text rows, ``tokens`` None.  Needs the fused route.
+        ``keep_trace=True``: ``out.trace`` (an ``ImageTrace``) keeps the image side of the steps in ``timesteps`` for
+        ``requery``; needs the fused route, bf16 precision and the default ``capture_independent_image``."""
+        if keep_trace and not fused:
+            raise ValueError("keep_trace needs the fused route: fused=False stacks the vectors and keeps no image side")
         if fused:   # (repeated timestep or layer indices still end on the stacked route: _generate_steps_inner)
             return self.generate_images(
                 [prompt], [concepts], seeds=[seed], latents=None if latent is None else [latent], width=width, height=height,
                 return_cross_attention=return_cross_attention, layer_indices=layer_indices, cmap=cmap, timesteps=timesteps,
                 return_pil_heatmaps=return_pil_heatmaps, num_inference_steps=num_inference_steps, guidance=guidance,
                 softmax=softmax, attention_norm=attention_norm, heatmap_renderer=heatmap_renderer, heatmap_size=heatmap_size,
-                heatmap_interpolation=heatmap_interpolation, overlay_alpha=overlay_alpha, token_maps=token_maps)[0]
+                heatmap_interpolation=heatmap_interpolation, overlay_alpha=overlay_alpha, token_maps=token_maps,
+                keep_trace=keep_trace)[0]
         norm = self._generate_norm(return_cross_attention, layer_indices, height, width, softmax, attention_norm)
         check_concept_count(norm, len(concepts))
         show = self._device_renderer(return_pil_heatmaps, cmap, heatmap_renderer, heatmap_size, heatmap_interpolation,
@@ -457,11 +509,13 @@ class ConceptAttentionFluxPipeline:
     @on_own_device
     def generate_on_device(self, latent, txt, vec, concept_embeddings, layer_indices=list(range(15, 19)),
                            num_inference_steps: int = 4, guidance: float = 0.0, timesteps=None, fused: bool = True,
-                           norm: int = 0, token_acc=None):
+                           norm: int = 0, token_acc=None, traces: Optional[dict] = None):
         """``token_acc``: per item, an fp32 [n_tok, patches] accumulator of the caller's for the prompt-token maps (zeroed
-        by the caller; None, or None for an item: no token maps).  The return tuple is the same with and without."""
+        by the caller; None, or None for an item: no token maps).  ``traces``: a dict of the caller's that receives step
+        index -> the ``StepTrace`` of every step in ``timesteps`` (fused route only).  The return tuple is the same with
+        and without either."""
         gen = self._generate_steps(self.model, latent, txt, vec, concept_embeddings, layer_indices,
-                                   num_inference_steps, guidance, timesteps, fused, norm, token_acc)
+                                   num_inference_steps, guidance, timesteps, fused, norm, token_acc, traces)
         while True:
             try:
                 next(gen)
@@ -470,7 +524,7 @@ class ConceptAttentionFluxPipeline:
 
     def _generate_steps(self, model, latent, txt, vec, concept_embeddings, layer_indices=list(range(15, 19)),
                         num_inference_steps: int = 4, guidance: float = 0.0, timesteps=None, fused: bool = True,
-                        norm: int = 0, token_acc=None):
+                        norm: int = 0, token_acc=None, traces: Optional[dict] = None):
         """The device-resident core of generate_image for B work items at once (B = 1 from the public API):
         latent (B,16,h/8,w/8), txt (B,T,4096), vec (B,768), concept_embeddings (B,C,4096) already in HBM ->
         (final latent tokens, concept heat maps fp32 [B,C,side,side], cross-attention maps fp32
@@ -500,17 +554,19 @@ class ConceptAttentionFluxPipeline:
         try:
             return (yield from self._generate_steps_inner(model, x, inp, con, con_ids, con_vec, schedule, ts, ls,
                                                           C, n_patches, guidance, layer_indices, timesteps, fused,
-                                                          norm, token_acc))
+                                                          norm, token_acc, traces))
         finally:
             model.keep_bf16_layers = keep_before  # this call's choice does not leak into later sweeps / encodes
 
     def _generate_steps_inner(self, model, x, inp, con, con_ids, con_vec, schedule, ts, ls, C, n_patches, guidance,
-                              layer_indices, timesteps, fused, norm=0, token_acc=None):
+                              layer_indices, timesteps, fused, norm=0, token_acc=None, traces=None):
         names = {v: k for k, v in _lib.NORMS.items()}
         # repeated indices weigh a (step, layer) pair repeatedly in the reference's fancy indexing
         # (concept_attention_pipeline.py:76-77); the fused accumulation covers distinct pairs only
         if fused and (len(set(ts)) != len(ts) or len(set(ls)) != len(ls)):
             fused = False
+        if traces is not None and not fused:
+            raise ValueError("keep_trace needs the fused route (fused=True, distinct timesteps and layer indices)")
         B = x.shape[0]
         if token_acc is not None and any(t is not None for t in token_acc):
             if not fused:
@@ -526,7 +582,7 @@ class ConceptAttentionFluxPipeline:
             img, _, _ = yield from sampling.denoise_steps(
                 model, **inp, timesteps=schedule, guidance=guidance, concepts=con, concept_ids=con_ids,
                 concept_vec=con_vec, return_intermediate_images=False, return_vectors=False, heatmaps=reqs,
-                heatmap_timesteps=ts)
+                heatmap_timesteps=ts, traces=traces)
             side = int(round(n_patches ** 0.5))
             return img, acc_o.view(B, C, side, side), acc_c.view(B, C, side, side)
         if B != 1:
@@ -621,7 +677,7 @@ class ConceptAttentionFluxPipeline:
                      attention_norm: str = "sparsemax", softmax=True,
                      joint_attention_kwargs=None, noise=None, vae_noise=None, heatmap_renderer: str = "host",
                      heatmap_size=None, heatmap_interpolation: str = "nearest",
-                     overlay_alpha=None, token_maps=None) -> ConceptAttentionPipelineOutput:
+                     overlay_alpha=None, token_maps=None, keep_trace: bool = False) -> ConceptAttentionPipelineOutput:
         """``image``: a latent tensor (1,16,h/8,w/8), or a PIL image when the pipeline has an autoencoder
         (``autoencoder="synthetic"``, a ``.safetensors`` path, or an injected object).
         One forward of the 19 double blocks per noise sample (stop_after_multimodal_attentions).
@@ -631,7 +687,9 @@ class ConceptAttentionFluxPipeline:
         ``vae_noise`` (1,16,h/8,w/8) is the autoencoder's sampling noise for a PIL image (drawn on the device when not
         given), so that a call is reproducible.  ``heatmap_renderer`` and the three keywords behind it: as in
         ``generate_image``; the overlays are laid over the INPUT image's bytes, which must already be height x width.
-        ``token_maps``: as in ``generate_image`` (the mean runs over heads, layers and noise samples)."""
+        ``token_maps``: as in ``generate_image`` (the mean runs over heads, layers and noise samples).
+        ``keep_trace=True``: ``out.trace`` keeps the image side of every noise sample's forward for ``requery`` (its
+        step keys are the sample indices)."""
         return self.encode_images(
             [image], [concepts], [prompt], width=width, height=height, layer_indices=layer_indices, num_samples=num_samples,
             num_steps=num_steps, noise_timestep=noise_timestep, seed=seed, noise=None if noise is None else [noise],
@@ -639,7 +697,7 @@ class ConceptAttentionFluxPipeline:
             stop_after_multi_modal_attentions=stop_after_multi_modal_attentions, attention_norm=attention_norm,
             softmax=softmax, joint_attention_kwargs=joint_attention_kwargs, heatmap_renderer=heatmap_renderer,
             heatmap_size=heatmap_size, heatmap_interpolation=heatmap_interpolation, overlay_alpha=overlay_alpha,
-            token_maps=token_maps)[0]
+            token_maps=token_maps, keep_trace=keep_trace)[0]
 
     def _encode_pixels(self, images, height: int, width: int, vae_noise=None) -> torch.Tensor:
         """PIL images -> bf16 latents (B,16,h/8,w/8).  The HIP autoencoder takes the bytes (``encode_pixels``: resize,
@@ -661,11 +719,12 @@ class ConceptAttentionFluxPipeline:
         return self.autoencoder.encode(torch.cat(xs), **kw).to(torch.bfloat16)
 
     def _encode_maps(self, model, latent, txt, vec, con, con_ids, con_vec, settings: EncodeSettings, *, noise=None,
-                     token_acc=None):
+                     token_acc=None, traces: Optional[dict] = None):
         """Device core of encode_image for B images at once (latent (B,16,h,w), txt (B,T,4096), ...): one forward
         per noise sample on ``model``; returns the two fp32 maps [B, C, side, side].  ``noise``: optional list of
         num_samples tensors (1 or B,16,h,w) used instead of get_noise(seed + i).  ``token_acc``: per item, the caller's
-        zeroed fp32 [n_tok, patches] accumulator of the prompt-token maps (or None); the return tuple stays."""
+        zeroed fp32 [n_tok, patches] accumulator of the prompt-token maps (or None); ``traces``: a dict of the caller's that
+        receives sample index -> the StepTrace of that sample's forward; the return tuple stays."""
         layer_indices, num_samples, noise_timestep = settings.layer_indices, settings.num_samples, settings.noise_timestep
         if noise is not None and len(noise) != num_samples:
             raise ValueError("noise: one tensor per noise sample")
@@ -695,7 +754,8 @@ class ConceptAttentionFluxPipeline:
                   concepts=con, concept_ids=con_ids, concept_vec=con_vec, y=con_vec, timesteps=t_vec,
                   guidance=torch.zeros(B, device=self.device),
                   stop_after_multimodal_attentions=settings.stop_after_multi_modal_attentions,
-                  joint_attention_kwargs=settings.joint_attention_kwargs, return_vectors=False, heatmaps=req)
+                  joint_attention_kwargs=settings.joint_attention_kwargs, return_vectors=False, heatmaps=req,
+                  **({} if traces is None else {"trace": traces.setdefault(i, StepTrace())}))
         side = int(round(n_patches ** 0.5))
         return acc_o.view(B, C, side, side), acc_c.view(B, C, side, side)
 
@@ -711,11 +771,12 @@ class ConceptAttentionFluxPipeline:
         return tuple(_cat(e[k] for e in emb) for k in range(n_out))
 
     def _encode_chunks(self, images, concepts, prompts, settings: EncodeSettings, *, noise=None, vae_noise=None,
-                       token_acc=None):
+                       token_acc=None, keep_trace: bool = False):
         """The forwards of ``encode_images``, one at a time: yields (item indices, acc_o, acc_c) with the two fp32 maps
         [len(indices), C, side, side] of the chunk still on the device (``_encode_maps``).  ``images`` and ``prompts`` are lists;
         ``settings`` was built with the call's largest concept count; ``noise`` / ``vae_noise``: as ``encode_images`` takes them;
-        ``token_acc``: per item of the call, the caller's accumulator of the prompt-token maps (or None)."""
+        ``token_acc``: per item of the call, the caller's accumulator of the prompt-token maps (or None).  With
+        ``keep_trace`` a fourth entry follows: sample index -> the StepTrace of the chunk's forward."""
         n, height, width = len(images), settings.height, settings.width
         concepts = _per_item(concepts, n, "encode_images: concepts")
         for name, v in (("prompts", prompts), ("noise", noise), ("vae_noise", vae_noise)):
@@ -735,9 +796,10 @@ class ConceptAttentionFluxPipeline:
                 raise ValueError("noise: one tensor per noise sample")
             nz = None if noise is None else [_cat(noise[i][s_].to(self.device, torch.bfloat16) for i in idx)
                                              for s_ in range(settings.num_samples)]
+            traces = {} if keep_trace else None
             ho, hc = self._encode_maps(self.model, latent, txt, vec, con, con_ids, con_vec, settings, noise=nz,
-                                       token_acc=None if token_acc is None else [token_acc[i] for i in idx])
-            yield idx, ho, hc
+                                       token_acc=None if token_acc is None else [token_acc[i] for i in idx], traces=traces)
+            yield (idx, ho, hc, traces) if keep_trace else (idx, ho, hc)
 
     @torch.no_grad()
     @on_own_device
@@ -747,7 +809,7 @@ class ConceptAttentionFluxPipeline:
                       return_pil_heatmaps: bool = True, cmap="plasma", stop_after_multi_modal_attentions=True,
                       attention_norm: str = "sparsemax", softmax=True, joint_attention_kwargs=None,
                       heatmap_renderer: str = "host", heatmap_size=None, heatmap_interpolation: str = "nearest",
-                      overlay_alpha=None, token_maps=None) -> list:
+                      overlay_alpha=None, token_maps=None, keep_trace: bool = False) -> list:
         """``encode_image`` for a list of images: a list of ConceptAttentionPipelineOutput in item order, every item with
         the maps of its own ``encode_image`` call.  ``images``: PIL images and / or latents (1,16,h/8,w/8);
         ``concepts``: one list for all items or one list per item; ``prompts``: one string per item (or one for all).
@@ -757,7 +819,10 @@ class ConceptAttentionFluxPipeline:
         tensor (1,16,h/8,w/8) -- without it the autoencoder draws one batch of noise per forward, so PIL items are then
         reproducible per call of this method, not against single calls.  ``heatmap_renderer="device"``: the pictures of
         a chunk come from one launch and one download (``_finish_device``).  ``token_maps``: as in ``encode_image``, for
-        every item's own prompt (the items of a chunk may have different numbers of tokens)."""
+        every item's own prompt (the items of a chunk may have different numbers of tokens).  ``keep_trace``: as in
+        ``encode_image``, per item."""
+        if keep_trace:
+            self.model._check_traceable("keep_trace", joint_attention_kwargs)
         images = list(images)
         n = len(images)
         prompts = [prompts] * n if isinstance(prompts, str) else list(prompts)
@@ -773,10 +838,16 @@ class ConceptAttentionFluxPipeline:
         pictures = [self._input_picture(im, height, width) for im in images] if show[0] and overlay_alpha is not None \
             else None
         results = {}
-        for idx, ho, hc in self._encode_chunks(images, concepts, prompts, settings, noise=noise, vae_noise=vae_noise,
-                                               token_acc=token_acc):
-            results.update(zip(idx, self._chunk_outputs(idx, [images[i] for i in idx], ho, hc, show, token_acc, tokens,
-                                                        None if pictures is None else [pictures[i] for i in idx])))
+        for idx, ho, hc, *traces in self._encode_chunks(images, concepts, prompts, settings, noise=noise,
+                                                        vae_noise=vae_noise, token_acc=token_acc, keep_trace=keep_trace):
+            outs = self._chunk_outputs(idx, [images[i] for i in idx], ho, hc, show, token_acc, tokens,
+                                       None if pictures is None else [pictures[i] for i in idx])
+            if keep_trace:
+                self._attach_traces(outs, traces[0], dict(
+                    call="encode_image", width=width, height=height, layer_indices=list(layer_indices),
+                    num_samples=num_samples, num_steps=num_steps, noise_timestep=noise_timestep, seed=seed,
+                    timesteps=sorted(traces[0])))
+            results.update(zip(idx, outs))
         return [results[i] for i in range(n)]
 
     @torch.no_grad()
@@ -786,14 +857,17 @@ class ConceptAttentionFluxPipeline:
                         num_inference_steps: int = 4, guidance: float = 0.0, timesteps=None, softmax: bool = True,
                         attention_norm: str = "sparsemax", cmap="plasma", batch: int = 5,
                         heatmap_renderer: str = "host", heatmap_size=None, heatmap_interpolation: str = "nearest",
-                        overlay_alpha=None, token_maps=None) -> list:
+                        overlay_alpha=None, token_maps=None, keep_trace: bool = False) -> list:
         """``generate_image`` for a list of prompts: a list of ConceptAttentionPipelineOutput in item order, every item
         with the image and maps of its own ``generate_image(prompt, concepts, seed=seeds[i], latent=latents[i])`` call on
         the fused route.  ``concepts``: one list for all items or one list per item; ``seeds``: one per item (default
         0, 1, 2, ...).  Items with one concept count go ``batch`` (at most 5) at a time through one text-encoder call,
         one denoising loop and one autoencoder pass whose bytes are made on the device.  ``token_maps``: as in
-        ``generate_image``, for every item's own prompt (the items of a chunk may have different numbers of tokens)."""
+        ``generate_image``, for every item's own prompt (the items of a chunk may have different numbers of tokens).
+        ``keep_trace``: as in ``generate_image``; every item's ``trace`` is its own view of its forward's storage."""
         norm = self._generate_norm(return_cross_attention, layer_indices, height, width, softmax, attention_norm)
+        if keep_trace:
+            self.model._check_traceable("keep_trace")
         show = self._device_renderer(return_pil_heatmaps, cmap, heatmap_renderer, heatmap_size, heatmap_interpolation,
                                      overlay_alpha)
         prompts = list(prompts)
@@ -811,13 +885,95 @@ class ConceptAttentionFluxPipeline:
             txt, vec, con = self._embed_chunk(prompts, concepts, idx, 3)
             x = _cat(latents[i].to(self.device, torch.bfloat16) if latents is not None else
                      sampling.get_noise(1, height, width, self.device, torch.bfloat16, seeds[i]) for i in idx)
+            traces = {} if keep_trace else None
             img, ho, hc = self.generate_on_device(x, txt, vec, con, layer_indices=layer_indices,
                                                   num_inference_steps=num_inference_steps, guidance=guidance,
                                                   timesteps=timesteps, fused=True, norm=norm,
-                                                  token_acc=None if token_acc is None else [token_acc[i] for i in idx])
+                                                  token_acc=None if token_acc is None else [token_acc[i] for i in idx],
+                                                  traces=traces)
             pictures, pix = self._decode(img, height, width, show[0] and overlay_alpha is not None)
-            results.update(zip(idx, self._chunk_outputs(idx, pictures, ho, hc, show, token_acc, tokens, pix)))
+            outs = self._chunk_outputs(idx, pictures, ho, hc, show, token_acc, tokens, pix)
+            if keep_trace:
+                self._attach_traces(outs, traces, dict(
+                    call="generate_image", width=width, height=height, layer_indices=list(layer_indices),
+                    num_inference_steps=num_inference_steps, guidance=guidance, timesteps=sorted(traces)))
+            results.update(zip(idx, outs))
         return [results[i] for i in range(n)]
+
+    @staticmethod
+    def _attach_traces(outs, traces: dict, settings: dict) -> None:
+        """``out.trace`` of every item of a chunk: ``traces`` maps a step key to the StepTrace of the chunk's forward."""
+        views = {k: t.items() for k, t in traces.items()}
+        for j, out in enumerate(outs):
+            out.trace = ImageTrace({k: v[j] for k, v in views.items()}, dict(settings), out.image)
+
+    # ------------------------------------------------------------------ concept re-query
+    @torch.no_grad()
+    @on_own_device
+    def requery(self, trace, concepts, layer_indices=None, timesteps=None, softmax: bool = True,
+                attention_norm: str = "sparsemax", cmap="plasma", return_pil_heatmaps: bool = True,
+                heatmap_renderer: str = "host", heatmap_size=None, heatmap_interpolation: str = "nearest",
+                overlay_alpha=None):
+        """Other concepts for a finished ``keep_trace=True`` call, without its image pass: only the concept rows' stream
+        through the double blocks runs, against the image keys, values and map operands the trace kept
+        (``HipFluxDiT.requery``).  ``trace``: an ``ImageTrace`` (-> one ConceptAttentionPipelineOutput) or a list of them
+        (-> a list, in item order); ``concepts``: one list of strings for all items or one list per item, any count
+        (sparse norms: at most 32), embedded as ``embed_many`` embeds them.  ``layer_indices`` / ``timesteps``: any subset
+        of the traced ones (default: all of them; for an encode trace the steps are its noise-sample indices); the maps
+        are the mean over that subset.  The other keywords: as in ``generate_image``; overlays are laid over the trace's
+        ``image``.  The output carries the trace's ``image`` and no token maps (the text side has not changed).  Items
+        that share a geometry and a concept count go through one pass, at most 5 at a time (``plan_requery``)."""
+        single = isinstance(trace, ImageTrace)
+        traces = [trace] if single else list(trace)
+        n = len(traces)
+        concepts = _per_item(concepts, n, "requery: concepts")
+        norm = resolve_norm(softmax, attention_norm)
+        check_concept_count(norm, max((len(c) for c in concepts), default=0))
+        show = self._device_renderer(return_pil_heatmaps, cmap, heatmap_renderer, heatmap_size, heatmap_interpolation,
+                                     overlay_alpha)
+        self.model._check_traceable("requery")
+        plans = []
+        for i, t in enumerate(traces):
+            if t.released or any(s.released for s in t.steps.values()):
+                raise ValueError(f"requery: trace {i} has been released")
+            if any(s.model is not self.model for s in t.steps.values()):
+                raise ValueError(f"requery: trace {i} comes from another model object")
+            if not concepts[i]:
+                raise ValueError("requery: at least one concept per item")
+            ls = t.layer_indices if layer_indices is None else [int(l) for l in layer_indices]
+            if any(l not in t.layer_indices for l in ls):
+                raise ValueError(f"requery: layer_indices {ls} lie outside trace {i} (traced layers {t.layer_indices})")
+            steps = t.settings.get("num_inference_steps")
+            ts = t.timesteps if timesteps is None else [int(s) % steps if steps else int(s) for s in timesteps]
+            if any(s not in t.steps for s in ts):
+                raise ValueError(f"requery: timesteps {ts} lie outside trace {i} (traced steps {t.timesteps})")
+            if len(set(ls)) != len(ls) or len(set(ts)) != len(ts) or not ls or not ts:
+                raise ValueError("requery: layer_indices and timesteps are non-empty lists of distinct entries")
+            s0 = t.steps[ts[0]]
+            plans.append((ls, ts, (s0.L, s0.layers, tuple(s0.split), tuple(s0.qk16), tuple(ls), tuple(ts))))
+        pictures = None
+        if show[0] and overlay_alpha is not None:
+            if any(not hasattr(t.image, "convert") for t in traces):
+                raise ValueError("overlay_alpha needs traces whose image is a picture (a pipeline with an autoencoder)")
+            pictures = [self._input_picture(t.image, *t.image.size[::-1]) for t in traces]
+        results = {}
+        for idx in plan_requery([p[2] for p in plans], [len(c) for c in concepts]):
+            ls, ts, _ = plans[idx[0]]
+            emb = self.flux_generator.embed_concepts_many([concepts[i] for i in idx])
+            con, con_ids = _cat(e[0] for e in emb), _cat(e[1] for e in emb)
+            B, C, n_patches = len(idx), con.shape[1], traces[idx[0]].steps[ts[0]].L
+            acc_o = torch.zeros(B, C, n_patches, device=self.device)
+            acc_c = torch.zeros(B, C, n_patches, device=self.device)
+            reqs = [HeatmapRequest(tuple(ls), 1.0 / (len(ts) * len(ls)), acc_o[j], acc_c[j], norm=norm) for j in range(B)]
+            for s in ts:
+                self.model.requery([traces[i].steps[s] for i in idx], con, con_ids, reqs)
+            side = int(round(n_patches ** 0.5))
+            outs = self._chunk_outputs(idx, [traces[i].image for i in idx], acc_o.view(B, C, side, side),
+                                       acc_c.view(B, C, side, side), show,
+                                       pictures=None if pictures is None else [pictures[i] for i in idx])
+            results.update(zip(idx, outs))
+        out = [results[i] for i in range(n)]
+        return out[0] if single else out
 
     @torch.no_grad()
     @on_own_device

@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 
 from . import ops
-from .flux_dit import DICT_KEYS, HeatmapRequest
+from .flux_dit import DICT_KEYS, HeatmapRequest, StepTrace
 
 
 def get_noise(num_samples: int, height: int, width: int, device, dtype, seed: int):
@@ -106,14 +106,15 @@ def concept_inputs(concept_embeddings: torch.Tensor, vec_like: torch.Tensor):
 def denoise(model, img, img_ids, txt, txt_ids, vec, timesteps: list[float], guidance: float = 4.0,
             concepts=None, concept_ids=None, concept_vec=None, return_intermediate_images: bool = True,
             joint_attention_kwargs=None, return_vectors: bool = True,
-            heatmaps: Optional[HeatmapRequest] = None, heatmap_timesteps=None):
+            heatmaps: Optional[HeatmapRequest] = None, heatmap_timesteps=None, traces: Optional[dict] = None):
     """Sequential Euler loop of flux/sampling.py:96-152.  Returns (img, intermediates, dict) with
     each dict entry stacked over time.  HIP-path extras: ``return_vectors=False`` +
     ``heatmaps`` (one HeatmapRequest per work item of the batch) / ``heatmap_timesteps`` accumulate the concept
-    maps inside the model call for the selected (step, layer) pairs instead of stacking the vectors."""
+    maps inside the model call for the selected (step, layer) pairs instead of stacking the vectors; ``traces`` (a dict
+    of the caller's) receives step index -> the ``StepTrace`` of every step whose maps are accumulated."""
     gen = denoise_steps(model, img, img_ids, txt, txt_ids, vec, timesteps, guidance, concepts, concept_ids,
                         concept_vec, return_intermediate_images, joint_attention_kwargs, return_vectors, heatmaps,
-                        heatmap_timesteps)
+                        heatmap_timesteps, traces)
     while True:
         try:
             next(gen)
@@ -123,7 +124,7 @@ def denoise(model, img, img_ids, txt, txt_ids, vec, timesteps: list[float], guid
 
 def denoise_steps(model, img, img_ids, txt, txt_ids, vec, timesteps, guidance=4.0, concepts=None, concept_ids=None,
                   concept_vec=None, return_intermediate_images=True, joint_attention_kwargs=None,
-                  return_vectors=True, heatmaps=None, heatmap_timesteps=None):
+                  return_vectors=True, heatmaps=None, heatmap_timesteps=None, traces=None):
     """Generator form of ``denoise``: yields after the launches of each diffusion step have been
     enqueued (nothing is synchronised), so a caller can interleave several independent work items on
     different HIP streams; the generator's return value is denoise's (img, intermediates, dict)."""
@@ -143,10 +144,13 @@ def denoise_steps(model, img, img_ids, txt, txt_ids, vec, timesteps, guidance=4.
     for it, (t_curr, t_prev) in enumerate(zip(timesteps[:-1], timesteps[1:])):
         t_vec = torch.full((img.shape[0],), t_curr, dtype=torch.float32, device=img.device)
         hm = heatmaps if (heatmaps is not None and (sel is None or it in sel)) else None
+        if traces is not None and hm is not None:   # only the steps whose maps are taken are traced
+            traces[it] = StepTrace()
         pred, d = model(img=img if lat32 is None else lat32, img_ids=img_ids, txt=txt, txt_ids=txt_ids, concepts=concepts,
                         concept_ids=concept_ids, concept_vec=concept_vec, y=vec, timesteps=t_vec,
                         guidance=guidance_vec, iteration=it, joint_attention_kwargs=joint_attention_kwargs,
-                        return_vectors=return_vectors, heatmaps=hm, **({"cond_slot": it} if slots else {}))
+                        return_vectors=return_vectors, heatmaps=hm, **({"cond_slot": it} if slots else {}),
+                        **({"trace": traces[it]} if traces is not None and hm is not None else {}))
         if lat32 is None:
             ops.axpy(img, pred.contiguous(), t_prev - t_curr)  # img = img + (t_prev - t_curr) * pred  (:141)
         else:
