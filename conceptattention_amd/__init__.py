@@ -32,6 +32,9 @@ def __getattr__(name):  # lazy: keep `import conceptattention_amd` light for hos
                 "map_predictions_to_class_indices", "multiclass_table"):
         from . import segmentation
         return getattr(segmentation, name)
+    if name in ("RawOutputSpaceSegmentationModel", "RawValueSpaceSegmentationModel", "RawCrossAttentionSegmentationModel"):
+        from . import baselines
+        return getattr(baselines, name)
     if name == "concept_attention_frames":
         from .video import concept_attention_frames
         return concept_attention_frames

@@ -12,13 +12,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CA_LIB_PATH: another build of the same library (an A/B against another source tree); still no fallback
 LIB_PATH = os.environ.get("CA_LIB_PATH") or os.path.join(_HERE, "libconceptattn.so")
 
-CA_VERSION = 136
+CA_VERSION = 137
 EPI_BIAS, EPI_GELU_TANH, EPI_GATE_RESIDUAL, EPI_SPLIT_GELU, EPI_QKV_NORM_ROPE = 0, 1, 2, 3, 4
 TILE_AUTO, TILE_256x256, TILE_256x192, TILE_256x128, TILE_256x64 = 0, 1, 2, 3, 4
 TILE_PP_256x256, TILE_PP_256x128, TILE_PP_256x192 = 5, 6, 7
 GEMM_KERNEL_NONE, GEMM_KERNEL_CLASSIC, GEMM_KERNEL_PP, GEMM_KERNEL_PP_FP8 = 0, 1, 2, 3
 NORM_SOFTMAX, NORM_SPARSEMAX, NORM_ENTMAX15 = 0, 1, 2
 NORMS = {"softmax": NORM_SOFTMAX, "sparsemax": NORM_SPARSEMAX, "entmax15": NORM_ENTMAX15}
+NORM_NONE = 3                        # ca_head_maps only (csrc/ca_headmap.h): the weights are the logits themselves
 MAX_SEGMENTS = 16
 GEMM_MAX_PROBLEMS = 2
 ATTN_MAX_PROBLEMS = 16
@@ -46,6 +47,7 @@ RENDER_BILINEAR, RENDER_BLEND = 1, 2
 TOKMAP_MAX_PROBLEMS = 16             # ca_token_maps: problems of one launch (ops.token_maps splits longer lists)
 TOKMAP_MAX_TEXT = 512                # ca_token_maps: n0, the text key rows of a problem
 TOKMAP_QK_F16 = 1                    # ca_token_maps flags: IEEE half bits in the bf16-typed q / k rows
+HEADMAP_MAX_HEADS = 65536            # ca_head_maps: num_heads (heads of 128 columns)
 ATTN_Q_PRESCALED = 0.0   # ca_attn_fwd_bf16(scale=...): the q rows already carry softmax_scale * log2(e)
 
 
@@ -87,6 +89,12 @@ class TokmapProblem(C.Structure):    # ca_tokmap_problem (csrc/ca_tokmap.h), fie
     _fields_ = [("q", C.c_void_p), ("k0", C.c_void_p), ("k1", C.c_void_p), ("acc", C.c_void_p), ("acc2", C.c_void_p),
                 ("lse", C.c_void_p), ("nq", C.c_int32), ("ldq", C.c_int32), ("n0", C.c_int32), ("n1", C.c_int32),
                 ("ldk", C.c_int32), ("n_tok", C.c_int32), ("weight", C.c_float), ("weight2", C.c_float)]
+
+
+class HeadmapProblem(C.Structure):   # ca_headmap_problem (csrc/ca_headmap.h), field for field
+    _fields_ = [("img", C.c_void_p), ("con", C.c_void_p), ("heads", C.c_void_p), ("acc", C.c_void_p), ("acc2", C.c_void_p),
+                ("ldi", C.c_int32), ("ldc", C.c_int32), ("img_f32", C.c_int32), ("con_f32", C.c_int32),
+                ("weight_h", C.c_float), ("weight", C.c_float), ("weight2", C.c_float), ("_pad", C.c_int32)]
 
 
 class SegProblem(C.Structure):
@@ -210,14 +218,16 @@ SIGNATURES = {
                                     C.c_void_p, C.c_float, C.c_int32, C.c_void_p]),
 }
 
-# exported by the library and bound here, not declared in include/conceptattn.h yet (csrc/ca_heatmap_core.h and
-# csrc/ca_tokmap.h declare them)
+# exported by the library and bound here, not declared in include/conceptattn.h yet (csrc/ca_heatmap_core.h,
+# csrc/ca_tokmap.h and csrc/ca_headmap.h declare them)
 INTERNAL_SIGNATURES = {
     "ca_heatmap_many": (C.c_int, [C.POINTER(HeatmapProblem), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_void_p]),
     "ca_token_maps": (C.c_int, [C.POINTER(TokmapProblem), C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p,
                                 C.c_int64, C.c_void_p]),
     "ca_token_maps_workspace_bytes": (C.c_int64, [C.POINTER(TokmapProblem), C.c_int32, C.c_int32]),
+    "ca_head_maps": (C.c_int, [C.POINTER(HeadmapProblem), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                               C.c_void_p]),
 }
 
 _lib = None

@@ -10,7 +10,7 @@ PKG = os.path.dirname(HERE)
 LIB = os.path.join(PKG, "libconceptattn.so")
 SOURCES = ["ca_api.hip", "ca_gemm.hip", "ca_attn.hip", "ca_attn4.hip", "ca_rowops.hip", "ca_vae.hip", "ca_t5.hip",
            "ca_clip.hip", "ca_pixels.hip", "ca_seg.hip", "ca_mseg.hip", "ca_segtab.hip",
-           "ca_render.hip", "ca_heatmap_many.hip", "ca_tokmap.hip"]
+           "ca_render.hip", "ca_heatmap_many.hip", "ca_tokmap.hip", "ca_headmap.hip"]
 # ca_attn4.hip owns the AGPR file by hand (literal a[...] registers in its asm statements): hipcc must never park a
 # VGPR there (its default spill target), and the emitted code is audited for it below
 EXTRA_FLAGS = {"ca_attn4.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-save-temps=obj"],
@@ -24,9 +24,11 @@ EXTRA_FLAGS = {"ca_attn4.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-save
                # (read for spills as well; contraction stays on: the unit shares ca_heatmap_core.h's arithmetic with
                # ca_rowops.hip and must round as that unit does)
                "ca_heatmap_many.hip": ["-save-temps=obj"],
-               "ca_tokmap.hip": ["-save-temps=obj"]}   # (read for spills below)
+               "ca_tokmap.hip": ["-save-temps=obj"],   # (read for spills below)
+               # (the same; contraction stays on for ca_heatmap_core.h's weighting, the unit's own sums switch it off)
+               "ca_headmap.hip": ["-save-temps=obj"]}
 HEADERS = ["ca_common.h", "ca_attn_common.h", "ca_attn4_sched.inc", "ca_attn4_kernel.inc", "ca_seg_core.h",
-           "ca_text_core.h", "ca_heatmap_core.h", "ca_tokmap.h"]
+           "ca_text_core.h", "ca_heatmap_core.h", "ca_tokmap.h", "ca_headmap.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function"]
 
@@ -138,6 +140,16 @@ def audit_tokmap(asm_path: str) -> None:
     tile's 16 scores per lane in registers, all indexed by unrolled loops.  Every kernel of the unit must report no spill
     and no scratch."""
     _audit_no_spill("ca_tokmap", asm_path)
+
+
+def audit_headmap(asm_path: str) -> None:
+    """ca_headmap_kernel keeps a head's logits, their weights, the sort's two copies and two patches' running head sums in
+    registers (six arrays of up to 32 floats per lane at 17 .. 32 concepts, which is why that instantiation runs 256
+    threads), all indexed by unrolled loops.  Every kernel of the unit must report no spill and no scratch.  What this audit
+    does not see: the 32-concept instantiation needs more than 256 registers and the compiler places the rest (40) in AGPRs,
+    and all three instantiations keep scalar values in VGPR lanes (27 / 89 / 155 SGPR spills, mostly the lane masks of the
+    unrolled selects); neither touches memory."""
+    _audit_no_spill("ca_headmap", asm_path)
 
 
 def audit_sgpr_hazards(text: str) -> list:
@@ -398,6 +410,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     audit_render(os.path.join(HERE, "ca_render-hip-amdgcn-amd-amdhsa-gfx950.s"))
     audit_heatmap_many(os.path.join(HERE, "ca_heatmap_many-hip-amdgcn-amd-amdhsa-gfx950.s"))
     audit_tokmap(os.path.join(HERE, "ca_tokmap-hip-amdgcn-amd-amdhsa-gfx950.s"))
+    audit_headmap(os.path.join(HERE, "ca_headmap-hip-amdgcn-amd-amdhsa-gfx950.s"))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
     if verbose:
         print(" ".join(cmd), flush=True)

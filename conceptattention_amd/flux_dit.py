@@ -33,7 +33,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .heatmaps import check_concept_count
+from .heatmaps import check_concept_count, linear_normalization
 from .params import FluxParams
 from .weights import iter_synthetic_state_dict, state_dict_spec
 
@@ -166,6 +166,33 @@ class HeatmapRequest:
     # their first / second dimension (at most the text length); None: no launch
     token_space: Optional[torch.Tensor] = None
     per_layer_token: Optional[torch.Tensor] = None
+    # per-head concept maps and the raw-space baselines (ops.head_maps): per head of 128 the concept rows against the
+    # image rows of a space, weighted across the concepts per head with ``head_norm`` (None: the logits themselves, or a
+    # _lib.NORM_*), accumulated over the captured layers with ``weight``.  heads_* fp32 [num_heads, C, L] (the
+    # head-resolved maps), raw_* fp32 [C, L] (their mean over the heads); None: no launch.  The spaces: "output"
+    # (ATT32 / ATTI32, which makes the forward take the fp32 image rows' route), "cross" (QPRE), "value" (the v third of
+    # QKV).  ``head_normalize_concepts``: heatmaps.linear_normalization across the concepts of the concept rows first
+    heads_out: Optional[torch.Tensor] = None
+    heads_cross: Optional[torch.Tensor] = None
+    heads_value: Optional[torch.Tensor] = None
+    raw_out: Optional[torch.Tensor] = None
+    raw_cross: Optional[torch.Tensor] = None
+    raw_value: Optional[torch.Tensor] = None
+    head_norm: Optional[int] = None
+    head_normalize_concepts: bool = False
+    # the same spaces under further norms in the same forward: HeatmapRequests of which only these head-map fields are read
+    head_more: tuple = ()
+
+    def head_spaces(self) -> tuple:
+        """The spaces this request asks head maps of, as (name, heads tensor, raw tensor)."""
+        return tuple((n, h, r) for n, h, r in (("output", self.heads_out, self.raw_out),
+                                               ("cross", self.heads_cross, self.raw_cross),
+                                               ("value", self.heads_value, self.raw_value))
+                     if h is not None or r is not None)
+
+    def head_requests(self) -> tuple:
+        """This request and those of ``head_more`` that ask for head maps: one (spaces, norm, normalisation) each."""
+        return tuple(r for r in (self,) + tuple(self.head_more) if r.head_spaces())
 
 
 def modulation_rows(params: FluxParams) -> int:
@@ -572,6 +599,7 @@ class HipFluxDiT:
         ``heatmaps``) keeps the image side of the requested layers for ``requery``: the captured layers then take the fp32
         image rows' route (epilogue_logits = False) and the prediction stays bit for bit what it is without."""
         assert concept_vec is not None, "Concept vectors must be provided for this implementation."
+        heads_out = self._check_head_maps(heatmaps, return_vectors, joint_attention_kwargs)
         if trace is not None:
             if trace.filled:
                 raise ValueError("trace: an empty StepTrace per forward (this one is already filled)")
@@ -588,8 +616,41 @@ class HipFluxDiT:
             finally:
                 self.epilogue_logits = before
                 self._end_traced_block()
+        if heads_out and self.epilogue_logits:
+            # output-space head maps read the fp32 image rows ATTI32, as a trace does: the same route for this forward
+            self.epilogue_logits = False
+            try:
+                return self._forward(img, img_ids, txt, txt_ids, concepts, concept_ids, concept_vec, timesteps, y, guidance,
+                                     stop_after_multimodal_attentions, joint_attention_kwargs, return_vectors, heatmaps,
+                                     cond_slot)
+            finally:
+                self.epilogue_logits = True
         return self._forward(img, img_ids, txt, txt_ids, concepts, concept_ids, concept_vec, timesteps, y, guidance,
                              stop_after_multimodal_attentions, joint_attention_kwargs, return_vectors, heatmaps, cond_slot)
+
+    def _check_head_maps(self, heatmaps, return_vectors, joint_attention_kwargs) -> bool:
+        """The settings per-head maps do not cover, each named and raised before anything is launched.  Returns whether a
+        request asks for the output space (the forward then needs the fp32 image rows)."""
+        reqs = () if heatmaps is None else heatmaps if isinstance(heatmaps, (list, tuple)) else [heatmaps]
+        reqs = [r for h in reqs for r in h.head_requests()]
+        spaces = {n for h in reqs for n, _, _ in h.head_spaces()}
+        if not spaces:
+            return False
+        if return_vectors:
+            raise ValueError("head maps: a forward with per-head maps takes return_vectors=False (the stacked route has no "
+                             "per-head launch)")
+        if "output" in spaces and self.capture_independent_image:
+            raise ValueError("head maps: capture_independent_image=True is not covered by the output-space head maps "
+                             "(\"cross\" and \"value\" are)")
+        jak = joint_attention_kwargs or {}
+        if not (jak.get("concept_cross_attention", True) and jak.get("concept_self_attention", True)):
+            raise ValueError("head maps: the ablation joint_attention_kwargs (concept_cross_attention / "
+                             "concept_self_attention = False) are not covered by the per-head maps")
+        for h in reqs:
+            if h.head_norm is not None and h.head_norm not in L.NORMS.values():
+                raise ValueError(f"head maps: head_norm must be None or one of _lib.NORM_SOFTMAX / NORM_SPARSEMAX / "
+                                 f"NORM_ENTMAX15, got {h.head_norm}")
+        return "output" in spaces
 
     def _check_traceable(self, what: str, joint_attention_kwargs=None) -> None:
         """The settings a trace and a re-query do not cover, each named; raised before anything is launched."""
@@ -1052,6 +1113,42 @@ class HipFluxDiT:
                 batch.append(pr)
                 seen |= ptrs
 
+    def _capture_head_maps(self, layer, g, NH, heatmaps):
+        """The per-head maps of a captured layer: ONE ops.head_maps launch (per norm) for all items and spaces that ask,
+        over rows this layer has just written: ATT32 / ATTI32 (output space), QPRE (cross space), the v third of QKV
+        (value space).  No launch when no item asks."""
+        H, C, T, Li, oI = self.hidden_size, g.C, g.T, g.L, g.oI
+        launches = {}   # norm -> problems
+        for j in range(g.B if heatmaps is not None and C > 0 else 0):
+            hm = heatmaps[j]
+            if layer not in hm.layer_indices:
+                continue
+            cj, ij = slice(j * C, (j + 1) * C), slice(oI + j * Li, oI + (j + 1) * Li)
+            for hr, (name, heads, raw) in ((hr, s) for hr in hm.head_requests() for s in hr.head_spaces()):
+                if name == "output":
+                    img, con = self.ATTI32[j, T:], self.ATT32[cj]
+                elif name == "cross":
+                    img, con = self.QPRE[ij], self.QPRE[cj]
+                else:
+                    img, con = self.QKV[ij, 2 * H:], self.QKV[cj, 2 * H:]
+                if hr.head_normalize_concepts:
+                    # (C x hidden elements with torch: not a hot path; the launch reads a normalised copy)
+                    con = linear_normalization(con.float(), dim=0).contiguous()
+                launches.setdefault(L.NORM_NONE if hr.head_norm is None else hr.head_norm, []).append(
+                    ops.HeadMaps(img, con, heads=heads, weight_h=hm.weight, acc=raw, weight=hm.weight))
+        for norm, probs in launches.items():
+            # (two requests that share an accumulator start a new launch, as the concept maps' do)
+            batch, seen = [], set()
+            for pr in probs + [None]:
+                ptrs = set() if pr is None else {t.data_ptr() for t in (pr.heads, pr.acc) if t is not None}
+                if pr is None or len(batch) == L.HEATMAP_MAX_PROBLEMS or (ptrs & seen):
+                    if batch:
+                        ops.head_maps(batch, NH, norm)
+                    batch, seen = [], set()
+                if pr is not None:
+                    batch.append(pr)
+                    seen |= ptrs
+
     def _token_maps_workspace(self, probs, NH):
         """ops.token_maps' scratch memory: a model buffer allocated on first use and grown on demand (None while the
         kernel needs none)."""
@@ -1078,6 +1175,7 @@ class HipFluxDiT:
             return ((img_out, self.ATT32[cj], self.PART[j] if route.use_part else None), (QPRE[ij], QPRE[cj], None))
         self._heatmap_updates(layer, C, heatmaps, operands, self.LOGITS)
         self._capture_token_maps(layer, g, NH, heatmaps, route)
+        self._capture_head_maps(layer, g, NH, heatmaps)
         if return_vectors:
             H = self.hidden_size
             cf = torch.contiguous_format
@@ -1185,6 +1283,8 @@ class HipFluxDiT:
             check_concept_count(h.norm, C)
             if h.token_space is not None or h.per_layer_token is not None:
                 raise ValueError("requery: token maps are not part of a re-query (the text side has not changed)")
+            if h.head_requests():
+                raise ValueError("requery: per-head maps are not part of a re-query yet (ask for them in the forward)")
             missing = [l for l in h.layer_indices if l not in t.layers]
             if missing:
                 raise ValueError(f"requery: layer_indices {missing} lie outside the trace (traced layers {list(t.layers)})")

@@ -739,6 +739,100 @@ def token_maps(problems: Sequence[TokenMaps], num_heads: int, scale_log2: float 
                                   _stream()), "ca_token_maps")
 
 
+@dataclass
+class HeadMaps:
+    """One problem of a per-head concept map launch (ca_head_maps): per head of 128 columns the logits of the C rows of
+    ``con`` against the L rows of ``img``, weighted across the concepts per head; then heads += weight_h * w,
+    acc += weight * mean_h(w) and / or acc2 += weight2 * mean_h(w).  img / con bf16|fp32 2-D views [rows, num_heads*128]
+    (row stride free), heads fp32 [num_heads, C, L] contiguous, acc / acc2 fp32 [C, L] contiguous."""
+    img: torch.Tensor
+    con: torch.Tensor
+    heads: Optional[torch.Tensor] = None
+    weight_h: float = 0.0
+    acc: Optional[torch.Tensor] = None
+    weight: float = 0.0
+    acc2: Optional[torch.Tensor] = None
+    weight2: float = 0.0
+
+
+HEADMAP_NORMS = (L.NORM_NONE, L.NORM_SOFTMAX, L.NORM_SPARSEMAX, L.NORM_ENTMAX15)
+
+
+def _head_maps_array(problems: Sequence[HeadMaps], num_heads: int):
+    """ops.head_maps' argument checks (no device needed for the shape rules) and the problem array; returns
+    (array, L, C)."""
+    FN = "head_maps"
+    width = num_heads * 128
+    arr = (L.HeadmapProblem * len(problems))()
+    seen = {}
+    Lp = Cc = None
+    for i, t in enumerate(problems):
+        p = arr[i]
+        for n, x in (("img", t.img), ("con", t.con)):
+            if not isinstance(x, torch.Tensor) or x.dtype not in (torch.bfloat16, torch.float32):
+                raise ValueError(f"{FN}[{i}]: {n}: expected dtype bf16 or fp32")
+            _chk(x, x.dtype, n)
+            if x.dim() != 2 or x.shape[1] != width:
+                raise ValueError(f"{FN}[{i}]: {n} must be 2-D with num_heads*128 = {width} columns (hidden % 128 == 0), "
+                                 f"got {tuple(x.shape)}")
+            ld = _i32(x.stride(0), "ldi" if n == "img" else "ldc")
+            if x.shape[0] == 1 and ld < width:   # (a one-row tensor's stride is free in torch; the library wants the width)
+                ld = width
+            if ld < width:
+                raise ValueError(f"{FN}[{i}]: {n} row stride {ld} is below the width num_heads*128 = {width}")
+            per16 = 8 if x.dtype == torch.bfloat16 else 4
+            if x.data_ptr() % 16 or ld % per16:
+                raise ValueError(f"{FN}[{i}]: {n} rows must be 16-byte aligned (row stride a multiple of {per16} elements), "
+                                 f"got stride {ld}")
+            if n == "img":
+                p.ldi = ld
+            else:
+                p.ldc = ld
+        if Lp is None:
+            Lp, Cc = t.img.shape[0], t.con.shape[0]
+        if (t.img.shape[0], t.con.shape[0]) != (Lp, Cc):
+            raise ValueError(f"{FN}[{i}]: all problems of a call share L and C")
+        if Lp < 1 or not 1 <= Cc <= L.HEATMAP_MAX_CONCEPTS:
+            raise ValueError(f"{FN}[{i}]: need L >= 1 and 1 <= C <= {L.HEATMAP_MAX_CONCEPTS}, got L = {Lp}, C = {Cc}")
+        if t.heads is None and t.acc is None and t.acc2 is None:
+            raise ValueError(f"{FN}[{i}]: every problem needs heads, acc or acc2")
+        for name, shape in (("heads", (num_heads, Cc, Lp)), ("acc", (Cc, Lp)), ("acc2", (Cc, Lp))):
+            x = getattr(t, name)
+            if x is None:
+                continue
+            _chk(x, torch.float32, name)
+            if tuple(x.shape) != shape or not x.is_contiguous():
+                raise ValueError(f"{FN}[{i}]: {name} must be contiguous fp32 {list(shape)}, got {tuple(x.shape)}")
+            if x.data_ptr() in seen:
+                raise ValueError(f"{FN}[{i}]: {name} is also an accumulator of problem {seen[x.data_ptr()]} of this call "
+                                 "(their updates would race)")
+            seen[x.data_ptr()] = i
+            setattr(p, name, x.data_ptr())
+        p.img, p.con = t.img.data_ptr(), t.con.data_ptr()
+        p.img_f32, p.con_f32 = int(t.img.dtype == torch.float32), int(t.con.dtype == torch.float32)
+        p.weight_h, p.weight, p.weight2 = float(t.weight_h), float(t.weight), float(t.weight2)
+    return arr, Lp, Cc
+
+
+def head_maps(problems: Sequence[HeadMaps], num_heads: int, norm: int = L.NORM_NONE) -> None:
+    """Per-head concept maps (ca_head_maps), up to L.HEATMAP_MAX_PROBLEMS problems per launch (longer lists are split, in
+    order).  ``norm``: L.NORM_NONE (the logits themselves), NORM_SOFTMAX, NORM_SPARSEMAX or NORM_ENTMAX15, across the
+    concepts per head and patch."""
+    if len(problems) < 1:
+        raise ValueError("head_maps: at least one problem")
+    if not 1 <= num_heads <= L.HEADMAP_MAX_HEADS:
+        raise ValueError(f"head_maps: num_heads must be in 1 .. {L.HEADMAP_MAX_HEADS}")
+    if norm not in HEADMAP_NORMS:
+        raise ValueError(f"head_maps: norm must be one of L.NORM_NONE / NORM_SOFTMAX / NORM_SPARSEMAX / NORM_ENTMAX15, got {norm}")
+    arr, Lp, Cc = _head_maps_array(problems, num_heads)
+    lib = L.load()
+    for s in range(0, len(problems), L.HEATMAP_MAX_PROBLEMS):
+        n = min(L.HEATMAP_MAX_PROBLEMS, len(problems) - s)
+        sub = (L.HeadmapProblem * n).from_buffer(arr, s * C.sizeof(L.HeadmapProblem))
+        L.check(lib.ca_head_maps(sub, n, _i32(Lp, "L"), _i32(Cc, "C"), _i32(num_heads, "num_heads"), int(norm), _stream()),
+                "ca_head_maps")
+
+
 def axpy(x, y, a: float) -> None:
     """x += a*y (bf16, fp32 math)."""
     lib = L.load()

@@ -41,6 +41,49 @@ class ConceptAttentionPipelineOutput:
     tokens: Optional[list] = None
     # keep_trace=True: the image side of the call's traced steps, for ``ConceptAttentionFluxPipeline.requery``
     trace: Optional["ImageTrace"] = None
+    # head_maps="output" | "cross" | "value" (or a tuple of them): per space the head-resolved concept maps, an fp32 device
+    # tensor (num_heads, C, h, w), and their mean over the heads (C, h, w): the raw-space baselines' maps (ops.head_maps)
+    head_maps: Optional[dict] = None
+    raw_heatmaps: Optional[dict] = None
+
+
+HEAD_SPACES = {"output": ("heads_out", "raw_out"), "cross": ("heads_cross", "raw_cross"),
+               "value": ("heads_value", "raw_value")}   # space -> its two HeatmapRequest fields
+
+
+@dataclass
+class HeadMapAccumulators:
+    """One item's per-head maps while its forwards run: per asked space the zeroed fp32 [num_heads, C, patches] and
+    [C, patches] accumulators, the norm across the concepts (None: the logits themselves) and whether the concept rows
+    are linearly normalised across the concepts first."""
+    heads: dict
+    raw: dict
+    norm: Optional[int] = None
+    normalize_concepts: bool = False
+    name: Optional[str] = None    # the norm's name in the call's ``head_norm``
+    more: tuple = ()              # the same spaces under the call's further norms (several names in ``head_norm``)
+
+    def request_fields(self) -> dict:
+        """The keywords of this item's ``HeatmapRequest``."""
+        kw = dict(head_norm=self.norm, head_normalize_concepts=self.normalize_concepts)
+        for space, (hf, rf) in HEAD_SPACES.items():
+            if space in self.heads:
+                kw[hf], kw[rf] = self.heads[space], self.raw[space]
+        if self.more:
+            kw["head_more"] = tuple(HeatmapRequest((), 0.0, None, None, **m.request_fields()) for m in self.more)
+        return kw
+
+    def outputs(self, side: int) -> tuple:
+        """(head_maps, raw_heatmaps) of the finished item: dicts space -> (num_heads, C, side, side) / (C, side, side);
+        with several norms in the call the keys are (space, norm name)."""
+        every = (self,) + tuple(self.more)
+        key = (lambda s, a: (s, a.name)) if self.more else (lambda s, a: s)
+        return ({key(s, a): t.view(*t.shape[:2], side, side) for a in every for s, t in a.heads.items()},
+                {key(s, a): t.view(t.shape[0], side, side) for a in every for s, t in a.raw.items()})
+
+
+def head_request_fields(head_acc, j: int) -> dict:
+    return {} if head_acc is None or head_acc[j] is None else head_acc[j].request_fields()
 
 
 @dataclass
@@ -279,6 +322,34 @@ class ConceptAttentionFluxPipeline:
         treq = [self._token_request(p, token_maps) for p in prompts]
         return [torch.zeros(n, p, device=self.device) for (n, _), p in zip(treq, n_patches)], [t for _, t in treq]
 
+    # ------------------------------------------------------------------ per-head maps
+    def _head_plan(self, head_maps, head_norm, concept_counts, n_patches, normalize_concepts: bool = False):
+        """head_acc of a call's ``head_maps`` / ``head_norm`` arguments: per item a ``HeadMapAccumulators`` with zeroed
+        accumulators for the asked spaces; None when no head maps are asked for.  ValueError for an unknown space or
+        norm name."""
+        if head_maps is None or head_maps is False:
+            if head_norm is not None:
+                raise ValueError("head_norm is the norm of head_maps=; the call asks for no head maps")
+            return None
+        spaces = (head_maps,) if isinstance(head_maps, str) else tuple(head_maps)
+        unknown = [s for s in spaces if s not in HEAD_SPACES]
+        if unknown or not spaces or len(set(spaces)) != len(spaces):
+            raise ValueError(f"head_maps = {head_maps!r}: one of {list(HEAD_SPACES)} or a tuple of distinct ones")
+        names = [head_norm] if head_norm is None or isinstance(head_norm, str) else list(head_norm)
+        if not names or len(set(names)) != len(names) or any(n is not None and n not in _lib.NORMS for n in names):
+            raise ValueError(f"head_norm = {head_norm!r}: None or one of {list(_lib.NORMS)}, or a sequence of distinct ones")
+        if "output" in spaces and self.model.capture_independent_image:
+            raise ValueError("head_maps: capture_independent_image=True is not covered by the output-space head maps")
+        NH = self.params.num_heads
+        for C in concept_counts:
+            if not 1 <= C <= _lib.HEATMAP_MAX_CONCEPTS:
+                raise ValueError(f"head_maps: {C} concepts; 1 .. {_lib.HEATMAP_MAX_CONCEPTS} per item")
+        def one(C, p, name, more=()):
+            return HeadMapAccumulators({s: torch.zeros(NH, C, p, device=self.device) for s in spaces},
+                                       {s: torch.zeros(C, p, device=self.device) for s in spaces},
+                                       None if name is None else _lib.NORMS[name], bool(normalize_concepts), name, more)
+        return [one(C, p, names[0], tuple(one(C, p, n) for n in names[1:])) for C, p in zip(concept_counts, n_patches)]
+
     @staticmethod
     def _device_renderer(return_pil_heatmaps, cmap, heatmap_renderer, heatmap_size, heatmap_interpolation,
                          overlay_alpha) -> tuple:
@@ -298,19 +369,25 @@ class ConceptAttentionFluxPipeline:
                 heatmap_interpolation, overlay_alpha)
 
     def _chunk_outputs(self, idx, images, concept_heatmaps, cross_attention_maps, show, token_acc=None, tokens=None,
-                       pictures=None) -> list:
+                       pictures=None, head_acc=None) -> list:
         """The one way out of every call: the ConceptAttentionPipelineOutput of the items ``idx`` of a call after their
         forward.  ``images``: what ``image`` becomes; the two maps [len(idx), C, side, side] on the device; ``show``:
         ``_device_renderer``'s tuple; ``token_acc`` / ``tokens``: the call's (``_token_plan``); ``pictures``: with an
-        overlay, the chunk's uint8 [H, W, 3] device tensors the maps are laid over."""
+        overlay, the chunk's uint8 [H, W, 3] device tensors the maps are laid over; ``head_acc``: the call's
+        (``_head_plan``)."""
         on_device, return_pil_heatmaps, cmap, heatmap_size, heatmap_interpolation, overlay_alpha = show
         tok = [None if token_acc is None else token_acc[i].view(-1, *concept_heatmaps.shape[-2:]) for i in idx]
         tokens = [None if tokens is None else tokens[i] for i in idx]
         if on_device:
-            return self._finish_device(images, concept_heatmaps, cross_attention_maps, cmap, heatmap_size,
+            outs = self._finish_device(images, concept_heatmaps, cross_attention_maps, cmap, heatmap_size,
                                        heatmap_interpolation, overlay_alpha, pictures, tok, tokens)
-        return [self._finish(images[k], concept_heatmaps[k:k + 1], cross_attention_maps[k:k + 1], return_pil_heatmaps, cmap,
-                             tok[k], tokens[k]) for k in range(len(idx))]
+        else:
+            outs = [self._finish(images[k], concept_heatmaps[k:k + 1], cross_attention_maps[k:k + 1], return_pil_heatmaps,
+                                 cmap, tok[k], tokens[k]) for k in range(len(idx))]
+        if head_acc is not None:
+            for out, i in zip(outs, idx):
+                out.head_maps, out.raw_heatmaps = head_acc[i].outputs(concept_heatmaps.shape[-1])
+        return outs
 
     def _input_picture(self, image, height: int, width: int) -> torch.Tensor:
         """The bytes of an encode call's input image on the device, for overlays: uint8 [height, width, 3]."""
@@ -399,7 +476,8 @@ class ConceptAttentionFluxPipeline:
                        attention_norm: str = "sparsemax", cmap="plasma", latent: Optional[torch.Tensor] = None,
                        fused: bool = True, heatmap_renderer: str = "host", heatmap_size=None,
                        heatmap_interpolation: str = "nearest", overlay_alpha=None,
-                       token_maps=None, keep_trace: bool = False) -> ConceptAttentionPipelineOutput:
+                       token_maps=None, keep_trace: bool = False, head_maps=None, head_norm=None,
+                       head_normalize_concepts: bool = False) -> ConceptAttentionPipelineOutput:
         """``latent`` (1,16,h/8,w/8) overrides get_noise (device RNG differs between platforms);
         ``fused=False`` takes the reference's route (stack the per-layer vectors, then reduce).
         ``heatmap_renderer="device"`` makes the PIL heat maps on the device (ops.heatmap_render; the same bytes as
@@ -411,9 +489,18 @@ class ConceptAttentionFluxPipeline:
         blocks ``layer_indices``, mean over heads, layers and ``timesteps`` (DAAM; ops.token_maps); an int n -> the first
         n text rows, ``tokens`` None.  Needs the fused route.
         ``keep_trace=True``: ``out.trace`` (an ``ImageTrace``) keeps the image side of the steps in ``timesteps`` for
-        ``requery``; needs the fused route, bf16 precision and the default ``capture_independent_image``."""
+        ``requery``; needs the fused route, bf16 precision and the default ``capture_independent_image``.
+        ``head_maps``: "output", "cross" or "value" (or a tuple of them) -> ``out.head_maps[space]`` is the head-resolved
+        fp32 device tensor (num_heads, C, h, w) of that space and ``out.raw_heatmaps[space]`` (C, h, w) its mean over the
+        heads, both means over ``layer_indices`` and ``timesteps`` (ops.head_maps; the raw-space baselines' maps).
+        ``head_norm``: None (the logits themselves), "softmax", "sparsemax" or "entmax15", across the concepts PER HEAD; a
+        sequence of several of them computes all in the same forwards and keys both dicts by (space, norm name);
+        ``head_normalize_concepts``: heatmaps.linear_normalization across the concepts of the concept rows first.  Needs
+        the fused route; "output" makes the forwards take the fp32 image rows' route, as ``keep_trace`` does."""
         if keep_trace and not fused:
             raise ValueError("keep_trace needs the fused route: fused=False stacks the vectors and keeps no image side")
+        if head_maps and not fused:
+            raise ValueError("head_maps needs the fused route (fused=True)")
         if fused:   # (repeated timestep or layer indices still end on the stacked route: _generate_steps_inner)
             return self.generate_images(
                 [prompt], [concepts], seeds=[seed], latents=None if latent is None else [latent], width=width, height=height,
@@ -421,7 +508,8 @@ class ConceptAttentionFluxPipeline:
                 return_pil_heatmaps=return_pil_heatmaps, num_inference_steps=num_inference_steps, guidance=guidance,
                 softmax=softmax, attention_norm=attention_norm, heatmap_renderer=heatmap_renderer, heatmap_size=heatmap_size,
                 heatmap_interpolation=heatmap_interpolation, overlay_alpha=overlay_alpha, token_maps=token_maps,
-                keep_trace=keep_trace)[0]
+                keep_trace=keep_trace, head_maps=head_maps, head_norm=head_norm,
+                head_normalize_concepts=head_normalize_concepts)[0]
         norm = self._generate_norm(return_cross_attention, layer_indices, height, width, softmax, attention_norm)
         check_concept_count(norm, len(concepts))
         show = self._device_renderer(return_pil_heatmaps, cmap, heatmap_renderer, heatmap_size, heatmap_interpolation,
@@ -509,13 +597,13 @@ class ConceptAttentionFluxPipeline:
     @on_own_device
     def generate_on_device(self, latent, txt, vec, concept_embeddings, layer_indices=list(range(15, 19)),
                            num_inference_steps: int = 4, guidance: float = 0.0, timesteps=None, fused: bool = True,
-                           norm: int = 0, token_acc=None, traces: Optional[dict] = None):
+                           norm: int = 0, token_acc=None, traces: Optional[dict] = None, head_acc=None):
         """``token_acc``: per item, an fp32 [n_tok, patches] accumulator of the caller's for the prompt-token maps (zeroed
         by the caller; None, or None for an item: no token maps).  ``traces``: a dict of the caller's that receives step
-        index -> the ``StepTrace`` of every step in ``timesteps`` (fused route only).  The return tuple is the same with
-        and without either."""
+        index -> the ``StepTrace`` of every step in ``timesteps`` (fused route only).  ``head_acc``: per item, the
+        caller's ``HeadMapAccumulators`` (or None).  The return tuple is the same with and without any of them."""
         gen = self._generate_steps(self.model, latent, txt, vec, concept_embeddings, layer_indices,
-                                   num_inference_steps, guidance, timesteps, fused, norm, token_acc, traces)
+                                   num_inference_steps, guidance, timesteps, fused, norm, token_acc, traces, head_acc)
         while True:
             try:
                 next(gen)
@@ -524,7 +612,7 @@ class ConceptAttentionFluxPipeline:
 
     def _generate_steps(self, model, latent, txt, vec, concept_embeddings, layer_indices=list(range(15, 19)),
                         num_inference_steps: int = 4, guidance: float = 0.0, timesteps=None, fused: bool = True,
-                        norm: int = 0, token_acc=None, traces: Optional[dict] = None):
+                        norm: int = 0, token_acc=None, traces: Optional[dict] = None, head_acc=None):
         """The device-resident core of generate_image for B work items at once (B = 1 from the public API):
         latent (B,16,h/8,w/8), txt (B,T,4096), vec (B,768), concept_embeddings (B,C,4096) already in HBM ->
         (final latent tokens, concept heat maps fp32 [B,C,side,side], cross-attention maps fp32
@@ -554,12 +642,12 @@ class ConceptAttentionFluxPipeline:
         try:
             return (yield from self._generate_steps_inner(model, x, inp, con, con_ids, con_vec, schedule, ts, ls,
                                                           C, n_patches, guidance, layer_indices, timesteps, fused,
-                                                          norm, token_acc, traces))
+                                                          norm, token_acc, traces, head_acc))
         finally:
             model.keep_bf16_layers = keep_before  # this call's choice does not leak into later sweeps / encodes
 
     def _generate_steps_inner(self, model, x, inp, con, con_ids, con_vec, schedule, ts, ls, C, n_patches, guidance,
-                              layer_indices, timesteps, fused, norm=0, token_acc=None, traces=None):
+                              layer_indices, timesteps, fused, norm=0, token_acc=None, traces=None, head_acc=None):
         names = {v: k for k, v in _lib.NORMS.items()}
         # repeated indices weigh a (step, layer) pair repeatedly in the reference's fancy indexing
         # (concept_attention_pipeline.py:76-77); the fused accumulation covers distinct pairs only
@@ -573,11 +661,17 @@ class ConceptAttentionFluxPipeline:
                 raise ValueError("token_maps needs the fused route (fused=True, distinct timesteps and layer indices)")
             if len(token_acc) != B:
                 raise ValueError("token_acc: one accumulator (or None) per work item")
+        if head_acc is not None:
+            if not fused:
+                raise ValueError("head_maps needs the fused route (fused=True, distinct timesteps and layer indices)")
+            if len(head_acc) != B:
+                raise ValueError("head_acc: one HeadMapAccumulators (or None) per work item")
         if fused:
             acc_o = torch.zeros(B, C, n_patches, device=self.device)
             acc_c = torch.zeros(B, C, n_patches, device=self.device)
             reqs = [HeatmapRequest(tuple(ls), 1.0 / (len(ts) * len(ls)), acc_o[j], acc_c[j], norm=norm,
-                                   token_space=None if token_acc is None else token_acc[j])
+                                   token_space=None if token_acc is None else token_acc[j],
+                                   **head_request_fields(head_acc, j))
                     for j in range(B)]
             img, _, _ = yield from sampling.denoise_steps(
                 model, **inp, timesteps=schedule, guidance=guidance, concepts=con, concept_ids=con_ids,
@@ -677,7 +771,8 @@ class ConceptAttentionFluxPipeline:
                      attention_norm: str = "sparsemax", softmax=True,
                      joint_attention_kwargs=None, noise=None, vae_noise=None, heatmap_renderer: str = "host",
                      heatmap_size=None, heatmap_interpolation: str = "nearest",
-                     overlay_alpha=None, token_maps=None, keep_trace: bool = False) -> ConceptAttentionPipelineOutput:
+                     overlay_alpha=None, token_maps=None, keep_trace: bool = False, head_maps=None, head_norm=None,
+                     head_normalize_concepts: bool = False) -> ConceptAttentionPipelineOutput:
         """``image``: a latent tensor (1,16,h/8,w/8), or a PIL image when the pipeline has an autoencoder
         (``autoencoder="synthetic"``, a ``.safetensors`` path, or an injected object).
         One forward of the 19 double blocks per noise sample (stop_after_multimodal_attentions).
@@ -689,7 +784,9 @@ class ConceptAttentionFluxPipeline:
         ``generate_image``; the overlays are laid over the INPUT image's bytes, which must already be height x width.
         ``token_maps``: as in ``generate_image`` (the mean runs over heads, layers and noise samples).
         ``keep_trace=True``: ``out.trace`` keeps the image side of every noise sample's forward for ``requery`` (its
-        step keys are the sample indices)."""
+        step keys are the sample indices).
+        ``head_maps`` / ``head_norm`` / ``head_normalize_concepts``: as in ``generate_image`` (the mean runs over layers
+        and noise samples); not with the ablation ``joint_attention_kwargs``."""
         return self.encode_images(
             [image], [concepts], [prompt], width=width, height=height, layer_indices=layer_indices, num_samples=num_samples,
             num_steps=num_steps, noise_timestep=noise_timestep, seed=seed, noise=None if noise is None else [noise],
@@ -697,7 +794,8 @@ class ConceptAttentionFluxPipeline:
             stop_after_multi_modal_attentions=stop_after_multi_modal_attentions, attention_norm=attention_norm,
             softmax=softmax, joint_attention_kwargs=joint_attention_kwargs, heatmap_renderer=heatmap_renderer,
             heatmap_size=heatmap_size, heatmap_interpolation=heatmap_interpolation, overlay_alpha=overlay_alpha,
-            token_maps=token_maps, keep_trace=keep_trace)[0]
+            token_maps=token_maps, keep_trace=keep_trace, head_maps=head_maps, head_norm=head_norm,
+            head_normalize_concepts=head_normalize_concepts)[0]
 
     def _encode_pixels(self, images, height: int, width: int, vae_noise=None) -> torch.Tensor:
         """PIL images -> bf16 latents (B,16,h/8,w/8).  The HIP autoencoder takes the bytes (``encode_pixels``: resize,
@@ -719,12 +817,13 @@ class ConceptAttentionFluxPipeline:
         return self.autoencoder.encode(torch.cat(xs), **kw).to(torch.bfloat16)
 
     def _encode_maps(self, model, latent, txt, vec, con, con_ids, con_vec, settings: EncodeSettings, *, noise=None,
-                     token_acc=None, traces: Optional[dict] = None):
+                     token_acc=None, traces: Optional[dict] = None, head_acc=None):
         """Device core of encode_image for B images at once (latent (B,16,h,w), txt (B,T,4096), ...): one forward
         per noise sample on ``model``; returns the two fp32 maps [B, C, side, side].  ``noise``: optional list of
         num_samples tensors (1 or B,16,h,w) used instead of get_noise(seed + i).  ``token_acc``: per item, the caller's
         zeroed fp32 [n_tok, patches] accumulator of the prompt-token maps (or None); ``traces``: a dict of the caller's that
-        receives sample index -> the StepTrace of that sample's forward; the return tuple stays."""
+        receives sample index -> the StepTrace of that sample's forward; ``head_acc``: per item, the caller's
+        ``HeadMapAccumulators`` (or None); the return tuple stays."""
         layer_indices, num_samples, noise_timestep = settings.layer_indices, settings.num_samples, settings.noise_timestep
         if noise is not None and len(noise) != num_samples:
             raise ValueError("noise: one tensor per noise sample")
@@ -739,7 +838,8 @@ class ConceptAttentionFluxPipeline:
         acc_o = torch.zeros(B, C, n_patches, device=self.device)
         acc_c = torch.zeros(B, C, n_patches, device=self.device)
         req = [HeatmapRequest(tuple(int(l) for l in layer_indices), 1.0 / (num_samples * len(layer_indices)),
-                              acc_o[j], acc_c[j], norm=settings.norm, token_space=None if token_acc is None else token_acc[j])
+                              acc_o[j], acc_c[j], norm=settings.norm, token_space=None if token_acc is None else token_acc[j],
+                              **head_request_fields(head_acc, j))
                for j in range(B)]
         schedule = sampling.get_schedule(settings.num_steps, n_patches, shift=(not self.is_schnell))
         for i in range(num_samples):
@@ -771,12 +871,13 @@ class ConceptAttentionFluxPipeline:
         return tuple(_cat(e[k] for e in emb) for k in range(n_out))
 
     def _encode_chunks(self, images, concepts, prompts, settings: EncodeSettings, *, noise=None, vae_noise=None,
-                       token_acc=None, keep_trace: bool = False):
+                       token_acc=None, keep_trace: bool = False, head_acc=None):
         """The forwards of ``encode_images``, one at a time: yields (item indices, acc_o, acc_c) with the two fp32 maps
         [len(indices), C, side, side] of the chunk still on the device (``_encode_maps``).  ``images`` and ``prompts`` are lists;
         ``settings`` was built with the call's largest concept count; ``noise`` / ``vae_noise``: as ``encode_images`` takes them;
         ``token_acc``: per item of the call, the caller's accumulator of the prompt-token maps (or None).  With
-        ``keep_trace`` a fourth entry follows: sample index -> the StepTrace of the chunk's forward."""
+        ``keep_trace`` a fourth entry follows: sample index -> the StepTrace of the chunk's forward.  ``head_acc``: per item
+        of the call, its ``HeadMapAccumulators`` (or None for the call)."""
         n, height, width = len(images), settings.height, settings.width
         concepts = _per_item(concepts, n, "encode_images: concepts")
         for name, v in (("prompts", prompts), ("noise", noise), ("vae_noise", vae_noise)):
@@ -798,7 +899,8 @@ class ConceptAttentionFluxPipeline:
                                              for s_ in range(settings.num_samples)]
             traces = {} if keep_trace else None
             ho, hc = self._encode_maps(self.model, latent, txt, vec, con, con_ids, con_vec, settings, noise=nz,
-                                       token_acc=None if token_acc is None else [token_acc[i] for i in idx], traces=traces)
+                                       token_acc=None if token_acc is None else [token_acc[i] for i in idx], traces=traces,
+                                       head_acc=None if head_acc is None else [head_acc[i] for i in idx])
             yield (idx, ho, hc, traces) if keep_trace else (idx, ho, hc)
 
     @torch.no_grad()
@@ -809,7 +911,8 @@ class ConceptAttentionFluxPipeline:
                       return_pil_heatmaps: bool = True, cmap="plasma", stop_after_multi_modal_attentions=True,
                       attention_norm: str = "sparsemax", softmax=True, joint_attention_kwargs=None,
                       heatmap_renderer: str = "host", heatmap_size=None, heatmap_interpolation: str = "nearest",
-                      overlay_alpha=None, token_maps=None, keep_trace: bool = False) -> list:
+                      overlay_alpha=None, token_maps=None, keep_trace: bool = False, head_maps=None, head_norm=None,
+                      head_normalize_concepts: bool = False) -> list:
         """``encode_image`` for a list of images: a list of ConceptAttentionPipelineOutput in item order, every item with
         the maps of its own ``encode_image`` call.  ``images``: PIL images and / or latents (1,16,h/8,w/8);
         ``concepts``: one list for all items or one list per item; ``prompts``: one string per item (or one for all).
@@ -820,7 +923,8 @@ class ConceptAttentionFluxPipeline:
         reproducible per call of this method, not against single calls.  ``heatmap_renderer="device"``: the pictures of
         a chunk come from one launch and one download (``_finish_device``).  ``token_maps``: as in ``encode_image``, for
         every item's own prompt (the items of a chunk may have different numbers of tokens).  ``keep_trace``: as in
-        ``encode_image``, per item."""
+        ``encode_image``, per item.  ``head_maps`` / ``head_norm`` / ``head_normalize_concepts``: as in ``encode_image``,
+        per item."""
         if keep_trace:
             self.model._check_traceable("keep_trace", joint_attention_kwargs)
         images = list(images)
@@ -837,11 +941,15 @@ class ConceptAttentionFluxPipeline:
             for im in images])
         pictures = [self._input_picture(im, height, width) for im in images] if show[0] and overlay_alpha is not None \
             else None
+        head_acc = self._head_plan(head_maps, head_norm, [len(c) for c in concepts], [
+            (im.shape[-1] // 2) * (im.shape[-2] // 2) if isinstance(im, torch.Tensor) else (height // 16) * (width // 16)
+            for im in images], head_normalize_concepts)
         results = {}
         for idx, ho, hc, *traces in self._encode_chunks(images, concepts, prompts, settings, noise=noise,
-                                                        vae_noise=vae_noise, token_acc=token_acc, keep_trace=keep_trace):
+                                                        vae_noise=vae_noise, token_acc=token_acc, keep_trace=keep_trace,
+                                                        head_acc=head_acc):
             outs = self._chunk_outputs(idx, [images[i] for i in idx], ho, hc, show, token_acc, tokens,
-                                       None if pictures is None else [pictures[i] for i in idx])
+                                       None if pictures is None else [pictures[i] for i in idx], head_acc)
             if keep_trace:
                 self._attach_traces(outs, traces[0], dict(
                     call="encode_image", width=width, height=height, layer_indices=list(layer_indices),
@@ -857,14 +965,16 @@ class ConceptAttentionFluxPipeline:
                         num_inference_steps: int = 4, guidance: float = 0.0, timesteps=None, softmax: bool = True,
                         attention_norm: str = "sparsemax", cmap="plasma", batch: int = 5,
                         heatmap_renderer: str = "host", heatmap_size=None, heatmap_interpolation: str = "nearest",
-                        overlay_alpha=None, token_maps=None, keep_trace: bool = False) -> list:
+                        overlay_alpha=None, token_maps=None, keep_trace: bool = False, head_maps=None, head_norm=None,
+                        head_normalize_concepts: bool = False) -> list:
         """``generate_image`` for a list of prompts: a list of ConceptAttentionPipelineOutput in item order, every item
         with the image and maps of its own ``generate_image(prompt, concepts, seed=seeds[i], latent=latents[i])`` call on
         the fused route.  ``concepts``: one list for all items or one list per item; ``seeds``: one per item (default
         0, 1, 2, ...).  Items with one concept count go ``batch`` (at most 5) at a time through one text-encoder call,
         one denoising loop and one autoencoder pass whose bytes are made on the device.  ``token_maps``: as in
         ``generate_image``, for every item's own prompt (the items of a chunk may have different numbers of tokens).
-        ``keep_trace``: as in ``generate_image``; every item's ``trace`` is its own view of its forward's storage."""
+        ``keep_trace``: as in ``generate_image``; every item's ``trace`` is its own view of its forward's storage.
+        ``head_maps`` / ``head_norm`` / ``head_normalize_concepts``: as in ``generate_image``, per item."""
         norm = self._generate_norm(return_cross_attention, layer_indices, height, width, softmax, attention_norm)
         if keep_trace:
             self.model._check_traceable("keep_trace")
@@ -880,6 +990,8 @@ class ConceptAttentionFluxPipeline:
                 raise ValueError(f"generate_images: {name} has {len(v)} entries for {n} prompts")
         shapes = [(16, height // 8, width // 8) if latents is None else tuple(latents[i].shape[1:]) for i in range(n)]
         token_acc, tokens = self._token_plan(prompts, token_maps, [(s[1] // 2) * (s[2] // 2) for s in shapes])
+        head_acc = self._head_plan(head_maps, head_norm, [len(c) for c in concepts],
+                                   [(s[1] // 2) * (s[2] // 2) for s in shapes], head_normalize_concepts)
         results = {}
         for idx in plan_batches([(shapes[i], len(concepts[i]), self._text_length()) for i in range(n)], batch):
             txt, vec, con = self._embed_chunk(prompts, concepts, idx, 3)
@@ -890,9 +1002,10 @@ class ConceptAttentionFluxPipeline:
                                                   num_inference_steps=num_inference_steps, guidance=guidance,
                                                   timesteps=timesteps, fused=True, norm=norm,
                                                   token_acc=None if token_acc is None else [token_acc[i] for i in idx],
-                                                  traces=traces)
+                                                  traces=traces,
+                                                  head_acc=None if head_acc is None else [head_acc[i] for i in idx])
             pictures, pix = self._decode(img, height, width, show[0] and overlay_alpha is not None)
-            outs = self._chunk_outputs(idx, pictures, ho, hc, show, token_acc, tokens, pix)
+            outs = self._chunk_outputs(idx, pictures, ho, hc, show, token_acc, tokens, pix, head_acc)
             if keep_trace:
                 self._attach_traces(outs, traces, dict(
                     call="generate_image", width=width, height=height, layer_indices=list(layer_indices),

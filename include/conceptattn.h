@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CA_VERSION 136 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
+#define CA_VERSION 137 /* 0.1.2: ca_gemm_problem.qpre_f32 / q_out_scale, fp32 image vectors in ca_heatmap_logits_bf16,
                           CA_ATTN_Q_PRESCALED; .1: ca_axpy_f32, ca_split_bf16; .2: ca_attn_stats; .3: ca_gemm_problem.qk_f16,
                           ca_attn_fwd_qk16; .4: ca_qpre_finish_rope_f32; .5: ca_heatmap_fused; .6: ca_gemm_plan;
                           .7: the autoencoder kernels (conv3x3_nhwc, groupnorm_nhwc, softmax_rows_f32, affine_rows_f32);
@@ -40,7 +40,8 @@ extern "C" {
                           133: multi-class segmentation scoring on the device (mseg_score);
                           134: sweep tables of maps scored against one label on the device (segtab_score);
                           135: heat-map pictures on the device (heatmap_render);
-                          136: sparse norms of heatmap_norm_accumulate up to C = 32 (CA_HEATMAP_MAX_CONCEPTS) */
+                          136: sparse norms of heatmap_norm_accumulate up to C = 32 (CA_HEATMAP_MAX_CONCEPTS);
+                          137: per-head concept maps (head_maps, declared in csrc/ca_headmap.h) */
 
 #define CA_OK 0
 #define CA_ERR_ARG (-1)    /* bad shape / null pointer / misalignment */
