@@ -32,7 +32,8 @@ def __getattr__(name):  # lazy: keep `import conceptattention_amd` light for hos
                 "map_predictions_to_class_indices", "multiclass_table"):
         from . import segmentation
         return getattr(segmentation, name)
-    if name in ("RawOutputSpaceSegmentationModel", "RawValueSpaceSegmentationModel", "RawCrossAttentionSegmentationModel"):
+    if name in ("RawOutputSpaceSegmentationModel", "RawValueSpaceSegmentationModel", "RawCrossAttentionSegmentationModel",
+                "DAAMFluxSegmentationModel"):
         from . import baselines
         return getattr(baselines, name)
     if name == "concept_attention_frames":

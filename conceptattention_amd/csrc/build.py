@@ -10,7 +10,8 @@ PKG = os.path.dirname(HERE)
 LIB = os.path.join(PKG, "libconceptattn.so")
 SOURCES = ["ca_api.hip", "ca_gemm.hip", "ca_attn.hip", "ca_attn4.hip", "ca_rowops.hip", "ca_vae.hip", "ca_t5.hip",
            "ca_clip.hip", "ca_pixels.hip", "ca_seg.hip", "ca_mseg.hip", "ca_segtab.hip",
-           "ca_render.hip", "ca_heatmap_many.hip", "ca_tokmap.hip", "ca_headmap.hip"]
+           "ca_render.hip", "ca_heatmap_many.hip", "ca_tokmap.hip", "ca_headmap.hip",
+           "ca_querymap.hip"]
 # ca_attn4.hip owns the AGPR file by hand (literal a[...] registers in its asm statements): hipcc must never park a
 # VGPR there (its default spill target), and the emitted code is audited for it below
 EXTRA_FLAGS = {"ca_attn4.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-save-temps=obj"],
@@ -26,9 +27,10 @@ EXTRA_FLAGS = {"ca_attn4.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-save
                "ca_heatmap_many.hip": ["-save-temps=obj"],
                "ca_tokmap.hip": ["-save-temps=obj"],   # (read for spills below)
                # (the same; contraction stays on for ca_heatmap_core.h's weighting, the unit's own sums switch it off)
-               "ca_headmap.hip": ["-save-temps=obj"]}
+               "ca_headmap.hip": ["-save-temps=obj"],
+               "ca_querymap.hip": ["-save-temps=obj"]}   # (read for spills below)
 HEADERS = ["ca_common.h", "ca_attn_common.h", "ca_attn4_sched.inc", "ca_attn4_kernel.inc", "ca_seg_core.h",
-           "ca_text_core.h", "ca_heatmap_core.h", "ca_tokmap.h", "ca_headmap.h"]
+           "ca_text_core.h", "ca_heatmap_core.h", "ca_tokmap.h", "ca_headmap.h", "ca_querymap.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function"]
 
@@ -150,6 +152,13 @@ def audit_headmap(asm_path: str) -> None:
     and all three instantiations keep scalar values in VGPR lanes (27 / 89 / 155 SGPR spills, mostly the lane masks of the
     unrolled selects); neither touches memory."""
     _audit_no_spill("ca_headmap", asm_path)
+
+
+def audit_querymap(asm_path: str) -> None:
+    """qm_emit_kernel keeps a head's q fragment and two key fragments (48 registers), the next head's (48) and the lane's
+    eight running head sums in registers, qm_stats_kernel a q fragment and two key fragments, all indexed by unrolled
+    loops.  Every kernel of the unit must report no spill and no scratch."""
+    _audit_no_spill("ca_querymap", asm_path)
 
 
 def audit_sgpr_hazards(text: str) -> list:
@@ -411,6 +420,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     audit_heatmap_many(os.path.join(HERE, "ca_heatmap_many-hip-amdgcn-amd-amdhsa-gfx950.s"))
     audit_tokmap(os.path.join(HERE, "ca_tokmap-hip-amdgcn-amd-amdhsa-gfx950.s"))
     audit_headmap(os.path.join(HERE, "ca_headmap-hip-amdgcn-amd-amdhsa-gfx950.s"))
+    audit_querymap(os.path.join(HERE, "ca_querymap-hip-amdgcn-amd-amdhsa-gfx950.s"))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
     if verbose:
         print(" ".join(cmd), flush=True)

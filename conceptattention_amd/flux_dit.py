@@ -166,6 +166,14 @@ class HeatmapRequest:
     # their first / second dimension (at most the text length); None: no launch
     token_space: Optional[torch.Tensor] = None
     per_layer_token: Optional[torch.Tensor] = None
+    # query-row maps (ops.query_maps), the other direction: where the item's first n_tok text rows, and its concept rows,
+    # look in the image -- the probability each such query row's own softmax puts on every image key, averaged over the
+    # heads, accumulated as the concept maps are.  Text rows: the joint [text | image] problem's; concept rows: their own
+    # [concept | image] problem's.  fp32 [n_tok, L] / [C, L] and / or [len(layer_indices), ., L]; None: no launch
+    token_query_space: Optional[torch.Tensor] = None
+    per_layer_token_query: Optional[torch.Tensor] = None
+    concept_query_space: Optional[torch.Tensor] = None
+    per_layer_concept_query: Optional[torch.Tensor] = None
     # per-head concept maps and the raw-space baselines (ops.head_maps): per head of 128 the concept rows against the
     # image rows of a space, weighted across the concepts per head with ``head_norm`` (None: the logits themselves, or a
     # _lib.NORM_*), accumulated over the captured layers with ``weight``.  heads_* fp32 [num_heads, C, L] (the
@@ -182,6 +190,12 @@ class HeatmapRequest:
     head_normalize_concepts: bool = False
     # the same spaces under further norms in the same forward: HeatmapRequests of which only these head-map fields are read
     head_more: tuple = ()
+
+    def query_kinds(self) -> tuple:
+        """The query-row maps this request asks for, as (kind, accumulator, per-layer table)."""
+        return tuple((k, a, t) for k, a, t in (("tokens", self.token_query_space, self.per_layer_token_query),
+                                               ("concepts", self.concept_query_space, self.per_layer_concept_query))
+                     if a is not None or t is not None)
 
     def head_spaces(self) -> tuple:
         """The spaces this request asks head maps of, as (name, heads tensor, raw tensor)."""
@@ -600,6 +614,7 @@ class HipFluxDiT:
         image rows' route (epilogue_logits = False) and the prediction stays bit for bit what it is without."""
         assert concept_vec is not None, "Concept vectors must be provided for this implementation."
         heads_out = self._check_head_maps(heatmaps, return_vectors, joint_attention_kwargs)
+        self._check_query_maps(heatmaps, joint_attention_kwargs)
         if trace is not None:
             if trace.filled:
                 raise ValueError("trace: an empty StepTrace per forward (this one is already filled)")
@@ -651,6 +666,16 @@ class HipFluxDiT:
                 raise ValueError(f"head maps: head_norm must be None or one of _lib.NORM_SOFTMAX / NORM_SPARSEMAX / "
                                  f"NORM_ENTMAX15, got {h.head_norm}")
         return "output" in spaces
+
+    def _check_query_maps(self, heatmaps, joint_attention_kwargs) -> None:
+        """The settings query-row maps do not cover, raised before anything is launched."""
+        reqs = () if heatmaps is None else heatmaps if isinstance(heatmaps, (list, tuple)) else [heatmaps]
+        kinds = {k for h in reqs for k, _, _ in h.query_kinds()}
+        jak = joint_attention_kwargs or {}
+        if "concepts" in kinds and not (jak.get("concept_cross_attention", True) and jak.get("concept_self_attention", True)):
+            raise ValueError("query maps: the ablation joint_attention_kwargs (concept_cross_attention / "
+                             "concept_self_attention = False) change the concept rows' key set and are not covered by the "
+                             "concept rows' query maps")
 
     def _check_traceable(self, what: str, joint_attention_kwargs=None) -> None:
         """The settings a trace and a re-query do not cover, each named; raised before anything is launched."""
@@ -1113,6 +1138,52 @@ class HipFluxDiT:
                 batch.append(pr)
                 seen |= ptrs
 
+    def _capture_query_maps(self, layer, g, NH, heatmaps, route):
+        """The query-row maps of a captured layer: ONE ops.query_maps call for all items and both kinds that ask, over the
+        q and k rows this layer's attention problems have just read (QKV still holds them).  Text rows: the first n_tok q
+        rows of the item's joint [text | image] problem against its keys.  Concept rows: the q rows of the concept rows' own
+        problem, concept_problem(j, qs, ..) of _double_block, against its [concept | image] keys -- on every route the q
+        third of QKV (under the split the low-plane launch has left the accurate q there; under
+        capture_independent_image it is the rows whose output feeds proj, as the token maps use the joint problem that
+        makes the image).  All these q rows carry Q_OUT_SCALE, so scale_log2 = 1.  No launch when no item asks."""
+        H, C, T, Li, oT, oI = self.hidden_size, g.C, g.T, g.L, g.oT, g.oI
+        qs, ks = self.QKV[:, :H], self.QKV[:, H:2 * H]
+        probs = []
+        for j in range(g.B if heatmaps is not None else 0):
+            hm = heatmaps[j]
+            if layer not in hm.layer_indices:
+                continue
+            li = hm.layer_indices.index(layer)
+            cj, tj, ij = slice(j * C, (j + 1) * C), slice(oT + j * T, oT + (j + 1) * T), slice(oI + j * Li, oI + (j + 1) * Li)
+            for kind, acc, tables in hm.query_kinds():
+                table = None if tables is None else tables[li]
+                if kind == "tokens":
+                    n_tok = (acc if acc is not None else table).shape[0]
+                    q, k0 = qs[tj][:n_tok], ks[tj]
+                else:
+                    q, k0 = qs[cj], ks[cj]
+                probs.append(ops.QueryMaps(q, k0, ks[ij], acc=acc, weight=hm.weight, acc2=table, weight2=hm.per_layer_weight))
+        # (two requests that share an accumulator start a new launch, as the concept maps' do)
+        batch, seen = [], set()
+        for pr in probs + [None]:
+            ptrs = set() if pr is None else {t.data_ptr() for t in (pr.acc, pr.acc2) if t is not None}
+            if pr is None or len(batch) == L.QUERYMAP_MAX_PROBLEMS or (ptrs & seen):
+                if batch:
+                    ops.query_maps(batch, NH, 1.0, qk_f16=route.qk16, workspace=self._query_maps_workspace(batch, NH))
+                batch, seen = [], set()
+            if pr is not None:
+                batch.append(pr)
+                seen |= ptrs
+
+    def _query_maps_workspace(self, probs, NH):
+        """ops.query_maps' scratch memory (8 bytes per head and query row): a model buffer allocated on first use and
+        grown on demand."""
+        need = ops.query_maps_workspace_bytes(probs, NH)
+        ws = getattr(self, "_querymap_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._querymap_ws = torch.empty(need, device=self.device, dtype=torch.uint8)
+        return ws
+
     def _capture_head_maps(self, layer, g, NH, heatmaps):
         """The per-head maps of a captured layer: ONE ops.head_maps launch (per norm) for all items and spaces that ask,
         over rows this layer has just written: ATT32 / ATTI32 (output space), QPRE (cross space), the v third of QKV
@@ -1175,6 +1246,7 @@ class HipFluxDiT:
             return ((img_out, self.ATT32[cj], self.PART[j] if route.use_part else None), (QPRE[ij], QPRE[cj], None))
         self._heatmap_updates(layer, C, heatmaps, operands, self.LOGITS)
         self._capture_token_maps(layer, g, NH, heatmaps, route)
+        self._capture_query_maps(layer, g, NH, heatmaps, route)
         self._capture_head_maps(layer, g, NH, heatmaps)
         if return_vectors:
             H = self.hidden_size
@@ -1283,6 +1355,8 @@ class HipFluxDiT:
             check_concept_count(h.norm, C)
             if h.token_space is not None or h.per_layer_token is not None:
                 raise ValueError("requery: token maps are not part of a re-query (the text side has not changed)")
+            if h.query_kinds():
+                raise ValueError("requery: query-row maps are not part of a re-query (ask for them in the forward)")
             if h.head_requests():
                 raise ValueError("requery: per-head maps are not part of a re-query yet (ask for them in the forward)")
             missing = [l for l in h.layer_indices if l not in t.layers]

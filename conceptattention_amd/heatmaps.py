@@ -46,6 +46,66 @@ def linear_normalization(x: torch.Tensor, dim: int) -> torch.Tensor:
     return x_shifted / x_sum
 
 
+WORD_MARK = "\u2581"          # sentencepiece's word-start mark
+_PUNCTUATION = "!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~"
+
+
+def word_groups(tokens) -> list:
+    """[(word, [token indices])] of a prompt's token strings, in order.  Sentencepiece pieces (any token carries the
+    word-start mark): a token that begins with the mark opens a word, the pieces behind it belong to it (the first token
+    opens one either way); the mark is not part of the word.  One-string-per-byte tokens (t5.ToyByteTokenizer): words
+    split at the space byte, which belongs to no word; the bytes are joined and read as UTF-8.  Any other token list:
+    every token is its own word.  A word without a character (a lone mark) is left out."""
+    tokens = list(tokens)
+    groups = []
+    if any(t.startswith(WORD_MARK) for t in tokens):
+        for i, t in enumerate(tokens):
+            if t.startswith(WORD_MARK) or not groups:
+                groups.append(["", []])
+            groups[-1][0] += t[len(WORD_MARK):] if t.startswith(WORD_MARK) else t
+            groups[-1][1].append(i)
+    elif tokens and all(len(t) == 1 and ord(t) < 256 for t in tokens):
+        open_ = False
+        for i, t in enumerate(tokens):
+            if t == " ":
+                open_ = False
+                continue
+            if not open_:
+                groups.append([b"", []])
+                open_ = True
+            groups[-1][0] += t.encode("latin-1")
+            groups[-1][1].append(i)
+        groups = [[w.decode("utf-8", errors="replace"), ix] for w, ix in groups]
+    else:
+        groups = [[t, [i]] for i, t in enumerate(tokens)]
+    return [(w, ix) for w, ix in groups if w]
+
+
+def normalize_word(word: str) -> str:
+    """How words are compared in look-ups: case-insensitive, surrounding punctuation stripped."""
+    return word.strip(_PUNCTUATION + " ").lower()
+
+
+def find_words(groups, phrase: str) -> list:
+    """Every occurrence of ``phrase`` (one word or several, split at white space) among the words of ``groups``, as the
+    list of its token indices; the comparison is ``normalize_word``'s.  [] when it does not occur."""
+    want = [normalize_word(w) for w in phrase.split()]
+    want = [w for w in want if w]
+    have = [normalize_word(w) for w, _ in groups]
+    if not want:
+        return []
+    return [[i for _, ix in groups[a:a + len(want)] for i in ix]
+            for a in range(len(have) - len(want) + 1) if have[a:a + len(want)] == want]
+
+
+def word_maps(token_maps: torch.Tensor, groups) -> torch.Tensor:
+    """[len(groups), ...] from per-token maps [n_tok, ...]: a word's map is the sum of its tokens' maps (DAAM's rule), on
+    the maps' device, every word summed in token order."""
+    if not groups:
+        return token_maps.new_zeros((0,) + tuple(token_maps.shape[1:]))
+    return torch.stack([token_maps[list(ix)].sum(0) for _, ix in groups])
+
+
 def compute_heatmaps_from_vectors(image_vectors, concept_vectors, layer_indices, timesteps=list(range(4)),
                                   softmax: bool = True, normalize_concepts: bool = False,
                                   attention_norm: str = "sparsemax"):

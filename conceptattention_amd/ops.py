@@ -740,6 +740,128 @@ def token_maps(problems: Sequence[TokenMaps], num_heads: int, scale_log2: float 
 
 
 @dataclass
+class QueryMaps:
+    """One problem of a query-row map launch (ca_query_maps): the probability that the softmax of every row of ``q`` over
+    the keys [k0 | k1] gives to each row of ``k1``, averaged over the heads: acc += weight * map and / or
+    acc2 += weight2 * map.  q / k0 / k1 bf16 2-D views [rows, num_heads*128] (row stride free, k0 and k1 share theirs; k0
+    may be None: no leading keys), acc / acc2 fp32 [nq, n1] contiguous, ``lse`` (optional output) fp32 [num_heads, nq]
+    contiguous: the natural-log sum of exponentials of every head's row."""
+    q: torch.Tensor
+    k0: Optional[torch.Tensor] = None
+    k1: Optional[torch.Tensor] = None
+    acc: Optional[torch.Tensor] = None
+    weight: float = 0.0
+    acc2: Optional[torch.Tensor] = None
+    weight2: float = 0.0
+    lse: Optional[torch.Tensor] = None
+
+
+def _query_maps_array(problems: Sequence[QueryMaps], num_heads: int):
+    """ops.query_maps' argument checks (no device needed for the shape rules) and the problem array."""
+    FN = "query_maps"
+    width = num_heads * 128
+    arr = (L.QuerymapProblem * len(problems))()
+    seen = {}
+    for i, t in enumerate(problems):
+        if t.k1 is None:
+            raise ValueError(f"{FN}[{i}]: k1, the emitted key rows, is required")
+        _chk(t.q, torch.bfloat16, "q"), _chk(t.k1, torch.bfloat16, "k1")
+        k0 = t.k0 if t.k0 is not None and t.k0.shape[0] > 0 else None
+        if k0 is not None:
+            _chk(k0, torch.bfloat16, "k0")
+        for n, x in (("q", t.q), ("k0", k0), ("k1", t.k1)):
+            if x is not None and (x.dim() != 2 or x.shape[1] != width):
+                raise ValueError(f"{FN}[{i}]: {n} must be 2-D with num_heads*128 = {width} columns, got {tuple(x.shape)}")
+        nq, n0, n1 = t.q.shape[0], 0 if k0 is None else k0.shape[0], t.k1.shape[0]
+        # (a one-row tensor's stride is free in torch; the library wants at least the width)
+        ldq, ld1 = _i32(t.q.stride(0), "ldq"), _i32(t.k1.stride(0), "ldk")
+        ld0 = ld1 if k0 is None else _i32(k0.stride(0), "ldk")
+        if nq == 1:
+            ldq = max(ldq, width)
+        ldk = ld1 if n1 > 1 else ld0 if n0 > 1 else max(ld1, width)
+        if n0 > 1 and n1 > 1 and ld0 != ld1:
+            raise ValueError(f"{FN}[{i}]: both key segments must share one row stride")
+        if not 1 <= nq <= L.QUERYMAP_MAX_QUERIES or n1 < 1 or n0 + n1 > L.QUERYMAP_MAX_ROWS:
+            raise ValueError(f"{FN}[{i}]: need 1 <= nq <= {L.QUERYMAP_MAX_QUERIES}, n1 >= 1 and n0 + n1 <= "
+                             f"{L.QUERYMAP_MAX_ROWS}, got nq = {nq}, n0 = {n0}, n1 = {n1}")
+        if t.acc is None and t.acc2 is None:
+            raise ValueError(f"{FN}[{i}]: every problem needs acc or acc2")
+        p = arr[i]
+        for name, shape in (("acc", (nq, n1)), ("acc2", (nq, n1)), ("lse", (num_heads, nq))):
+            x = getattr(t, name)
+            if x is None:
+                continue
+            _chk(x, torch.float32, name)
+            if tuple(x.shape) != shape or not x.is_contiguous():
+                raise ValueError(f"{FN}[{i}]: {name} must be contiguous fp32 {list(shape)}, got {tuple(x.shape)}")
+            if name != "lse":
+                if x.data_ptr() in seen:
+                    raise ValueError(f"{FN}[{i}]: {name} is also an accumulator of problem {seen[x.data_ptr()]} of this "
+                                     "call (their updates would race)")
+                seen[x.data_ptr()] = i
+            setattr(p, name, x.data_ptr())
+        p.q, p.k0, p.k1 = t.q.data_ptr(), _ptr(k0), t.k1.data_ptr()
+        p.nq, p.n0, p.n1 = nq, _i32(n0, "n0"), _i32(n1, "n1")
+        p.ldq, p.ldk = ldq, ldk
+        p.weight, p.weight2 = float(t.weight), float(t.weight2)
+    return arr
+
+
+def _query_maps_launches(arr, n_total: int):
+    for s in range(0, n_total, L.QUERYMAP_MAX_PROBLEMS):
+        n = min(L.QUERYMAP_MAX_PROBLEMS, n_total - s)
+        yield (L.QuerymapProblem * n).from_buffer(arr, s * C.sizeof(L.QuerymapProblem)), n
+
+
+def query_maps_workspace_bytes(problems: Sequence[QueryMaps], num_heads: int) -> int:
+    """The scratch memory one ops.query_maps call over these problems needs (the largest of its launches): 8 bytes per
+    (head, query row)."""
+    lib = L.load()
+    if len(problems) < 1:
+        raise ValueError("query_maps_workspace_bytes: at least one problem")
+    arr = _query_maps_array(problems, num_heads)
+    need = 0
+    for sub, n in _query_maps_launches(arr, len(problems)):
+        rc = lib.ca_query_maps_workspace_bytes(sub, n, _i32(num_heads, "num_heads"))
+        if rc < 0:
+            L.check(int(rc), "ca_query_maps_workspace_bytes")
+        need = max(need, int(rc))
+    return need
+
+
+def query_maps(problems: Sequence[QueryMaps], num_heads: int, scale_log2: float = 1.0, qk_f16: bool = False,
+               workspace: Optional[torch.Tensor] = None) -> None:
+    """Query-row attention maps (ca_query_maps), up to L.QUERYMAP_MAX_PROBLEMS problems per launch pair (longer lists are
+    split, in order; the launches of one call share the workspace, which stream order makes safe).  ``scale_log2``: 1.0
+    for q rows that already carry softmax_scale * log2(e) (the model's), otherwise softmax_scale * log2(e).  ``qk_f16``:
+    the q and k rows hold IEEE half bits in their bf16-typed tensors (Gemm.qk_f16).  ``workspace``: a uint8 device tensor
+    of at least query_maps_workspace_bytes() bytes, 16-byte aligned; None: one is allocated from torch's caching allocator
+    (not under graph capture: pass one there)."""
+    lib = L.load()
+    if len(problems) < 1:
+        raise ValueError("query_maps: at least one problem")
+    if not num_heads >= 1:
+        raise ValueError("query_maps: num_heads must be >= 1")
+    if not math.isfinite(scale_log2):
+        raise ValueError("query_maps: scale_log2 must be finite")
+    arr = _query_maps_array(problems, num_heads)
+    if workspace is None:
+        need = sum(((num_heads * p.q.shape[0] * 8 + 15) // 16) * 16 for p in problems[:L.QUERYMAP_MAX_PROBLEMS])
+        for s in range(L.QUERYMAP_MAX_PROBLEMS, len(problems), L.QUERYMAP_MAX_PROBLEMS):
+            need = max(need, sum(((num_heads * p.q.shape[0] * 8 + 15) // 16) * 16
+                                 for p in problems[s:s + L.QUERYMAP_MAX_PROBLEMS]))
+        workspace = torch.empty(need, dtype=torch.uint8, device=problems[0].q.device)
+    _chk(workspace, torch.uint8, "workspace")
+    if not workspace.is_contiguous():
+        raise ValueError("query_maps: workspace must be contiguous")
+    ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel()
+    flags = L.QUERYMAP_QK_F16 if qk_f16 else 0
+    for sub, n in _query_maps_launches(arr, len(problems)):
+        L.check(lib.ca_query_maps(sub, n, _i32(num_heads, "num_heads"), float(scale_log2), flags, ws_ptr, ws_bytes,
+                                  _stream()), "ca_query_maps")
+
+
+@dataclass
 class HeadMaps:
     """One problem of a per-head concept map launch (ca_head_maps): per head of 128 columns the logits of the C rows of
     ``con`` against the L rows of ``img``, weighted across the concepts per head; then heads += weight_h * w,

@@ -24,7 +24,7 @@ import torch
 
 from . import _lib, ops, sampling
 from .flux_dit import HeatmapRequest, HipFluxDiT, StepTrace, on_own_device
-from .heatmaps import check_concept_count, compute_heatmaps_from_vectors, resolve_norm
+from .heatmaps import check_concept_count, compute_heatmaps_from_vectors, resolve_norm, word_groups, word_maps
 from .params import configs
 
 
@@ -45,8 +45,17 @@ class ConceptAttentionPipelineOutput:
     # tensor (num_heads, C, h, w), and their mean over the heads (C, h, w): the raw-space baselines' maps (ops.head_maps)
     head_maps: Optional[dict] = None
     raw_heatmaps: Optional[dict] = None
+    # token_maps=True: the prompt's words (heatmaps.word_groups of ``tokens``) and one map per word, the sum of its tokens'
+    # maps (DAAM's rule; heatmaps.word_maps), in the form of ``token_heatmaps``
+    words: Optional[list] = None
+    word_heatmaps: Optional[object] = None
+    # query_maps="tokens" | "concepts" (or both): the other direction, where a token's / a concept's own query row looks in
+    # the image (ops.query_maps), keyed by kind; "words" beside "tokens" when the call has the token strings.  fp32 device
+    # tensors (n, h, w) with return_pil_heatmaps=False, lists of PIL pictures otherwise (one min-max per item and kind)
+    query_heatmaps: Optional[dict] = None
 
 
+QUERY_KINDS = ("tokens", "concepts")
 HEAD_SPACES = {"output": ("heads_out", "raw_out"), "cross": ("heads_cross", "raw_cross"),
                "value": ("heads_value", "raw_value")}   # space -> its two HeatmapRequest fields
 
@@ -84,6 +93,12 @@ class HeadMapAccumulators:
 
 def head_request_fields(head_acc, j: int) -> dict:
     return {} if head_acc is None or head_acc[j] is None else head_acc[j].request_fields()
+
+
+def query_request_fields(query_acc, j: int) -> dict:
+    """The HeatmapRequest keywords of item j's query-row accumulators (a dict kind -> fp32 [n, patches], or None)."""
+    acc = {} if query_acc is None or query_acc[j] is None else query_acc[j]
+    return dict(token_query_space=acc.get("tokens"), concept_query_space=acc.get("concepts"))
 
 
 @dataclass
@@ -322,6 +337,44 @@ class ConceptAttentionFluxPipeline:
         treq = [self._token_request(p, token_maps) for p in prompts]
         return [torch.zeros(n, p, device=self.device) for (n, _), p in zip(treq, n_patches)], [t for _, t in treq]
 
+    # ------------------------------------------------------------------ query-row maps
+    @staticmethod
+    def _query_kinds(query_maps) -> tuple:
+        """The kinds a call's ``query_maps`` argument names, in QUERY_KINDS' order; () for None / False."""
+        if query_maps is None or query_maps is False:
+            return ()
+        kinds = (query_maps,) if isinstance(query_maps, str) else tuple(query_maps)
+        if not kinds or len(set(kinds)) != len(kinds) or any(k not in QUERY_KINDS for k in kinds):
+            raise ValueError(f"query_maps = {query_maps!r}: one of {list(QUERY_KINDS)} or a tuple of distinct ones")
+        return tuple(k for k in QUERY_KINDS if k in kinds)
+
+    def _query_plan(self, query_maps, prompts, token_maps, concept_counts, n_patches, joint_attention_kwargs=None):
+        """query_acc of a call's ``query_maps`` argument: per item a dict kind -> zeroed fp32 [n, n_patches[i]] accumulator
+        (n: the item's token count as ``token_maps`` gives it, or its concept count); None when no query maps are asked
+        for.  ValueError, before anything is launched, for an unknown kind, "tokens" without ``token_maps`` (which says
+        which tokens), and "concepts" with the ablation ``joint_attention_kwargs`` (they change the concept rows' key set)."""
+        kinds = self._query_kinds(query_maps)
+        if not kinds:
+            return None
+        if "tokens" in kinds and (token_maps is None or token_maps is False):
+            raise ValueError("query_maps: \"tokens\" needs token_maps= (True or a count) to say which tokens")
+        jak = joint_attention_kwargs or {}
+        if "concepts" in kinds and not (jak.get("concept_cross_attention", True) and jak.get("concept_self_attention", True)):
+            raise ValueError("query_maps: \"concepts\" is not covered under the ablation joint_attention_kwargs "
+                             "(concept_cross_attention / concept_self_attention = False change the concept rows' key set)")
+        for C in concept_counts:
+            if "concepts" in kinds and not 1 <= C <= _lib.QUERYMAP_MAX_QUERIES:
+                raise ValueError(f"query_maps: {C} concepts; 1 .. {_lib.QUERYMAP_MAX_QUERIES} per item")
+        acc = []
+        for prompt, C, p in zip(prompts, concept_counts, n_patches):
+            d = {}
+            if "tokens" in kinds:
+                d["tokens"] = torch.zeros(self._token_request(prompt, token_maps)[0], p, device=self.device)
+            if "concepts" in kinds:
+                d["concepts"] = torch.zeros(C, p, device=self.device)
+            acc.append(d)
+        return acc
+
     # ------------------------------------------------------------------ per-head maps
     def _head_plan(self, head_maps, head_norm, concept_counts, n_patches, normalize_concepts: bool = False):
         """head_acc of a call's ``head_maps`` / ``head_norm`` arguments: per item a ``HeadMapAccumulators`` with zeroed
@@ -369,25 +422,57 @@ class ConceptAttentionFluxPipeline:
                 heatmap_interpolation, overlay_alpha)
 
     def _chunk_outputs(self, idx, images, concept_heatmaps, cross_attention_maps, show, token_acc=None, tokens=None,
-                       pictures=None, head_acc=None) -> list:
+                       pictures=None, head_acc=None, query_acc=None) -> list:
         """The one way out of every call: the ConceptAttentionPipelineOutput of the items ``idx`` of a call after their
         forward.  ``images``: what ``image`` becomes; the two maps [len(idx), C, side, side] on the device; ``show``:
         ``_device_renderer``'s tuple; ``token_acc`` / ``tokens``: the call's (``_token_plan``); ``pictures``: with an
         overlay, the chunk's uint8 [H, W, 3] device tensors the maps are laid over; ``head_acc``: the call's
-        (``_head_plan``)."""
+        (``_head_plan``); ``query_acc``: the call's (``_query_plan``)."""
         on_device, return_pil_heatmaps, cmap, heatmap_size, heatmap_interpolation, overlay_alpha = show
-        tok = [None if token_acc is None else token_acc[i].view(-1, *concept_heatmaps.shape[-2:]) for i in idx]
+        grid = tuple(concept_heatmaps.shape[-2:])
+        tok = [None if token_acc is None else token_acc[i].view(-1, *grid) for i in idx]
         tokens = [None if tokens is None else tokens[i] for i in idx]
+        # the word maps and the query-row maps: per item, name -> fp32 [n, side, side] on the device ("word": the summed
+        # token maps; "q:<kind>": a kind of query_heatmaps)
+        extras, words = [{} for _ in idx], [None] * len(idx)
+        for k, i in enumerate(idx):
+            groups = None
+            if tokens[k] is not None and tok[k] is not None:
+                groups = word_groups(tokens[k])
+                words[k] = [w for w, _ in groups]
+                extras[k]["word"] = word_maps(tok[k], groups)
+            for kind, acc in (query_acc[i] if query_acc is not None and query_acc[i] else {}).items():
+                extras[k]["q:" + kind] = acc.view(-1, *grid)
+                if kind == "tokens" and groups is not None:
+                    extras[k]["q:words"] = word_maps(extras[k]["q:tokens"], groups)
         if on_device:
             outs = self._finish_device(images, concept_heatmaps, cross_attention_maps, cmap, heatmap_size,
-                                       heatmap_interpolation, overlay_alpha, pictures, tok, tokens)
+                                       heatmap_interpolation, overlay_alpha, pictures, tok, tokens, extras)
         else:
             outs = [self._finish(images[k], concept_heatmaps[k:k + 1], cross_attention_maps[k:k + 1], return_pil_heatmaps,
                                  cmap, tok[k], tokens[k]) for k in range(len(idx))]
+            for out, ex in zip(outs, extras):                # (one global min-max per item and kind, as the token maps)
+                for name, maps in ex.items():
+                    if return_pil_heatmaps:
+                        maps = colorize_heatmaps(maps.to(torch.float32).cpu().numpy(), cmap) if maps.shape[0] else []
+                    elif name == "word":
+                        maps = maps.to(torch.float32).cpu().numpy()
+                    self._set_extra(out, name, maps)
+        for out, w in zip(outs, words):
+            out.words = w
         if head_acc is not None:
             for out, i in zip(outs, idx):
                 out.head_maps, out.raw_heatmaps = head_acc[i].outputs(concept_heatmaps.shape[-1])
         return outs
+
+    @staticmethod
+    def _set_extra(out, name: str, maps) -> None:
+        """An extra map set of ``_chunk_outputs`` into its output field."""
+        if name == "word":
+            out.word_heatmaps = maps
+        else:
+            out.query_heatmaps = dict(out.query_heatmaps or {})
+            out.query_heatmaps[name[2:]] = maps
 
     def _input_picture(self, image, height: int, width: int) -> torch.Tensor:
         """The bytes of an encode call's input image on the device, for overlays: uint8 [height, width, 3]."""
@@ -401,13 +486,14 @@ class ConceptAttentionFluxPipeline:
 
     def _finish_device(self, images, concept_heatmaps, cross_attention_maps, cmap, heatmap_size=None,
                        heatmap_interpolation="nearest", overlay_alpha=None, pictures=None, token_maps=None,
-                       tokens=None) -> list:
+                       tokens=None, extras=None) -> list:
         """``_finish`` with PIL heat maps for the B items of a chunk, the pictures made on the device (ops.heatmap_render):
         one group per item and space (the reference's "global min-max over ALL concepts"), one launch, one download of
         bytes.  Without the three options the bytes are those of ``colorize_heatmaps``.  ``pictures``: with
         ``overlay_alpha``, the uint8 [H, W, 3] device tensor of every item that the maps are laid over.  ``token_maps``:
         per item, the prompt-token maps [n_tok, side, side] or None -- one more group per item in the same launch;
-        ``tokens``: per item, the token strings."""
+        ``tokens``: per item, the token strings.  ``extras``: per item, name -> further maps [n, side, side] (the word maps,
+        the query-row maps of every kind): one more group each, behind the token groups, in the same call."""
         import PIL.Image
         ho = concept_heatmaps.to(torch.float32).contiguous()
         hc = cross_attention_maps.to(torch.float32).contiguous()
@@ -422,22 +508,40 @@ class ConceptAttentionFluxPipeline:
                              f"{tuple(pictures[0].shape[:2])}")
         with_tok = [k for k in range(B) if token_maps is not None and token_maps[k] is not None]
         n_tok = [token_maps[k].shape[0] for k in with_tok]
-        # one allocation: the 2 B groups of C planes, then the token groups (n_tok planes each)
-        flat = torch.empty((2 * B * C + sum(n_tok)) * H * W * 3, dtype=torch.uint8, device=self.device)
+        more = [(k, name, m.to(torch.float32).contiguous()) for k in range(B) for name, m in (extras[k] if extras else {}).items()
+                if m.shape[0]]
+        n_more = [m.shape[0] for _, _, m in more]
+        # one allocation: the 2 B groups of C planes, then the token groups (n_tok planes each), then the extra groups
+        flat = torch.empty((2 * B * C + sum(n_tok) + sum(n_more)) * H * W * 3, dtype=torch.uint8, device=self.device)
         buf = flat[:2 * B * C * H * W * 3].view(2 * B, C, H, W, 3)
         tok_out, o = [], 2 * B * C
-        for n in n_tok:
+        for n in n_tok + n_more:
             tok_out.append(flat[o * H * W * 3:(o + n) * H * W * 3].view(n, H, W, 3))
             o += n
         ops.heatmap_render([ho[k] for k in range(B)] + [hc[k] for k in range(B)] +
-                           [token_maps[k].to(torch.float32).contiguous() for k in with_tok],
+                           [token_maps[k].to(torch.float32).contiguous() for k in with_tok] + [m for _, _, m in more],
                            ops.colormap_lut(cmap, self.device),
                            size=(H, W), bilinear=heatmap_interpolation == "bilinear",
-                           images=None if overlay_alpha is None else list(pictures) * 2 + [pictures[k] for k in with_tok],
+                           images=None if overlay_alpha is None else list(pictures) * 2 + [pictures[k] for k in with_tok] +
+                           [pictures[k] for k, _, _ in more],
                            alpha=overlay_alpha, out=list(buf) + tok_out)
         host = flat.cpu().numpy()                      # the one download of the chunk
         planes = host.reshape(-1, H, W, 3)
         first = {k: 2 * B * C + sum(n_tok[:i]) for i, k in enumerate(with_tok)}
+        outs = self._device_outputs(images, planes, B, C, first, token_maps, tokens)
+        o = 2 * B * C + sum(n_tok)
+        for k in range(B):                               # (a set without a plane, a prompt without a word: an empty list)
+            for name, m in (extras[k] if extras else {}).items():
+                if not m.shape[0]:
+                    self._set_extra(outs[k], name, [])
+        for (k, name, m), n in zip(more, n_more):
+            self._set_extra(outs[k], name, [PIL.Image.fromarray(planes[o + t]) for t in range(n)])
+            o += n
+        return outs
+
+    @staticmethod
+    def _device_outputs(images, planes, B, C, first, token_maps, tokens) -> list:
+        import PIL.Image
         return [ConceptAttentionPipelineOutput(
             image=images[k], concept_heatmaps=[PIL.Image.fromarray(planes[k * C + c]) for c in range(C)],
             cross_attention_maps=[PIL.Image.fromarray(planes[(B + k) * C + c]) for c in range(C)],
@@ -477,7 +581,7 @@ class ConceptAttentionFluxPipeline:
                        fused: bool = True, heatmap_renderer: str = "host", heatmap_size=None,
                        heatmap_interpolation: str = "nearest", overlay_alpha=None,
                        token_maps=None, keep_trace: bool = False, head_maps=None, head_norm=None,
-                       head_normalize_concepts: bool = False) -> ConceptAttentionPipelineOutput:
+                       head_normalize_concepts: bool = False, query_maps=None) -> ConceptAttentionPipelineOutput:
         """``latent`` (1,16,h/8,w/8) overrides get_noise (device RNG differs between platforms);
         ``fused=False`` takes the reference's route (stack the per-layer vectors, then reduce).
         ``heatmap_renderer="device"`` makes the PIL heat maps on the device (ops.heatmap_render; the same bytes as
@@ -496,7 +600,14 @@ class ConceptAttentionFluxPipeline:
         ``head_norm``: None (the logits themselves), "softmax", "sparsemax" or "entmax15", across the concepts PER HEAD; a
         sequence of several of them computes all in the same forwards and keys both dicts by (space, norm name);
         ``head_normalize_concepts``: heatmaps.linear_normalization across the concepts of the concept rows first.  Needs
-        the fused route; "output" makes the forwards take the fp32 image rows' route, as ``keep_trace`` does."""
+        the fused route; "output" makes the forwards take the fp32 image rows' route, as ``keep_trace`` does.
+        ``query_maps``: "tokens", "concepts" or both -> ``out.query_heatmaps[kind]``: where the prompt tokens' / the
+        concept tokens' own query rows look in the image, the softmax probability each row puts on every image key in the
+        double blocks ``layer_indices``, mean over heads, layers and ``timesteps`` (ops.query_maps).  "tokens" needs
+        ``token_maps`` to say which tokens; with the token strings ``query_heatmaps["words"]`` holds the words' sums.
+        Needs the fused route."""
+        if self._query_kinds(query_maps) and not fused:
+            raise ValueError("query_maps needs the fused route (fused=True)")
         if keep_trace and not fused:
             raise ValueError("keep_trace needs the fused route: fused=False stacks the vectors and keeps no image side")
         if head_maps and not fused:
@@ -509,7 +620,7 @@ class ConceptAttentionFluxPipeline:
                 softmax=softmax, attention_norm=attention_norm, heatmap_renderer=heatmap_renderer, heatmap_size=heatmap_size,
                 heatmap_interpolation=heatmap_interpolation, overlay_alpha=overlay_alpha, token_maps=token_maps,
                 keep_trace=keep_trace, head_maps=head_maps, head_norm=head_norm,
-                head_normalize_concepts=head_normalize_concepts)[0]
+                head_normalize_concepts=head_normalize_concepts, query_maps=query_maps)[0]
         norm = self._generate_norm(return_cross_attention, layer_indices, height, width, softmax, attention_norm)
         check_concept_count(norm, len(concepts))
         show = self._device_renderer(return_pil_heatmaps, cmap, heatmap_renderer, heatmap_size, heatmap_interpolation,
@@ -597,13 +708,16 @@ class ConceptAttentionFluxPipeline:
     @on_own_device
     def generate_on_device(self, latent, txt, vec, concept_embeddings, layer_indices=list(range(15, 19)),
                            num_inference_steps: int = 4, guidance: float = 0.0, timesteps=None, fused: bool = True,
-                           norm: int = 0, token_acc=None, traces: Optional[dict] = None, head_acc=None):
+                           norm: int = 0, token_acc=None, traces: Optional[dict] = None, head_acc=None, query_acc=None):
         """``token_acc``: per item, an fp32 [n_tok, patches] accumulator of the caller's for the prompt-token maps (zeroed
         by the caller; None, or None for an item: no token maps).  ``traces``: a dict of the caller's that receives step
         index -> the ``StepTrace`` of every step in ``timesteps`` (fused route only).  ``head_acc``: per item, the
-        caller's ``HeadMapAccumulators`` (or None).  The return tuple is the same with and without any of them."""
+        caller's ``HeadMapAccumulators`` (or None).  ``query_acc``: per item, a dict kind ("tokens" | "concepts") -> the caller's
+        zeroed fp32 [n, patches] accumulator of that kind's query-row maps (or None).  The return tuple is the same with and
+        without any of them."""
         gen = self._generate_steps(self.model, latent, txt, vec, concept_embeddings, layer_indices,
-                                   num_inference_steps, guidance, timesteps, fused, norm, token_acc, traces, head_acc)
+                                   num_inference_steps, guidance, timesteps, fused, norm, token_acc, traces, head_acc,
+                                   query_acc)
         while True:
             try:
                 next(gen)
@@ -612,7 +726,7 @@ class ConceptAttentionFluxPipeline:
 
     def _generate_steps(self, model, latent, txt, vec, concept_embeddings, layer_indices=list(range(15, 19)),
                         num_inference_steps: int = 4, guidance: float = 0.0, timesteps=None, fused: bool = True,
-                        norm: int = 0, token_acc=None, traces: Optional[dict] = None, head_acc=None):
+                        norm: int = 0, token_acc=None, traces: Optional[dict] = None, head_acc=None, query_acc=None):
         """The device-resident core of generate_image for B work items at once (B = 1 from the public API):
         latent (B,16,h/8,w/8), txt (B,T,4096), vec (B,768), concept_embeddings (B,C,4096) already in HBM ->
         (final latent tokens, concept heat maps fp32 [B,C,side,side], cross-attention maps fp32
@@ -642,12 +756,13 @@ class ConceptAttentionFluxPipeline:
         try:
             return (yield from self._generate_steps_inner(model, x, inp, con, con_ids, con_vec, schedule, ts, ls,
                                                           C, n_patches, guidance, layer_indices, timesteps, fused,
-                                                          norm, token_acc, traces, head_acc))
+                                                          norm, token_acc, traces, head_acc, query_acc))
         finally:
             model.keep_bf16_layers = keep_before  # this call's choice does not leak into later sweeps / encodes
 
     def _generate_steps_inner(self, model, x, inp, con, con_ids, con_vec, schedule, ts, ls, C, n_patches, guidance,
-                              layer_indices, timesteps, fused, norm=0, token_acc=None, traces=None, head_acc=None):
+                              layer_indices, timesteps, fused, norm=0, token_acc=None, traces=None, head_acc=None,
+                              query_acc=None):
         names = {v: k for k, v in _lib.NORMS.items()}
         # repeated indices weigh a (step, layer) pair repeatedly in the reference's fancy indexing
         # (concept_attention_pipeline.py:76-77); the fused accumulation covers distinct pairs only
@@ -666,12 +781,17 @@ class ConceptAttentionFluxPipeline:
                 raise ValueError("head_maps needs the fused route (fused=True, distinct timesteps and layer indices)")
             if len(head_acc) != B:
                 raise ValueError("head_acc: one HeadMapAccumulators (or None) per work item")
+        if query_acc is not None and any(query_acc):
+            if not fused:
+                raise ValueError("query_maps needs the fused route (fused=True, distinct timesteps and layer indices)")
+            if len(query_acc) != B:
+                raise ValueError("query_acc: one dict of accumulators (or None) per work item")
         if fused:
             acc_o = torch.zeros(B, C, n_patches, device=self.device)
             acc_c = torch.zeros(B, C, n_patches, device=self.device)
             reqs = [HeatmapRequest(tuple(ls), 1.0 / (len(ts) * len(ls)), acc_o[j], acc_c[j], norm=norm,
                                    token_space=None if token_acc is None else token_acc[j],
-                                   **head_request_fields(head_acc, j))
+                                   **head_request_fields(head_acc, j), **query_request_fields(query_acc, j))
                     for j in range(B)]
             img, _, _ = yield from sampling.denoise_steps(
                 model, **inp, timesteps=schedule, guidance=guidance, concepts=con, concept_ids=con_ids,
@@ -747,12 +867,14 @@ class ConceptAttentionFluxPipeline:
     @on_own_device
     def layer_noise_sweep(self, image, concepts: list, prompt: str, noise_levels, num_steps: int = 50, layer_indices=None,
                           num_samples: int = 1, seed: int = 0, width: int = 1024, height: int = 1024, batch: int = 5,
-                          vae_noise=None):
+                          vae_noise=None, query_maps=None):
         """``layer_noise_sweep_on_device`` from an image and strings: ``image`` is a latent tensor (1,16,h/8,w/8) or, with
         an autoencoder in the pipeline, a PIL image (``vae_noise`` (1,16,h/8,w/8): its sampling noise, drawn on the
         device when not given); ``concepts`` and ``prompt`` go through the text encoders as in ``encode_image``.
         Returns the two DEVICE tables (out_space, cross_space), fp32 [len(noise_levels), len(layer_indices), C, side,
-        side]; ``batch`` levels share one forward."""
+        side]; ``batch`` levels share one forward.  ``query_maps``: refused (the tables hold the concept maps only)."""
+        if self._query_kinds(query_maps):
+            raise ValueError("layer_noise_sweep: query_maps are not part of the sweep tables (ask encode_image for them)")
         assert height == width, "Height and width must be the same for now"
         latent = image.to(self.device, torch.bfloat16) if isinstance(image, torch.Tensor) else \
             self._encode_pixels([image], height, width, vae_noise)
@@ -772,7 +894,7 @@ class ConceptAttentionFluxPipeline:
                      joint_attention_kwargs=None, noise=None, vae_noise=None, heatmap_renderer: str = "host",
                      heatmap_size=None, heatmap_interpolation: str = "nearest",
                      overlay_alpha=None, token_maps=None, keep_trace: bool = False, head_maps=None, head_norm=None,
-                     head_normalize_concepts: bool = False) -> ConceptAttentionPipelineOutput:
+                     head_normalize_concepts: bool = False, query_maps=None) -> ConceptAttentionPipelineOutput:
         """``image``: a latent tensor (1,16,h/8,w/8), or a PIL image when the pipeline has an autoencoder
         (``autoencoder="synthetic"``, a ``.safetensors`` path, or an injected object).
         One forward of the 19 double blocks per noise sample (stop_after_multimodal_attentions).
@@ -786,7 +908,9 @@ class ConceptAttentionFluxPipeline:
         ``keep_trace=True``: ``out.trace`` keeps the image side of every noise sample's forward for ``requery`` (its
         step keys are the sample indices).
         ``head_maps`` / ``head_norm`` / ``head_normalize_concepts``: as in ``generate_image`` (the mean runs over layers
-        and noise samples); not with the ablation ``joint_attention_kwargs``."""
+        and noise samples); not with the ablation ``joint_attention_kwargs``.
+        ``query_maps``: as in ``generate_image`` (the mean runs over heads, layers and noise samples); "concepts" not with
+        the ablation ``joint_attention_kwargs``."""
         return self.encode_images(
             [image], [concepts], [prompt], width=width, height=height, layer_indices=layer_indices, num_samples=num_samples,
             num_steps=num_steps, noise_timestep=noise_timestep, seed=seed, noise=None if noise is None else [noise],
@@ -795,7 +919,7 @@ class ConceptAttentionFluxPipeline:
             softmax=softmax, joint_attention_kwargs=joint_attention_kwargs, heatmap_renderer=heatmap_renderer,
             heatmap_size=heatmap_size, heatmap_interpolation=heatmap_interpolation, overlay_alpha=overlay_alpha,
             token_maps=token_maps, keep_trace=keep_trace, head_maps=head_maps, head_norm=head_norm,
-            head_normalize_concepts=head_normalize_concepts)[0]
+            head_normalize_concepts=head_normalize_concepts, query_maps=query_maps)[0]
 
     def _encode_pixels(self, images, height: int, width: int, vae_noise=None) -> torch.Tensor:
         """PIL images -> bf16 latents (B,16,h/8,w/8).  The HIP autoencoder takes the bytes (``encode_pixels``: resize,
@@ -817,19 +941,22 @@ class ConceptAttentionFluxPipeline:
         return self.autoencoder.encode(torch.cat(xs), **kw).to(torch.bfloat16)
 
     def _encode_maps(self, model, latent, txt, vec, con, con_ids, con_vec, settings: EncodeSettings, *, noise=None,
-                     token_acc=None, traces: Optional[dict] = None, head_acc=None):
+                     token_acc=None, traces: Optional[dict] = None, head_acc=None, query_acc=None):
         """Device core of encode_image for B images at once (latent (B,16,h,w), txt (B,T,4096), ...): one forward
         per noise sample on ``model``; returns the two fp32 maps [B, C, side, side].  ``noise``: optional list of
         num_samples tensors (1 or B,16,h,w) used instead of get_noise(seed + i).  ``token_acc``: per item, the caller's
         zeroed fp32 [n_tok, patches] accumulator of the prompt-token maps (or None); ``traces``: a dict of the caller's that
         receives sample index -> the StepTrace of that sample's forward; ``head_acc``: per item, the caller's
-        ``HeadMapAccumulators`` (or None); the return tuple stays."""
+        ``HeadMapAccumulators`` (or None); ``query_acc``: per item, a dict kind -> the caller's zeroed accumulator of the
+        query-row maps (or None); the return tuple stays."""
         layer_indices, num_samples, noise_timestep = settings.layer_indices, settings.num_samples, settings.noise_timestep
         if noise is not None and len(noise) != num_samples:
             raise ValueError("noise: one tensor per noise sample")
         B, C = con.shape[0], con.shape[1]
         if token_acc is not None and len(token_acc) != B:
             raise ValueError("token_acc: one accumulator (or None) per work item")
+        if query_acc is not None and len(query_acc) != B:
+            raise ValueError("query_acc: one dict of accumulators (or None) per work item")
         n_patches = (latent.shape[-1] // 2) * (latent.shape[-2] // 2)
         height, width = latent.shape[-2] * 8, latent.shape[-1] * 8
         # the reference indexes the stacked samples with the float schedule values
@@ -839,7 +966,7 @@ class ConceptAttentionFluxPipeline:
         acc_c = torch.zeros(B, C, n_patches, device=self.device)
         req = [HeatmapRequest(tuple(int(l) for l in layer_indices), 1.0 / (num_samples * len(layer_indices)),
                               acc_o[j], acc_c[j], norm=settings.norm, token_space=None if token_acc is None else token_acc[j],
-                              **head_request_fields(head_acc, j))
+                              **head_request_fields(head_acc, j), **query_request_fields(query_acc, j))
                for j in range(B)]
         schedule = sampling.get_schedule(settings.num_steps, n_patches, shift=(not self.is_schnell))
         for i in range(num_samples):
@@ -871,13 +998,14 @@ class ConceptAttentionFluxPipeline:
         return tuple(_cat(e[k] for e in emb) for k in range(n_out))
 
     def _encode_chunks(self, images, concepts, prompts, settings: EncodeSettings, *, noise=None, vae_noise=None,
-                       token_acc=None, keep_trace: bool = False, head_acc=None):
+                       token_acc=None, keep_trace: bool = False, head_acc=None, query_acc=None):
         """The forwards of ``encode_images``, one at a time: yields (item indices, acc_o, acc_c) with the two fp32 maps
         [len(indices), C, side, side] of the chunk still on the device (``_encode_maps``).  ``images`` and ``prompts`` are lists;
         ``settings`` was built with the call's largest concept count; ``noise`` / ``vae_noise``: as ``encode_images`` takes them;
         ``token_acc``: per item of the call, the caller's accumulator of the prompt-token maps (or None).  With
         ``keep_trace`` a fourth entry follows: sample index -> the StepTrace of the chunk's forward.  ``head_acc``: per item
-        of the call, its ``HeadMapAccumulators`` (or None for the call)."""
+        of the call, its ``HeadMapAccumulators`` (or None for the call); ``query_acc``: per item of the call, its dict of
+        query-row accumulators (or None for the call)."""
         n, height, width = len(images), settings.height, settings.width
         concepts = _per_item(concepts, n, "encode_images: concepts")
         for name, v in (("prompts", prompts), ("noise", noise), ("vae_noise", vae_noise)):
@@ -900,7 +1028,8 @@ class ConceptAttentionFluxPipeline:
             traces = {} if keep_trace else None
             ho, hc = self._encode_maps(self.model, latent, txt, vec, con, con_ids, con_vec, settings, noise=nz,
                                        token_acc=None if token_acc is None else [token_acc[i] for i in idx], traces=traces,
-                                       head_acc=None if head_acc is None else [head_acc[i] for i in idx])
+                                       head_acc=None if head_acc is None else [head_acc[i] for i in idx],
+                                       query_acc=None if query_acc is None else [query_acc[i] for i in idx])
             yield (idx, ho, hc, traces) if keep_trace else (idx, ho, hc)
 
     @torch.no_grad()
@@ -912,7 +1041,7 @@ class ConceptAttentionFluxPipeline:
                       attention_norm: str = "sparsemax", softmax=True, joint_attention_kwargs=None,
                       heatmap_renderer: str = "host", heatmap_size=None, heatmap_interpolation: str = "nearest",
                       overlay_alpha=None, token_maps=None, keep_trace: bool = False, head_maps=None, head_norm=None,
-                      head_normalize_concepts: bool = False) -> list:
+                      head_normalize_concepts: bool = False, query_maps=None) -> list:
         """``encode_image`` for a list of images: a list of ConceptAttentionPipelineOutput in item order, every item with
         the maps of its own ``encode_image`` call.  ``images``: PIL images and / or latents (1,16,h/8,w/8);
         ``concepts``: one list for all items or one list per item; ``prompts``: one string per item (or one for all).
@@ -924,7 +1053,8 @@ class ConceptAttentionFluxPipeline:
         a chunk come from one launch and one download (``_finish_device``).  ``token_maps``: as in ``encode_image``, for
         every item's own prompt (the items of a chunk may have different numbers of tokens).  ``keep_trace``: as in
         ``encode_image``, per item.  ``head_maps`` / ``head_norm`` / ``head_normalize_concepts``: as in ``encode_image``,
-        per item."""
+        per item.  ``query_maps``: as in ``encode_image``, per item; one ops.query_maps launch per captured layer and
+        forward for all items and kinds."""
         if keep_trace:
             self.model._check_traceable("keep_trace", joint_attention_kwargs)
         images = list(images)
@@ -944,12 +1074,15 @@ class ConceptAttentionFluxPipeline:
         head_acc = self._head_plan(head_maps, head_norm, [len(c) for c in concepts], [
             (im.shape[-1] // 2) * (im.shape[-2] // 2) if isinstance(im, torch.Tensor) else (height // 16) * (width // 16)
             for im in images], head_normalize_concepts)
+        query_acc = self._query_plan(query_maps, prompts, token_maps, [len(c) for c in concepts], [
+            (im.shape[-1] // 2) * (im.shape[-2] // 2) if isinstance(im, torch.Tensor) else (height // 16) * (width // 16)
+            for im in images], joint_attention_kwargs)
         results = {}
         for idx, ho, hc, *traces in self._encode_chunks(images, concepts, prompts, settings, noise=noise,
                                                         vae_noise=vae_noise, token_acc=token_acc, keep_trace=keep_trace,
-                                                        head_acc=head_acc):
+                                                        head_acc=head_acc, query_acc=query_acc):
             outs = self._chunk_outputs(idx, [images[i] for i in idx], ho, hc, show, token_acc, tokens,
-                                       None if pictures is None else [pictures[i] for i in idx], head_acc)
+                                       None if pictures is None else [pictures[i] for i in idx], head_acc, query_acc)
             if keep_trace:
                 self._attach_traces(outs, traces[0], dict(
                     call="encode_image", width=width, height=height, layer_indices=list(layer_indices),
@@ -966,7 +1099,7 @@ class ConceptAttentionFluxPipeline:
                         attention_norm: str = "sparsemax", cmap="plasma", batch: int = 5,
                         heatmap_renderer: str = "host", heatmap_size=None, heatmap_interpolation: str = "nearest",
                         overlay_alpha=None, token_maps=None, keep_trace: bool = False, head_maps=None, head_norm=None,
-                        head_normalize_concepts: bool = False) -> list:
+                        head_normalize_concepts: bool = False, query_maps=None) -> list:
         """``generate_image`` for a list of prompts: a list of ConceptAttentionPipelineOutput in item order, every item
         with the image and maps of its own ``generate_image(prompt, concepts, seed=seeds[i], latent=latents[i])`` call on
         the fused route.  ``concepts``: one list for all items or one list per item; ``seeds``: one per item (default
@@ -974,7 +1107,8 @@ class ConceptAttentionFluxPipeline:
         one denoising loop and one autoencoder pass whose bytes are made on the device.  ``token_maps``: as in
         ``generate_image``, for every item's own prompt (the items of a chunk may have different numbers of tokens).
         ``keep_trace``: as in ``generate_image``; every item's ``trace`` is its own view of its forward's storage.
-        ``head_maps`` / ``head_norm`` / ``head_normalize_concepts``: as in ``generate_image``, per item."""
+        ``head_maps`` / ``head_norm`` / ``head_normalize_concepts``: as in ``generate_image``, per item.
+        ``query_maps``: as in ``generate_image``, per item."""
         norm = self._generate_norm(return_cross_attention, layer_indices, height, width, softmax, attention_norm)
         if keep_trace:
             self.model._check_traceable("keep_trace")
@@ -992,6 +1126,12 @@ class ConceptAttentionFluxPipeline:
         token_acc, tokens = self._token_plan(prompts, token_maps, [(s[1] // 2) * (s[2] // 2) for s in shapes])
         head_acc = self._head_plan(head_maps, head_norm, [len(c) for c in concepts],
                                    [(s[1] // 2) * (s[2] // 2) for s in shapes], head_normalize_concepts)
+        query_acc = self._query_plan(query_maps, prompts, token_maps, [len(c) for c in concepts],
+                                     [(s[1] // 2) * (s[2] // 2) for s in shapes])
+        if query_acc is not None:
+            ts = list(range(num_inference_steps)) if timesteps is None else [int(t) % max(num_inference_steps, 1) for t in timesteps]
+            if len(set(ts)) != len(ts) or len(set(int(l) for l in layer_indices)) != len(list(layer_indices)):
+                raise ValueError("query_maps needs the fused route (fused=True, distinct timesteps and layer indices)")
         results = {}
         for idx in plan_batches([(shapes[i], len(concepts[i]), self._text_length()) for i in range(n)], batch):
             txt, vec, con = self._embed_chunk(prompts, concepts, idx, 3)
@@ -1003,9 +1143,10 @@ class ConceptAttentionFluxPipeline:
                                                   timesteps=timesteps, fused=True, norm=norm,
                                                   token_acc=None if token_acc is None else [token_acc[i] for i in idx],
                                                   traces=traces,
-                                                  head_acc=None if head_acc is None else [head_acc[i] for i in idx])
+                                                  head_acc=None if head_acc is None else [head_acc[i] for i in idx],
+                                                  query_acc=None if query_acc is None else [query_acc[i] for i in idx])
             pictures, pix = self._decode(img, height, width, show[0] and overlay_alpha is not None)
-            outs = self._chunk_outputs(idx, pictures, ho, hc, show, token_acc, tokens, pix, head_acc)
+            outs = self._chunk_outputs(idx, pictures, ho, hc, show, token_acc, tokens, pix, head_acc, query_acc)
             if keep_trace:
                 self._attach_traces(outs, traces, dict(
                     call="generate_image", width=width, height=height, layer_indices=list(layer_indices),
@@ -1026,7 +1167,7 @@ class ConceptAttentionFluxPipeline:
     def requery(self, trace, concepts, layer_indices=None, timesteps=None, softmax: bool = True,
                 attention_norm: str = "sparsemax", cmap="plasma", return_pil_heatmaps: bool = True,
                 heatmap_renderer: str = "host", heatmap_size=None, heatmap_interpolation: str = "nearest",
-                overlay_alpha=None):
+                overlay_alpha=None, query_maps=None):
         """Other concepts for a finished ``keep_trace=True`` call, without its image pass: only the concept rows' stream
         through the double blocks runs, against the image keys, values and map operands the trace kept
         (``HipFluxDiT.requery``).  ``trace``: an ``ImageTrace`` (-> one ConceptAttentionPipelineOutput) or a list of them
@@ -1036,6 +1177,9 @@ class ConceptAttentionFluxPipeline:
         are the mean over that subset.  The other keywords: as in ``generate_image``; overlays are laid over the trace's
         ``image``.  The output carries the trace's ``image`` and no token maps (the text side has not changed).  Items
         that share a geometry and a concept count go through one pass, at most 5 at a time (``plan_requery``)."""
+        if self._query_kinds(query_maps):
+            raise ValueError("requery: query_maps are not part of a re-query (the trace keeps no text q rows, and the concept "
+                             "rows' query maps are asked for in the forward)")
         single = isinstance(trace, ImageTrace)
         traces = [trace] if single else list(trace)
         n = len(traces)

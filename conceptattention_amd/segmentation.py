@@ -663,6 +663,8 @@ class ConceptAttentionSegmentationModel:
         if any(s not in SWEEP_SPACES for s in spaces):
             raise ValueError("target_space: 'output', 'cross_attention' or None for both")
         kw = dict(sweep_kwargs)
+        if kw.pop("query_maps", None):
+            raise ValueError("score_sweep: query_maps are not part of the sweep tables (ask encode_images for them)")
         unknown = set(kw) - {"num_steps", "layer_indices", "num_samples", "seed", "width", "height", "batch", "vae_noise"}
         if unknown:
             raise TypeError(f"score_sweep: unexpected arguments {sorted(unknown)}")
