@@ -30,7 +30,7 @@ EXTRA_FLAGS = {"ca_attn4.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-save
                "ca_headmap.hip": ["-save-temps=obj"],
                "ca_querymap.hip": ["-save-temps=obj"]}   # (read for spills below)
 HEADERS = ["ca_common.h", "ca_attn_common.h", "ca_attn4_sched.inc", "ca_attn4_kernel.inc", "ca_seg_core.h",
-           "ca_text_core.h", "ca_heatmap_core.h", "ca_tokmap.h", "ca_headmap.h", "ca_querymap.h"]
+           "ca_text_core.h", "ca_heatmap_core.h", "ca_tokmap.h", "ca_headmap.h", "ca_querymap.h", "ca_qkmap_core.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function"]
 

@@ -1,8 +1,9 @@
 // ca_query_maps: query-row attention maps.  For each of a few query rows (text tokens or concept tokens), the probability
 // its softmax over the keys [k0 | k1] gives to every one of the n1 emitted keys, averaged over the heads (semantics:
 // ca_querymap.h).  The transpose of ca_token_maps' problem: at most 512 query rows against thousands of emitted keys, so
-// the [nq, n1] output cannot live in LDS and the grid tiles the emitted keys as well as the query rows.  A kernel family of
-// its own: it re-reads the q and k rows an attention launch has read and shares no code with the attention kernels.
+// the [nq, n1] output cannot live in LDS and the grid tiles the emitted keys as well as the query rows.  It re-reads the q
+// and k rows an attention launch has read; the fragments, the key rows, the score step, the accumulators' write-out and the
+// common entry rules are ca_qkmap_core.h's, shared with ca_tokmap.hip; nothing is shared with the attention kernels.
 //
 // Two launches, one stream, no atomics; every output cell and every workspace cell has exactly one writer.
 //
@@ -28,9 +29,7 @@
 // lanes that share the row); the next tile's / head's loads are issued before the current MFMAs.  No LDS tiles.
 // Resources (hipcc, gfx950, both storage types alike): statistics 64 VGPRs, 0 scratch, 512 bytes of LDS (the two
 // cross-wave reductions); emit 128 VGPRs, 0 scratch, no LDS.  build.py's audit refuses a spill.
-#include <math.h>
-
-#include "ca_common.h"
+#include "ca_qkmap_core.h"
 #include "ca_querymap.h"
 
 namespace {   // device code
@@ -41,9 +40,6 @@ constexpr int QM_TILE = 64;                 // statistics: keys of a tile (16 pe
 constexpr int QM_EMIT_KEYS = 128;           // emit: keys of a workgroup (32 per wave)
 constexpr float QM_M_INIT = -3.0e38f;       // a finite "no key yet": exp2(-inf - QM_M_INIT) is 0, not NaN
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 struct QuerymapLaunch {
   ca_querymap_problem p[CA_QUERYMAP_MAX_PROBLEMS];
   int64_t ws_off[CA_QUERYMAP_MAX_PROBLEMS];   // bytes from workspace to the problem's [num_heads][nq] (M, L) pairs
@@ -51,36 +47,6 @@ struct QuerymapLaunch {
   int32_t num_heads;
   float scale_log2, inv_heads;
 };
-
-template <bool F16>
-__device__ __forceinline__ f32x4 qm_mfma(u32x4 k, u32x4 q, f32x4 c) {
-  if constexpr (F16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, k), __builtin_bit_cast(f16x8, q), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, k), __builtin_bit_cast(bf16x8, q), c, 0, 0, 0);
-}
-
-// the address of key row j (0 <= j < n0 + n1) of a problem, head columns not included
-__device__ __forceinline__ const uint16_t *qm_key_row(const ca_querymap_problem &P, int j) {
-  return j < P.n0 ? (const uint16_t *)P.k0 + (size_t)j * (size_t)P.ldk
-                  : (const uint16_t *)P.k1 + (size_t)(j - P.n0) * (size_t)P.ldk;
-}
-
-// a lane's fragment of 16 rows, head h: row (lane & 15) of the 16, columns 8 (lane >> 4) + 32 ks .. of the head
-__device__ __forceinline__ void qm_frag_load(const uint16_t *row, int h, u32x4 (&f)[4]) {
-  const uint16_t *p = row + (size_t)h * 128 + ((threadIdx.x & 63) >> 4) * 8;
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) f[ks] = *(const u32x4 *)(p + ks * 32);
-}
-
-// the scores of 16 keys against 16 queries: lane l gets keys 4 (l >> 4) + 0..3 of query l & 15, times scale_log2
-template <bool F16>
-__device__ __forceinline__ f32x4 qm_scores(const u32x4 (&kf)[4], const u32x4 (&qf)[4], float scale_log2) {
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) s = qm_mfma<F16>(kf[ks], qf[ks], s);
-  return s * scale_log2;
-}
 
 template <bool F16>
 __global__ __launch_bounds__(QM_THREADS) void qm_stats_kernel(QuerymapLaunch A) {
@@ -94,15 +60,15 @@ __global__ __launch_bounds__(QM_THREADS) void qm_stats_kernel(QuerymapLaunch A) 
   const int qi = row0 + (lane & 15);                       // this lane's query row
   const int qrow = min(qi, P.nq - 1);                      // (rows past the end repeat the last one and are dropped)
   u32x4 qf[4], kf[4], kn[4];
-  qm_frag_load((const uint16_t *)P.q + (size_t)qrow * (size_t)P.ldq, h, qf);
+  qk_frag_load((const uint16_t *)P.q + (size_t)qrow * (size_t)P.ldq, h, qf);
   // (key rows past the end repeat the last key; their scores are masked)
-  qm_frag_load(qm_key_row(P, min(wave * 16 + (lane & 15), ntot - 1)), h, kn);
+  qk_frag_load(qk_key_row(P, min(wave * 16 + (lane & 15), ntot - 1)), h, kn);
   float m = QM_M_INIT, l = 0.f;
   for (int t = 0; t < tiles; ++t) {
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) kf[ks] = kn[ks];
-    if (t + 1 < tiles) qm_frag_load(qm_key_row(P, min((t + 1) * QM_TILE + wave * 16 + (lane & 15), ntot - 1)), h, kn);
-    f32x4 s = qm_scores<F16>(kf, qf, A.scale_log2);
+    if (t + 1 < tiles) qk_frag_load(qk_key_row(P, min((t + 1) * QM_TILE + wave * 16 + (lane & 15), ntot - 1)), h, kn);
+    f32x4 s = qk_scores<F16>(kf, qf, A.scale_log2);
     if (t == tiles - 1) {                                  // keys past the end (the last tile only)
 #pragma unroll
       for (int e = 0; e < 4; ++e)
@@ -153,9 +119,9 @@ __global__ __launch_bounds__(QM_THREADS) void qm_emit_kernel(QuerymapLaunch A) {
     kp[g] = (const uint16_t *)P.k1 + (size_t)min(key0 + g * 16 + (lane & 15), P.n1 - 1) * (size_t)P.ldk;
   const float2 *stat = (const float2 *)(A.workspace + A.ws_off[blockIdx.z]) + qrow;
   u32x4 qf[4], qn[4], kf[2][4], kn[2][4];
-  qm_frag_load(qp, 0, qn);
-  qm_frag_load(kp[0], 0, kn[0]);
-  qm_frag_load(kp[1], 0, kn[1]);
+  qk_frag_load(qp, 0, qn);
+  qk_frag_load(kp[0], 0, kn[0]);
+  qk_frag_load(kp[1], 0, kn[1]);
   float2 mn = stat[0];
   f32x4 sum[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};   // (0 + p is p: head 0 starts the sum)
   for (int h = 0; h < A.num_heads; ++h) {
@@ -163,14 +129,14 @@ __global__ __launch_bounds__(QM_THREADS) void qm_emit_kernel(QuerymapLaunch A) {
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) qf[ks] = qn[ks], kf[0][ks] = kn[0][ks], kf[1][ks] = kn[1][ks];
     if (h + 1 < A.num_heads) {                             // the next head, in flight during this head's MFMAs
-      qm_frag_load(qp, h + 1, qn);
-      qm_frag_load(kp[0], h + 1, kn[0]);
-      qm_frag_load(kp[1], h + 1, kn[1]);
+      qk_frag_load(qp, h + 1, qn);
+      qk_frag_load(kp[0], h + 1, kn[0]);
+      qk_frag_load(kp[1], h + 1, kn[1]);
       mn = stat[(size_t)(h + 1) * (size_t)P.nq];
     }
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-      const f32x4 s = qm_scores<F16>(kf[g], qf, A.scale_log2);
+      const f32x4 s = qk_scores<F16>(kf[g], qf, A.scale_log2);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float p = __builtin_amdgcn_exp2f(s[e] - ml.x) / ml.y;
@@ -185,10 +151,7 @@ __global__ __launch_bounds__(QM_THREADS) void qm_emit_kernel(QuerymapLaunch A) {
     for (int e = 0; e < 4; ++e) {
       const int j = key0 + g * 16 + (lane >> 4) * 4 + e;
       if (j >= P.n1) continue;
-      const float v = sum[g][e] * A.inv_heads;
-      const size_t o = (size_t)qi * (size_t)P.n1 + j;
-      if (P.acc) P.acc[o] = __builtin_fmaf(P.weight, v, P.acc[o]);
-      if (P.acc2) P.acc2[o] = __builtin_fmaf(P.weight2, v, P.acc2[o]);
+      qk_accumulate(P, (size_t)qi * (size_t)P.n1 + j, sum[g][e] * A.inv_heads);
     }
 }
 
@@ -196,34 +159,18 @@ int64_t qm_problem_bytes(const ca_querymap_problem &p, int32_t num_heads) {
   return ((int64_t)num_heads * p.nq * 8 + 15) & ~(int64_t)15;
 }
 
+// the unit's size rule (n0 + n1 leaves room for the round-up to whole key tiles / key blocks in 32-bit arithmetic)
+bool qm_sizes_ok(const char *FN, int i, const ca_querymap_problem &p) {
+  if (p.nq >= 1 && p.nq <= CA_QUERYMAP_MAX_QUERIES && p.n0 >= 0 && p.n1 >= 1 && (int64_t)p.n0 + p.n1 <= CA_QUERYMAP_MAX_ROWS)
+    return true;
+  ca_set_error("%s: problem %d sizes invalid (nq=%d n0=%d n1=%d; need 1 <= nq <= %d, n0 >= 0, n1 >= 1, n0 + n1 <= %d)",
+               FN, i, p.nq, p.n0, p.n1, CA_QUERYMAP_MAX_QUERIES, CA_QUERYMAP_MAX_ROWS);
+  return false;
+}
+
 // the argument rules of both entry points; 0 or CA_ERR_ARG with the text under FN
 int qm_check(const char *FN, const ca_querymap_problem *problems, int32_t n_problems, int32_t num_heads) {
-  if (!problems || n_problems < 1 || n_problems > CA_QUERYMAP_MAX_PROBLEMS || num_heads < 1 || num_heads > (1 << 16)) {
-    ca_set_error("%s: bad arguments (n_problems=%d num_heads=%d; need 1 <= n_problems <= %d, 1 <= num_heads <= 65536)", FN,
-                 n_problems, num_heads, CA_QUERYMAP_MAX_PROBLEMS);
-    return CA_ERR_ARG;
-  }
-  const int64_t width = (int64_t)num_heads * 128;
-  for (int i = 0; i < n_problems; ++i) {
-    const ca_querymap_problem &p = problems[i];
-    // (n0 + n1 leaves room for the round-up to whole key tiles / key blocks in 32-bit arithmetic)
-    if (p.nq < 1 || p.nq > CA_QUERYMAP_MAX_QUERIES || p.n0 < 0 || p.n1 < 1 || (int64_t)p.n0 + p.n1 > CA_QUERYMAP_MAX_ROWS) {
-      ca_set_error("%s: problem %d sizes invalid (nq=%d n0=%d n1=%d; need 1 <= nq <= %d, n0 >= 0, n1 >= 1, n0 + n1 <= %d)",
-                   FN, i, p.nq, p.n0, p.n1, CA_QUERYMAP_MAX_QUERIES, CA_QUERYMAP_MAX_ROWS);
-      return CA_ERR_ARG;
-    }
-    if (!p.q || !p.k1 || (p.n0 > 0 && !p.k0) || (((uintptr_t)p.q | (uintptr_t)p.k0 | (uintptr_t)p.k1) & 15) ||
-        p.ldq < width || p.ldk < width || p.ldq % 8 || p.ldk % 8) {
-      ca_set_error("%s: problem %d rows invalid (ldq=%d ldk=%d; q, k1 and, with n0 > 0, k0 non-null and 16-byte aligned, row "
-                   "strides >= num_heads*128 = %lld and a multiple of 8)", FN, i, p.ldq, p.ldk, (long long)width);
-      return CA_ERR_ARG;
-    }
-    if ((!p.acc && !p.acc2) || (((uintptr_t)p.acc | (uintptr_t)p.acc2 | (uintptr_t)p.lse) & 3)) {
-      ca_set_error("%s: problem %d outputs invalid (at least one of acc / acc2; acc, acc2 and lse 4-byte aligned)", FN, i);
-      return CA_ERR_ARG;
-    }
-  }
-  return CA_OK;
+  return qk_check(FN, problems, n_problems, num_heads, CA_QUERYMAP_MAX_PROBLEMS, true, "q, k1 and, with n0 > 0, k0", qm_sizes_ok);
 }
 
 }  // namespace
@@ -239,11 +186,7 @@ extern "C" int ca_query_maps(const ca_querymap_problem *problems, int32_t n_prob
                              int32_t flags, void *workspace, int64_t workspace_bytes, ca_stream_t stream) {
   const char *FN = "ca_query_maps";
   if (qm_check(FN, problems, n_problems, num_heads) != CA_OK) return CA_ERR_ARG;
-  if (!isfinite(scale_log2) || (flags & ~CA_QUERYMAP_QK_F16)) {
-    ca_set_error("%s: bad arguments (scale_log2=%g flags=%d; need a finite scale_log2, flags 0 or %d)", FN,
-                 (double)scale_log2, flags, CA_QUERYMAP_QK_F16);
-    return CA_ERR_ARG;
-  }
+  if (qk_check_scale_flags(FN, scale_log2, flags, CA_QUERYMAP_QK_F16) != CA_OK) return CA_ERR_ARG;
   QuerymapLaunch A = {};
   int64_t need = 0;
   int max_nq = 0, max_n1 = 0;

@@ -1,6 +1,7 @@
 // ca_token_maps: prompt-token attention maps.  For every image query row, the probability its joint [text | image] softmax
-// gives to each of the first n_tok text keys, averaged over the heads (semantics: ca_tokmap.h).  A kernel family of its
-// own: it re-reads the q and k rows an attention launch has read and shares no code with the attention kernels.
+// gives to each of the first n_tok text keys, averaged over the heads (semantics: ca_tokmap.h).  It re-reads the q
+// and k rows an attention launch has read; the fragments, the key rows, the accumulators' write-out and the common entry
+// rules are ca_qkmap_core.h's, shared with ca_querymap.hip; nothing is shared with the attention kernels.
 //
 // One workgroup of four waves owns 64 query rows (16 per wave) of one problem and walks ALL heads, so that the sum over
 // the heads stays inside the workgroup: every (token, row) cell lives in LDS, is added to by one lane only, in head
@@ -12,9 +13,7 @@
 //           (two shuffles), l is summed across them once at the end of the pass.
 //   pass B  the text tiles again (ceil(n_tok / 64) of them): exp2(s - m) / l into the LDS cells.
 // The next tile's global loads are issued before the current tile's MFMAs (registers -> LDS at the top of the next round).
-#include <math.h>
-
-#include "ca_common.h"
+#include "ca_qkmap_core.h"
 #include "ca_tokmap.h"
 
 namespace {   // device code
@@ -26,28 +25,11 @@ constexpr int TM_PITCH = 272;               // bytes of a tile row in LDS: 256 +
                                             // (ds_read_b128, one row per lane) start 4 banks apart
 constexpr int TM_TILE_BYTES = TM_TILE * TM_PITCH;
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 struct TokmapLaunch {
   ca_tokmap_problem p[CA_TOKMAP_MAX_PROBLEMS];
   int32_t num_heads;
   float scale_log2, inv_heads;
 };
-
-template <bool F16>
-__device__ __forceinline__ f32x4 tm_mfma(u32x4 k, u32x4 q, f32x4 c) {
-  if constexpr (F16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, k), __builtin_bit_cast(f16x8, q), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, k), __builtin_bit_cast(bf16x8, q), c, 0, 0, 0);
-}
-
-// the address of key row j (0 <= j < n0 + n1) of a problem, head columns not included
-__device__ __forceinline__ const uint16_t *tm_key_row(const ca_tokmap_problem &P, int j) {
-  return j < P.n0 ? (const uint16_t *)P.k0 + (size_t)j * (size_t)P.ldk
-                  : (const uint16_t *)P.k1 + (size_t)(j - P.n0) * (size_t)P.ldk;
-}
 
 // a thread's four 16-byte pieces of key tile `tile`, head h: piece i = tile row (tid >> 4) + 16 i, columns 8 (tid & 15)..;
 // rows past the last key repeat the last key (their scores are masked)
@@ -55,7 +37,7 @@ __device__ __forceinline__ void tm_tile_load(const ca_tokmap_problem &P, int nto
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int j = min(tile * TM_TILE + (int)(threadIdx.x >> 4) + 16 * i, ntot - 1);
-    st[i] = *(const u32x4 *)(tm_key_row(P, j) + (size_t)h * 128 + (threadIdx.x & 15) * 8);
+    st[i] = *(const u32x4 *)(qk_key_row(P, j) + (size_t)h * 128 + (threadIdx.x & 15) * 8);
   }
 }
 
@@ -73,15 +55,8 @@ __device__ __forceinline__ f32x4 tm_scores(const char *tile_lds, int g, const u3
   const char *row = tile_lds + (g * 16 + (lane & 15)) * TM_PITCH + (lane >> 4) * 16;
   f32x4 s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) s = tm_mfma<F16>(*(const u32x4 *)(row + ks * 64), qf[ks], s);
+  for (int ks = 0; ks < 4; ++ks) s = qk_mfma<F16>(*(const u32x4 *)(row + ks * 64), qf[ks], s);
   return s * scale_log2;
-}
-
-__device__ __forceinline__ void tm_q_load(const ca_tokmap_problem &P, int qrow, int h, u32x4 (&qf)[4]) {
-  const int lane = threadIdx.x & 63;
-  const uint16_t *q = (const uint16_t *)P.q + (size_t)qrow * (size_t)P.ldq + (size_t)h * 128 + (lane >> 4) * 8;
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const u32x4 *)(q + ks * 32);
 }
 
 template <bool F16>
@@ -104,7 +79,8 @@ __global__ __launch_bounds__(TM_THREADS) void ca_tokmap_kernel(TokmapLaunch A) {
 
   const int per_head = nA + nB, rounds = A.num_heads * per_head;
   u32x4 st[4], qf[4], qn[4];
-  tm_q_load(P, qrow, 0, qn);
+  // (the row's address is formed at each load: kept in a variable it changes hipcc's code for the whole kernel)
+  qk_frag_load((const uint16_t *)P.q + (size_t)qrow * (size_t)P.ldq, 0, qn);
   tm_tile_load(P, ntot, 0, 0, st);
   float m = -INFINITY, l = 0.f;
   int h = 0, r = 0;                                        // round -> (head, tile job of the head)
@@ -115,7 +91,7 @@ __global__ __launch_bounds__(TM_THREADS) void ca_tokmap_kernel(TokmapLaunch A) {
     if (r == 0) {
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) qf[ks] = qn[ks];
-      if (h + 1 < A.num_heads) tm_q_load(P, qrow, h + 1, qn);
+      if (h + 1 < A.num_heads) qk_frag_load((const uint16_t *)P.q + (size_t)qrow * (size_t)P.ldq, h + 1, qn);
       m = -INFINITY, l = 0.f;
     }
     {                                                      // the next round's tile, in flight during this round's MFMAs
@@ -180,44 +156,26 @@ __global__ __launch_bounds__(TM_THREADS) void ca_tokmap_kernel(TokmapLaunch A) {
     if (i >= P.nq) continue;
     const float v = all[(size_t)(row >> 4) * ngroups * 256 + (((t >> 4) * 4 + (t & 3)) * 4 + ((t >> 2) & 3)) * 16 + (row & 15)] *
                     A.inv_heads;
-    const size_t o = (size_t)t * (size_t)P.nq + i;
-    if (P.acc) P.acc[o] = __builtin_fmaf(P.weight, v, P.acc[o]);
-    if (P.acc2) P.acc2[o] = __builtin_fmaf(P.weight2, v, P.acc2[o]);
+    qk_accumulate(P, (size_t)t * (size_t)P.nq + i, v);
   }
 }
 
 size_t tm_lds_bytes(int n_tok) { return (size_t)TM_TILE_BYTES + (size_t)((n_tok + 15) / 16) * 256 * 4 * sizeof(float); }
 
+// the unit's size rule (nq and n0 + n1 leave room for the round-up to whole row blocks / key tiles in 32-bit arithmetic)
+bool tm_sizes_ok(const char *FN, int i, const ca_tokmap_problem &p) {
+  if (p.nq >= 1 && p.nq <= CA_TOKMAP_MAX_ROWS && p.n0 >= 1 && p.n0 <= CA_TOKMAP_MAX_TEXT && p.n_tok >= 1 && p.n_tok <= p.n0 &&
+      p.n1 >= 0 && (int64_t)p.n0 + p.n1 <= CA_TOKMAP_MAX_ROWS)
+    return true;
+  ca_set_error("%s: problem %d sizes invalid (nq=%d n0=%d n1=%d n_tok=%d; need 1 <= nq <= %d, 1 <= n_tok <= n0 <= %d, "
+               "n1 >= 0, n0 + n1 <= %d)", FN, i, p.nq, p.n0, p.n1, p.n_tok, CA_TOKMAP_MAX_ROWS, CA_TOKMAP_MAX_TEXT,
+               CA_TOKMAP_MAX_ROWS);
+  return false;
+}
+
 // the argument rules of both entry points; 0 or CA_ERR_ARG with the text under FN
 int tm_check(const char *FN, const ca_tokmap_problem *problems, int32_t n_problems, int32_t num_heads) {
-  if (!problems || n_problems < 1 || n_problems > CA_TOKMAP_MAX_PROBLEMS || num_heads < 1 || num_heads > (1 << 16)) {
-    ca_set_error("%s: bad arguments (n_problems=%d num_heads=%d; need 1 <= n_problems <= %d, 1 <= num_heads <= 65536)", FN,
-                 n_problems, num_heads, CA_TOKMAP_MAX_PROBLEMS);
-    return CA_ERR_ARG;
-  }
-  const int64_t width = (int64_t)num_heads * 128;
-  for (int i = 0; i < n_problems; ++i) {
-    const ca_tokmap_problem &p = problems[i];
-    // (nq and n0 + n1 leave room for the round-up to whole row blocks / key tiles in 32-bit arithmetic)
-    if (p.nq < 1 || p.nq > CA_TOKMAP_MAX_ROWS || p.n0 < 1 || p.n0 > CA_TOKMAP_MAX_TEXT || p.n_tok < 1 || p.n_tok > p.n0 ||
-        p.n1 < 0 || (int64_t)p.n0 + p.n1 > CA_TOKMAP_MAX_ROWS) {
-      ca_set_error("%s: problem %d sizes invalid (nq=%d n0=%d n1=%d n_tok=%d; need 1 <= nq <= %d, 1 <= n_tok <= n0 <= %d, "
-                   "n1 >= 0, n0 + n1 <= %d)", FN, i, p.nq, p.n0, p.n1, p.n_tok, CA_TOKMAP_MAX_ROWS, CA_TOKMAP_MAX_TEXT,
-                   CA_TOKMAP_MAX_ROWS);
-      return CA_ERR_ARG;
-    }
-    if (!p.q || !p.k0 || (p.n1 > 0 && !p.k1) || (((uintptr_t)p.q | (uintptr_t)p.k0 | (uintptr_t)p.k1) & 15) ||
-        p.ldq < width || p.ldk < width || p.ldq % 8 || p.ldk % 8) {
-      ca_set_error("%s: problem %d rows invalid (ldq=%d ldk=%d; q, k0 and, with n1 > 0, k1 non-null and 16-byte aligned, row "
-                   "strides >= num_heads*128 = %lld and a multiple of 8)", FN, i, p.ldq, p.ldk, (long long)width);
-      return CA_ERR_ARG;
-    }
-    if ((!p.acc && !p.acc2) || (((uintptr_t)p.acc | (uintptr_t)p.acc2 | (uintptr_t)p.lse) & 3)) {
-      ca_set_error("%s: problem %d outputs invalid (at least one of acc / acc2; acc, acc2 and lse 4-byte aligned)", FN, i);
-      return CA_ERR_ARG;
-    }
-  }
-  return CA_OK;
+  return qk_check(FN, problems, n_problems, num_heads, CA_TOKMAP_MAX_PROBLEMS, false, "q, k0 and, with n1 > 0, k1", tm_sizes_ok);
 }
 
 }  // namespace
@@ -231,11 +189,7 @@ extern "C" int ca_token_maps(const ca_tokmap_problem *problems, int32_t n_proble
                              int32_t flags, void *workspace, int64_t workspace_bytes, ca_stream_t stream) {
   const char *FN = "ca_token_maps";
   if (tm_check(FN, problems, n_problems, num_heads) != CA_OK) return CA_ERR_ARG;
-  if (!isfinite(scale_log2) || (flags & ~CA_TOKMAP_QK_F16)) {
-    ca_set_error("%s: bad arguments (scale_log2=%g flags=%d; need a finite scale_log2, flags 0 or %d)", FN,
-                 (double)scale_log2, flags, CA_TOKMAP_QK_F16);
-    return CA_ERR_ARG;
-  }
+  if (qk_check_scale_flags(FN, scale_log2, flags, CA_TOKMAP_QK_F16) != CA_OK) return CA_ERR_ARG;
   const int64_t need = ca_token_maps_workspace_bytes(problems, n_problems, num_heads);
   if (workspace_bytes < need || (need > 0 && !workspace)) {
     ca_set_error("%s: workspace too small (workspace_bytes=%lld, ca_token_maps_workspace_bytes says %lld)", FN,

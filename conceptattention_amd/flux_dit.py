@@ -209,6 +209,23 @@ class HeatmapRequest:
         return tuple(r for r in (self,) + tuple(self.head_more) if r.head_spaces())
 
 
+def _launch_apart(probs: list, accumulators, launch, limit: Optional[int] = None) -> None:
+    """``launch(batch)`` over the map problems ``probs``, in order and in as few batches as this allows: a problem that
+    names an accumulator already in the batch (``accumulators(problem)``: its tensors or None; two requests may share
+    one) starts a new batch, since within a launch the updates are unordered read-modify-writes, and so does a batch of
+    ``limit`` problems (None: the launch splits longer lists itself).  No launch for no problems."""
+    batch, seen = [], set()
+    for pr in probs + [None]:
+        ptrs = set() if pr is None else {t.data_ptr() for t in accumulators(pr) if t is not None}
+        if pr is None or len(batch) == limit or (ptrs & seen):
+            if batch:
+                launch(batch)
+            batch, seen = [], set()
+        if pr is not None:
+            batch.append(pr)
+            seen |= ptrs
+
+
 def modulation_rows(params: FluxParams) -> int:
     """Rows of the stacked adaLN matrix (FluxWeights.mod_rows): 2 x 6H per double block, 3H per single block, 2H for the
     final layer.  One fp32 vector of that length is every block's shift / scale / gate for one conditioning vector."""
@@ -1126,17 +1143,8 @@ class HipFluxDiT:
             tj, ij = slice(oT + j * T, oT + (j + 1) * T), slice(oI + j * Li, oI + (j + 1) * Li)
             probs.append(ops.TokenMaps(qs[ij], ks[tj], ks[ij], n_tok, acc=hm.token_space, weight=hm.weight, acc2=table,
                                        weight2=hm.per_layer_weight))
-        # (two requests that share an accumulator start a new launch, as the concept maps' do)
-        batch, seen = [], set()
-        for pr in probs + [None]:
-            ptrs = set() if pr is None else {t.data_ptr() for t in (pr.acc, pr.acc2) if t is not None}
-            if pr is None or (ptrs & seen):
-                if batch:
-                    ops.token_maps(batch, NH, 1.0, qk_f16=route.qk16, workspace=self._token_maps_workspace(batch, NH))
-                batch, seen = [], set()
-            if pr is not None:
-                batch.append(pr)
-                seen |= ptrs
+        _launch_apart(probs, lambda pr: (pr.acc, pr.acc2), lambda batch: ops.token_maps(
+            batch, NH, 1.0, qk_f16=route.qk16, workspace=self._token_maps_workspace(batch, NH)))
 
     def _capture_query_maps(self, layer, g, NH, heatmaps, route):
         """The query-row maps of a captured layer: ONE ops.query_maps call for all items and both kinds that ask, over the
@@ -1163,26 +1171,23 @@ class HipFluxDiT:
                 else:
                     q, k0 = qs[cj], ks[cj]
                 probs.append(ops.QueryMaps(q, k0, ks[ij], acc=acc, weight=hm.weight, acc2=table, weight2=hm.per_layer_weight))
-        # (two requests that share an accumulator start a new launch, as the concept maps' do)
-        batch, seen = [], set()
-        for pr in probs + [None]:
-            ptrs = set() if pr is None else {t.data_ptr() for t in (pr.acc, pr.acc2) if t is not None}
-            if pr is None or len(batch) == L.QUERYMAP_MAX_PROBLEMS or (ptrs & seen):
-                if batch:
-                    ops.query_maps(batch, NH, 1.0, qk_f16=route.qk16, workspace=self._query_maps_workspace(batch, NH))
-                batch, seen = [], set()
-            if pr is not None:
-                batch.append(pr)
-                seen |= ptrs
+        _launch_apart(probs, lambda pr: (pr.acc, pr.acc2), lambda batch: ops.query_maps(
+            batch, NH, 1.0, qk_f16=route.qk16, workspace=self._query_maps_workspace(batch, NH)), L.QUERYMAP_MAX_PROBLEMS)
+
+    def _maps_workspace(self, attr, need):
+        """A map launch's scratch memory: the model buffer ``attr``, allocated on first use and grown on demand (None
+        while the kernel needs none)."""
+        if need == 0:
+            return None
+        ws = getattr(self, attr, None)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, device=self.device, dtype=torch.uint8)
+            setattr(self, attr, ws)
+        return ws
 
     def _query_maps_workspace(self, probs, NH):
-        """ops.query_maps' scratch memory (8 bytes per head and query row): a model buffer allocated on first use and
-        grown on demand."""
-        need = ops.query_maps_workspace_bytes(probs, NH)
-        ws = getattr(self, "_querymap_ws", None)
-        if ws is None or ws.numel() < need:
-            ws = self._querymap_ws = torch.empty(need, device=self.device, dtype=torch.uint8)
-        return ws
+        """ops.query_maps' scratch memory (8 bytes per head and query row)."""
+        return self._maps_workspace("_querymap_ws", ops.query_maps_workspace_bytes(probs, NH))
 
     def _capture_head_maps(self, layer, g, NH, heatmaps):
         """The per-head maps of a captured layer: ONE ops.head_maps launch (per norm) for all items and spaces that ask,
@@ -1208,28 +1213,12 @@ class HipFluxDiT:
                 launches.setdefault(L.NORM_NONE if hr.head_norm is None else hr.head_norm, []).append(
                     ops.HeadMaps(img, con, heads=heads, weight_h=hm.weight, acc=raw, weight=hm.weight))
         for norm, probs in launches.items():
-            # (two requests that share an accumulator start a new launch, as the concept maps' do)
-            batch, seen = [], set()
-            for pr in probs + [None]:
-                ptrs = set() if pr is None else {t.data_ptr() for t in (pr.heads, pr.acc) if t is not None}
-                if pr is None or len(batch) == L.HEATMAP_MAX_PROBLEMS or (ptrs & seen):
-                    if batch:
-                        ops.head_maps(batch, NH, norm)
-                    batch, seen = [], set()
-                if pr is not None:
-                    batch.append(pr)
-                    seen |= ptrs
+            _launch_apart(probs, lambda pr: (pr.heads, pr.acc), lambda batch, norm=norm: ops.head_maps(batch, NH, norm),
+                          L.HEATMAP_MAX_PROBLEMS)
 
     def _token_maps_workspace(self, probs, NH):
-        """ops.token_maps' scratch memory: a model buffer allocated on first use and grown on demand (None while the
-        kernel needs none)."""
-        need = ops.token_maps_workspace_bytes(probs, NH)
-        if need == 0:
-            return None
-        ws = getattr(self, "_tokmap_ws", None)
-        if ws is None or ws.numel() < need:
-            ws = self._tokmap_ws = torch.empty(need, device=self.device, dtype=torch.uint8)
-        return ws
+        """ops.token_maps' scratch memory (none today: the head sum lives in LDS)."""
+        return self._maps_workspace("_tokmap_ws", ops.token_maps_workspace_bytes(probs, NH))
 
     def _capture(self, out, layer, g, NH, return_vectors, heatmaps, route):
         """Dict capture (modified_double_stream_block.py:185-191) and/or fused heat-map update, per work item;
@@ -1299,19 +1288,9 @@ class HipFluxDiT:
                     ops.heatmap_norm_accumulate(logits[:C], acc, hm.weight, hm.norm)
                 if table is not None:
                     ops.heatmap_norm_accumulate(logits[:C], table[li], hm.per_layer_weight, hm.norm)
-        for norm, probs in launches.items():
-            # one launch per norm; problems that name an accumulator already in the launch (two requests sharing a
-            # tensor) start a new one: within a launch the updates are unordered read-modify-writes
-            batch, seen = [], set()
-            for pr in probs + [None]:
-                ptrs = set() if pr is None else {t.data_ptr() for t in (pr.acc, pr.acc2) if t is not None}
-                if pr is None or len(batch) == L.HEATMAP_MAX_PROBLEMS or (ptrs & seen):
-                    if batch:
-                        launch(batch, norm)
-                    batch, seen = [], set()
-                if pr is not None:
-                    batch.append(pr)
-                    seen |= ptrs
+        for norm, probs in launches.items():        # one launch per norm
+            _launch_apart(probs, lambda pr: (pr.acc, pr.acc2), lambda batch, norm=norm: launch(batch, norm),
+                          L.HEATMAP_MAX_PROBLEMS)
 
     # ------------------------------------------------------------------ concept re-query
     @torch.no_grad()

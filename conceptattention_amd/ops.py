@@ -652,31 +652,49 @@ class TokenMaps:
     lse: Optional[torch.Tensor] = None
 
 
-def _token_maps_array(problems: Sequence[TokenMaps], num_heads: int):
-    """ops.token_maps' argument checks (no device needed for the shape rules) and the problem array."""
-    FN = "token_maps"
+def _qk_maps_array(FN: str, struct, problems, num_heads: int, optional: str, missing: Optional[str], sizes,
+                   one_row_strides: bool):
+    """The argument checks of ops.token_maps and ops.query_maps (no device needed for the shape rules) and their problem
+    array of ``struct``.  What differs between the two is data.  ``optional``: the key segment, "k0" or "k1", that may be
+    None or empty; the other one is required, and ``missing`` is the text for it being None (None: left to _chk).
+    ``sizes(t, nq, n0, n1)``: the op's size rule: the accumulators' shape, the (name, value) struct fields only this op
+    has, and its own text when the sizes are refused.  ``one_row_strides``: the row stride of a one-row tensor, which is free in
+    torch, is not held against the other segment's and is replaced by one the library takes."""
     width = num_heads * 128
-    arr = (L.TokmapProblem * len(problems))()
+    required = "k1" if optional == "k0" else "k0"
+    arr = (struct * len(problems))()
     seen = {}
-    for i, t in enumerate(problems):
-        _chk(t.q, torch.bfloat16, "q"), _chk(t.k0, torch.bfloat16, "k0")
-        k1 = t.k1 if t.k1 is not None and t.k1.shape[0] > 0 else None
-        if k1 is not None:
-            _chk(k1, torch.bfloat16, "k1")
-        for n, x in (("q", t.q), ("k0", t.k0), ("k1", k1)):
+    for i, t in enumerate(problems):    # (this loop is host time of every launch: the texts are formed only when raised)
+        k = {"k0": t.k0, "k1": t.k1}
+        if k[required] is None and missing:
+            raise ValueError(f"{FN}[{i}]: {missing}")
+        _chk(t.q, torch.bfloat16, "q"), _chk(k[required], torch.bfloat16, required)
+        if k[optional] is not None and k[optional].shape[0] == 0:
+            k[optional] = None
+        if k[optional] is not None:
+            _chk(k[optional], torch.bfloat16, optional)
+        k0, k1 = k["k0"], k["k1"]
+        for n, x in (("q", t.q), ("k0", k0), ("k1", k1)):
             if x is not None and (x.dim() != 2 or x.shape[1] != width):
                 raise ValueError(f"{FN}[{i}]: {n} must be 2-D with num_heads*128 = {width} columns, got {tuple(x.shape)}")
-        if k1 is not None and k1.stride(0) != t.k0.stride(0):
+        nq, n0, n1 = t.q.shape[0], 0 if k0 is None else k0.shape[0], 0 if k1 is None else k1.shape[0]
+        # the row strides: of the key segments, those that have one (under one_row_strides a one-row segment has none)
+        ldq = _i32(t.q.stride(0), "ldq")
+        ld0 = None if k0 is None or (one_row_strides and n0 <= 1) else _i32(k0.stride(0), "ldk")
+        ld1 = None if k1 is None or (one_row_strides and n1 <= 1) else _i32(k1.stride(0), "ldk")
+        if ld0 is not None and ld1 is not None and ld0 != ld1:
             raise ValueError(f"{FN}[{i}]: both key segments must share one row stride")
-        nq, n0 = t.q.shape[0], t.k0.shape[0]
-        n_tok = n0 if t.n_tok is None else int(t.n_tok)
-        if nq < 1 or not 1 <= n_tok <= n0 <= L.TOKMAP_MAX_TEXT:
-            raise ValueError(f"{FN}[{i}]: need nq >= 1 and 1 <= n_tok <= n0 <= {L.TOKMAP_MAX_TEXT}, got nq = {nq}, "
-                             f"n_tok = {n_tok}, n0 = {n0}")
+        # (neither has one: the library wants at least the width)
+        ldk = ld0 if ld0 is not None else ld1 if ld1 is not None else max(_i32(k[required].stride(0), "ldk"), width)
+        if one_row_strides and nq == 1:
+            ldq = max(ldq, width)
+        acc_shape, own_fields, complaint = sizes(t, nq, n0, n1)
+        if complaint:
+            raise ValueError(f"{FN}[{i}]: {complaint}")
         if t.acc is None and t.acc2 is None:
             raise ValueError(f"{FN}[{i}]: every problem needs acc or acc2")
         p = arr[i]
-        for name, shape in (("acc", (n_tok, nq)), ("acc2", (n_tok, nq)), ("lse", (num_heads, nq))):
+        for name, shape in (("acc", acc_shape), ("acc2", acc_shape), ("lse", (num_heads, nq))):
             x = getattr(t, name)
             if x is None:
                 continue
@@ -689,26 +707,59 @@ def _token_maps_array(problems: Sequence[TokenMaps], num_heads: int):
                                      "call (their updates would race)")
                 seen[x.data_ptr()] = i
             setattr(p, name, x.data_ptr())
-        p.q, p.k0, p.k1 = t.q.data_ptr(), t.k0.data_ptr(), _ptr(k1)
-        p.nq, p.n0, p.n1, p.n_tok = _i32(nq, "nq"), n0, _i32(0 if k1 is None else k1.shape[0], "n1"), n_tok
-        p.ldq, p.ldk = _i32(t.q.stride(0), "ldq"), _i32(t.k0.stride(0), "ldk")
+        p.q, p.k0, p.k1 = t.q.data_ptr(), _ptr(k0), _ptr(k1)
+        p.nq, p.n0, p.n1 = _i32(nq, "nq"), _i32(n0, "n0"), _i32(n1, "n1")
+        for name, value in own_fields:
+            setattr(p, name, value)
+        p.ldq, p.ldk = ldq, ldk
         p.weight, p.weight2 = float(t.weight), float(t.weight2)
     return arr
 
 
-def token_maps_workspace_bytes(problems: Sequence[TokenMaps], num_heads: int) -> int:
-    """The scratch memory one ops.token_maps call over these problems needs (the largest of its launches)."""
-    lib = L.load()
-    arr = _token_maps_array(problems, num_heads)
+def _launch_slices(arr, struct, limit: int):
+    """(sub-array, its length) of every launch of a problem array: at most ``limit`` problems each, in order."""
+    for s in range(0, len(arr), limit):
+        n = min(limit, len(arr) - s)
+        yield (struct * n).from_buffer(arr, s * C.sizeof(struct)), n
+
+
+def _maps_workspace_bytes(entry: str, arr, struct, limit: int, num_heads: int) -> int:
+    """The largest workspace any launch of ``arr`` needs, as the library's ``entry`` says."""
+    query = getattr(L.load(), entry)
     need = 0
-    for s in range(0, len(problems), L.TOKMAP_MAX_PROBLEMS):
-        n = min(L.TOKMAP_MAX_PROBLEMS, len(problems) - s)
-        sub = (L.TokmapProblem * n).from_buffer(arr, s * C.sizeof(L.TokmapProblem))
-        rc = lib.ca_token_maps_workspace_bytes(sub, n, _i32(num_heads, "num_heads"))
+    for sub, n in _launch_slices(arr, struct, limit):
+        rc = query(sub, n, _i32(num_heads, "num_heads"))
         if rc < 0:
-            L.check(int(rc), "ca_token_maps_workspace_bytes")
+            L.check(int(rc), entry)
         need = max(need, int(rc))
     return need
+
+
+def _maps_workspace_arg(FN: str, workspace: torch.Tensor):
+    """(pointer, bytes) of a caller's workspace tensor."""
+    _chk(workspace, torch.uint8, "workspace")
+    if not workspace.is_contiguous():
+        raise ValueError(f"{FN}: workspace must be contiguous")
+    return workspace.data_ptr(), workspace.numel()
+
+
+def _token_sizes(t: TokenMaps, nq: int, n0: int, n1: int):
+    n_tok = n0 if t.n_tok is None else int(t.n_tok)
+    bad = nq < 1 or not 1 <= n_tok <= n0 <= L.TOKMAP_MAX_TEXT
+    return (n_tok, nq), (("n_tok", n_tok),), bad and (f"need nq >= 1 and 1 <= n_tok <= n0 <= {L.TOKMAP_MAX_TEXT}, got "
+                                                      f"nq = {nq}, n_tok = {n_tok}, n0 = {n0}")
+
+
+def _token_maps_array(problems: Sequence[TokenMaps], num_heads: int):
+    """ops.token_maps' argument checks (no device needed for the shape rules) and the problem array."""
+    return _qk_maps_array("token_maps", L.TokmapProblem, problems, num_heads, optional="k1", missing=None,
+                          sizes=_token_sizes, one_row_strides=False)
+
+
+def token_maps_workspace_bytes(problems: Sequence[TokenMaps], num_heads: int) -> int:
+    """The scratch memory one ops.token_maps call over these problems needs (the largest of its launches)."""
+    return _maps_workspace_bytes("ca_token_maps_workspace_bytes", _token_maps_array(problems, num_heads), L.TokmapProblem,
+                                 L.TOKMAP_MAX_PROBLEMS, num_heads)
 
 
 def token_maps(problems: Sequence[TokenMaps], num_heads: int, scale_log2: float = 1.0, qk_f16: bool = False,
@@ -725,16 +776,9 @@ def token_maps(problems: Sequence[TokenMaps], num_heads: int, scale_log2: float 
     if not math.isfinite(scale_log2):
         raise ValueError("token_maps: scale_log2 must be finite")
     arr = _token_maps_array(problems, num_heads)
-    ws_ptr, ws_bytes = None, 0
-    if workspace is not None:
-        _chk(workspace, torch.uint8, "workspace")
-        if not workspace.is_contiguous():
-            raise ValueError("token_maps: workspace must be contiguous")
-        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel()
+    ws_ptr, ws_bytes = (None, 0) if workspace is None else _maps_workspace_arg("token_maps", workspace)
     flags = L.TOKMAP_QK_F16 if qk_f16 else 0
-    for s in range(0, len(problems), L.TOKMAP_MAX_PROBLEMS):
-        n = min(L.TOKMAP_MAX_PROBLEMS, len(problems) - s)
-        sub = (L.TokmapProblem * n).from_buffer(arr, s * C.sizeof(L.TokmapProblem))
+    for sub, n in _launch_slices(arr, L.TokmapProblem, L.TOKMAP_MAX_PROBLEMS):
         L.check(lib.ca_token_maps(sub, n, _i32(num_heads, "num_heads"), float(scale_log2), flags, ws_ptr, ws_bytes,
                                   _stream()), "ca_token_maps")
 
@@ -756,77 +800,29 @@ class QueryMaps:
     lse: Optional[torch.Tensor] = None
 
 
+def _query_sizes(t: QueryMaps, nq: int, n0: int, n1: int):
+    bad = not 1 <= nq <= L.QUERYMAP_MAX_QUERIES or n1 < 1 or n0 + n1 > L.QUERYMAP_MAX_ROWS
+    return (nq, n1), (), bad and (f"need 1 <= nq <= {L.QUERYMAP_MAX_QUERIES}, n1 >= 1 and n0 + n1 <= "
+                                  f"{L.QUERYMAP_MAX_ROWS}, got nq = {nq}, n0 = {n0}, n1 = {n1}")
+
+
 def _query_maps_array(problems: Sequence[QueryMaps], num_heads: int):
     """ops.query_maps' argument checks (no device needed for the shape rules) and the problem array."""
-    FN = "query_maps"
-    width = num_heads * 128
-    arr = (L.QuerymapProblem * len(problems))()
-    seen = {}
-    for i, t in enumerate(problems):
-        if t.k1 is None:
-            raise ValueError(f"{FN}[{i}]: k1, the emitted key rows, is required")
-        _chk(t.q, torch.bfloat16, "q"), _chk(t.k1, torch.bfloat16, "k1")
-        k0 = t.k0 if t.k0 is not None and t.k0.shape[0] > 0 else None
-        if k0 is not None:
-            _chk(k0, torch.bfloat16, "k0")
-        for n, x in (("q", t.q), ("k0", k0), ("k1", t.k1)):
-            if x is not None and (x.dim() != 2 or x.shape[1] != width):
-                raise ValueError(f"{FN}[{i}]: {n} must be 2-D with num_heads*128 = {width} columns, got {tuple(x.shape)}")
-        nq, n0, n1 = t.q.shape[0], 0 if k0 is None else k0.shape[0], t.k1.shape[0]
-        # (a one-row tensor's stride is free in torch; the library wants at least the width)
-        ldq, ld1 = _i32(t.q.stride(0), "ldq"), _i32(t.k1.stride(0), "ldk")
-        ld0 = ld1 if k0 is None else _i32(k0.stride(0), "ldk")
-        if nq == 1:
-            ldq = max(ldq, width)
-        ldk = ld1 if n1 > 1 else ld0 if n0 > 1 else max(ld1, width)
-        if n0 > 1 and n1 > 1 and ld0 != ld1:
-            raise ValueError(f"{FN}[{i}]: both key segments must share one row stride")
-        if not 1 <= nq <= L.QUERYMAP_MAX_QUERIES or n1 < 1 or n0 + n1 > L.QUERYMAP_MAX_ROWS:
-            raise ValueError(f"{FN}[{i}]: need 1 <= nq <= {L.QUERYMAP_MAX_QUERIES}, n1 >= 1 and n0 + n1 <= "
-                             f"{L.QUERYMAP_MAX_ROWS}, got nq = {nq}, n0 = {n0}, n1 = {n1}")
-        if t.acc is None and t.acc2 is None:
-            raise ValueError(f"{FN}[{i}]: every problem needs acc or acc2")
-        p = arr[i]
-        for name, shape in (("acc", (nq, n1)), ("acc2", (nq, n1)), ("lse", (num_heads, nq))):
-            x = getattr(t, name)
-            if x is None:
-                continue
-            _chk(x, torch.float32, name)
-            if tuple(x.shape) != shape or not x.is_contiguous():
-                raise ValueError(f"{FN}[{i}]: {name} must be contiguous fp32 {list(shape)}, got {tuple(x.shape)}")
-            if name != "lse":
-                if x.data_ptr() in seen:
-                    raise ValueError(f"{FN}[{i}]: {name} is also an accumulator of problem {seen[x.data_ptr()]} of this "
-                                     "call (their updates would race)")
-                seen[x.data_ptr()] = i
-            setattr(p, name, x.data_ptr())
-        p.q, p.k0, p.k1 = t.q.data_ptr(), _ptr(k0), t.k1.data_ptr()
-        p.nq, p.n0, p.n1 = nq, _i32(n0, "n0"), _i32(n1, "n1")
-        p.ldq, p.ldk = ldq, ldk
-        p.weight, p.weight2 = float(t.weight), float(t.weight2)
-    return arr
+    return _qk_maps_array("query_maps", L.QuerymapProblem, problems, num_heads, optional="k0",
+                          missing="k1, the emitted key rows, is required", sizes=_query_sizes, one_row_strides=True)
 
 
-def _query_maps_launches(arr, n_total: int):
-    for s in range(0, n_total, L.QUERYMAP_MAX_PROBLEMS):
-        n = min(L.QUERYMAP_MAX_PROBLEMS, n_total - s)
-        yield (L.QuerymapProblem * n).from_buffer(arr, s * C.sizeof(L.QuerymapProblem)), n
+def _query_maps_need(arr, num_heads: int) -> int:
+    return _maps_workspace_bytes("ca_query_maps_workspace_bytes", arr, L.QuerymapProblem, L.QUERYMAP_MAX_PROBLEMS, num_heads)
 
 
 def query_maps_workspace_bytes(problems: Sequence[QueryMaps], num_heads: int) -> int:
     """The scratch memory one ops.query_maps call over these problems needs (the largest of its launches): 8 bytes per
     (head, query row)."""
-    lib = L.load()
+    L.load()
     if len(problems) < 1:
         raise ValueError("query_maps_workspace_bytes: at least one problem")
-    arr = _query_maps_array(problems, num_heads)
-    need = 0
-    for sub, n in _query_maps_launches(arr, len(problems)):
-        rc = lib.ca_query_maps_workspace_bytes(sub, n, _i32(num_heads, "num_heads"))
-        if rc < 0:
-            L.check(int(rc), "ca_query_maps_workspace_bytes")
-        need = max(need, int(rc))
-    return need
+    return _query_maps_need(_query_maps_array(problems, num_heads), num_heads)
 
 
 def query_maps(problems: Sequence[QueryMaps], num_heads: int, scale_log2: float = 1.0, qk_f16: bool = False,
@@ -846,17 +842,10 @@ def query_maps(problems: Sequence[QueryMaps], num_heads: int, scale_log2: float 
         raise ValueError("query_maps: scale_log2 must be finite")
     arr = _query_maps_array(problems, num_heads)
     if workspace is None:
-        need = sum(((num_heads * p.q.shape[0] * 8 + 15) // 16) * 16 for p in problems[:L.QUERYMAP_MAX_PROBLEMS])
-        for s in range(L.QUERYMAP_MAX_PROBLEMS, len(problems), L.QUERYMAP_MAX_PROBLEMS):
-            need = max(need, sum(((num_heads * p.q.shape[0] * 8 + 15) // 16) * 16
-                                 for p in problems[s:s + L.QUERYMAP_MAX_PROBLEMS]))
-        workspace = torch.empty(need, dtype=torch.uint8, device=problems[0].q.device)
-    _chk(workspace, torch.uint8, "workspace")
-    if not workspace.is_contiguous():
-        raise ValueError("query_maps: workspace must be contiguous")
-    ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel()
+        workspace = torch.empty(_query_maps_need(arr, num_heads), dtype=torch.uint8, device=problems[0].q.device)
+    ws_ptr, ws_bytes = _maps_workspace_arg("query_maps", workspace)
     flags = L.QUERYMAP_QK_F16 if qk_f16 else 0
-    for sub, n in _query_maps_launches(arr, len(problems)):
+    for sub, n in _launch_slices(arr, L.QuerymapProblem, L.QUERYMAP_MAX_PROBLEMS):
         L.check(lib.ca_query_maps(sub, n, _i32(num_heads, "num_heads"), float(scale_log2), flags, ws_ptr, ws_bytes,
                                   _stream()), "ca_query_maps")
 
@@ -948,9 +937,7 @@ def head_maps(problems: Sequence[HeadMaps], num_heads: int, norm: int = L.NORM_N
         raise ValueError(f"head_maps: norm must be one of L.NORM_NONE / NORM_SOFTMAX / NORM_SPARSEMAX / NORM_ENTMAX15, got {norm}")
     arr, Lp, Cc = _head_maps_array(problems, num_heads)
     lib = L.load()
-    for s in range(0, len(problems), L.HEATMAP_MAX_PROBLEMS):
-        n = min(L.HEATMAP_MAX_PROBLEMS, len(problems) - s)
-        sub = (L.HeadmapProblem * n).from_buffer(arr, s * C.sizeof(L.HeadmapProblem))
+    for sub, n in _launch_slices(arr, L.HeadmapProblem, L.HEATMAP_MAX_PROBLEMS):
         L.check(lib.ca_head_maps(sub, n, _i32(Lp, "L"), _i32(Cc, "C"), _i32(num_heads, "num_heads"), int(norm), _stream()),
                 "ca_head_maps")
 

@@ -77,9 +77,12 @@ def test_the_build_and_the_source():
     src = open(os.path.join(CSRC, "build.py")).read()
     assert '_audit_no_spill("ca_querymap", asm_path)' in src
     assert re.search(r'audit_querymap\(os\.path\.join\(HERE, "ca_querymap-hip-amdgcn-amd-amdhsa-gfx950\.s"\)\)', src)
-    kernel = open(os.path.join(CSRC, "ca_querymap.hip")).read()
+    # (the unit together with the header that holds the device code it shares with ca_tokmap.hip)
+    unit, core = (open(os.path.join(CSRC, name)).read() for name in ("ca_querymap.hip", "ca_qkmap_core.h"))
+    assert '#include "ca_qkmap_core.h"' in unit
+    kernel = core + unit
     assert "__builtin_amdgcn_mfma_f32_16x16x32_bf16" in kernel and "__builtin_amdgcn_mfma_f32_16x16x32_f16" in kernel
-    code = kernel.split("namespace {")[1]
+    code = core + unit.split("namespace {")[1]
     assert "atomic" not in code and "asm" not in code             # plain HIP with builtins, no atomics
 
 

@@ -78,9 +78,12 @@ def test_the_build_and_the_documents():
     src = open(os.path.join(CSRC, "build.py")).read()
     assert '_audit_no_spill("ca_tokmap", asm_path)' in src
     assert re.search(r'audit_tokmap\(os\.path\.join\(HERE, "ca_tokmap-hip-amdgcn-amd-amdhsa-gfx950\.s"\)\)', src)
-    kernel = open(os.path.join(CSRC, "ca_tokmap.hip")).read()
+    # (the unit together with the header that holds the device code it shares with ca_querymap.hip)
+    unit, core = (open(os.path.join(CSRC, name)).read() for name in ("ca_tokmap.hip", "ca_qkmap_core.h"))
+    assert '#include "ca_qkmap_core.h"' in unit
+    kernel = core + unit
     assert "__builtin_amdgcn_mfma_f32_16x16x32_bf16" in kernel and "__builtin_amdgcn_mfma_f32_16x16x32_f16" in kernel
-    assert "atomic" not in re.sub(r"std::atomic<unsigned long long> attr_done", "", kernel.split("namespace {")[1])
+    assert "atomic" not in re.sub(r"std::atomic<unsigned long long> attr_done", "", core + unit.split("namespace {")[1])
     assert "asm" not in kernel                                     # plain HIP with builtins
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     assert "Prompt-token maps" in doc and "ca_token_maps" in doc
