@@ -51,6 +51,11 @@ QUERYMAP_MAX_PROBLEMS = 16           # ca_query_maps: problems of one launch (op
 QUERYMAP_MAX_QUERIES = 512           # ca_query_maps: nq, the query rows of a problem
 QUERYMAP_MAX_ROWS = 2 ** 31 - 128    # ca_query_maps: n0 + n1, the key rows of a problem
 QUERYMAP_QK_F16 = 1                  # ca_query_maps flags: IEEE half bits in the bf16-typed q / k rows
+PROPMAP_MAX_PROBLEMS = 16            # ca_propagate_maps: problems of one launch (ops.propagate_maps splits longer lists)
+PROPMAP_MAX_CONCEPTS = 32            # ca_propagate_maps: C, the map rows of a problem
+PROPMAP_MAX_ROWS = 2 ** 31 - 128     # ca_propagate_maps: n0 + n1, the key rows of a problem
+PROPMAP_MAX_HEADS = 65535            # ca_propagate_maps: num_heads
+PROPMAP_QK_F16 = 1                   # ca_propagate_maps flags: IEEE half bits in the bf16-typed q / k rows
 HEADMAP_MAX_HEADS = 65536            # ca_head_maps: num_heads (heads of 128 columns)
 ATTN_Q_PRESCALED = 0.0   # ca_attn_fwd_bf16(scale=...): the q rows already carry softmax_scale * log2(e)
 
@@ -99,6 +104,13 @@ class QuerymapProblem(C.Structure):  # ca_querymap_problem (csrc/ca_querymap.h),
     _fields_ = [("q", C.c_void_p), ("k0", C.c_void_p), ("k1", C.c_void_p), ("acc", C.c_void_p), ("acc2", C.c_void_p),
                 ("lse", C.c_void_p), ("nq", C.c_int32), ("ldq", C.c_int32), ("n0", C.c_int32), ("n1", C.c_int32),
                 ("ldk", C.c_int32), ("_pad", C.c_int32), ("weight", C.c_float), ("weight2", C.c_float)]
+
+
+class PropmapProblem(C.Structure):   # ca_propmap_problem (csrc/ca_propmap.h), field for field
+    _fields_ = [("q", C.c_void_p), ("k0", C.c_void_p), ("k1", C.c_void_p), ("v", C.c_void_p), ("acc", C.c_void_p),
+                ("acc2", C.c_void_p), ("nq", C.c_int32), ("ldq", C.c_int32), ("n0", C.c_int32), ("n1", C.c_int32),
+                ("ldk", C.c_int32), ("C", C.c_int32), ("ldv", C.c_int32), ("_pad", C.c_int32), ("weight", C.c_float),
+                ("weight2", C.c_float)]
 
 
 class HeadmapProblem(C.Structure):   # ca_headmap_problem (csrc/ca_headmap.h), field for field
@@ -229,7 +241,7 @@ SIGNATURES = {
 }
 
 # exported by the library and bound here, not declared in include/conceptattn.h yet (csrc/ca_heatmap_core.h,
-# csrc/ca_tokmap.h, csrc/ca_headmap.h and csrc/ca_querymap.h declare them)
+# csrc/ca_tokmap.h, csrc/ca_headmap.h, csrc/ca_querymap.h and csrc/ca_propmap.h declare them)
 INTERNAL_SIGNATURES = {
     "ca_heatmap_many": (C.c_int, [C.POINTER(HeatmapProblem), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_void_p]),
@@ -241,6 +253,9 @@ INTERNAL_SIGNATURES = {
     "ca_query_maps": (C.c_int, [C.POINTER(QuerymapProblem), C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p,
                                 C.c_int64, C.c_void_p]),
     "ca_query_maps_workspace_bytes": (C.c_int64, [C.POINTER(QuerymapProblem), C.c_int32, C.c_int32]),
+    "ca_propagate_maps": (C.c_int, [C.POINTER(PropmapProblem), C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p,
+                                    C.c_int64, C.c_void_p]),
+    "ca_propagate_maps_workspace_bytes": (C.c_int64, [C.POINTER(PropmapProblem), C.c_int32, C.c_int32]),
 }
 
 _lib = None

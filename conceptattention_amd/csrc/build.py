@@ -11,7 +11,7 @@ LIB = os.path.join(PKG, "libconceptattn.so")
 SOURCES = ["ca_api.hip", "ca_gemm.hip", "ca_attn.hip", "ca_attn4.hip", "ca_rowops.hip", "ca_vae.hip", "ca_t5.hip",
            "ca_clip.hip", "ca_pixels.hip", "ca_seg.hip", "ca_mseg.hip", "ca_segtab.hip",
            "ca_render.hip", "ca_heatmap_many.hip", "ca_tokmap.hip", "ca_headmap.hip",
-           "ca_querymap.hip"]
+           "ca_querymap.hip", "ca_propmap.hip"]
 # ca_attn4.hip owns the AGPR file by hand (literal a[...] registers in its asm statements): hipcc must never park a
 # VGPR there (its default spill target), and the emitted code is audited for it below
 EXTRA_FLAGS = {"ca_attn4.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-save-temps=obj"],
@@ -28,9 +28,11 @@ EXTRA_FLAGS = {"ca_attn4.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-save
                "ca_tokmap.hip": ["-save-temps=obj"],   # (read for spills below)
                # (the same; contraction stays on for ca_heatmap_core.h's weighting, the unit's own sums switch it off)
                "ca_headmap.hip": ["-save-temps=obj"],
-               "ca_querymap.hip": ["-save-temps=obj"]}   # (read for spills below)
+               "ca_querymap.hip": ["-save-temps=obj"],   # (read for spills below)
+               "ca_propmap.hip": ["-save-temps=obj"]}    # (the same)
 HEADERS = ["ca_common.h", "ca_attn_common.h", "ca_attn4_sched.inc", "ca_attn4_kernel.inc", "ca_seg_core.h",
-           "ca_text_core.h", "ca_heatmap_core.h", "ca_tokmap.h", "ca_headmap.h", "ca_querymap.h", "ca_qkmap_core.h"]
+           "ca_text_core.h", "ca_heatmap_core.h", "ca_tokmap.h", "ca_headmap.h", "ca_querymap.h", "ca_qkmap_core.h",
+           "ca_propmap.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function"]
 
@@ -159,6 +161,14 @@ def audit_querymap(asm_path: str) -> None:
     eight running head sums in registers, qm_stats_kernel a q fragment and two key fragments, all indexed by unrolled
     loops.  Every kernel of the unit must report no spill and no scratch."""
     _audit_no_spill("ca_querymap", asm_path)
+
+
+def audit_propmap(asm_path: str) -> None:
+    """pm_attn_kernel keeps the q fragments of four groups of 16 query rows (64 registers), a key fragment and the next
+    tile's (32), two tiles' map values (16), and per group of rows a running maximum, a running sum and two accumulators of
+    16 concepts (40 in all) in registers, all indexed by unrolled loops under wave-uniform branches.  Every kernel of the
+    unit must report no spill and no scratch."""
+    _audit_no_spill("ca_propmap", asm_path)
 
 
 def audit_sgpr_hazards(text: str) -> list:
@@ -421,6 +431,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     audit_tokmap(os.path.join(HERE, "ca_tokmap-hip-amdgcn-amd-amdhsa-gfx950.s"))
     audit_headmap(os.path.join(HERE, "ca_headmap-hip-amdgcn-amd-amdhsa-gfx950.s"))
     audit_querymap(os.path.join(HERE, "ca_querymap-hip-amdgcn-amd-amdhsa-gfx950.s"))
+    audit_propmap(os.path.join(HERE, "ca_propmap-hip-amdgcn-amd-amdhsa-gfx950.s"))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
     if verbose:
         print(" ".join(cmd), flush=True)

@@ -190,6 +190,12 @@ class HeatmapRequest:
     head_normalize_concepts: bool = False
     # the same spaces under further norms in the same forward: HeatmapRequests of which only these head-map fields are read
     head_more: tuple = ()
+    # propagated concept maps (ops.propagate_maps): per captured layer the layer's own concept map of a space -- the map
+    # that layer adds, times ``weight``, into out_space / cross_space -- carried ``prop_steps`` times (1 .. 4) through the
+    # head mean of the image rows' softmax over the image keys, then added with ``weight``.  fp32 [C, L]; None: no launch
+    prop_out: Optional[torch.Tensor] = None
+    prop_cross: Optional[torch.Tensor] = None
+    prop_steps: int = 1
 
     def query_kinds(self) -> tuple:
         """The query-row maps this request asks for, as (kind, accumulator, per-layer table)."""
@@ -203,6 +209,11 @@ class HeatmapRequest:
                                                ("cross", self.heads_cross, self.raw_cross),
                                                ("value", self.heads_value, self.raw_value))
                      if h is not None or r is not None)
+
+    def prop_spaces(self) -> tuple:
+        """The spaces this request asks propagated maps of, as (name, accumulator, the space's per-layer table)."""
+        return tuple((n, a, t) for n, a, t in (("output", self.prop_out, self.per_layer_out),
+                                               ("cross", self.prop_cross, self.per_layer_cross)) if a is not None)
 
     def head_requests(self) -> tuple:
         """This request and those of ``head_more`` that ask for head maps: one (spaces, norm, normalisation) each."""
@@ -632,6 +643,7 @@ class HipFluxDiT:
         assert concept_vec is not None, "Concept vectors must be provided for this implementation."
         heads_out = self._check_head_maps(heatmaps, return_vectors, joint_attention_kwargs)
         self._check_query_maps(heatmaps, joint_attention_kwargs)
+        self._check_propagated(heatmaps, return_vectors, concepts)
         if trace is not None:
             if trace.filled:
                 raise ValueError("trace: an empty StepTrace per forward (this one is already filled)")
@@ -693,6 +705,32 @@ class HipFluxDiT:
             raise ValueError("query maps: the ablation joint_attention_kwargs (concept_cross_attention / "
                              "concept_self_attention = False) change the concept rows' key set and are not covered by the "
                              "concept rows' query maps")
+
+    def _check_propagated(self, heatmaps, return_vectors, concepts) -> None:
+        """The settings propagated maps do not cover, raised before anything is launched."""
+        reqs = () if heatmaps is None else heatmaps if isinstance(heatmaps, (list, tuple)) else [heatmaps]
+        reqs = [h for h in reqs if h.prop_spaces()]
+        if not reqs:
+            return
+        if return_vectors:
+            raise ValueError("propagated maps: a forward with propagated maps takes return_vectors=False (the stacked route "
+                             "has no launch for them)")
+        C = concepts.shape[1]
+        if not 1 <= C <= L.PROPMAP_MAX_CONCEPTS:
+            raise ValueError(f"propagated maps: {C} concepts; 1 .. {L.PROPMAP_MAX_CONCEPTS} per item")
+        for h in reqs:
+            if not isinstance(h.prop_steps, int) or not 1 <= h.prop_steps <= 4:
+                raise ValueError(f"propagated maps: prop_steps = {h.prop_steps!r}; an int in 1 .. 4")
+            for name, acc, table in h.prop_spaces():
+                if (h.out_space if name == "output" else h.cross_space) is None:
+                    raise ValueError(f"propagated maps: the {name} space's concept maps are not computed by this request "
+                                     "(the propagation starts from the map the layer adds into out_space / cross_space)")
+                if table is not None:
+                    raise ValueError(f"propagated maps: the {name} space also has a per-layer table (the heat-map launch's "
+                                     "second accumulator carries the layer's map to the propagation; the sweeps are not covered)")
+                if acc.dtype != torch.float32 or acc.dim() != 2 or acc.shape[0] != C or not acc.is_contiguous():
+                    raise ValueError(f"propagated maps: prop_{'out' if name == 'output' else 'cross'} must be contiguous fp32 "
+                                     f"[C = {C}, L], got {tuple(acc.shape)} {acc.dtype}")
 
     def _check_traceable(self, what: str, joint_attention_kwargs=None) -> None:
         """The settings a trace and a re-query do not cover, each named; raised before anything is launched."""
@@ -1216,6 +1254,58 @@ class HipFluxDiT:
             _launch_apart(probs, lambda pr: (pr.heads, pr.acc), lambda batch, norm=norm: ops.head_maps(batch, NH, norm),
                           L.HEATMAP_MAX_PROBLEMS)
 
+    def _prop_buffer(self, key, C, Li):
+        """One of the propagated maps' fp32 [C, L] model buffers (allocated on first use, kept for the next forward),
+        zeroed on the stream."""
+        bufs = self.__dict__.setdefault("_prop_bufs", {})
+        t = bufs.get(key)
+        if t is None or tuple(t.shape) != (C, Li):
+            t = bufs[key] = torch.empty(C, Li, device=self.device, dtype=torch.float32)
+        return t.zero_()
+
+    def _propagated_sources(self, layer, g, heatmaps) -> dict:
+        """{(item, space): zeroed fp32 [C, L] model buffer} for every item and space that asks for propagated maps in this
+        layer: _heatmap_updates leaves the layer's own map there.  Empty, and nothing launched, when no item asks."""
+        self._prop_layer = {}
+        for j in range(g.B if heatmaps is not None else 0):
+            hm = heatmaps[j]
+            if layer in hm.layer_indices:
+                for space, _, _ in hm.prop_spaces():
+                    self._prop_layer[j, space] = self._prop_buffer((j, space, "map"), g.C, g.L)
+        return self._prop_layer
+
+    def _capture_propagated(self, layer, g, NH, heatmaps, route):
+        """The propagated maps of a captured layer: prop += weight * (A^n . map), with map the layer's own concept map
+        (_propagated_sources: what _heatmap_updates has just added, times weight, into out_space / cross_space) and A the
+        head mean of the image rows' softmax over the image keys ONLY (row-stochastic: a constant map stays constant), over
+        the q and k rows this layer's joint attention problems have just read (QKV still holds them; the rows
+        _capture_token_maps reads, which carry Q_OUT_SCALE, so scale_log2 = 1).  n = prop_steps launches per item and
+        space: step s < n goes into one of two zeroed scratch buffers at weight 1, the last one into prop at hm.weight;
+        all items and both spaces of a step share one ops.propagate_maps call.  No launch when no item asks."""
+        sources = self._prop_layer
+        if not sources:
+            return
+        H, Li, oI = self.hidden_size, g.L, g.oI
+        qs, ks = self.QKV[:, :H], self.QKV[:, H:2 * H]
+        steps = max(heatmaps[j].prop_steps for j, _ in sources)
+        cur = dict(sources)
+        for s in range(steps):
+            probs = []
+            for (j, space), src in cur.items():
+                hm = heatmaps[j]
+                if s >= hm.prop_steps:
+                    continue
+                ij = slice(oI + j * Li, oI + (j + 1) * Li)
+                if s == hm.prop_steps - 1:
+                    dst, w = (hm.prop_out if space == "output" else hm.prop_cross), hm.weight
+                else:
+                    dst, w = self._prop_buffer((j, space, s & 1), g.C, Li), 1.0
+                    cur[j, space] = dst
+                probs.append(ops.PropagateMaps(qs[ij], None, ks[ij], src, acc=dst, weight=w))
+            _launch_apart(probs, lambda pr: (pr.acc,), lambda batch: ops.propagate_maps(
+                batch, NH, 1.0, qk_f16=route.qk16, workspace=self._maps_workspace(
+                    "_propmap_ws", ops.propagate_maps_workspace_bytes(batch, NH))), L.PROPMAP_MAX_PROBLEMS)
+
     def _token_maps_workspace(self, probs, NH):
         """ops.token_maps' scratch memory (none today: the head sum lives in LDS)."""
         return self._maps_workspace("_tokmap_ws", ops.token_maps_workspace_bytes(probs, NH))
@@ -1233,7 +1323,8 @@ class HipFluxDiT:
             cj, ij = slice(j * C, (j + 1) * C), slice(oI + j * Li, oI + (j + 1) * Li)
             img_out = None if route.use_part else self.ATTI32[j, g.T:]   # (a layer with maps has use_part or f32img)
             return ((img_out, self.ATT32[cj], self.PART[j] if route.use_part else None), (QPRE[ij], QPRE[cj], None))
-        self._heatmap_updates(layer, C, heatmaps, operands, self.LOGITS)
+        self._heatmap_updates(layer, C, heatmaps, operands, self.LOGITS, self._propagated_sources(layer, g, heatmaps))
+        self._capture_propagated(layer, g, NH, heatmaps, route)
         self._capture_token_maps(layer, g, NH, heatmaps, route)
         self._capture_query_maps(layer, g, NH, heatmaps, route)
         self._capture_head_maps(layer, g, NH, heatmaps)
@@ -1252,11 +1343,14 @@ class HipFluxDiT:
             out["cross_attention_image_vectors"].append(
                 QPRE[oI:].view(B, Li, NH, 128).permute(0, 2, 1, 3).to(torch.bfloat16, memory_format=cf, copy=True))
 
-    def _heatmap_updates(self, layer, C, heatmaps, operands, logits):
+    def _heatmap_updates(self, layer, C, heatmaps, operands, logits, layer_maps=None):
         """The heat-map updates of one captured layer for every work item whose request names it.  ``operands(j)``: item
         j's (image vectors, concept vectors, per-head partial logits or None) of the output space and of the
         cross-attention space -- the forward's own buffers, or in a re-query the image side a trace kept; ``logits``: fp32
-        [>= C, L] scratch of the three-launch form."""
+        [>= C, L] scratch of the three-launch form.  ``layer_maps``: {(item, space): zeroed fp32 [C, L]} that receives the
+        layer's own map of that space as the launch's second accumulator at weight 1 (fma(1, x, 0) is x: the bits the first
+        accumulator is given; such a space has no per-layer table, _check_propagated)."""
+        layer_maps = layer_maps or {}
         # one launch per layer: ca_heatmap_fused up to 8 concepts, ca_heatmap_many for 9 .. 32 (the concept vectors through
         # LDS in chunks; its image vectors are the fp32 rows ATTI32, as use_part needs C <= 8); the three-launch form
         # otherwise (fused_heatmaps = False, the parity reference, or more than 32 concepts with the softmax)
@@ -1272,22 +1366,24 @@ class HipFluxDiT:
                 continue
             li = hm.layer_indices.index(layer)
             (img_out, con_out, part), (img_q, con_q, _) = operands(j)
-            for img_vec, con_vec, acc, table in ((img_out, con_out, hm.out_space, hm.per_layer_out),
-                                                 (img_q, con_q, hm.cross_space, hm.per_layer_cross)):
+            for space, img_vec, con_vec, acc, table in (("output", img_out, con_out, hm.out_space, hm.per_layer_out),
+                                                        ("cross", img_q, con_q, hm.cross_space, hm.per_layer_cross)):
                 if acc is None and table is None:
                     continue
+                second, w2 = (None if table is None else table[li]), hm.per_layer_weight
+                if (j, space) in layer_maps:
+                    second, w2 = layer_maps[j, space], 1.0
                 if fused:
                     launches.setdefault(hm.norm, []).append(ops.Heatmap(
-                        img_vec, None if img_vec is None else con_vec, acc, hm.weight,
-                        None if table is None else table[li], hm.per_layer_weight,
+                        img_vec, None if img_vec is None else con_vec, acc, hm.weight, second, w2,
                         part=part if img_vec is None else None))
                     continue
                 # the three-launch form (more than 32 concepts, or fused_heatmaps = False: the parity reference)
                 ops.heatmap_logits(img_vec, con_vec, logits[:C])
                 if acc is not None:
                     ops.heatmap_norm_accumulate(logits[:C], acc, hm.weight, hm.norm)
-                if table is not None:
-                    ops.heatmap_norm_accumulate(logits[:C], table[li], hm.per_layer_weight, hm.norm)
+                if second is not None:
+                    ops.heatmap_norm_accumulate(logits[:C], second, w2, hm.norm)
         for norm, probs in launches.items():        # one launch per norm
             _launch_apart(probs, lambda pr: (pr.acc, pr.acc2), lambda batch, norm=norm: launch(batch, norm),
                           L.HEATMAP_MAX_PROBLEMS)
@@ -1336,6 +1432,8 @@ class HipFluxDiT:
                 raise ValueError("requery: token maps are not part of a re-query (the text side has not changed)")
             if h.query_kinds():
                 raise ValueError("requery: query-row maps are not part of a re-query (ask for them in the forward)")
+            if h.prop_spaces():
+                raise ValueError("requery: propagated maps are not part of a re-query (a trace keeps no image q rows)")
             if h.head_requests():
                 raise ValueError("requery: per-head maps are not part of a re-query yet (ask for them in the forward)")
             missing = [l for l in h.layer_indices if l not in t.layers]

@@ -654,7 +654,7 @@ class TokenMaps:
 
 def _qk_maps_array(FN: str, struct, problems, num_heads: int, optional: str, missing: Optional[str], sizes,
                    one_row_strides: bool):
-    """The argument checks of ops.token_maps and ops.query_maps (no device needed for the shape rules) and their problem
+    """The argument checks of ops.token_maps, ops.query_maps and ops.propagate_maps (no device needed for the shape rules) and their problem
     array of ``struct``.  What differs between the two is data.  ``optional``: the key segment, "k0" or "k1", that may be
     None or empty; the other one is required, and ``missing`` is the text for it being None (None: left to _chk).
     ``sizes(t, nq, n0, n1)``: the op's size rule: the accumulators' shape, the (name, value) struct fields only this op
@@ -695,7 +695,7 @@ def _qk_maps_array(FN: str, struct, problems, num_heads: int, optional: str, mis
             raise ValueError(f"{FN}[{i}]: every problem needs acc or acc2")
         p = arr[i]
         for name, shape in (("acc", acc_shape), ("acc2", acc_shape), ("lse", (num_heads, nq))):
-            x = getattr(t, name)
+            x = getattr(t, name, None)    # (ops.PropagateMaps has no lse)
             if x is None:
                 continue
             _chk(x, torch.float32, name)
@@ -848,6 +848,98 @@ def query_maps(problems: Sequence[QueryMaps], num_heads: int, scale_log2: float 
     for sub, n in _launch_slices(arr, L.QuerymapProblem, L.QUERYMAP_MAX_PROBLEMS):
         L.check(lib.ca_query_maps(sub, n, _i32(num_heads, "num_heads"), float(scale_log2), flags, ws_ptr, ws_bytes,
                                   _stream()), "ca_query_maps")
+
+
+@dataclass
+class PropagateMaps:
+    """One problem of a map propagation launch (ca_propagate_maps): the rows of ``v`` (fp32 [C, n1], one value per row of
+    ``k1``) carried through the attention of the rows of ``q`` over the keys [k0 | k1], averaged over the heads:
+    out[c, i] = mean_h sum_j softmax_j(<q_h[i], k_h[j]>)[n0 + j] * v[c, j], then acc += weight * out and / or
+    acc2 += weight2 * out.  q / k0 / k1 bf16 2-D views [rows, num_heads*128] (row stride free, k0 and k1 share theirs; k0
+    may be None: no leading keys, and the weights of a row then sum to 1), v fp32 [C, n1] (row stride free, at least n1),
+    acc / acc2 fp32 [C, nq] contiguous.  v may not overlap an accumulator of any problem of the call."""
+    q: torch.Tensor
+    k0: Optional[torch.Tensor] = None
+    k1: Optional[torch.Tensor] = None
+    v: Optional[torch.Tensor] = None
+    acc: Optional[torch.Tensor] = None
+    weight: float = 0.0
+    acc2: Optional[torch.Tensor] = None
+    weight2: float = 0.0
+
+
+def _propagate_sizes(t: PropagateMaps, nq: int, n0: int, n1: int):
+    if t.v is None:
+        return (0, nq), (), "v, the map rows to propagate, is required"
+    _chk(t.v, torch.float32, "v")
+    if t.v.dim() != 2 or t.v.shape[1] != n1:
+        return (0, nq), (), f"v must be 2-D fp32 [C, n1 = {n1}], got {tuple(t.v.shape)}"
+    Cc = t.v.shape[0]
+    if not 1 <= Cc <= L.PROPMAP_MAX_CONCEPTS or nq < 1 or n1 < 1 or n0 + n1 > L.PROPMAP_MAX_ROWS:
+        return (Cc, nq), (), (f"need 1 <= C <= {L.PROPMAP_MAX_CONCEPTS}, nq >= 1, n1 >= 1 and n0 + n1 <= {L.PROPMAP_MAX_ROWS}, "
+                              f"got C = {Cc}, nq = {nq}, n0 = {n0}, n1 = {n1}")
+    ldv = _i32(t.v.stride(0), "ldv")
+    if Cc == 1:                     # (the row stride of a one-row tensor is free in torch)
+        ldv = max(ldv, n1)
+    if ldv < n1:
+        return (Cc, nq), (), f"v's row stride {ldv} is below n1 = {n1}"
+    if t.v.data_ptr() % 4:
+        return (Cc, nq), (), "v must be 4-byte aligned"
+    return (Cc, nq), (("v", t.v.data_ptr()), ("C", Cc), ("ldv", ldv)), False
+
+
+def _propagate_maps_array(problems: Sequence[PropagateMaps], num_heads: int):
+    """ops.propagate_maps' argument checks (no device needed for the shape rules) and the problem array."""
+    arr = _qk_maps_array("propagate_maps", L.PropmapProblem, problems, num_heads, optional="k0",
+                         missing="k1, the valued key rows, is required", sizes=_propagate_sizes, one_row_strides=True)
+    # the kernel reads v while cells are written: no v may overlap an accumulator of the call
+    outs = [(x.data_ptr(), x.data_ptr() + 4 * x.numel(), j, name) for j, t in enumerate(problems)
+            for name, x in (("acc", t.acc), ("acc2", t.acc2)) if x is not None]
+    for i, (t, p) in enumerate(zip(problems, arr)):
+        lo, hi = t.v.data_ptr(), t.v.data_ptr() + 4 * ((p.C - 1) * p.ldv + p.n1)
+        for a, b, j, name in outs:
+            if lo < b and a < hi:
+                raise ValueError(f"propagate_maps[{i}]: v overlaps {name} of problem {j} of this call (the kernel reads v "
+                                 "while the cells are written)")
+    return arr
+
+
+def _propagate_maps_need(arr, num_heads: int) -> int:
+    return _maps_workspace_bytes("ca_propagate_maps_workspace_bytes", arr, L.PropmapProblem, L.PROPMAP_MAX_PROBLEMS, num_heads)
+
+
+def propagate_maps_workspace_bytes(problems: Sequence[PropagateMaps], num_heads: int) -> int:
+    """The scratch memory one ops.propagate_maps call over these problems needs (the largest of its launches): 4 bytes
+    per (head, map row, query row)."""
+    L.load()
+    if len(problems) < 1:
+        raise ValueError("propagate_maps_workspace_bytes: at least one problem")
+    return _propagate_maps_need(_propagate_maps_array(problems, num_heads), num_heads)
+
+
+def propagate_maps(problems: Sequence[PropagateMaps], num_heads: int, scale_log2: float = 1.0, qk_f16: bool = False,
+                   workspace: Optional[torch.Tensor] = None) -> None:
+    """Map rows propagated through the query rows' attention (ca_propagate_maps), up to L.PROPMAP_MAX_PROBLEMS problems per
+    launch pair (longer lists are split, in order; the launches of one call share the workspace, which stream order makes
+    safe).  ``scale_log2``: 1.0 for q rows that already carry softmax_scale * log2(e) (the model's), otherwise
+    softmax_scale * log2(e).  ``qk_f16``: the q and k rows hold IEEE half bits in their bf16-typed tensors (Gemm.qk_f16).
+    ``workspace``: a uint8 device tensor of at least propagate_maps_workspace_bytes() bytes, 16-byte aligned; None: one is
+    allocated from torch's caching allocator (not under graph capture: pass one there)."""
+    lib = L.load()
+    if len(problems) < 1:
+        raise ValueError("propagate_maps: at least one problem")
+    if not num_heads >= 1:
+        raise ValueError("propagate_maps: num_heads must be >= 1")
+    if not math.isfinite(scale_log2):
+        raise ValueError("propagate_maps: scale_log2 must be finite")
+    arr = _propagate_maps_array(problems, num_heads)
+    if workspace is None:
+        workspace = torch.empty(_propagate_maps_need(arr, num_heads), dtype=torch.uint8, device=problems[0].q.device)
+    ws_ptr, ws_bytes = _maps_workspace_arg("propagate_maps", workspace)
+    flags = L.PROPMAP_QK_F16 if qk_f16 else 0
+    for sub, n in _launch_slices(arr, L.PropmapProblem, L.PROPMAP_MAX_PROBLEMS):
+        L.check(lib.ca_propagate_maps(sub, n, _i32(num_heads, "num_heads"), float(scale_log2), flags, ws_ptr, ws_bytes,
+                                      _stream()), "ca_propagate_maps")
 
 
 @dataclass

@@ -53,8 +53,14 @@ class ConceptAttentionPipelineOutput:
     # the image (ops.query_maps), keyed by kind; "words" beside "tokens" when the call has the token strings.  fp32 device
     # tensors (n, h, w) with return_pil_heatmaps=False, lists of PIL pictures otherwise (one min-max per item and kind)
     query_heatmaps: Optional[dict] = None
+    # propagate="output" | "cross" (or both): per space the concept maps carried through the image rows' own attention
+    # (ops.propagate_maps): every captured layer's map replaced by the attention-weighted mean of the patches each patch
+    # attends to, mean over heads, layers and steps.  fp32 device tensors (C, h, w) with return_pil_heatmaps=False, lists
+    # of PIL pictures otherwise (one min-max per item and space)
+    propagated_heatmaps: Optional[dict] = None
 
 
+PROPAGATE_SPACES = {"output": "prop_out", "cross": "prop_cross"}   # space -> its HeatmapRequest field
 QUERY_KINDS = ("tokens", "concepts")
 HEAD_SPACES = {"output": ("heads_out", "raw_out"), "cross": ("heads_cross", "raw_cross"),
                "value": ("heads_value", "raw_value")}   # space -> its two HeatmapRequest fields
@@ -99,6 +105,15 @@ def query_request_fields(query_acc, j: int) -> dict:
     """The HeatmapRequest keywords of item j's query-row accumulators (a dict kind -> fp32 [n, patches], or None)."""
     acc = {} if query_acc is None or query_acc[j] is None else query_acc[j]
     return dict(token_query_space=acc.get("tokens"), concept_query_space=acc.get("concepts"))
+
+
+def propagate_request_fields(prop_acc, j: int) -> dict:
+    """The HeatmapRequest keywords of item j's propagated-map accumulators ((dict space -> fp32 [C, patches], steps), or
+    None)."""
+    if prop_acc is None or prop_acc[j] is None:
+        return {}
+    acc, steps = prop_acc[j]
+    return dict(prop_steps=steps, **{PROPAGATE_SPACES[space]: t for space, t in acc.items()})
 
 
 @dataclass
@@ -375,6 +390,36 @@ class ConceptAttentionFluxPipeline:
             acc.append(d)
         return acc
 
+    # ------------------------------------------------------------------ propagated maps
+    @staticmethod
+    def _propagate_spaces(propagate) -> tuple:
+        """The spaces a call's ``propagate`` argument names, in PROPAGATE_SPACES' order; () for None / False."""
+        if propagate is None or propagate is False:
+            return ()
+        spaces = (propagate,) if isinstance(propagate, str) else tuple(propagate)
+        if not spaces or len(set(spaces)) != len(spaces) or any(s not in PROPAGATE_SPACES for s in spaces):
+            raise ValueError(f"propagate = {propagate!r}: one of {list(PROPAGATE_SPACES)} or a tuple of distinct ones (the "
+                             "spaces whose concept maps the call computes)")
+        return tuple(s for s in PROPAGATE_SPACES if s in spaces)
+
+    def _propagate_plan(self, propagate, propagate_steps, concept_counts, n_patches, fused: bool = True):
+        """prop_acc of a call's ``propagate`` / ``propagate_steps`` arguments: per item (dict space -> zeroed fp32
+        [C, n_patches[i]] accumulator, steps); None when no propagated maps are asked for.  ValueError, before anything
+        is launched, for an unknown space, steps outside 1 .. 4, an item without concepts or with more than the kernel
+        takes, and the stacked route (fused=False keeps no q / k rows to propagate through)."""
+        spaces = self._propagate_spaces(propagate)
+        if not spaces:
+            return None
+        if not isinstance(propagate_steps, int) or isinstance(propagate_steps, bool) or not 1 <= propagate_steps <= 4:
+            raise ValueError(f"propagate_steps = {propagate_steps!r}: an int in 1 .. 4")
+        if not fused:
+            raise ValueError("propagate needs the fused route (fused=True)")
+        for C in concept_counts:
+            if not 1 <= C <= _lib.PROPMAP_MAX_CONCEPTS:
+                raise ValueError(f"propagate: {C} concepts; 1 .. {_lib.PROPMAP_MAX_CONCEPTS} per item")
+        return [({s: torch.zeros(C, p, device=self.device) for s in spaces}, propagate_steps)
+                for C, p in zip(concept_counts, n_patches)]
+
     # ------------------------------------------------------------------ per-head maps
     def _head_plan(self, head_maps, head_norm, concept_counts, n_patches, normalize_concepts: bool = False):
         """head_acc of a call's ``head_maps`` / ``head_norm`` arguments: per item a ``HeadMapAccumulators`` with zeroed
@@ -422,18 +467,18 @@ class ConceptAttentionFluxPipeline:
                 heatmap_interpolation, overlay_alpha)
 
     def _chunk_outputs(self, idx, images, concept_heatmaps, cross_attention_maps, show, token_acc=None, tokens=None,
-                       pictures=None, head_acc=None, query_acc=None) -> list:
+                       pictures=None, head_acc=None, query_acc=None, prop_acc=None) -> list:
         """The one way out of every call: the ConceptAttentionPipelineOutput of the items ``idx`` of a call after their
         forward.  ``images``: what ``image`` becomes; the two maps [len(idx), C, side, side] on the device; ``show``:
         ``_device_renderer``'s tuple; ``token_acc`` / ``tokens``: the call's (``_token_plan``); ``pictures``: with an
         overlay, the chunk's uint8 [H, W, 3] device tensors the maps are laid over; ``head_acc``: the call's
-        (``_head_plan``); ``query_acc``: the call's (``_query_plan``)."""
+        (``_head_plan``); ``query_acc``: the call's (``_query_plan``); ``prop_acc``: the call's (``_propagate_plan``)."""
         on_device, return_pil_heatmaps, cmap, heatmap_size, heatmap_interpolation, overlay_alpha = show
         grid = tuple(concept_heatmaps.shape[-2:])
         tok = [None if token_acc is None else token_acc[i].view(-1, *grid) for i in idx]
         tokens = [None if tokens is None else tokens[i] for i in idx]
         # the word maps and the query-row maps: per item, name -> fp32 [n, side, side] on the device ("word": the summed
-        # token maps; "q:<kind>": a kind of query_heatmaps)
+        # token maps; "q:<kind>": a kind of query_heatmaps; "p:<space>": a space of propagated_heatmaps)
         extras, words = [{} for _ in idx], [None] * len(idx)
         for k, i in enumerate(idx):
             groups = None
@@ -445,6 +490,8 @@ class ConceptAttentionFluxPipeline:
                 extras[k]["q:" + kind] = acc.view(-1, *grid)
                 if kind == "tokens" and groups is not None:
                     extras[k]["q:words"] = word_maps(extras[k]["q:tokens"], groups)
+            for space, acc in (prop_acc[i][0] if prop_acc is not None and prop_acc[i] else {}).items():
+                extras[k]["p:" + space] = acc.view(-1, *grid)
         if on_device:
             outs = self._finish_device(images, concept_heatmaps, cross_attention_maps, cmap, heatmap_size,
                                        heatmap_interpolation, overlay_alpha, pictures, tok, tokens, extras)
@@ -470,6 +517,9 @@ class ConceptAttentionFluxPipeline:
         """An extra map set of ``_chunk_outputs`` into its output field."""
         if name == "word":
             out.word_heatmaps = maps
+        elif name.startswith("p:"):
+            out.propagated_heatmaps = dict(out.propagated_heatmaps or {})
+            out.propagated_heatmaps[name[2:]] = maps
         else:
             out.query_heatmaps = dict(out.query_heatmaps or {})
             out.query_heatmaps[name[2:]] = maps
@@ -581,7 +631,8 @@ class ConceptAttentionFluxPipeline:
                        fused: bool = True, heatmap_renderer: str = "host", heatmap_size=None,
                        heatmap_interpolation: str = "nearest", overlay_alpha=None,
                        token_maps=None, keep_trace: bool = False, head_maps=None, head_norm=None,
-                       head_normalize_concepts: bool = False, query_maps=None) -> ConceptAttentionPipelineOutput:
+                       head_normalize_concepts: bool = False, query_maps=None, propagate=None,
+                       propagate_steps: int = 1) -> ConceptAttentionPipelineOutput:
         """``latent`` (1,16,h/8,w/8) overrides get_noise (device RNG differs between platforms);
         ``fused=False`` takes the reference's route (stack the per-layer vectors, then reduce).
         ``heatmap_renderer="device"`` makes the PIL heat maps on the device (ops.heatmap_render; the same bytes as
@@ -612,6 +663,8 @@ class ConceptAttentionFluxPipeline:
             raise ValueError("keep_trace needs the fused route: fused=False stacks the vectors and keeps no image side")
         if head_maps and not fused:
             raise ValueError("head_maps needs the fused route (fused=True)")
+        if self._propagate_spaces(propagate) and not fused:
+            raise ValueError("propagate needs the fused route (fused=True)")
         if fused:   # (repeated timestep or layer indices still end on the stacked route: _generate_steps_inner)
             return self.generate_images(
                 [prompt], [concepts], seeds=[seed], latents=None if latent is None else [latent], width=width, height=height,
@@ -620,7 +673,8 @@ class ConceptAttentionFluxPipeline:
                 softmax=softmax, attention_norm=attention_norm, heatmap_renderer=heatmap_renderer, heatmap_size=heatmap_size,
                 heatmap_interpolation=heatmap_interpolation, overlay_alpha=overlay_alpha, token_maps=token_maps,
                 keep_trace=keep_trace, head_maps=head_maps, head_norm=head_norm,
-                head_normalize_concepts=head_normalize_concepts, query_maps=query_maps)[0]
+                head_normalize_concepts=head_normalize_concepts, query_maps=query_maps, propagate=propagate,
+                propagate_steps=propagate_steps)[0]
         norm = self._generate_norm(return_cross_attention, layer_indices, height, width, softmax, attention_norm)
         check_concept_count(norm, len(concepts))
         show = self._device_renderer(return_pil_heatmaps, cmap, heatmap_renderer, heatmap_size, heatmap_interpolation,
@@ -708,16 +762,18 @@ class ConceptAttentionFluxPipeline:
     @on_own_device
     def generate_on_device(self, latent, txt, vec, concept_embeddings, layer_indices=list(range(15, 19)),
                            num_inference_steps: int = 4, guidance: float = 0.0, timesteps=None, fused: bool = True,
-                           norm: int = 0, token_acc=None, traces: Optional[dict] = None, head_acc=None, query_acc=None):
+                           norm: int = 0, token_acc=None, traces: Optional[dict] = None, head_acc=None, query_acc=None,
+                           prop_acc=None):
         """``token_acc``: per item, an fp32 [n_tok, patches] accumulator of the caller's for the prompt-token maps (zeroed
         by the caller; None, or None for an item: no token maps).  ``traces``: a dict of the caller's that receives step
         index -> the ``StepTrace`` of every step in ``timesteps`` (fused route only).  ``head_acc``: per item, the
         caller's ``HeadMapAccumulators`` (or None).  ``query_acc``: per item, a dict kind ("tokens" | "concepts") -> the caller's
-        zeroed fp32 [n, patches] accumulator of that kind's query-row maps (or None).  The return tuple is the same with and
-        without any of them."""
+        zeroed fp32 [n, patches] accumulator of that kind's query-row maps (or None).  ``prop_acc``: per item, (dict space
+        ("output" | "cross") -> the caller's zeroed fp32 [C, patches] accumulator of that space's propagated maps, steps), or
+        None.  The return tuple is the same with and without any of them."""
         gen = self._generate_steps(self.model, latent, txt, vec, concept_embeddings, layer_indices,
                                    num_inference_steps, guidance, timesteps, fused, norm, token_acc, traces, head_acc,
-                                   query_acc)
+                                   query_acc, prop_acc)
         while True:
             try:
                 next(gen)
@@ -726,7 +782,8 @@ class ConceptAttentionFluxPipeline:
 
     def _generate_steps(self, model, latent, txt, vec, concept_embeddings, layer_indices=list(range(15, 19)),
                         num_inference_steps: int = 4, guidance: float = 0.0, timesteps=None, fused: bool = True,
-                        norm: int = 0, token_acc=None, traces: Optional[dict] = None, head_acc=None, query_acc=None):
+                        norm: int = 0, token_acc=None, traces: Optional[dict] = None, head_acc=None, query_acc=None,
+                        prop_acc=None):
         """The device-resident core of generate_image for B work items at once (B = 1 from the public API):
         latent (B,16,h/8,w/8), txt (B,T,4096), vec (B,768), concept_embeddings (B,C,4096) already in HBM ->
         (final latent tokens, concept heat maps fp32 [B,C,side,side], cross-attention maps fp32
@@ -756,13 +813,13 @@ class ConceptAttentionFluxPipeline:
         try:
             return (yield from self._generate_steps_inner(model, x, inp, con, con_ids, con_vec, schedule, ts, ls,
                                                           C, n_patches, guidance, layer_indices, timesteps, fused,
-                                                          norm, token_acc, traces, head_acc, query_acc))
+                                                          norm, token_acc, traces, head_acc, query_acc, prop_acc))
         finally:
             model.keep_bf16_layers = keep_before  # this call's choice does not leak into later sweeps / encodes
 
     def _generate_steps_inner(self, model, x, inp, con, con_ids, con_vec, schedule, ts, ls, C, n_patches, guidance,
                               layer_indices, timesteps, fused, norm=0, token_acc=None, traces=None, head_acc=None,
-                              query_acc=None):
+                              query_acc=None, prop_acc=None):
         names = {v: k for k, v in _lib.NORMS.items()}
         # repeated indices weigh a (step, layer) pair repeatedly in the reference's fancy indexing
         # (concept_attention_pipeline.py:76-77); the fused accumulation covers distinct pairs only
@@ -786,12 +843,18 @@ class ConceptAttentionFluxPipeline:
                 raise ValueError("query_maps needs the fused route (fused=True, distinct timesteps and layer indices)")
             if len(query_acc) != B:
                 raise ValueError("query_acc: one dict of accumulators (or None) per work item")
+        if prop_acc is not None and any(prop_acc):
+            if not fused:
+                raise ValueError("propagate needs the fused route (fused=True, distinct timesteps and layer indices)")
+            if len(prop_acc) != B:
+                raise ValueError("prop_acc: one (dict of accumulators, steps) (or None) per work item")
         if fused:
             acc_o = torch.zeros(B, C, n_patches, device=self.device)
             acc_c = torch.zeros(B, C, n_patches, device=self.device)
             reqs = [HeatmapRequest(tuple(ls), 1.0 / (len(ts) * len(ls)), acc_o[j], acc_c[j], norm=norm,
                                    token_space=None if token_acc is None else token_acc[j],
-                                   **head_request_fields(head_acc, j), **query_request_fields(query_acc, j))
+                                   **head_request_fields(head_acc, j), **query_request_fields(query_acc, j),
+                                   **propagate_request_fields(prop_acc, j))
                     for j in range(B)]
             img, _, _ = yield from sampling.denoise_steps(
                 model, **inp, timesteps=schedule, guidance=guidance, concepts=con, concept_ids=con_ids,
@@ -867,14 +930,17 @@ class ConceptAttentionFluxPipeline:
     @on_own_device
     def layer_noise_sweep(self, image, concepts: list, prompt: str, noise_levels, num_steps: int = 50, layer_indices=None,
                           num_samples: int = 1, seed: int = 0, width: int = 1024, height: int = 1024, batch: int = 5,
-                          vae_noise=None, query_maps=None):
+                          vae_noise=None, query_maps=None, propagate=None):
         """``layer_noise_sweep_on_device`` from an image and strings: ``image`` is a latent tensor (1,16,h/8,w/8) or, with
         an autoencoder in the pipeline, a PIL image (``vae_noise`` (1,16,h/8,w/8): its sampling noise, drawn on the
         device when not given); ``concepts`` and ``prompt`` go through the text encoders as in ``encode_image``.
         Returns the two DEVICE tables (out_space, cross_space), fp32 [len(noise_levels), len(layer_indices), C, side,
-        side]; ``batch`` levels share one forward.  ``query_maps``: refused (the tables hold the concept maps only)."""
+        side]; ``batch`` levels share one forward.  ``query_maps`` / ``propagate``: refused (the tables hold the concept maps only)."""
         if self._query_kinds(query_maps):
             raise ValueError("layer_noise_sweep: query_maps are not part of the sweep tables (ask encode_image for them)")
+        if self._propagate_spaces(propagate):
+            raise ValueError("layer_noise_sweep: propagated maps are not part of the sweep tables (the tables take the "
+                             "heat-map launch's second accumulator; ask encode_image for them)")
         assert height == width, "Height and width must be the same for now"
         latent = image.to(self.device, torch.bfloat16) if isinstance(image, torch.Tensor) else \
             self._encode_pixels([image], height, width, vae_noise)
@@ -894,7 +960,8 @@ class ConceptAttentionFluxPipeline:
                      joint_attention_kwargs=None, noise=None, vae_noise=None, heatmap_renderer: str = "host",
                      heatmap_size=None, heatmap_interpolation: str = "nearest",
                      overlay_alpha=None, token_maps=None, keep_trace: bool = False, head_maps=None, head_norm=None,
-                     head_normalize_concepts: bool = False, query_maps=None) -> ConceptAttentionPipelineOutput:
+                     head_normalize_concepts: bool = False, query_maps=None, propagate=None,
+                       propagate_steps: int = 1) -> ConceptAttentionPipelineOutput:
         """``image``: a latent tensor (1,16,h/8,w/8), or a PIL image when the pipeline has an autoencoder
         (``autoencoder="synthetic"``, a ``.safetensors`` path, or an injected object).
         One forward of the 19 double blocks per noise sample (stop_after_multimodal_attentions).
@@ -919,7 +986,8 @@ class ConceptAttentionFluxPipeline:
             softmax=softmax, joint_attention_kwargs=joint_attention_kwargs, heatmap_renderer=heatmap_renderer,
             heatmap_size=heatmap_size, heatmap_interpolation=heatmap_interpolation, overlay_alpha=overlay_alpha,
             token_maps=token_maps, keep_trace=keep_trace, head_maps=head_maps, head_norm=head_norm,
-            head_normalize_concepts=head_normalize_concepts, query_maps=query_maps)[0]
+            head_normalize_concepts=head_normalize_concepts, query_maps=query_maps, propagate=propagate,
+                propagate_steps=propagate_steps)[0]
 
     def _encode_pixels(self, images, height: int, width: int, vae_noise=None) -> torch.Tensor:
         """PIL images -> bf16 latents (B,16,h/8,w/8).  The HIP autoencoder takes the bytes (``encode_pixels``: resize,
@@ -941,14 +1009,15 @@ class ConceptAttentionFluxPipeline:
         return self.autoencoder.encode(torch.cat(xs), **kw).to(torch.bfloat16)
 
     def _encode_maps(self, model, latent, txt, vec, con, con_ids, con_vec, settings: EncodeSettings, *, noise=None,
-                     token_acc=None, traces: Optional[dict] = None, head_acc=None, query_acc=None):
+                     token_acc=None, traces: Optional[dict] = None, head_acc=None, query_acc=None, prop_acc=None):
         """Device core of encode_image for B images at once (latent (B,16,h,w), txt (B,T,4096), ...): one forward
         per noise sample on ``model``; returns the two fp32 maps [B, C, side, side].  ``noise``: optional list of
         num_samples tensors (1 or B,16,h,w) used instead of get_noise(seed + i).  ``token_acc``: per item, the caller's
         zeroed fp32 [n_tok, patches] accumulator of the prompt-token maps (or None); ``traces``: a dict of the caller's that
         receives sample index -> the StepTrace of that sample's forward; ``head_acc``: per item, the caller's
         ``HeadMapAccumulators`` (or None); ``query_acc``: per item, a dict kind -> the caller's zeroed accumulator of the
-        query-row maps (or None); the return tuple stays."""
+        query-row maps (or None); ``prop_acc``: per item, (dict space -> the caller's zeroed accumulator of the propagated
+        maps, steps) (or None); the return tuple stays."""
         layer_indices, num_samples, noise_timestep = settings.layer_indices, settings.num_samples, settings.noise_timestep
         if noise is not None and len(noise) != num_samples:
             raise ValueError("noise: one tensor per noise sample")
@@ -957,6 +1026,8 @@ class ConceptAttentionFluxPipeline:
             raise ValueError("token_acc: one accumulator (or None) per work item")
         if query_acc is not None and len(query_acc) != B:
             raise ValueError("query_acc: one dict of accumulators (or None) per work item")
+        if prop_acc is not None and len(prop_acc) != B:
+            raise ValueError("prop_acc: one (dict of accumulators, steps) (or None) per work item")
         n_patches = (latent.shape[-1] // 2) * (latent.shape[-2] // 2)
         height, width = latent.shape[-2] * 8, latent.shape[-1] * 8
         # the reference indexes the stacked samples with the float schedule values
@@ -966,7 +1037,8 @@ class ConceptAttentionFluxPipeline:
         acc_c = torch.zeros(B, C, n_patches, device=self.device)
         req = [HeatmapRequest(tuple(int(l) for l in layer_indices), 1.0 / (num_samples * len(layer_indices)),
                               acc_o[j], acc_c[j], norm=settings.norm, token_space=None if token_acc is None else token_acc[j],
-                              **head_request_fields(head_acc, j), **query_request_fields(query_acc, j))
+                              **head_request_fields(head_acc, j), **query_request_fields(query_acc, j),
+                              **propagate_request_fields(prop_acc, j))
                for j in range(B)]
         schedule = sampling.get_schedule(settings.num_steps, n_patches, shift=(not self.is_schnell))
         for i in range(num_samples):
@@ -998,14 +1070,15 @@ class ConceptAttentionFluxPipeline:
         return tuple(_cat(e[k] for e in emb) for k in range(n_out))
 
     def _encode_chunks(self, images, concepts, prompts, settings: EncodeSettings, *, noise=None, vae_noise=None,
-                       token_acc=None, keep_trace: bool = False, head_acc=None, query_acc=None):
+                       token_acc=None, keep_trace: bool = False, head_acc=None, query_acc=None, prop_acc=None):
         """The forwards of ``encode_images``, one at a time: yields (item indices, acc_o, acc_c) with the two fp32 maps
         [len(indices), C, side, side] of the chunk still on the device (``_encode_maps``).  ``images`` and ``prompts`` are lists;
         ``settings`` was built with the call's largest concept count; ``noise`` / ``vae_noise``: as ``encode_images`` takes them;
         ``token_acc``: per item of the call, the caller's accumulator of the prompt-token maps (or None).  With
         ``keep_trace`` a fourth entry follows: sample index -> the StepTrace of the chunk's forward.  ``head_acc``: per item
         of the call, its ``HeadMapAccumulators`` (or None for the call); ``query_acc``: per item of the call, its dict of
-        query-row accumulators (or None for the call)."""
+        query-row accumulators (or None for the call); ``prop_acc``: per item of the call, its propagated-map accumulators
+        (or None for the call)."""
         n, height, width = len(images), settings.height, settings.width
         concepts = _per_item(concepts, n, "encode_images: concepts")
         for name, v in (("prompts", prompts), ("noise", noise), ("vae_noise", vae_noise)):
@@ -1029,7 +1102,8 @@ class ConceptAttentionFluxPipeline:
             ho, hc = self._encode_maps(self.model, latent, txt, vec, con, con_ids, con_vec, settings, noise=nz,
                                        token_acc=None if token_acc is None else [token_acc[i] for i in idx], traces=traces,
                                        head_acc=None if head_acc is None else [head_acc[i] for i in idx],
-                                       query_acc=None if query_acc is None else [query_acc[i] for i in idx])
+                                       query_acc=None if query_acc is None else [query_acc[i] for i in idx],
+                                       prop_acc=None if prop_acc is None else [prop_acc[i] for i in idx])
             yield (idx, ho, hc, traces) if keep_trace else (idx, ho, hc)
 
     @torch.no_grad()
@@ -1041,7 +1115,8 @@ class ConceptAttentionFluxPipeline:
                       attention_norm: str = "sparsemax", softmax=True, joint_attention_kwargs=None,
                       heatmap_renderer: str = "host", heatmap_size=None, heatmap_interpolation: str = "nearest",
                       overlay_alpha=None, token_maps=None, keep_trace: bool = False, head_maps=None, head_norm=None,
-                      head_normalize_concepts: bool = False, query_maps=None) -> list:
+                      head_normalize_concepts: bool = False, query_maps=None, propagate=None,
+                       propagate_steps: int = 1) -> list:
         """``encode_image`` for a list of images: a list of ConceptAttentionPipelineOutput in item order, every item with
         the maps of its own ``encode_image`` call.  ``images``: PIL images and / or latents (1,16,h/8,w/8);
         ``concepts``: one list for all items or one list per item; ``prompts``: one string per item (or one for all).
@@ -1077,12 +1152,16 @@ class ConceptAttentionFluxPipeline:
         query_acc = self._query_plan(query_maps, prompts, token_maps, [len(c) for c in concepts], [
             (im.shape[-1] // 2) * (im.shape[-2] // 2) if isinstance(im, torch.Tensor) else (height // 16) * (width // 16)
             for im in images], joint_attention_kwargs)
+        prop_acc = self._propagate_plan(propagate, propagate_steps, [len(c) for c in concepts], [
+            (im.shape[-1] // 2) * (im.shape[-2] // 2) if isinstance(im, torch.Tensor) else (height // 16) * (width // 16)
+            for im in images])
         results = {}
         for idx, ho, hc, *traces in self._encode_chunks(images, concepts, prompts, settings, noise=noise,
                                                         vae_noise=vae_noise, token_acc=token_acc, keep_trace=keep_trace,
-                                                        head_acc=head_acc, query_acc=query_acc):
+                                                        head_acc=head_acc, query_acc=query_acc, prop_acc=prop_acc):
             outs = self._chunk_outputs(idx, [images[i] for i in idx], ho, hc, show, token_acc, tokens,
-                                       None if pictures is None else [pictures[i] for i in idx], head_acc, query_acc)
+                                       None if pictures is None else [pictures[i] for i in idx], head_acc, query_acc,
+                                       prop_acc)
             if keep_trace:
                 self._attach_traces(outs, traces[0], dict(
                     call="encode_image", width=width, height=height, layer_indices=list(layer_indices),
@@ -1099,7 +1178,8 @@ class ConceptAttentionFluxPipeline:
                         attention_norm: str = "sparsemax", cmap="plasma", batch: int = 5,
                         heatmap_renderer: str = "host", heatmap_size=None, heatmap_interpolation: str = "nearest",
                         overlay_alpha=None, token_maps=None, keep_trace: bool = False, head_maps=None, head_norm=None,
-                        head_normalize_concepts: bool = False, query_maps=None) -> list:
+                        head_normalize_concepts: bool = False, query_maps=None, propagate=None,
+                       propagate_steps: int = 1) -> list:
         """``generate_image`` for a list of prompts: a list of ConceptAttentionPipelineOutput in item order, every item
         with the image and maps of its own ``generate_image(prompt, concepts, seed=seeds[i], latent=latents[i])`` call on
         the fused route.  ``concepts``: one list for all items or one list per item; ``seeds``: one per item (default
@@ -1128,6 +1208,12 @@ class ConceptAttentionFluxPipeline:
                                    [(s[1] // 2) * (s[2] // 2) for s in shapes], head_normalize_concepts)
         query_acc = self._query_plan(query_maps, prompts, token_maps, [len(c) for c in concepts],
                                      [(s[1] // 2) * (s[2] // 2) for s in shapes])
+        prop_acc = self._propagate_plan(propagate, propagate_steps, [len(c) for c in concepts],
+                                        [(s[1] // 2) * (s[2] // 2) for s in shapes])
+        if prop_acc is not None:
+            ts = list(range(num_inference_steps)) if timesteps is None else [int(t) % max(num_inference_steps, 1) for t in timesteps]
+            if len(set(ts)) != len(ts) or len(set(int(l) for l in layer_indices)) != len(list(layer_indices)):
+                raise ValueError("propagate needs the fused route (fused=True, distinct timesteps and layer indices)")
         if query_acc is not None:
             ts = list(range(num_inference_steps)) if timesteps is None else [int(t) % max(num_inference_steps, 1) for t in timesteps]
             if len(set(ts)) != len(ts) or len(set(int(l) for l in layer_indices)) != len(list(layer_indices)):
@@ -1144,9 +1230,10 @@ class ConceptAttentionFluxPipeline:
                                                   token_acc=None if token_acc is None else [token_acc[i] for i in idx],
                                                   traces=traces,
                                                   head_acc=None if head_acc is None else [head_acc[i] for i in idx],
-                                                  query_acc=None if query_acc is None else [query_acc[i] for i in idx])
+                                                  query_acc=None if query_acc is None else [query_acc[i] for i in idx],
+                                                  prop_acc=None if prop_acc is None else [prop_acc[i] for i in idx])
             pictures, pix = self._decode(img, height, width, show[0] and overlay_alpha is not None)
-            outs = self._chunk_outputs(idx, pictures, ho, hc, show, token_acc, tokens, pix, head_acc, query_acc)
+            outs = self._chunk_outputs(idx, pictures, ho, hc, show, token_acc, tokens, pix, head_acc, query_acc, prop_acc)
             if keep_trace:
                 self._attach_traces(outs, traces, dict(
                     call="generate_image", width=width, height=height, layer_indices=list(layer_indices),
@@ -1167,7 +1254,7 @@ class ConceptAttentionFluxPipeline:
     def requery(self, trace, concepts, layer_indices=None, timesteps=None, softmax: bool = True,
                 attention_norm: str = "sparsemax", cmap="plasma", return_pil_heatmaps: bool = True,
                 heatmap_renderer: str = "host", heatmap_size=None, heatmap_interpolation: str = "nearest",
-                overlay_alpha=None, query_maps=None):
+                overlay_alpha=None, query_maps=None, propagate=None):
         """Other concepts for a finished ``keep_trace=True`` call, without its image pass: only the concept rows' stream
         through the double blocks runs, against the image keys, values and map operands the trace kept
         (``HipFluxDiT.requery``).  ``trace``: an ``ImageTrace`` (-> one ConceptAttentionPipelineOutput) or a list of them
@@ -1180,6 +1267,9 @@ class ConceptAttentionFluxPipeline:
         if self._query_kinds(query_maps):
             raise ValueError("requery: query_maps are not part of a re-query (the trace keeps no text q rows, and the concept "
                              "rows' query maps are asked for in the forward)")
+        if self._propagate_spaces(propagate):
+            raise ValueError("requery: propagated maps are not part of a re-query (a trace keeps no image q rows; ask for "
+                             "them in the call that makes the image)")
         single = isinstance(trace, ImageTrace)
         traces = [trace] if single else list(trace)
         n = len(traces)

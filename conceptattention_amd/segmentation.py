@@ -665,6 +665,8 @@ class ConceptAttentionSegmentationModel:
         kw = dict(sweep_kwargs)
         if kw.pop("query_maps", None):
             raise ValueError("score_sweep: query_maps are not part of the sweep tables (ask encode_images for them)")
+        if kw.pop("propagate", None):
+            raise ValueError("score_sweep: propagated maps are not part of the sweep tables (ask encode_images for them)")
         unknown = set(kw) - {"num_steps", "layer_indices", "num_samples", "seed", "width", "height", "batch", "vae_noise"}
         if unknown:
             raise TypeError(f"score_sweep: unexpected arguments {sorted(unknown)}")
